@@ -5,14 +5,18 @@
                     2,1,0 x <= 10 LM iterations, mu/sigma, outlier passes) on the 20 KF x 5000 pts x 100 text-plane window
                     (SURVEY.md 8d, config C4), the window resident in HBM when the timed region starts.
   N > 1 (default)   global BA: residuals/s of one complete optimizer::GlobalBA on the synthetic 5000-KF / ~500 k-observation map
-                    (config C6) sharded over the N GPUs (strong scaling: the map is fixed); the line carries the 1-GPU time of
+                    (config C6) sharded over the N GPUs (strong scaling: the map is fixed); the line carries (--full) the 1-GPU time of
                     the same map measured in the same run (`scaling_reference`), the RCCL rank count and the bytes every rank
                     exchanges per LM trial.
   --workload local_ba | global_ba | orb selects explicitly (local BA and ORB at N > 1 are independent replicas).
 
 residuals/s (`value`, round 6) = SURVEY 8d's count / wall time; `residuals_per_s_all_evaluations` = scalar residuals evaluated (once per linearisation and once per LM trial step); `residuals_per_s_8d` (= value) counts
-SURVEY 8d's way (one residual + Jacobian evaluation per LM trial).  At N = 1 the local-BA line also carries `also`: the other BASELINE configs
-(C3, C5, C6 as an open chain / with 1 % long-range observations / after a loop closure, the ORB batch), each a few solves, no CPU leg.
+SURVEY 8d's way (one residual + Jacobian evaluation per LM trial).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds everything that takes runs of its own: the CPU baseline,
+the roofline figures (timed kernel launches), the one-shot / sliding-window / C++ adapter calls, the 1-GPU scaling reference of a sharded run and,
+at N = 1, `also`: the other BASELINE configs (C3, C5, C6 as an open chain / with 1 % long-range observations / after a loop closure, the ORB
+batch), each a few solves, no CPU leg.  --dump-outputs DIR writes what the last timed step computed (DIR/<name>.npy, seeded inputs).
 
 Launch: `python bench.py --gpus N` spawns the N ranks itself (one process per GPU, RCCL over xGMI); under a launcher that already
 set RANK / LOCAL_RANK / WORLD_SIZE (torch.distributed.run) it is one of the ranks -- --gpus must then agree with WORLD_SIZE.
@@ -29,6 +33,33 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8 TB/s
 F64_MFMA_PEAK_TFLOPS = 78.6      # dense fp64 matrix rate (= the fp64 vector rate on this part)
+DUMP_LIMIT_BYTES = 63 << 20      # --dump-outputs: the arrays' data together (64 MB with the .npy headers)
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: one d/<name>.npy per array; float32 and uint8 / bool arrays are written as float32, everything else as float64
+    (integers exactly).  Past DUMP_LIMIT_BYTES in all, every array of more than 1 MB keeps a fixed, seeded sample of its rows, in order,
+    the same fraction of each."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: a.astype(np.float32 if a.dtype in (np.float32, np.uint8, np.bool_) else np.float64) for k, a in arrays.items()}
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= 1 << 20)
+    large = sum(a.nbytes for a in arrays.values()) - small
+    for k, a in arrays.items():
+        if small + large > DUMP_LIMIT_BYTES and a.nbytes > 1 << 20:
+            keep = max(1, a.shape[0]*(DUMP_LIMIT_BYTES - small)//large)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
+def ba_outputs(gpu, prob, rep):
+    """What a caller of the timed solve receives: the report's per-pass costs / iterations and the parameters + good flags
+    tsba_download copies back (pose, rho, theta, sgood, tobs_good, tfgood)."""
+    q = gpu.download(prob.copy())
+    out = {k: getattr(q, k) for k in ("pose", "rho", "theta", "sgood", "tobs_good", "tfgood")}
+    out.update({"report_" + k: rep[k] for k in ("iters", "accepted", "cost0", "cost1", "n_sblock", "n_tblock")})
+    return out
 
 
 def _pmc_traffic(name):
@@ -129,7 +160,11 @@ def bench_orb(args, rank, local_rank, world, dist, torch):
     for _ in range(args.steps):
         ex.run()
     sync(); dt = time.perf_counter() - t0
-    nk = sum(len(k) for k, _ in ex.download())
+    res = ex.download()
+    nk = sum(len(k) for k, _ in res)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"keypoints": np.concatenate([k for k, _ in res]), "descriptors": np.concatenate([d for _, d in res]),
+                                          "keypoints_per_frame": [len(k) for k, _ in res]})
     if dist is not None:
         t = torch.tensor([dt, float(nk)], dtype=torch.float64, device="cuda")
         tm = t.clone(); dist.all_reduce(tm, op=dist.ReduceOp.MAX); dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -145,7 +180,7 @@ def bench_orb(args, rank, local_rank, world, dist, torch):
         out["roofline"] = {"bound": "hbm", "kernel": "whole ORB pipeline (pyramid, FAST, quadtree, orientation, blur, rBRIEF)", "achieved": algo*world/(dt/args.steps)/1e9,
                            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": algo/(dt/args.steps)/1e9/HBM_PEAK_GBS, "traffic": traffic, "traffic_source": src,
                            "algorithmic_bytes_per_launch": algo}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             import oracle
             t0 = time.perf_counter(); n = 0
             for f in range(16):
@@ -294,8 +329,11 @@ def main():
     ap.add_argument("--far", type=float, default=0.0, help="global_ba: fraction of loop-closure-like long-range observations")
     ap.add_argument("--loop", action="store_true", help="global_ba: closed trajectory (the map right after a loop closure: ring-shaped co-visibility)")
     ap.add_argument("--loop-at", type=int, default=0, help="global_ba --loop: the loop starts at this keyframe (a tail before the loop)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="local_ba at 1 GPU: skip the `also` object (the other BASELINE configs: C3, C5, C6 incl. long-range / loop-closure maps, ORB)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline, roofline figures, one-shot / adapter calls, the 1-GPU scaling "
+                                                        "reference and (local_ba at 1 GPU) the `also` object; off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full, local_ba at 1 GPU: skip the `also` object (the other BASELINE configs: C3, C5, C6 incl. long-range / loop-closure maps, ORB)")
     ap.add_argument("--check-single", action="store_true", help="global_ba, N > 1: compare the N-rank result with the 1-rank solve")
     args = ap.parse_args()
 
@@ -349,7 +387,7 @@ def main():
         prob = synth.config_global(n_kf=args.kf, n_pt=args.pts, band=args.band, far_frac=args.far, loop=args.loop, loop_at=args.loop_at)      # identical on every rank
         opt = abi.options_global()
         if world > 1:
-            if rank == 0:                                  # the 1-GPU time of the SAME map, same run: the strong-scaling reference
+            if rank == 0 and (args.full or args.check_single):       # the 1-GPU time of the SAME map, same run: the strong-scaling reference
                 gpu.upload(prob, opt)
                 rep1, dt1 = timed(gpu, args.steps, args.warmup, barrier=False)
                 reference = {"n_gpus": 1, "ms_per_step": dt1/args.steps*1e3, "value": _evals_8d(rep1)*args.steps/dt1}
@@ -377,6 +415,8 @@ def main():
             evals_all = float(ev.item())
     else:
         evals_all = float(rep["n_resid_evals"])
+    if args.dump_outputs and rank == 0:                    # before --full's other calls replace the context's last solve
+        write_outputs(args.dump_outputs, ba_outputs(gpu, prob, rep))
     ms_per_step = dt/args.steps*1e3
     # `value` = SURVEY 8d's residuals/s (round 6; rounds 1-5 reported the library's count of ALL evaluations there, ~1.9 x, and this one as residuals_per_s_8d).
     # Global BA: the block counts are global in every rank's report; local BA at N > 1: independent replicas of the same window shape
@@ -387,8 +427,8 @@ def main():
     out = None
     if workload == "global_ba":
         # every rank takes part in the timed launches of the linearisation (the pass set-up all-reduces in a sharded run)
-        lin_ms, algo_bytes = gpu.time_linearize(0, 50)
-        sol_ms = gpu.time_solve(20) if world == 1 else None
+        lin_ms, algo_bytes = gpu.time_linearize(0, 50) if args.full else (None, None)
+        sol_ms = gpu.time_solve(20) if world == 1 and args.full else None
         ex = gpu.exchange_bytes()
         if rank == 0:
             n6 = 6*args.kf
@@ -411,11 +451,12 @@ def main():
                 out["scaling_note"] = ("strong scaling of ONE 5000-keyframe solve is expected to be flat: the reduced-system solve (two thirds of an LM trial on one GPU, "
                                        "a latency chain that every rank repeats) does not shard; per-rank kernel times give a ceiling of 1.42 x at 8 ranks before "
                                        "16.6 MB of all-reduce per trial (DESIGN.md 7).  INTEGRATION.md tells callers to keep a map on one GPU")
-            traffic, src = _pmc_traffic("c6_linearize") if args.kf == 5000 else (_pmc_traffic("c5_linearize") if args.kf == 500 else (None, None))
-            achieved = algo_bytes/(lin_ms*1e-3)/1e9
-            out["roofline"] = {"bound": "hbm", "kernel": "k_linearize<FULL,4> (level 0, this rank's shard)", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                               "unit": "GB/s", "frac": achieved/HBM_PEAK_GBS, "traffic": traffic if world == 1 else None, "traffic_source": src if world == 1 else None,
-                               "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_us": lin_ms*1e3}
+            if lin_ms is not None:
+                traffic, src = _pmc_traffic("c6_linearize") if args.kf == 5000 else (_pmc_traffic("c5_linearize") if args.kf == 500 else (None, None))
+                achieved = algo_bytes/(lin_ms*1e-3)/1e9
+                out["roofline"] = {"bound": "hbm", "kernel": "k_linearize<FULL,4> (level 0, this rank's shard)", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                                   "unit": "GB/s", "frac": achieved/HBM_PEAK_GBS, "traffic": traffic if world == 1 else None, "traffic_source": src if world == 1 else None,
+                                   "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_us": lin_ms*1e3}
             if sol_ms is not None and not args.loop and not info.get("far_band_blocks"):
                 # the dominant phase of an LM trial: the band solve of the reduced camera system -- LDL^T of an n x n band of half width
                 # bw: n (bw^2 + 3 bw) flops + two triangular sweeps 4 n bw
@@ -428,9 +469,22 @@ def main():
             if check is not None:
                 got = gpu.download(prob.copy())
                 out["config"]["max_pose_diff_vs_single_rank"] = float(np.abs(got.pose - check.pose).max())
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 out["cpu_baseline"] = cpu_baseline_global(prob, opt)
     elif rank == 0:
+        out = {
+            "metric": "local_ba_residuals_per_s", "value": value, "unit": "residuals/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "C4 local BA: 20 KF x 5000 pts x 100 text planes (%d (KF,plane) pairs x 64 features), "
+                                   "passes 2,1,0 x <=10 LM its" % prob.n_tobs,
+                       "parallelism": "replicas x%d" % world if world > 1 else "1 GPU",
+                       "residual_blocks_level0": {"scene": rep["n_sblock"][-1], "text": rep["n_tblock"][-1]},
+                       "lm_iterations": rep["iters"], "resid_evals_per_call": rep["n_resid_evals"]},
+            "local_ba_wall_ms": ms_per_step,
+            "residuals_per_s_8d": value, "residuals_per_s_all_evaluations": value_all, "counting": COUNTING,
+        }
+    if args.full and workload == "local_ba" and rank == 0:
         # the same window through the one-shot ABI entry point (what the TextSLAM adapter calls per keyframe)
         cold = []
         for _ in range(3):
@@ -438,7 +492,6 @@ def main():
         cold_ms = min(cold)
         # the call TextSLAM makes once per new keyframe: the window slides by one (tracking.cc:828-842), 19 of its 20 keyframes were in the last call --
         # with the keyframes' identities (tsba_problem.kf_id) the context keeps their pyramid planes on the device and copies the new one only
-        import numpy as np
         slide = []
         for it in range(4):
             g2 = prob.copy(); g2.kf_id = np.arange(20, dtype=np.int64) + 1000; g2.kf_id[19] = 5000 + it
@@ -449,9 +502,8 @@ def main():
         exe = os.path.join(ROOT, "tests", "cxx", "abi_from_cxx")
         if os.path.exists(exe):
             import tempfile
-            from textslam_amd import abi as _abi
             with tempfile.TemporaryDirectory() as td:
-                _abi.write_dump(os.path.join(td, "c4.bin"), prob.copy())
+                abi.write_dump(os.path.join(td, "c4.bin"), prob.copy())
                 r = subprocess.run([exe, os.path.join(td, "c4.bin"), "time_local", os.path.join(td, "t.json"), "5"], capture_output=True, text=True, timeout=300)
                 if r.returncode == 0:
                     adapter = json.load(open(os.path.join(td, "t.json")))
@@ -465,17 +517,7 @@ def main():
         sol_ms = gpu.time_solve(200)
         n = 6*(prob.n_kf - 3)                                      # 17 free poses: the first three keyframes of the window are the gauge
         flops = n**3/3.0 + 4.0*n*n                                 # LDL^T + forward / backward substitution
-        out = {
-            "metric": "local_ba_residuals_per_s", "value": value, "unit": "residuals/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "C4 local BA: 20 KF x 5000 pts x 100 text planes (%d (KF,plane) pairs x 64 features), "
-                                   "passes 2,1,0 x <=10 LM its" % prob.n_tobs,
-                       "parallelism": "replicas x%d" % world if world > 1 else "1 GPU",
-                       "residual_blocks_level0": {"scene": rep["n_sblock"][-1], "text": rep["n_tblock"][-1]},
-                       "lm_iterations": rep["iters"], "resid_evals_per_call": rep["n_resid_evals"]},
-            "local_ba_wall_ms": ms_per_step,
-            "residuals_per_s_8d": value, "residuals_per_s_all_evaluations": value_all, "counting": COUNTING,
+        out.update({
             "local_ba_cold_call_ms": cold_ms,          # PCIe-inclusive: plan construction + upload + solve + download (never `value`)
             "local_ba_sliding_call_ms": slide_ms,      # the same call with keyframe identities: 19 of the 20 keyframes' planes already on the device
             "local_ba_adapter_call": adapter,          # C++: gather from the object graph + tsba_local_ba + scatter (what optimizer::LocalBundleAdjustment costs its caller)
@@ -486,7 +528,7 @@ def main():
                                   "achieved": flops/(sol_ms*1e-3)/1e12, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                                   "frac": flops/(sol_ms*1e-3)/1e12/F64_MFMA_PEAK_TFLOPS, "flops_per_launch": flops, "avg_launch_us": sol_ms*1e3,
                                   "note": "a dependent chain of %d pivots inside one workgroup: latency-bound, the FLOP fraction is not its figure of merit" % n},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:        # (the CPU baseline is reported at N = 1 only)
             out["cpu_baseline"] = cpu_baseline_local(prob, opt)
         if world == 1 and not args.no_also:                # the other BASELINE configs, outside the timed region of `value`

@@ -23,3 +23,21 @@ def test_gpus_spawns_one_process_per_rank(tmp_path):
         assert r.returncode == 0 and '"n_gpus": 2' in r.stdout
     else:
         assert r.returncode != 0 and "rank exit codes" in r.stderr and '"n_gpus": 1' not in r.stdout
+
+
+def test_dump_outputs_dtypes_cap_and_fixed_sample(tmp_path):
+    """--dump-outputs: float32 / uint8 arrays are written as float32, the rest as float64; past 64 MB in all, every array keeps the same
+    seeded sample of its rows, so two runs (two builds) write the same rows."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = {"pose": np.random.default_rng(1).random((9_000_000, 1)), "flags": np.ones(1000, np.uint8), "iters": [10, 7, 3]}
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["flags.npy", "iters.npy", "pose.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert a["flags.npy"].dtype == np.float32 and a["iters.npy"].dtype == np.float64 and a["pose.npy"].dtype == np.float64
+    assert np.array_equal(a["iters.npy"], [10, 7, 3])
+    assert all(np.array_equal(a[f], np.load(tmp_path / "b" / f)) for f in files)

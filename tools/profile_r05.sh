@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
 stats() {   # name, bench args...
   local name=$1; shift
-  rm -rf /tmp/prof_$name; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o $name -- python $OLDPWD/bench.py "$@" --no-cpu-baseline --no-also > $OLDPWD/$OUT/r05_${name}_bench_under_rocprof.json 2> /tmp/prof_$name.err )
+  rm -rf /tmp/prof_$name; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o $name -- python $OLDPWD/bench.py "$@" --full --no-cpu-baseline --no-also > $OLDPWD/$OUT/r05_${name}_bench_under_rocprof.json 2> /tmp/prof_$name.err )
   python profiles/rocpd_top_kernels.py $(find /tmp/prof_$name -name "*.db" | head -1) > $OUT/r05_${name}_kernel_stats.txt 2>&1
 }
 diag() {    # name, gpu_diag_far args...
@@ -18,7 +18,7 @@ diag() {    # name, gpu_diag_far args...
 }
 pmc() {     # name, counter, kernel filter, bench args...
   local name=$1 ctr=$2 filt=$3; shift 3
-  rm -rf /tmp/pmc_$name; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc $ctr -d /tmp/pmc_$name -o $name -- python $OLDPWD/bench.py "$@" --no-cpu-baseline --no-also > /dev/null 2> /tmp/pmc_$name.err )
+  rm -rf /tmp/pmc_$name; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc $ctr -d /tmp/pmc_$name -o $name -- python $OLDPWD/bench.py "$@" --full --no-cpu-baseline --no-also > /dev/null 2> /tmp/pmc_$name.err )
   python profiles/rocpd_pmc_by_kernel.py $(find /tmp/pmc_$name -name "*.db" | head -1) $filt > $OUT/r05_${name}.txt 2>&1
 }
 ONLY=${1:-all}      # "orb": just the ORB legs (after a change of that pipeline)

@@ -9,10 +9,10 @@ grep -v "^ \|^$" $OUT/r05c_tests.log | tail -25
 timeout 300 python tools/diag/gpu_ab_window.py > $OUT/r05c_ab.log 2>&1
 grep -v "^{" $OUT/r05c_ab.log | tail -14
 name=c4_local_ba
-rm -rf /tmp/prof_$name; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o $name -- python $OLDPWD/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-also > $OLDPWD/$OUT/r05c_${name}_bench_under_rocprof.json 2> /tmp/prof_$name.err )
+rm -rf /tmp/prof_$name; ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o $name -- python $OLDPWD/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-also > $OLDPWD/$OUT/r05c_${name}_bench_under_rocprof.json 2> /tmp/prof_$name.err )
 python profiles/rocpd_top_kernels.py $(find /tmp/prof_$name -name "*.db" | head -1) > $OUT/r05c_${name}_kernel_stats.txt 2>&1
 cat $OUT/r05c_${name}_kernel_stats.txt | head -24
-timeout 600 python bench.py > $OUT/r05c_bench.json 2> $OUT/r05c_bench.err
+timeout 600 python bench.py --full > $OUT/r05c_bench.json 2> $OUT/r05c_bench.err
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r05c_bench.json"))

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
 timeout 1800 python -m pytest tests -m gpu -q -p no:cacheprovider --timeout 900 -s 2>&1 | tail -150 > $OUT/r05_final_tests.log
 grep -v "^ \|^$" $OUT/r05_final_tests.log | tail -12
-timeout 600 python bench.py > $OUT/r05_bench_line.json 2> $OUT/r05_bench.err
+timeout 600 python bench.py --full > $OUT/r05_bench_line.json 2> $OUT/r05_bench.err
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r05_bench_line.json"))
