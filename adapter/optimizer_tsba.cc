@@ -135,4 +135,33 @@ bool optimizer::ThetaOptimMultiFs(const frame &F, mapText *&obj) {
     return true;
 }
 
+// tracking::TextUpdate's loop (tracking.cc:1917-1946) with ONE call: objs = the planes that passed TextJudgeSingle, res[i] = what ThetaOptimMultiFs(F, objs[i])
+// would have returned.  The planes are independent (each problem reads and writes only its own theta / Covariance), so the caller applies the per-text post-step
+// (:1950-1958) afterwards in the original order.  One Packed per slot, kept between frames.
+void optimizer::ThetaOptimMultiFsBatch(const frame &F, vector<mapText*> &objs, vector<bool> &res) {
+    static thread_local std::vector<Packed> slots;
+    double K[4]; k_of(vK[0], K);
+    const size_t n = objs.size();
+    if (slots.size() < n) slots.resize(n);
+    vector<tsba_problem*> probs(n);
+    vector<double> cov(9*n);
+    vector<tsba_report> reps(n);
+    for (size_t i = 0; i < n; i++) {
+        slots[i].reset();
+        tsba_adapter::pack_theta<TT>(F, *objs[i], 3, K, slots[i]);                                                        // :565-603
+        probs[i] = &slots[i].p;
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) cov[9*i + 3*r + c] = objs[i]->Covariance(r, c);            // kept where the information matrix is singular
+    }
+    tsba_options o; tsba_default_options_theta(&o);
+    res.assign(n, false);
+    if (failed(tsba_theta_optim_batch(tsba_ctx(), probs.data(), (int)n, &o, cov.data(), reps.data()), "tsba_theta_optim_batch")) return;
+    for (size_t i = 0; i < n; i++) {
+        if (reps[i].status != TSBA_OK) { cout << "PyrThetaOptim failed, return false." << endl; continue; }                 // :605-618
+        TT::set_theta(*objs[i], slots[i].p.theta);                                                                        // :620-621
+        Mat33 thetaVariance; for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) thetaVariance(r, c) = cov[9*i + 3*r + c];
+        objs[i]->Covariance = thetaVariance;                                                                               // :622
+        res[i] = true;
+    }
+}
+
 }  // namespace TextSLAM

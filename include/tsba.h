@@ -183,6 +183,7 @@ typedef struct tsba_report {
 #define TSBA_SOLVER_BAND_LOWRANK 6   /* band part + exact low-rank correction for a few loop closures (one or two refinement iterations) */
 #define TSBA_SOLVER_BAND_PCG     7   /* band part as preconditioner of conjugate gradients (scattered long-range observations) */
 #define TSBA_SOLVER_POSE         8   /* one free pose: 6x6 in registers (tsba_pose_optim) */
+#define TSBA_SOLVER_THETA        9   /* one plane per workgroup, all passes in one launch (tsba_theta_optim_batch) */
 
 /* Reference defaults for the three public methods. */
 void tsba_default_options_local (tsba_options *o);   /* levels 2,1,0 x10, chi2 12.25 / .5 .5 .5(.95 at 0) */
@@ -220,6 +221,27 @@ int  tsba_global_ba (void *ctx, tsba_problem *p, const tsba_options *o, tsba_rep
  * as it was when Covariance::Compute fails (optimizer.cc:2224-2241) -- the call returns TSBA_OK, cov[] is left untouched and
  * r->cov_valid = 0 (1 when cov[] was written). */
 int  tsba_theta_optim(void *ctx, tsba_problem *p, const tsba_options *o, int text, double cov[9], tsba_report *r);
+/* optimizer::ThetaOptimMultiFs for n independent planes (tracking::TextUpdate, tracking.cc:1917-1946) in one call: one workgroup per plane runs all its
+ * passes and LM iterations, one launch whatever n is.  probs[i]: one ThetaOptimMultiFs problem as adapter pack_theta builds it.  Each plane gets its own
+ * LM solve, passes, report and covariance, exactly as n calls of tsba_theta_optim on single-plane problems would (within rounding: same iterations and
+ * terminations).  cov: [n][9], row i written only where reps[i].cov_valid == 1.  reps: [n].
+ *   shape of every probs[i], checked before anything runs: n_text == 1 and 0 <= text_host[0] < n_kf; n_pt == 0 and every n_sobs[l] == 0; every
+ *     kf_initial[k] == 1; every tobs_text == 0; every level that o->levels[] uses exists (image of at most 640 x 480 = MS_MASK_WORDS x 32 pixels,
+ *     the general path's limit).
+ *   options: one shared o with use_text == 1, filter_good == 0, outlier_scene == outlier_text == 0 (tsba_default_options_theta: PyrThetaOptim filters
+ *     nothing and runs no outlier pass); huber_text is honoured (1e300 = no loss).
+ *   errors: any violation returns TSBA_ERR_ARG and writes nothing; tsba_last_error names the problem index and the reason.  n == 0 returns TSBA_OK.
+ *   parameters: theta of each plane is written back into probs[i]->theta; poses are untouched.
+ *   covariance: the rule of tsba_theta_optim (the last pass whose V is positive definite with reciprocal condition number >= 1e-14); none: cov row i
+ *     untouched, reps[i].cov_valid = 0, still TSBA_OK.  A plane whose solve fails (reps[i].status = TSBA_ERR_NUMERIC, as tsba_theta_optim would return)
+ *     leaves its cov row untouched as well; the call itself returns TSBA_OK.
+ *   reports: per plane status, n_passes, iters, accepted, termination, cost0, cost1, n_tblock, n_resid_evals, cov_valid; t_upload_ms / t_solve_ms /
+ *     t_download_ms are the call's, the same in every report; solver_path = TSBA_SOLVER_THETA.
+ *   images: img_on_device as in the other calls; host planes referenced by several problems (by pointer) are copied once per call.  kf_id is
+ *     not used here: there is no plane cache across batch calls (the resident problem's cache is not touched), every call copies what it needs.
+ *   resident state: the problem of tsba_upload (and its plane cache) is left untouched -- the call has an arena of its own.
+ * No struct changed for it: TSBA_ABI_VERSION stays 5. */
+int  tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const tsba_options *o, double *cov, tsba_report *reps);
 
 /* Text label image of keyframe `kf` at pyramid level `level` for the state left by the last solve on this context (one-shot
  * entry points leave it too).  Replaces the label part of optimizer::ShowBAReproj_TextBox (src/optimizer.cc:2508-2582 ->

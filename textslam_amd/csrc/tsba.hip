@@ -50,6 +50,7 @@
 #include "tsba_pcg.h"
 #include "tsba_wb.h"
 #include "tsba_pose.h"
+#include "tsba_theta.h"
 
 #include "tsba_kernels_step.h"
 #include "tsba_kernels_pass.h"
@@ -142,6 +143,9 @@ struct Ctx {
     MsBuf ms{}; double *ms_alloc = nullptr; size_t ms_bytes = 0; int ms_cap = 0;      // multi-right-hand-side solve phase of the partitioned band solver (tsba_bandms.h)
     std::vector<int32_t> rb_r, rb_c; std::vector<double> rb_v;      // tsba_debug_reduced_blocks: the blocks between its two calls
     int cov_text = -1; double *cov_log = nullptr;     // tsba_theta_optim: V of this plane at the end of every pass [TSBA_MAX_LEVELS][6]
+    // tsba_theta_optim_batch: an arena of its own (the resident problem of tsba_upload, its slabs and its plane cache are never touched).  dev = staged
+    // block | scratch | output records; host = the pinned staging block (headers, frames, features, image planes); out = the pinned output records
+    unsigned char *tb_dev = nullptr, *tb_host = nullptr, *tb_out = nullptr; size_t tb_dev_cap = 0, tb_host_cap = 0, tb_out_cap = 0;
     int far_B = 0, n_far = 0, pcg_parts = 0; unsigned int pcg_seq = 0;      // band + long-range blocks (tsba_pcg.h): band of M in pose blocks, blocks outside it, partial sums per vector kernel
     int rank = 0, world = 1; bool force_multi = false;
     tsba_debug_options dbg{};                      // test / diagnostics switches (tsba_debug_set), all zero in production
@@ -337,6 +341,7 @@ int tsba_destroy(void *ctx) {
     hipHostFree(c->st_host); hipFree(c->st_log); if (c->hprog) hipHostFree(c->hprog);
     if (c->lbl_dev) hipFree(c->lbl_dev); if (c->lbl_host) hipHostFree(c->lbl_host);
     if (c->ic.dev) hipFree(c->ic.dev); if (c->ic.stage) hipHostFree(c->ic.stage);
+    if (c->tb_dev) hipFree(c->tb_dev); if (c->tb_host) hipHostFree(c->tb_host); if (c->tb_out) hipHostFree(c->tb_out);
     if (c->ms_alloc) hipFree(c->ms_alloc);
     if (c->sv_alloc) hipFree(c->sv_alloc);
     if (c->dl_dev) hipFree(c->dl_dev);
@@ -1685,22 +1690,13 @@ int tsba_pose_optim(void *ctx, tsba_problem *p, const tsba_options *o, tsba_repo
     return one_shot(ctx, p, o, r);
 }
 int tsba_global_ba(void *ctx, tsba_problem *p, const tsba_options *o, tsba_report *r) { return one_shot(ctx, p, o, r); }
-int tsba_theta_optim(void *ctx, tsba_problem *p, const tsba_options *o, int text, double cov[9], tsba_report *r) {
-    Ctx *c = (Ctx *)ctx;
-    if (!c || !p || !o || !cov || !r || text < 0 || text >= p->n_text) return TSBA_ERR_ARG;
-    c->cov_text = text;
-    int rc = one_shot(ctx, p, o, r);
-    c->cov_text = -1;
-    if (rc) return rc;
-    // Information matrix of theta[text] = V of the linearisation at the end of a pass (undamped, loss-corrected J^T J).  The reference
-    // runs ceres::Covariance after EVERY pyramid pass and keeps the last one that succeeds (optimizer.cc:2219-2238: thetaVariance is only
-    // overwritten when Compute returns true): the passes are tried from the last to the first.  A pass fails when V is not positive
-    // definite or its reciprocal condition number is below 1e-14 (Ceres' min_reciprocal_condition_number; recalled, oracle/RECALLED.md).
-    // No pass succeeds: as the reference (PyrThetaOptim still returns true, optimizer.cc:2224-2241) not an error, cov[] untouched.
-    double Vall[6*TSBA_MAX_LEVELS];
-    CK(hipMemcpy(Vall, c->cov_log, sizeof(Vall), hipMemcpyDeviceToHost));
-    r->cov_valid = 0;
-    for (int ps = std::min(o->n_passes, TSBA_MAX_LEVELS) - 1; ps >= 0; ps--) {
+// Information matrix of theta = V of the linearisation at the end of a pass (undamped, loss-corrected J^T J).  The reference runs ceres::Covariance after
+// EVERY pyramid pass and keeps the last one that succeeds (optimizer.cc:2219-2238: thetaVariance is only overwritten when Compute returns true): the passes are
+// tried from the last to the first.  A pass fails when V is not positive definite or its reciprocal condition number is below 1e-14 (Ceres'
+// min_reciprocal_condition_number; recalled, oracle/RECALLED.md).  No pass succeeds: as the reference (PyrThetaOptim still returns true,
+// optimizer.cc:2224-2241) not an error, cov[] untouched.  Vall: [passes][6] (xx xy xz yy yz zz).  Returns cov_valid.
+static int theta_cov_select(const double *Vall, int n_passes, double cov[9]) {
+    for (int ps = std::min(n_passes, TSBA_MAX_LEVELS) - 1; ps >= 0; ps--) {
         const double *V = Vall + 6*ps;
         const double a = V[0], b = V[1], cc = V[2], e = V[3], f = V[4], i = V[5];
         const double A = e*i - f*f, B = -(b*i - cc*f), C = b*f - cc*e, det = a*A + b*B + cc*C;
@@ -1716,9 +1712,153 @@ int tsba_theta_optim(void *ctx, tsba_problem *p, const tsba_options *o, int text
         const double id = 1.0/det;
         cov[0] = A*id; cov[1] = B*id; cov[2] = C*id; cov[3] = B*id; cov[4] = (a*i - cc*cc)*id; cov[5] = -(a*f - b*cc)*id;
         cov[6] = C*id; cov[7] = cov[5]; cov[8] = (a*e - b*b)*id;
-        r->cov_valid = 1;
-        break;
+        return 1;
     }
+    return 0;
+}
+int tsba_theta_optim(void *ctx, tsba_problem *p, const tsba_options *o, int text, double cov[9], tsba_report *r) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || !p || !o || !cov || !r || text < 0 || text >= p->n_text) return TSBA_ERR_ARG;
+    c->cov_text = text;
+    int rc = one_shot(ctx, p, o, r);
+    c->cov_text = -1;
+    if (rc) return rc;
+    double Vall[6*TSBA_MAX_LEVELS];
+    CK(hipMemcpy(Vall, c->cov_log, sizeof(Vall), hipMemcpyDeviceToHost));
+    r->cov_valid = theta_cov_select(Vall, o->n_passes, cov);
+    return TSBA_OK;
+}
+
+// optimizer::ThetaOptimMultiFs for n independent planes in one launch (k_theta_batch, tsba_theta.h).  Host side: validate every problem, pack every plane's
+// header, frames, features and the deduplicated host image planes into one pinned block (one host-to-device copy), one launch, one copy of the output
+// records back, the covariance rule of tsba_theta_optim per plane.
+static int theta_batch_check(Ctx *c, tsba_problem *const *probs, int n, const tsba_options *o) {
+    auto bad = [&](int i, const std::string &why) { set_err(c, "tsba_theta_optim_batch: " + (i >= 0 ? "problem " + std::to_string(i) + ": " : std::string()) + why); return TSBA_ERR_ARG; };
+    if (o->use_text != 1 || o->filter_good != 0 || o->outlier_scene != 0 || o->outlier_text != 0)
+        return bad(-1, "options need use_text = 1, filter_good = 0, outlier_scene = outlier_text = 0 (tsba_default_options_theta)");
+    if (o->text_jacobian != 0) return bad(-1, "text_jacobian must be 0 (analytic)");
+    if (o->n_passes < 1 || o->n_passes > TSBA_MAX_LEVELS) return bad(-1, "n_passes out of range");
+    for (int ps = 0; ps < o->n_passes; ps++) if (o->levels[ps] < 0 || o->levels[ps] >= TSBA_MAX_LEVELS) return bad(-1, "options.levels out of range");
+    for (int i = 0; i < n; i++) {
+        const tsba_problem *p = probs[i];
+        if (!p) return bad(i, "NULL problem");
+        if (p->n_text != 1 || !p->theta || !p->text_host || !p->text_box_ray) return bad(i, "needs n_text == 1");
+        if (p->n_kf < 1 || !p->pose || !p->kf_initial || p->text_host[0] < 0 || p->text_host[0] >= p->n_kf) return bad(i, "needs 0 <= text_host[0] < n_kf");
+        if (p->n_pt != 0) return bad(i, "needs n_pt == 0");
+        for (int l = 0; l < TSBA_MAX_LEVELS; l++) if (p->n_sobs[l] != 0) return bad(i, "needs n_sobs[l] == 0 at every level");
+        for (int k = 0; k < p->n_kf; k++) if (p->kf_initial[k] != 1) return bad(i, "needs kf_initial[k] == 1 for every keyframe (all poses constant)");
+        if (p->n_tobs < 0 || (p->n_tobs > 0 && (!p->tobs_kf || !p->tobs_text))) return bad(i, "bad text observations");
+        for (int t = 0; t < p->n_tobs; t++) {
+            if (p->tobs_text[t] != 0) return bad(i, "needs tobs_text[t] == 0");
+            if (p->tobs_kf[t] < 0 || p->tobs_kf[t] >= p->n_kf) return bad(i, "tobs_kf out of range");
+        }
+        for (int ps = 0; ps < o->n_passes; ps++) {
+            const int l = o->levels[ps];
+            if (l >= p->n_levels) return bad(i, "level " + std::to_string(l) + " of the options does not exist");
+            if (!p->img[l] || p->img_w[l] <= 0 || p->img_h[l] <= 0 || p->img_w[l]*p->img_h[l] > MS_MASK_WORDS*32) return bad(i, "missing image level or image larger than 640x480");
+            if (!p->tfeat_off[l] || p->tfeat_off[l][0] != 0 || p->tfeat_off[l][1] < 0 || p->tfeat_off[l][1] > p->n_tfeat[l]
+                || (p->tfeat_off[l][1] > 0 && (!p->tfeat_uv[l] || !p->tfeat_ref[l]))) return bad(i, "bad reference features");
+            for (int t = 0; t < p->n_tobs; t++) if (!p->img[l][p->tobs_kf[t]]) return bad(i, "NULL image plane");
+        }
+    }
+    return TSBA_OK;
+}
+static int tb_reserve(Ctx *c, unsigned char **buf, size_t *cap, size_t need, bool pinned) {
+    if (need <= *cap) return TSBA_OK;
+    CK(hipStreamSynchronize(c->stream));
+    if (*buf) { if (pinned) hipHostFree(*buf); else hipFree(*buf); }
+    *buf = nullptr; *cap = 0;
+    const size_t nc = need + need/4;
+    if (pinned) CK(hipHostMalloc((void **)buf, nc, hipHostMallocDefault)); else CK(hipMalloc((void **)buf, nc));
+    *cap = nc; return TSBA_OK;
+}
+int tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const tsba_options *o, double *cov, tsba_report *reps) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return TSBA_ERR_ARG;
+    if (n < 0 || (n > 0 && (!probs || !o || !cov || !reps))) { set_err(c, "tsba_theta_optim_batch: bad arguments"); return TSBA_ERR_ARG; }
+    if (n == 0) return TSBA_OK;
+    int rc = theta_batch_check(c, probs, n, o); if (rc) return rc;
+    hipSetDevice(c->device);
+    auto t0 = std::chrono::steady_clock::now();
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    // ---- layout of the staged block: headers | frames | feature uv | feature ref | image planes (each host plane once per call)
+    int n_obs = 0; size_t n_feat = 0;
+    for (int i = 0; i < n; i++) { const tsba_problem *p = probs[i]; n_obs += p->n_tobs;
+        for (int l = 0; l < p->n_levels && l < TSBA_MAX_LEVELS; l++) if (p->tfeat_off[l]) n_feat += (size_t)p->tfeat_off[l][1]; }
+    const size_t o_hdr = 0, o_obs = up(sizeof(ThHdr)*n), o_uv = o_obs + up(sizeof(ThObs)*std::max(n_obs, 1)), o_ref = o_uv + up(sizeof(double)*2*std::max<size_t>(n_feat, 1));
+    const size_t o_img = o_ref + up(sizeof(double)*8*std::max<size_t>(n_feat, 1));
+    struct Plane { const uint8_t *src; size_t off, len; };
+    std::vector<Plane> planes;                                                  // host planes in first-use order
+    std::map<const uint8_t *, size_t> seen;
+    size_t img_end = o_img;
+    if (!o->img_on_device)
+        for (int i = 0; i < n; i++) { const tsba_problem *p = probs[i];
+            for (int ps = 0; ps < o->n_passes; ps++) { const int l = o->levels[ps];
+                for (int t = 0; t < p->n_tobs; t++) { const uint8_t *src = p->img[l][p->tobs_kf[t]];
+                    if (seen.count(src)) continue;
+                    const size_t len = (size_t)p->img_w[l]*p->img_h[l];
+                    seen[src] = img_end; planes.push_back({src, img_end, len}); img_end += up(len + 2); } } }      // (+2: tap_fetch's 2-byte loads)
+    const size_t staged = img_end, o_scr = up(staged), o_out = o_scr + up(sizeof(double)*THETA_SCR*std::max(n_obs, 1)), dev_total = o_out + up(sizeof(ThOut)*n);
+    rc = tb_reserve(c, &c->tb_host, &c->tb_host_cap, staged, true); if (rc) return rc;
+    rc = tb_reserve(c, &c->tb_dev, &c->tb_dev_cap, dev_total, false); if (rc) return rc;
+    rc = tb_reserve(c, &c->tb_out, &c->tb_out_cap, sizeof(ThOut)*n, true); if (rc) return rc;
+    unsigned char *hb = c->tb_host, *db = c->tb_dev;
+    ThHdr *hh = (ThHdr *)(hb + o_hdr); ThObs *ho = (ThObs *)(hb + o_obs); double *huv = (double *)(hb + o_uv), *href = (double *)(hb + o_ref);
+    int ob = 0; size_t fb = 0;
+    for (int i = 0; i < n; i++) {
+        const tsba_problem *p = probs[i]; ThHdr &H = hh[i];
+        memset(&H, 0, sizeof(H));
+        for (int k = 0; k < 4; k++) H.K[k] = p->K[k];
+        for (int k = 0; k < 3; k++) H.theta[k] = p->theta[k];
+        for (int k = 0; k < 7; k++) H.host[k] = p->pose[7*p->text_host[0] + k];
+        for (int k = 0; k < 8; k++) H.box[k] = p->text_box_ray[k];
+        H.n_obs = p->n_tobs; H.o_obs = ob;
+        for (int t = 0; t < p->n_tobs; t++) { ThObs &O = ho[ob + t]; const int kf = p->tobs_kf[t];
+            for (int k = 0; k < 7; k++) O.pose[k] = p->pose[7*kf + k];
+            for (int l = 0; l < TSBA_MAX_LEVELS; l++) O.img[l] = nullptr; }
+        for (int l = 0; l < p->n_levels && l < TSBA_MAX_LEVELS; l++) {
+            const int nf = p->tfeat_off[l] ? p->tfeat_off[l][1] : 0;
+            H.nf[l] = nf; H.o_feat[l] = (int)fb; H.w[l] = p->img_w[l]; H.h[l] = p->img_h[l];
+            if (nf) { memcpy(huv + 2*fb, p->tfeat_uv[l], sizeof(double)*2*nf); memcpy(href + 8*fb, p->tfeat_ref[l], sizeof(double)*8*nf); }
+            fb += nf;
+        }
+        for (int ps = 0; ps < o->n_passes; ps++) { const int l = o->levels[ps];
+            for (int t = 0; t < p->n_tobs; t++) { const uint8_t *src = p->img[l][p->tobs_kf[t]];
+                ho[ob + t].img[l] = o->img_on_device ? src : (const uint8_t *)(db + seen[src]); } }
+        ob += p->n_tobs;
+    }
+    for (size_t q = 0; q < planes.size(); q++) {                   // the image planes: a memcpy each into the pinned block (one copy to the device for all)
+        const size_t end = q + 1 < planes.size() ? planes[q + 1].off : img_end;
+        memcpy(hb + planes[q].off, planes[q].src, planes[q].len); memset(hb + planes[q].off + planes[q].len, 0, end - planes[q].off - planes[q].len);
+    }
+    CK(hipMemcpyAsync(db, hb, staged, hipMemcpyHostToDevice, c->stream));
+    auto t1 = std::chrono::steady_clock::now();
+    ThArgs A; A.hdr = (const ThHdr *)(db + o_hdr); A.obs = (const ThObs *)(db + o_obs); A.fuv = (const double *)(db + o_uv); A.fref = (const double *)(db + o_ref);
+    A.scr = (double *)(db + o_scr); A.out = (ThOut *)(db + o_out);
+    LAUNCHK(k_theta_batch<THETA_WG>, dim3(n), dim3(THETA_WG), 0, c->stream, A, *o);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(c->tb_out, db + o_out, sizeof(ThOut)*n, hipMemcpyDeviceToHost, c->stream));
+    CK(hipStreamSynchronize(c->stream));
+    auto t2 = std::chrono::steady_clock::now();
+    const ThOut *out = (const ThOut *)c->tb_out;
+    for (int i = 0; i < n; i++) {
+        tsba_problem *p = probs[i]; const ThOut &R = out[i]; tsba_report &r = reps[i];
+        memset(&r, 0, sizeof(r));
+        r.n_passes = o->n_passes; r.solver_path = TSBA_SOLVER_THETA;
+        for (int ps = 0; ps < o->n_passes; ps++) {
+            const int l = o->levels[ps]; const long long nt = (long long)p->n_tobs*(p->tfeat_off[l] ? p->tfeat_off[l][1] : 0);
+            r.iters[ps] = R.iters[ps]; r.accepted[ps] = R.accepted[ps]; r.termination[ps] = R.term[ps];
+            r.cost0[ps] = R.cost0[ps]; r.cost1[ps] = R.cost1[ps]; r.n_tblock[ps] = nt;
+            r.n_resid_evals += R.evals[ps]*8LL*nt;
+            if (R.term[ps] == 5) r.status = TSBA_ERR_NUMERIC;
+        }
+        for (int k = 0; k < 3; k++) p->theta[k] = R.theta[k];
+        if (r.status == TSBA_OK) r.cov_valid = theta_cov_select(&R.V[0][0], o->n_passes, cov + 9*(size_t)i);     // (a failed solve, as tsba_theta_optim: cov untouched)
+    }
+    auto t3 = std::chrono::steady_clock::now();
+    const double tu = std::chrono::duration<double, std::milli>(t1 - t0).count(), tsv = std::chrono::duration<double, std::milli>(t2 - t1).count(),
+                 td = std::chrono::duration<double, std::milli>(t3 - t2).count();
+    for (int i = 0; i < n; i++) { reps[i].t_upload_ms = tu; reps[i].t_solve_ms = tsv; reps[i].t_download_ms = td; }
     return TSBA_OK;
 }
 

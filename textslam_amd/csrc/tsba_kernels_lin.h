@@ -236,49 +236,34 @@ __global__ __launch_bounds__(1024) void k_gauge_par(Work W, const uint8_t *kf_in
 // with cv::fillPoly's scan conversion (boundary Bresenham lines + 16.16 fixed-point scanline spans).  One workgroup per
 // (KF, text) observation; the polygon mask of the clamped bounding box lives in LDS as a bit field.
 #define MS_THREADS 256
-__device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, const int g, const double *pose, const double *theta) {
-    __shared__ unsigned mask[MS_MASK_WORDS];
-    __shared__ unsigned hist[256];
-    __shared__ int s_xy[8], s_bb[4];
-    __shared__ double s_red[MS_THREADS];
-    const int tid = threadIdx.x;
-    // (round 6) the group's static record (tobs, keyframe, text, host: one 16-byte load) instead of three lists and then the host; what hangs off it -- the good
-    // flag, both poses, the plane, the corner, the keyframe's image pointer -- requested together by every thread BEFORE the flag is looked at (a request under a
-    // lane-dependent branch is waited for at the end of that branch): one dependent round trip where there were three, and the image pointer is there when the
-    // histogram needs it
 #ifdef MID_STAMPS                           // (tools/mid_stamps.sh: cycles of a mu / sigma workgroup by phase into W.dbg[56..63] -- the slots of k_schur_t's gradient rows in that build)
-    const long long us_t0 = clock64();
-#define MS_STAMP(slot) do { if (threadIdx.x == 0) atomicAdd((unsigned long long *)&W.dbg[56 + (slot)], (unsigned long long)(clock64() - us_t0)); } while (0)
+#define MS_STAMP(slot) do { if (threadIdx.x == 0 && dbg) atomicAdd((unsigned long long *)&dbg[56 + (slot)], (unsigned long long)(clock64() - us_t0)); } while (0)
 #else
 #define MS_STAMP(slot) do { } while (0)
 #endif
-    const int4 ra = ((const int4 *)L.tg_rec)[2*g];
-    const int tb = ra.x, kf = ra.y, j = ra.z, h = ra.w;
-    const uint8_t good_t = W.tobs_good[tb];
-    const uint8_t *img = L.img[kf];
-    const int bq_ = tid & 3;
-    double pc[7], ph[12], th[3], mx, my;
-#pragma unroll
-    for (int k = 0; k < 7; k++) pc[k] = pose[7*kf + k];
-#pragma unroll
-    for (int k = 0; k < 12; k++) ph[k] = h >= 0 ? (k < 7 ? pose[7*h + k] : 0.0) : W.text_Twr[12*(size_t)j + k];
-#pragma unroll
-    for (int k = 0; k < 3; k++) th[k] = theta[3*j + k];
-    mx = W.text_box[(j*4 + bq_)*2]; my = W.text_box[(j*4 + bq_)*2 + 1];
-    if (W.filter_good && !good_t) { if (tid == 0) { W.musig[2*tb] = 0; W.musig[2*tb+1] = 0; } return; }
-    MS_STAMP(0);                                              // (operands there)
-    const int w = L.img_w, hh = L.img_h;
-    __shared__ int s_c[16];
+// The rasteriser / histogram core shared by musigma_wg and the batched theta solve (tsba_theta.h): one box, one image, NT >= 256 threads (the moments
+// sum the 256 bins through block_sum<NT>: the slots past 255 add +0.0, so every NT gives the bits of NT = 256).  pc: the observing pose, ph: the host
+// pose (h_in) or its T_wr (3x4), th: the plane, (mx, my): box corner tid & 3.  Returns n < 2 (no moments: mu = sigma = 0) as false; *mu / *sigma in
+// every thread otherwise.  LDS: mask [MS_MASK_WORDS], hist [256], s_xy [8], s_bb [4], s_c [16], s_red [NT].
+template <int NT>
+__device__ __forceinline__ bool musigma_core(const double pc[7], const double ph[12], bool h_in, const double th[3], double mx, double my,
+                                             const double K[4], int w, int hh, const uint8_t *img,
+                                             unsigned *mask, unsigned *hist, int *s_xy, int *s_bb, int *s_c, double *s_red, double *mu_out, double *sig_out
+#ifdef MID_STAMPS
+                                             , long long *dbg, long long us_t0
+#endif
+                                             ) {
+    const int tid = threadIdx.x;
     if (tid < 4) {                                            // one box corner per lane (the serial walk over the four cost ~1.5 us of divisions)
         const int b = tid;
         Pose C; load_pose(pc, C);
         PairT T;
-        if (h >= 0) { Pose Hs; load_pose(ph, Hs); pair_from_poses(C, Hs, T); }
+        if (h_in) { Pose Hs; load_pose(ph, Hs); pair_from_poses(C, Hs, T); }
         else pair_from_Twr(C, ph, T);
         double invz = -(mx*th[0] + my*th[1] + th[2]);
         double m[3] = { mx, my, 1.0 }, Rm[3]; mat3_vec(T.Rcr, m, Rm);
         double X = Rm[0]/invz + T.tq[0] + C.t[0], Y = Rm[1]/invz + T.tq[1] + C.t[1], Z = Rm[2]/invz + T.tq[2] + C.t[2];
-        double cu = L.K[0]*X/Z + L.K[2], cv = L.K[1]*Y/Z + L.K[3];
+        double cu = K[0]*X/Z + K[2], cv = K[1]*Y/Z + K[3];
         s_xy[2*b] = (int)cu; s_xy[2*b+1] = (int)cv;
         // the reference updates xMax / xMin only on strict improvement, starting from -1 / w + 1: a corner that does not improve
         // contributes nothing -- the same as taking max / min over the corners that do
@@ -302,29 +287,29 @@ __device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, con
         s_bb[0] = xMin; s_bb[1] = xMax; s_bb[2] = yMin; s_bb[3] = yMax;
     }
     MS_STAMP(1);                                              // (corners projected)
-    for (int k = tid; k < min((w*hh + 31) >> 5, MS_MASK_WORDS); k += MS_THREADS) mask[k] = 0;
-    hist[tid] = 0;
+    for (int k = tid; k < min((w*hh + 31) >> 5, MS_MASK_WORDS); k += NT) mask[k] = 0;
+    if (tid < 256) hist[tid] = 0;
     __syncthreads();
     const int xMin = s_bb[0], xMax = s_bb[1], yMin = s_bb[2], yMax = s_bb[3];
     MS_STAMP(2);                                              // (mask cleared)
 #ifdef MID_STAMPS
-    raster_quad(mask, s_xy, w, hh, tid, MS_THREADS, W.dbg + 48);
+    raster_quad(mask, s_xy, w, hh, tid, NT, dbg ? dbg + 48 : nullptr);
 #else
-    raster_quad(mask, s_xy, w, hh, tid, MS_THREADS);
+    raster_quad(mask, s_xy, w, hh, tid, NT);
 #endif
     __syncthreads();
     MS_STAMP(3);                                              // (quad rasterised)
     // histogram of masked pixels inside the clamped bounding box (tool.cc:1217-1232)
     int bw = xMax - xMin + 1, bh = yMax - yMin + 1;
     {   // four pixels per thread and round with their loads in flight together; (x, y) advance without a division per pixel
-        const int npx = bw*bh, dx = MS_THREADS % bw, dy = MS_THREADS / bw;
+        const int npx = bw*bh, dx = NT % bw, dy = NT / bw;
         int x = tid % bw, y = tid / bw;
-        for (int k0 = tid; k0 < npx; k0 += 4*MS_THREADS) {
+        for (int k0 = tid; k0 < npx; k0 += 4*NT) {
             int bit[4]; bool in[4]; unsigned px[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 bit[u] = (yMin + y)*w + xMin + x;
-                in[u] = k0 + u*MS_THREADS < npx && (mask[bit[u] >> 5] & (1u << (bit[u] & 31)));
+                in[u] = k0 + u*NT < npx && (mask[bit[u] >> 5] & (1u << (bit[u] & 31)));
                 x += dx; y += dy; if (x >= bw) { x -= bw; y++; }
             }
 #pragma unroll
@@ -335,13 +320,57 @@ __device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, con
     }
     __syncthreads();
     MS_STAMP(4);                                              // (histogram)
-    double cnt = (double)hist[tid], sum = (double)hist[tid]*(double)tid;
-    double n = block_sum<MS_THREADS>(cnt, s_red), sm = block_sum<MS_THREADS>(sum, s_red);
-    if (n < 2.0) { if (tid == 0) { W.musig[2*tb] = 0; W.musig[2*tb+1] = 0; } return; }
+    const double hv = tid < 256 ? (double)hist[tid] : 0.0;
+    double cnt = hv, sum = hv*(double)tid;
+    double n = block_sum<NT>(cnt, s_red), sm = block_sum<NT>(sum, s_red);
+    if (n < 2.0) { *mu_out = 0.0; *sig_out = 0.0; return false; }
     double mu = sm/n;
     double d = (double)tid - mu;
-    double ss = block_sum<MS_THREADS>((double)hist[tid]*d*d, s_red);
-    if (tid == 0) { W.musig[2*tb] = mu; W.musig[2*tb+1] = sqrt(ss/(n - 1.0)); }
+    double ss = block_sum<NT>(hv*d*d, s_red);
+    *mu_out = mu; *sig_out = sqrt(ss/(n - 1.0));
+    return true;
+}
+
+// ---- mu / sigma of a projected text box: tool::GetProjText x4 + tool::CalTextinfo (src/tool.cc:1178-1262,1655-1728)
+// with cv::fillPoly's scan conversion (boundary Bresenham lines + 16.16 fixed-point scanline spans).  One workgroup per
+// (KF, text) observation; the polygon mask of the clamped bounding box lives in LDS as a bit field.
+__device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, const int g, const double *pose, const double *theta) {
+    __shared__ unsigned mask[MS_MASK_WORDS];
+    __shared__ unsigned hist[256];
+    __shared__ int s_xy[8], s_bb[4];
+    __shared__ double s_red[MS_THREADS];
+    const int tid = threadIdx.x;
+    // (round 6) the group's static record (tobs, keyframe, text, host: one 16-byte load) instead of three lists and then the host; what hangs off it -- the good
+    // flag, both poses, the plane, the corner, the keyframe's image pointer -- requested together by every thread BEFORE the flag is looked at (a request under a
+    // lane-dependent branch is waited for at the end of that branch): one dependent round trip where there were three, and the image pointer is there when the
+    // histogram needs it
+#ifdef MID_STAMPS
+    const long long us_t0 = clock64(); long long *dbg = W.dbg;
+#endif
+    const int4 ra = ((const int4 *)L.tg_rec)[2*g];
+    const int tb = ra.x, kf = ra.y, j = ra.z, h = ra.w;
+    const uint8_t good_t = W.tobs_good[tb];
+    const uint8_t *img = L.img[kf];
+    const int bq_ = tid & 3;
+    double pc[7], ph[12], th[3], mx, my;
+#pragma unroll
+    for (int k = 0; k < 7; k++) pc[k] = pose[7*kf + k];
+#pragma unroll
+    for (int k = 0; k < 12; k++) ph[k] = h >= 0 ? (k < 7 ? pose[7*h + k] : 0.0) : W.text_Twr[12*(size_t)j + k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) th[k] = theta[3*j + k];
+    mx = W.text_box[(j*4 + bq_)*2]; my = W.text_box[(j*4 + bq_)*2 + 1];
+    if (W.filter_good && !good_t) { if (tid == 0) { W.musig[2*tb] = 0; W.musig[2*tb+1] = 0; } return; }
+    MS_STAMP(0);                                              // (operands there)
+    __shared__ int s_c[16];
+    double mu, sigma;
+    const bool ok = musigma_core<MS_THREADS>(pc, ph, h >= 0, th, mx, my, L.K, L.img_w, L.img_h, img, mask, hist, s_xy, s_bb, s_c, s_red, &mu, &sigma
+#ifdef MID_STAMPS
+                                             , dbg, us_t0
+#endif
+                                             );
+    if (tid == 0) { W.musig[2*tb] = mu; W.musig[2*tb+1] = sigma; }
+    if (!ok) return;
     MS_STAMP(5);
 #ifdef MID_STAMPS
     if (threadIdx.x == 0) atomicAdd((unsigned long long *)&W.dbg[63], 1ull);

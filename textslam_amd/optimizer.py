@@ -64,6 +64,8 @@ def load_library():
     L.tsba_comm_init_local.argtypes = [vp, vp, C.c_int, C.c_int]
     L.tsba_debug_set.argtypes = [vp, C.POINTER(TsbaDebugOptions)]
     L.tsba_theta_optim.argtypes = [vp, C.POINTER(TsbaProblem), C.POINTER(TsbaOptions), C.c_int, dp, C.POINTER(TsbaReport)]
+    L.tsba_theta_optim_batch.argtypes = [vp, C.POINTER(C.POINTER(TsbaProblem)), C.c_int, C.POINTER(TsbaOptions), dp, C.POINTER(TsbaReport)]
+    L.tsba_theta_optim_batch.restype = C.c_int
     for name in ("tsba_default_options_local", "tsba_default_options_pose", "tsba_default_options_global",
                  "tsba_default_options_init", "tsba_default_options_landmarker", "tsba_default_options_theta"):
         getattr(L, name).argtypes = [C.POINTER(TsbaOptions)]
@@ -77,7 +79,7 @@ EXPORTED_SYMBOLS = [
     "tsba_default_options_local", "tsba_default_options_pose", "tsba_default_options_global",
     "tsba_abi_version", "tsba_create", "tsba_destroy", "tsba_last_error",
     "tsba_default_options_init", "tsba_default_options_landmarker", "tsba_default_options_theta",
-    "tsba_local_ba", "tsba_pose_optim", "tsba_global_ba", "tsba_theta_optim", "tsba_text_label_image",
+    "tsba_local_ba", "tsba_pose_optim", "tsba_global_ba", "tsba_theta_optim", "tsba_theta_optim_batch", "tsba_text_label_image",
     "tsba_upload", "tsba_solve", "tsba_download", "tsba_eval", "tsba_time_linearize",
     "tsba_comm_unique_id", "tsba_comm_load", "tsba_comm_init", "tsba_comm_init_local", "tsba_local_group_create", "tsba_local_group_destroy",
     "tsba_debug_set", "tsba_debug_reduced_system",
@@ -159,6 +161,22 @@ class Optimizer:
         cov = np.zeros(9) if cov0 is None else np.ascontiguousarray(cov0, np.float64).reshape(9).copy()
         self._check(self.lib.tsba_theta_optim(self.ctx, C.byref(s), C.byref(o), text, _dp(cov), C.byref(rep)), "tsba_theta_optim")
         return rep.as_dict(), cov.reshape(3, 3)
+
+    def ThetaOptimMultiFsBatch(self, probs, options: TsbaOptions = None, cov0=None):
+        """optimizer::ThetaOptimMultiFs on n independent single-plane problems in one call (tracking::TextUpdate's loop, tracking.cc:1917-1946).
+        Mutates every problem's theta; returns (list of report dicts, covs [n, 3, 3]).  Where a plane's report has cov_valid == 0 its matrix is
+        cov0[i] (zeros when cov0 is not given), as ThetaOptimMultiFs returns it."""
+        o = options or options_theta()
+        n = len(probs)
+        structs, keep = [], []
+        for P in probs:                               # (struct() keeps its pointer tables on the problem: a problem listed twice would drop the first's)
+            structs.append(P.struct())
+            keep.append(P._keep)
+        arr = (C.POINTER(TsbaProblem) * max(n, 1))(*[C.pointer(s) for s in structs])
+        reps = (TsbaReport * max(n, 1))()
+        cov = np.zeros((max(n, 1), 9)) if cov0 is None else np.ascontiguousarray(np.asarray(cov0, np.float64).reshape(n, 9)).copy()
+        self._check(self.lib.tsba_theta_optim_batch(self.ctx, arr, n, C.byref(o), _dp(cov), reps), "tsba_theta_optim_batch")
+        return [reps[i].as_dict() for i in range(n)], cov[:n].reshape(n, 3, 3)
 
     def TextLabelImage(self, kf: int, level: int, shape):
         """Label image (float32 h x w, -1 = background) of keyframe kf for the state left by the last solve

@@ -669,3 +669,32 @@ def window_of(Q, k0, n, kf_ids=None):
     W_.kf_id = None if kf_ids is None else np.asarray(kf_ids, np.int64)[k0:k0 + n].copy()
     W_.truth = {}
     return W_.normalise()
+
+
+def theta_planes(seed=SEED, n=12, max_obs=6, lm_rel=0.15, singular=None):
+    """n single-plane ThetaOptimMultiFs problems in adapter pack_theta's layout (tracking::TextUpdate's immature planes of one frame): the host
+    keyframe first, its observers next, the current frame last, every pose constant and at its true value, theta perturbed by up to lm_rel.
+    The set varies the number of observing frames (1 .. max_obs) and the feature counts per level.  singular: index of a plane whose box is moved
+    off the images (sigma = 0 in every frame: a singular information matrix), or None."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        n_obs = int(rng.integers(1, max_obs + 1))
+        f0 = int(rng.integers(16, 65))
+        feats = (f0, int(rng.integers(6, min(f0, 32) + 1)), int(rng.integers(4, 13)))
+        P = make_problem(n_obs + 1, 0, 1, int(rng.integers(1 << 30)), feats=feats, n_levels=3, frozen_frac=0.0, text_targets=n_obs,
+                         self_obs=False, n_fixed=n_obs + 1, kf_initial=np.ones(n_obs + 1, np.uint8), lm_rel=lm_rel)
+        keep = np.concatenate([[int(P.text_host[0])], np.sort(P.tobs_kf)]).astype(np.int64)    # host, then the observers in keyframe order
+        remap = np.full(P.n_kf, -1, np.int32)
+        remap[keep] = np.arange(keep.size, dtype=np.int32)
+        P.pose = P.pose[keep]
+        P.kf_initial = np.ones(keep.size, np.uint8)
+        for l in range(P.n_levels):
+            P.img[l] = P.img[l][keep]
+        P.text_host = remap[P.text_host]
+        P.tobs_kf = remap[P.tobs_kf]
+        P.truth = {k: (v[keep] if k == "pose" else v) for k, v in P.truth.items()}
+        if singular is not None and i == singular:
+            P.text_box_ray = P.text_box_ray + 50.0
+        out.append(P.normalise())
+    return out
