@@ -5,6 +5,7 @@
  *   tool::GetPyramidPts (text, scene)   /root/reference/src/tool.cc:564-710,862-980 -> tsframe_pyramid_pts
  *   tool::CalNormvec / GetNeighbour     /root/reference/src/tool.cc:1342-1364,1540-1566 (INTERVAL8) -> tsframe_neighbours
  *   tool::GetBoxAllPixs                 /root/reference/src/tool.cc:1264-1337     -> tsframe_box_pixels
+ *   tracking::TextJudgeSingle (xn)      /root/reference/src/tracking.cc:1991-2131 -> tsframe_text_judge
  * The pyramid stays resident in HBM: tsframe_level_ptr hands the device pointers to the BA library, so the four levels of a
  * keyframe need no host round trip between GetPyrMat and the photometric residuals.
  * All functions return 0 on success, a negative TSFRAME_ERR_* otherwise; tsframe_last_error gives the text. */
@@ -55,6 +56,32 @@ int tsframe_neighbours(void *ctx, int level, const double *uv, int n, double mu,
  * arrays, cap == 0 only counts (outputs may be NULL); n_out > cap: TSFRAME_ERR_ARG with *n_out set. */
 int tsframe_box_pixels(void *ctx, int level, const double *quad, double mu, double sigma, int cap, int32_t *n_out,
                        int32_t *u, int32_t *v, double *inten, double *ninten);
+
+/* Reasons of tsframe_text_judge, in the order the reference tests them. */
+#define TSFRAME_JUDGE_PASS 0
+#define TSFRAME_JUDGE_ORIENT 1   /* tool::CheckOrientation: |cos| < cos_min */
+#define TSFRAME_JUDGE_DEPTH 2    /* a projected box corner has depth < 0 */
+#define TSFRAME_JUDGE_BOX 3      /* a projected box corner is within out_margin of the image border (<=, >=) */
+#define TSFRAME_JUDGE_ZNCC 4     /* tool::CheckZNCC failed: zncc < zncc_min, a constant vector, or fewer than 2 reference pixels */
+
+/* tracking::TextJudgeSingle (/root/reference/src/tracking.cc:1991-2131) for n planes on the resident level image of this context
+ * (the current frame), one launch, one workgroup per plane.
+ * theta[n][3] = RefKF->mNcr[GetNidx()]; Tcr[n][12] = row-major 3x4 of F.mTcw * RefKF->mTcw.inverse() (computed by the caller);
+ * box_ray[n][4][2] = vTextDeteRay.  Reference pixels (vRefPixs) in CSR: plane i owns [pix_off[i], pix_off[i+1]), pix_off[0] == 0;
+ * pix_uv[][2] = int16 level-0 pixel (u, v) of the reference keyframe, pix_inten[] = featureInten.  The rays are rebuilt on the device as
+ * ((u - cx) / fx, (v - cy) / fy, 1) with K_ref = {fx, fy, cx, cy} (the level-0 K the reference built them with); K = vK_scale[level] of
+ * this frame.  cos_min: the reference passes 0 (its int parameter truncates the callers' 0.5), so 0 is the drop-in value; out_margin >= 0;
+ * zncc_min <= -2 skips the ZNCC test.  dete_xy[n_dete][2] = vTextDeteCenter (level 0); with dete_bits non-NULL, bit j of plane i's
+ * (n_dete + 31) / 32 words is set when the plane passed and detection j lies in its projected quad (cv::fillPoly on a label image of
+ * the level-0 size, which must be at most 640 x 480; a centre outside that image is not associated).
+ * Out, per plane: pass (1 / 0), reason (TSFRAME_JUDGE_*), cos, zncc (NaN when not computed or fewer than 2 pixels, -100 for a constant
+ * vector, as the reference), box_uv[8] = the four projected corners (always all four).  n == 0 launches nothing.  The resident planes
+ * are read in place and left unchanged. */
+int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const double *Tcr, const double *box_ray,
+                       const int32_t *pix_off, const int16_t *pix_uv, const uint8_t *pix_inten,
+                       const double K_ref[4], const double K[4], double cos_min, int out_margin, double zncc_min,
+                       int n_dete, const double *dete_xy,
+                       uint8_t *pass, int32_t *reason, double *cos, double *zncc, double *box_uv, uint32_t *dete_bits);
 
 #ifdef __cplusplus
 }

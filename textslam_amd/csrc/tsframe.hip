@@ -179,6 +179,149 @@ __global__ __launch_bounds__(1024) void k_box_pixels(const uint8_t *__restrict__
     if (tid == 0) *cnt = base;
 }
 
+// ---- tracking::TextJudgeSingle (tracking.cc:1991-2131) for a batch of planes: one workgroup per plane, no waits between workgroups, so a
+// plane's outputs do not depend on its neighbours or its position in the batch.  Thread 0 takes the orientation and the four corners
+// (tool::CheckOrientation, GetProjText of vTextDeteRay); then three strided sweeps over the plane's reference pixels with fixed-order block
+// sums (means, centred variances, products of the normalised samples: tool::CheckZNCC -> VectorNorm -> CalZNCC without its unused top
+// fractions); then, for a plane that passed, cv::fillPoly of the projected quad into an LDS bit mask (raster_quad) tested at the rounded
+// detection centres.  The current-image samples of the first JUDGE_CACHE pixels stay in LDS between the sweeps, the rest are recomputed
+// (same code, same bits); the cache and the mask share the same LDS.
+#define JUDGE_NT 256
+#ifndef JUDGE_CACHE
+#define JUDGE_CACHE (MS_MASK_WORDS/2)                           /* doubles: the union with the label mask, 38.4 KB (-DJUDGE_CACHE=0: recompute every sweep) */
+#endif
+struct JudgePlane { double theta[3], T[12], ray[8]; };          // in: one plane (184 B)
+struct JudgeOut { double cos, zncc, box[8]; int32_t reason, pad; };   // out: one plane (88 B)
+struct JudgeArgs {
+    int w, h, w0, h0, margin, n_dete, dete_words; double Kr[4], K[4], cos_min, zncc_min;
+};
+
+__device__ __forceinline__ double judge_block_sum(double v, double *lds) {      // fixed order: lane-strided column sums, then a wave butterfly
+    const int t = threadIdx.x;
+    lds[t] = v; __syncthreads();
+    if (t < 64) {
+        double s = lds[t];
+#pragma unroll
+        for (int k = 64; k < JUDGE_NT; k += 64) s += lds[t + k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (t == 0) lds[0] = s;
+    }
+    __syncthreads();
+    const double r = lds[0]; __syncthreads();
+    return r;
+}
+
+// tool::GetProjText (Mat31 overload, tool.cc:1593) of the reference pixel (u, v) and tool::GetIntenBilinterPtr on the current level image: the
+// depth's sign is ignored, a sample outside the image (or at a NaN position, which the reference's int conversion sends below 0) gives 0.
+__device__ __forceinline__ double judge_sample(const uint8_t *__restrict__ img, const JudgeArgs &A, const double *th, const double *T, int u, int v) {
+    const double r0 = ((double)u - A.Kr[2])/A.Kr[0], r1 = ((double)v - A.Kr[3])/A.Kr[1], r2 = 1.0;
+    const double invz = -(r0*th[0] + r1*th[1] + r2*th[2]);
+    const double X = (T[0]*r0 + T[1]*r1 + T[2]*r2)/invz + T[3];
+    const double Y = (T[4]*r0 + T[5]*r1 + T[6]*r2)/invz + T[7];
+    const double Z = (T[8]*r0 + T[9]*r1 + T[10]*r2)/invz + T[11];
+    const double pu = A.K[0]*X/Z + A.K[2], pv = A.K[1]*Y/Z + A.K[3];
+    double I = 0.0;
+    if (pu == pu && pv == pv) bilinear(img, A.w, A.h, pu, pv, I);
+    return I;
+}
+
+__global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restrict__ img, JudgeArgs A, const JudgePlane *__restrict__ planes,
+                                                         const int *__restrict__ pix_off, const short *__restrict__ pix_uv,
+                                                         const uint8_t *__restrict__ pix_inten, const double *__restrict__ dete_xy,
+                                                         JudgeOut *__restrict__ out, unsigned *__restrict__ dete_bits) {
+    __shared__ union { double cache[JUDGE_CACHE > 0 ? JUDGE_CACHE : 1]; unsigned mask[MS_MASK_WORDS]; } s_u;
+    __shared__ double s_red[JUDGE_NT], s_th[3], s_T[12];
+    __shared__ int s_reason, s_xy[8];
+    const int tid = threadIdx.x, p = blockIdx.x;
+    const JudgePlane &P = planes[p];
+    if (tid < 3) s_th[tid] = P.theta[tid];
+    if (tid < 12) s_T[tid] = P.T[tid];
+    if (tid == 0) {
+        const double *th = P.theta, *T = P.T;
+        // 1. tool::CheckOrientation (tool.cc:1393-1407): c = third column of R_cr^T, norms as sqrt of the squared norms
+        const double c0 = T[8], c1 = T[9], c2 = T[10];
+        const double nv = sqrt(th[0]*th[0] + th[1]*th[1] + th[2]*th[2])*sqrt(c0*c0 + c1*c1 + c2*c2);
+        const double cs = (th[0]*c0 + th[1]*c1 + th[2]*c2)/nv;
+        int reason = fabs(cs) < A.cos_min ? TSFRAME_JUDGE_ORIENT : TSFRAME_JUDGE_PASS;
+        // 2. the four corners (GetProjText, Vec2 overload, tool.cc:1608-1623): the first corner behind the camera or at the border decides
+        for (int b = 0; b < 4; b++) {
+            const double r0 = P.ray[2*b], r1 = P.ray[2*b + 1], r2 = 1.0;
+            const double invz = -(r0*th[0] + r1*th[1] + r2*th[2]);
+            const double X = (T[0]*r0 + T[1]*r1 + T[2]*r2)/invz + T[3];
+            const double Y = (T[4]*r0 + T[5]*r1 + T[6]*r2)/invz + T[7];
+            const double Z = (T[8]*r0 + T[9]*r1 + T[10]*r2)/invz + T[11];
+            const double u = A.K[0]*X/Z + A.K[2], v = A.K[1]*Y/Z + A.K[3];
+            out[p].box[2*b] = u; out[p].box[2*b + 1] = v;
+            s_xy[2*b] = (u > -1e9 && u < 1e9) ? (int)u : 0; s_xy[2*b + 1] = (v > -1e9 && v < 1e9) ? (int)v : 0;   // cv::Point truncation (used only if passed)
+            if (reason == TSFRAME_JUDGE_PASS) {
+                if (Z < 0) reason = TSFRAME_JUDGE_DEPTH;
+                else if (u <= (double)A.margin || u >= (double)(A.w - A.margin) || v <= (double)A.margin || v >= (double)(A.h - A.margin)) reason = TSFRAME_JUDGE_BOX;
+            }
+        }
+        out[p].cos = cs;
+        s_reason = reason;
+    }
+    __syncthreads();
+    int reason = s_reason;                                      // (every thread: the branches below are uniform in the workgroup)
+    double zncc = __builtin_nan("");
+    // 3. tool::CheckZNCC: ref = featureInten, cur = the bilinear samples; mean, sample std (n - 1), mean of the normalised products
+    if (reason == TSFRAME_JUDGE_PASS && A.zncc_min > -2.0) {
+        const int i0 = pix_off[p], n = pix_off[p + 1] - i0;
+        if (n >= 2) {
+            double sr = 0.0, sc = 0.0;
+            for (int i = tid; i < n; i += JUDGE_NT) {
+                const double c = judge_sample(img, A, s_th, s_T, pix_uv[2*(i0 + i)], pix_uv[2*(i0 + i) + 1]);
+                if (i < JUDGE_CACHE) s_u.cache[i] = c;
+                sr += (double)pix_inten[i0 + i]; sc += c;
+            }
+            const double mr = judge_block_sum(sr, s_red)/(double)n, mc = judge_block_sum(sc, s_red)/(double)n;
+            double vr = 0.0, vc = 0.0;
+            for (int i = tid; i < n; i += JUDGE_NT) {
+                const double c = i < JUDGE_CACHE ? s_u.cache[i] : judge_sample(img, A, s_th, s_T, pix_uv[2*(i0 + i)], pix_uv[2*(i0 + i) + 1]);
+                const double r = (double)pix_inten[i0 + i];
+                vr += (r - mr)*(r - mr); vc += (c - mc)*(c - mc);
+            }
+            const double sdr = sqrt(judge_block_sum(vr, s_red)/(double)(n - 1)), sdc = sqrt(judge_block_sum(vc, s_red)/(double)(n - 1));
+            if (sdr != 0.0 && sdc != 0.0) {
+                double sp = 0.0;
+                for (int i = tid; i < n; i += JUDGE_NT) {
+                    const double c = i < JUDGE_CACHE ? s_u.cache[i] : judge_sample(img, A, s_th, s_T, pix_uv[2*(i0 + i)], pix_uv[2*(i0 + i) + 1]);
+                    const double r = (double)pix_inten[i0 + i];
+                    sp += ((r - mr)/sdr)*((c - mc)/sdc);
+                }
+                zncc = judge_block_sum(sp, s_red)/(double)n;
+            } else {
+                zncc = -100.0;
+            }
+        }
+        if (!(zncc >= A.zncc_min)) reason = TSFRAME_JUDGE_ZNCC;   // (n < 2: NaN)
+        __syncthreads();                                        // (the cache is done before the mask reuses it)
+    }
+    if (tid == 0) { out[p].zncc = zncc; out[p].reason = reason; out[p].pad = 0; }
+    // 4. detection association (tracking.cc:2116-2128): label image = the quad filled by cv::fillPoly; centre (round(u), round(v)), half away from zero
+    if (dete_bits && A.dete_words > 0) {
+        unsigned *bits = dete_bits + (size_t)p*A.dete_words;
+        if (reason == TSFRAME_JUDGE_PASS) {
+            for (int k = tid; k < (A.w0*A.h0 + 31) >> 5; k += JUDGE_NT) s_u.mask[k] = 0;
+            __syncthreads();
+            raster_quad(s_u.mask, s_xy, A.w0, A.h0, tid, JUDGE_NT);
+            __syncthreads();
+        }
+        for (int k = tid; k < A.dete_words; k += JUDGE_NT) {
+            unsigned word = 0;
+            if (reason == TSFRAME_JUDGE_PASS)
+                for (int j = 32*k; j < min(32*k + 32, A.n_dete); j++) {
+                    const double ru = round(dete_xy[2*j]), rv = round(dete_xy[2*j + 1]);
+                    if (!(ru >= 0.0 && ru <= (double)(A.w0 - 1) && rv >= 0.0 && rv <= (double)(A.h0 - 1))) continue;
+                    const int bit = (int)rv*A.w0 + (int)ru;
+                    if ((s_u.mask[bit >> 5] >> (bit & 31)) & 1u) word |= 1u << (j & 31);
+                }
+            bits[k] = word;
+        }
+    }
+}
+
 static int ensure_host(FCtx *c, size_t bytes) {
     if (bytes <= c->h_cap) return 0;
     if (c->h_stage) hipHostFree(c->h_stage);
@@ -387,6 +530,66 @@ int tsframe_box_pixels(void *ctx, int level, const double *quad, double mu, doub
     CKF(hipStreamSynchronize(c->stream));
     memcpy(u, c->h_stage + o_u, 4*(size_t)n); memcpy(v, c->h_stage + o_v, 4*(size_t)n);
     memcpy(inten, c->h_stage + o_I, 8*(size_t)n); memcpy(ninten, c->h_stage + o_N, 8*(size_t)n);
+    return TSFRAME_OK;
+}
+
+int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const double *Tcr, const double *box_ray,
+                       const int32_t *pix_off, const int16_t *pix_uv, const uint8_t *pix_inten,
+                       const double K_ref[4], const double K[4], double cos_min, int out_margin, double zncc_min,
+                       int n_dete, const double *dete_xy,
+                       uint8_t *pass, int32_t *reason, double *cos, double *zncc, double *box_uv, uint32_t *dete_bits) {
+    FCtx *c = (FCtx *)ctx;
+    if (!c) return TSFRAME_ERR_ARG;
+    auto bad = [&](const char *what) { c->err = std::string("tsframe_text_judge: ") + what; return TSFRAME_ERR_ARG; };
+    if (n < 0) return bad("n < 0");
+    if (level < 0) return bad("level < 0");
+    if (n_dete < 0 || (n_dete > 0 && !dete_xy)) return bad("n_dete < 0, or dete_xy NULL with n_dete > 0");
+    if (out_margin < 0) return bad("out_margin < 0");
+    if (n == 0) return TSFRAME_OK;
+    if (!theta || !Tcr || !box_ray || !pix_off || !K_ref || !K || !pass || !reason || !cos || !zncc || !box_uv) return bad("NULL array");
+    for (int k = 0; k < 4; k++)
+        if (!std::isfinite(K_ref[k]) || !std::isfinite(K[k]) || (k < 2 && (K_ref[k] == 0.0 || K[k] == 0.0))) return bad("K_ref / K not finite or zero focal length");
+    if (pix_off[0] != 0) return bad("pix_off[0] != 0");
+    for (int i = 0; i < n; i++) if (pix_off[i + 1] < pix_off[i]) return bad("pix_off decreasing");
+    const size_t npix = (size_t)pix_off[n];
+    if (npix > 0 && (!pix_uv || !pix_inten)) return bad("pix_uv / pix_inten NULL with pixels");
+    if (c->n_levels == 0) { c->err = "tsframe_text_judge: no image set"; return TSFRAME_ERR_STATE; }
+    if (level >= c->n_levels) { c->err = "tsframe_text_judge: level not built"; return TSFRAME_ERR_STATE; }
+    const int words = dete_bits ? (n_dete + 31)/32 : 0;
+    if (words > 0 && (size_t)c->w[0]*c->h[0] > (size_t)MS_MASK_WORDS*32) return bad("detection association needs a level-0 image of at most 640 x 480 pixels");
+    hipSetDevice(c->device);
+    JudgeArgs A;
+    A.w = c->w[level]; A.h = c->h[level]; A.w0 = c->w[0]; A.h0 = c->h[0]; A.margin = out_margin; A.n_dete = n_dete; A.dete_words = words;
+    for (int k = 0; k < 4; k++) { A.Kr[k] = K_ref[k]; A.K[k] = K[k]; }
+    A.cos_min = cos_min; A.zncc_min = zncc_min;
+    // one pinned block, inputs then outputs: planes | dete_xy | pix_off | pix_uv | pix_inten || out | bits
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nd = words > 0 ? (size_t)n_dete : 0;
+    const size_t o_pl = 0, o_dx = o_pl + al(sizeof(JudgePlane)*(size_t)n), o_off = o_dx + al(16*nd), o_uv = o_off + al(4*((size_t)n + 1)),
+                 o_in = o_uv + al(4*npix), o_out = o_in + al(npix), o_bits = o_out + al(sizeof(JudgeOut)*(size_t)n), tot = o_bits + al(4*(size_t)n*words);
+    int rc = ensure_work(c, tot); if (rc) return rc;
+    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    uint8_t *h = c->h_stage, *d = c->d_work;
+    JudgePlane *hp = (JudgePlane *)(h + o_pl);
+    for (int i = 0; i < n; i++) {
+        memcpy(hp[i].theta, theta + 3*(size_t)i, 24); memcpy(hp[i].T, Tcr + 12*(size_t)i, 96); memcpy(hp[i].ray, box_ray + 8*(size_t)i, 64);
+    }
+    if (nd) memcpy(h + o_dx, dete_xy, 16*nd);
+    memcpy(h + o_off, pix_off, 4*((size_t)n + 1));
+    if (npix) { memcpy(h + o_uv, pix_uv, 4*npix); memcpy(h + o_in, pix_inten, npix); }
+    CKF(hipMemcpyAsync(d, h, o_out, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_text_judge, dim3(n), dim3(JUDGE_NT), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], A, (const JudgePlane *)(d + o_pl),
+                       (const int *)(d + o_off), (const short *)(d + o_uv), (const uint8_t *)(d + o_in), (const double *)(d + o_dx),
+                       (JudgeOut *)(d + o_out), words > 0 ? (unsigned *)(d + o_bits) : nullptr);
+    CKF(hipGetLastError());
+    CKF(hipMemcpyAsync(h + o_out, d + o_out, tot - o_out, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipStreamSynchronize(c->stream));
+    const JudgeOut *ho = (const JudgeOut *)(h + o_out);
+    for (int i = 0; i < n; i++) {
+        reason[i] = ho[i].reason; pass[i] = ho[i].reason == TSFRAME_JUDGE_PASS ? 1 : 0; cos[i] = ho[i].cos; zncc[i] = ho[i].zncc;
+        memcpy(box_uv + 8*(size_t)i, ho[i].box, 64);
+    }
+    if (words > 0) memcpy(dete_bits, h + o_bits, 4*(size_t)n*words);
     return TSFRAME_OK;
 }
 

@@ -4,6 +4,7 @@
   Frame.GetPyramidPts(...) / GetPyramidPtsScene(...)  tool::GetPyramidPts       /root/reference/src/tool.cc:564-710, 862-980
   Frame.CalNormvec(level, uv, mu, std)                tool::CalNormvec          /root/reference/src/tool.cc:1342-1364 (GetNeighbour INTERVAL8)
   Frame.GetBoxAllPixs(level, vTextDete, mu, std, K)   tool::GetBoxAllPixs       /root/reference/src/tool.cc:1264-1337
+  Frame.TextJudgeBatch(...)                           tracking::TextJudgeSingle /root/reference/src/tracking.cc:1991-2131 (n planes, one launch)
 
 No CPU fallback: without the HIP library / a GPU every call raises.
 """
@@ -14,8 +15,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libtsframe.so")
 EXPORTED_SYMBOLS = ["tsframe_create", "tsframe_destroy", "tsframe_last_error", "tsframe_set_image", "tsframe_level_size", "tsframe_level_ptr",
-                    "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_neighbours", "tsframe_box_pixels"]
+                    "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_neighbours", "tsframe_box_pixels", "tsframe_text_judge"]
 IMG, GRAD, GRADX, GRADY = 0, 1, 2, 3
+JUDGE_PASS, JUDGE_ORIENT, JUDGE_DEPTH, JUDGE_BOX, JUDGE_ZNCC = 0, 1, 2, 3, 4
 
 
 class FrameError(RuntimeError):
@@ -37,6 +39,9 @@ def _load():
     L.tsframe_pyramid_pts.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, dp, dp, ip, dp, dp, ip, dp, up]
     L.tsframe_neighbours.argtypes = [vp, C.c_int, dp, C.c_int, C.c_double, C.c_double, dp, dp, up]
     L.tsframe_box_pixels.argtypes = [vp, C.c_int, dp, C.c_double, C.c_double, C.c_int, ip, ip, ip, dp, dp]
+    L.tsframe_text_judge.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, ip, C.POINTER(C.c_int16), up, dp, dp, C.c_double, C.c_int, C.c_double,
+                                     C.c_int, dp, up, ip, dp, dp, dp, C.POINTER(C.c_uint32)]
+    L.tsframe_text_judge.restype = C.c_int
     return L
 
 
@@ -123,4 +128,37 @@ class Frame:
         if K is not None:
             fx, fy, cx, cy = K
             out["ray"] = np.stack([(out["u"] - cx)/fx, (out["v"] - cy)/fy, np.ones(m)], 1)
+        return out
+
+    def TextJudgeBatch(self, level, theta, Tcr, box_ray, pix_off, pix_uv, pix_inten, K_ref, K, cos_min=0.0, out_margin=6, zncc_min=0.1,
+                       dete_xy=None):
+        """tracking::TextJudgeSingle for n planes on this frame's level image in one launch (include/tsframe.h: tsframe_text_judge).
+        theta [n, 3]; Tcr [n, 3, 4] (or [n, 4, 4]: the top three rows); box_ray [n, 4, 2]; the reference pixels in CSR: pix_off [n + 1],
+        pix_uv [m, 2] (level-0 u, v), pix_inten [m]; K_ref, K = (fx, fy, cx, cy).  dete_xy [n_dete, 2] or None (the 4-argument overload).
+        Returns a dict of pass (bool), reason (JUDGE_*), cos, zncc, box_uv [n, 4, 2] and, with dete_xy, dete [n, n_dete] (bool) and the raw
+        dete_bits [n, (n_dete + 31) // 32]."""
+        theta = np.ascontiguousarray(theta, np.float64).reshape(-1, 3); n = len(theta)
+        T = np.asarray(Tcr, np.float64).reshape(n, -1, 4)[:, :3, :]
+        T = np.ascontiguousarray(T).reshape(n, 12)
+        ray = np.ascontiguousarray(box_ray, np.float64).reshape(n, 8)
+        off = np.ascontiguousarray(pix_off, np.int32).reshape(-1); assert len(off) == n + 1
+        uv = np.ascontiguousarray(pix_uv, np.int16).reshape(-1, 2); I = np.ascontiguousarray(pix_inten, np.uint8).reshape(-1)
+        Kr = np.ascontiguousarray(K_ref, np.float64).reshape(4); Kc = np.ascontiguousarray(K, np.float64).reshape(4)
+        nd = 0 if dete_xy is None else len(dete_xy)
+        dxy = None if dete_xy is None else np.ascontiguousarray(dete_xy, np.float64).reshape(nd, 2)
+        words = (nd + 31)//32
+        m = max(n, 1)
+        ok = np.zeros(m, np.uint8); reason = np.zeros(m, np.int32); cs = np.zeros(m); zn = np.zeros(m); box = np.zeros((m, 8))
+        bits = np.zeros((m, max(words, 1)), np.uint32)
+        self._check(self.lib.tsframe_text_judge(self.ctx, level, n, _dp(theta), _dp(T), _dp(ray), off.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                uv.ctypes.data_as(C.POINTER(C.c_int16)), _up(I), _dp(Kr), _dp(Kc), float(cos_min), int(out_margin),
+                                                float(zncc_min), nd, _dp(dxy) if dxy is not None else None, _up(ok),
+                                                reason.ctypes.data_as(C.POINTER(C.c_int32)), _dp(cs), _dp(zn), _dp(box),
+                                                bits.ctypes.data_as(C.POINTER(C.c_uint32)) if dxy is not None else None), "tsframe_text_judge")
+        out = {"pass": ok[:n].astype(bool), "reason": reason[:n], "cos": cs[:n], "zncc": zn[:n], "box_uv": box[:n].reshape(n, 4, 2)}
+        if dxy is not None:
+            b = bits[:n, :words]
+            out["dete_bits"] = b
+            j = np.arange(nd)
+            out["dete"] = ((b[:, j // 32] >> (j % 32).astype(np.uint32)) & 1).astype(bool) if nd else np.zeros((n, 0), bool)
         return out

@@ -698,3 +698,90 @@ def theta_planes(seed=SEED, n=12, max_obs=6, lm_rel=0.15, singular=None):
             P.text_box_ray = P.text_box_ray + 50.0
         out.append(P.normalise())
     return out
+
+
+def _judge_corners(theta, T, box_ray, K):
+    """tool::GetProjText (Vec2 overload) of the four box rays, in the operation order of the device (tsframe_text_judge): (u [4], v [4], z [4])."""
+    fx, fy, cx, cy = K
+    r0, r1, r2 = box_ray[:, 0], box_ray[:, 1], 1.0
+    invz = -(r0*theta[0] + r1*theta[1] + r2*theta[2])
+    X = (T[0, 0]*r0 + T[0, 1]*r1 + T[0, 2]*r2)/invz + T[0, 3]
+    Y = (T[1, 0]*r0 + T[1, 1]*r1 + T[1, 2]*r2)/invz + T[1, 3]
+    Z = (T[2, 0]*r0 + T[2, 1]*r1 + T[2, 2]*r2)/invz + T[2, 3]
+    return fx*X/Z + cx, fy*Y/Z + cy, Z
+
+
+def text_judge_planes(seed=SEED, n=8, tiny=True, huge=True):
+    """Inputs of tracking::TextJudgeSingle for one current frame (tsframe_text_judge): make_problem renders n true text planes into a reference
+    keyframe and the next frame, and the set adds the planes the judge must tell apart.  Returns a dict: ref_img, cur_img (uint8, level 0),
+    K (fx, fy, cx, cy), and per plane theta [m, 3], Tcr [m, 3, 4], box_ray [m, 4, 2], quad [m, 4, 2] (the level-0 reference-image quad whose
+    pixels -- tool::GetBoxAllPixs -- are the plane's vRefPixs) and kind [m]; dete_xy [k, 2] = detection centres of the current frame.
+    Kinds: 'true' (the rendered plane at its true pose: a high ZNCC), 'perturbed' (theta scaled by 1.35: a low one), 'oblique' (the normal
+    turned by 66 degrees: |cos| < 0.5), 'behind' (the current camera moved 30 m forward: depth < 0), 'margin' (plane z = 1 seen from the
+    reference pose; corner 0 projects to u == 6.0 exactly), 'constant' (true plane 1 over a patch of the current image painted 0: std 0),
+    'tiny0' .. 'tiny5' (a true plane with 0 .. 5 reference pixels), 'huge' (a true plane whose pixel quad is a 200 x 100 region)."""
+    rng = np.random.default_rng(seed)
+    P = make_problem(2, 0, n, int(rng.integers(1 << 30)), n_levels=1, frozen_frac=0.0, text_targets=1, self_obs=False, n_fixed=2,
+                     kf_initial=np.ones(2, np.uint8), perturb=False)
+    K = P.K.copy(); fx, fy, cx, cy = K
+    ref, cur = P.img[0][0].copy(), P.img[0][1].copy()
+    Rw = [_q_to_R(P.truth["pose"][k, :4]) for k in range(2)]
+    tw = [P.truth["pose"][k, 4:] for k in range(2)]
+    R = Rw[1] @ Rw[0].T
+    Ttrue = np.concatenate([R, (tw[1] - R @ tw[0])[:, None]], 1)
+    th_true = P.truth["theta"]
+
+    def quad_of(ray):
+        return np.stack([fx*ray[:, 0] + cx, fy*ray[:, 1] + cy], 1)
+
+    planes = []                                               # (kind, theta, T, box_ray, quad)
+    for j in range(n):
+        planes.append(("true", th_true[j].copy(), Ttrue.copy(), P.text_box_ray[j].copy(), quad_of(P.text_box_ray[j])))
+    j = 0
+    planes.append(("perturbed", th_true[j]*1.35, Ttrue.copy(), P.text_box_ray[j].copy(), quad_of(P.text_box_ray[j])))
+    nrm = -th_true[j]/np.linalg.norm(th_true[j])
+    X0 = np.array([*P.text_box_ray[j].mean(0), 1.0])/float(-(np.array([*P.text_box_ray[j].mean(0), 1.0]) @ th_true[j]))
+    n_obl = _rodrigues(np.deg2rad(66.0)*np.array([1.0, 0.0, 0.0])) @ nrm
+    planes.append(("oblique", n_obl/float(-(n_obl @ X0)), Ttrue.copy(), P.text_box_ray[j].copy(), quad_of(P.text_box_ray[j])))
+    Tb = Ttrue.copy(); Tb[2, 3] -= 30.0
+    planes.append(("behind", th_true[j].copy(), Tb, P.text_box_ray[j].copy(), quad_of(P.text_box_ray[j])))
+    # margin: identity pose, plane z = 1: u = fl(fx * rx) + cx exactly; step rx by ulps until corner 0 lands on 6.0
+    Tm = np.concatenate([np.eye(3), np.zeros((3, 1))], 1); thm = np.array([0.0, 0.0, -1.0])
+    ray_m = np.array([[(6.0 - cx)/fx, (100.0 - cy)/fy], [(200.0 - cx)/fx, (100.0 - cy)/fy], [(200.0 - cx)/fx, (200.0 - cy)/fy], [(6.0 - cx)/fx, (200.0 - cy)/fy]])
+    for _ in range(4096):
+        u0 = _judge_corners(thm, Tm, ray_m, K)[0][0]
+        if u0 == 6.0:
+            break
+        ray_m[0, 0] = np.nextafter(ray_m[0, 0], np.inf if u0 < 6.0 else -np.inf)
+    else:
+        raise RuntimeError("no box ray projects to u == 6.0")
+    planes.append(("margin", thm, Tm, ray_m, quad_of(ray_m)))
+    # constant: true plane jc over a patch of the current image painted 0 (every bilinear sample exactly 0: std 0)
+    jc = min(1, n - 1)
+    u, v, _ = _judge_corners(th_true[jc], Ttrue, P.text_box_ray[jc], K)
+    x0, x1 = int(max(0, np.floor(u.min()) - 3)), int(min(W - 1, np.ceil(u.max()) + 3))
+    y0, y1 = int(max(0, np.floor(v.min()) - 3)), int(min(H - 1, np.ceil(v.max()) + 3))
+    cur[y0:y1 + 1, x0:x1 + 1] = 0
+    planes[jc] = ("constant",) + planes[jc][1:]
+    if tiny:
+        qc = quad_of(P.text_box_ray[j]).mean(0).astype(int).astype(np.float64) + 0.25
+        shapes = {0: [(-60, -60), (-50, -60), (-50, -50), (-60, -50)], 1: [(0, 0)]*4, 2: [(0, 0), (1, 0), (1, 0), (0, 0)],
+                  3: [(0, 0), (2, 0), (2, 0), (0, 0)], 4: [(0, 0), (1, 0), (1, 1), (0, 1)], 5: [(0, 0), (4, 0), (4, 0), (0, 0)]}
+        for k, sh in shapes.items():
+            q = np.array(sh, np.float64) + (qc if k > 0 else 0.0)
+            planes.append(("tiny%d" % k, th_true[j].copy(), Ttrue.copy(), P.text_box_ray[j].copy(), q))
+    if huge:
+        qc = quad_of(P.text_box_ray[j]).mean(0)
+        q = np.clip(qc + np.array([[-100.0, -50.0], [100.0, -50.0], [100.0, 50.0], [-100.0, 50.0]]), [1.0, 1.0], [W - 2.0, H - 2.0])
+        planes.append(("huge", th_true[j].copy(), Ttrue.copy(), P.text_box_ray[j].copy(), q))
+    # detection centres: inside each true plane, on a truncated corner (the quad's boundary), at .5 (half away from zero), outside the image
+    dete = []
+    for k in range(n):
+        u, v, _ = _judge_corners(th_true[k], Ttrue, P.text_box_ray[k], K)
+        dete.append((u.mean(), v.mean()))
+        dete.append((float(int(u[0])), float(int(v[0]))))
+        dete.append((np.floor(u.mean()) + 0.5, np.floor(v.mean()) + 0.5))
+    dete += [(-0.5, 10.0), (-3.0, 10.0), (W - 0.5, 10.0), (10.0, H - 0.4), (1e12, 5.0), (np.nan, 5.0), (0.49, 0.49)]
+    return {"ref_img": ref, "cur_img": cur, "K": K, "kind": [p[0] for p in planes], "theta": np.stack([p[1] for p in planes]),
+            "Tcr": np.stack([p[2] for p in planes]), "box_ray": np.stack([p[3] for p in planes]), "quad": np.stack([p[4] for p in planes]),
+            "dete_xy": np.array(dete, np.float64)}
