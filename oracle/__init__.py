@@ -64,22 +64,59 @@ def count_blocks(prob: BAProblem, opt: TsbaOptions, level: int):
     return ns.value, nt.value
 
 
-def evaluate(prob: BAProblem, opt: TsbaOptions, level: int, jac=True):
-    """-> dict(resid, jac_scene [ns,2,13], jac_text [nt,8,15], musigma [n_tobs,2], ns, nt)"""
+TAP_CELL, TAP_INOUT, TAP_OUT = 1, 2, 4       # tsba_oracle_eval_taps' tap codes (tsba_oracle.h)
+
+
+def evaluate(prob: BAProblem, opt: TsbaOptions, level: int, jac=True, straddle=False):
+    """-> dict(resid, jac_scene [ns,2,13], jac_text [nt,8,15], musigma [n_tobs,2], ns, nt)
+    straddle (numeric mode only, opt.text_jacobian == 1): also "straddle" [nt,8] bool -- the taps whose central-difference stencil
+    moved them to another pixel cell or across the image's in/out rule -- and "tap_out" [nt,8] bool -- the taps outside the image."""
+    if straddle and not (jac and opt.text_jacobian == 1):
+        raise ValueError("straddle=True needs jac=True and the numeric text Jacobian (text_jacobian = 1)")
     ns, nt = count_blocks(prob, opt, level)
     resid = np.zeros(2 * ns + 8 * nt)
     J = np.zeros(26 * ns + 120 * nt) if jac else None
     ms = np.zeros((max(prob.n_tobs, 1), 2))
+    code = np.zeros(max(8 * nt, 1), np.uint8)
     s = prob.struct()
     a, b = C.c_int64(0), C.c_int64(0)
-    rc = lib().tsba_oracle_eval(C.byref(s), C.byref(opt), level, _dp(resid), _dp(J) if jac else None, _dp(ms),
-                                C.byref(a), C.byref(b))
+    L = lib()
+    L.tsba_oracle_eval_taps.argtypes = [C.POINTER(TsbaProblem), C.POINTER(TsbaOptions), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)]
+    L.tsba_oracle_eval_taps.restype = C.c_int
+    rc = L.tsba_oracle_eval_taps(C.byref(s), C.byref(opt), level, _dp(resid), _dp(J) if jac else None, _dp(ms),
+                                 C.byref(a), C.byref(b), code.ctypes.data_as(C.POINTER(C.c_uint8)) if straddle else None)
     assert rc == 0, rc
     out = {"resid": resid, "ns": ns, "nt": nt, "musigma": ms[:prob.n_tobs]}
     if jac:
         out["jac_scene"] = J[:26 * ns].reshape(ns, 2, 13)
         out["jac_text"] = J[26 * ns:].reshape(nt, 8, 15)
+    if straddle:
+        code = code[:8 * nt].reshape(nt, 8)
+        out["straddle"] = (code & (TAP_CELL | TAP_INOUT)) != 0
+        out["straddle_inout"] = (code & TAP_INOUT) != 0
+        out["tap_out"] = (code & TAP_OUT) != 0
     return out
+
+
+def outlier_stats(prob: BAProblem, opt: TsbaOptions, ps: int, end=None):
+    """The outlier pass of pass `ps` (tsba_oracle_outlier_stats): the blocks, flags and mu / sigma of `prob` as the pass starts, residuals at
+    the parameters of `end` (a BAProblem where the pass's LM loop ended; default prob itself).  -> dict(s_stat [n_sgood], tf_stat [n_tfgood],
+    tobs_ratio [n_tobs], NaN where the pass judges nothing; chi2_mono (as applied), chi2_text, text_bad_ratio).  A flag drops where its
+    statistic exceeds its threshold."""
+    end = end or prob
+    L = lib()
+    L.tsba_oracle_outlier_stats.argtypes = [C.POINTER(TsbaProblem), C.POINTER(TsbaOptions), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.tsba_oracle_outlier_stats.restype = C.c_int
+    ss, tf, tr, thr = np.full(max(prob.sgood.size, 1), np.nan), np.full(max(prob.tfgood.size, 1), np.nan), np.full(max(prob.n_tobs, 1), np.nan), np.zeros(2)
+    pose, rho, theta = (np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1)) for v in (end.pose, end.rho, end.theta))
+    s = prob.struct()
+    rc = L.tsba_oracle_outlier_stats(C.byref(s), C.byref(opt), ps, _dp(pose), _dp(np.concatenate([rho, [0.0]])), _dp(np.concatenate([theta, [0.0]])),
+                                     _dp(ss), _dp(tf), _dp(tr), _dp(thr))
+    assert rc == 0, rc
+    return {"s_stat": ss[:prob.sgood.size], "tf_stat": tf[:prob.tfgood.size], "tobs_ratio": tr[:prob.n_tobs],
+            "chi2_mono": float(thr[0]), "chi2_text": float(thr[1]), "text_bad_ratio": float(opt.text_bad_ratio)}
 
 
 def solve(prob: BAProblem, opt: TsbaOptions, library=None):
@@ -296,6 +333,51 @@ def solve_traced(prob: BAProblem, opt: TsbaOptions, cap=64):
     finally:
         L.tsba_oracle_set_trace(None, 0)
     return rep, [buf[k, :min(rep["iters"][k], cap)].copy() for k in range(rep["n_passes"])]
+
+
+def pass_options(opt: TsbaOptions, ps: int):
+    """A copy of opt that runs only its pass `ps`: n_passes = 1, that pass's levels / its / chi2_mono / chi2_text moved to index 0."""
+    o = type(opt).from_buffer_copy(opt)
+    o.n_passes = 1
+    o.levels[0], o.its[0], o.chi2_mono[0], o.chi2_text[0] = opt.levels[ps], opt.its[ps], opt.chi2_mono[ps], opt.chi2_text[ps]
+    return o
+
+
+def solve_by_pass(prob: BAProblem, opt: TsbaOptions, cap=64):
+    """solve_traced, one pass per call (pass_options): the same arithmetic, each pass starts from the problem as the last one left it.
+    In place like solve().  -> (report dict over all passes, traces as solve_traced's, starts: a copy of the problem as each pass starts)."""
+    rep, traces, starts = None, [], []
+    for ps in range(opt.n_passes):
+        starts.append(prob.copy())
+        r, tr = solve_traced(prob, pass_options(opt, ps), cap)
+        traces += tr
+        if rep is None:
+            rep = dict(r)
+        else:
+            for k, v in r.items():
+                if isinstance(v, list):
+                    rep[k] = rep[k] + v
+    rep["n_passes"] = opt.n_passes
+    return rep, traces, starts
+
+
+def straddle_gap(jac_text, ev_numeric):
+    """An analytic text Jacobian [nt,8,15] against evaluate(..., straddle=True) in numeric mode: per tap, the largest entry difference relative
+    to the largest analytic entry.  -> dict(unmasked: the largest over the taps outside the straddle mask, masked: over the mask, n_straddle,
+    n_taps, rel [nt,8])."""
+    J = np.asarray(jac_text)
+    assert J.shape == ev_numeric["jac_text"].shape, (J.shape, ev_numeric["jac_text"].shape)
+    rel = np.abs(J - ev_numeric["jac_text"]).max(axis=2) / max(np.abs(J).max(), 1e-300)
+    m = ev_numeric["straddle"]
+    return {"unmasked": float(rel[~m].max()) if (~m).any() else 0.0, "masked": float(rel[m].max()) if m.any() else 0.0,
+            "n_straddle": int(m.sum()), "n_taps": int(m.size), "rel": rel}
+
+
+def set_trace(buf=None, cap=0):
+    """Record every LM trial of the following solves into buf [4 passes][cap][4] (solve_traced's layout); set_trace() stops."""
+    L = lib()
+    L.tsba_oracle_set_trace.argtypes = [C.POINTER(C.c_double), C.c_int]; L.tsba_oracle_set_trace.restype = None
+    L.tsba_oracle_set_trace(_dp(buf) if buf is not None else None, cap)
 
 
 def partial_system(prob: BAProblem, opt: TsbaOptions, level: int, radius: float):

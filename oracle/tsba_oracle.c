@@ -129,7 +129,7 @@ static double bilinear(const uint8_t *img, int w, int h, double u, double v, dou
 /* shared tail of nume_BAText / nume_PoseOptimText: 8 taps through T_cr (R,t), plane theta */
 static void f_text_taps(const double Rcr[9], const double tcr[3], const double theta[3], const double fu, const double fv,
                         const double Kl[4], const uint8_t *img, int w, int h, const double ref[8],
-                        double mu, double sigma, double wT, double r[8]) {
+                        double mu, double sigma, double wT, double r[8], double *uv) {
     for (int k = 0; k < 8; k++) {
         double ray[3] = { (fu + TAP_DX[k] - Kl[2])/Kl[0], (fv + TAP_DY[k] - Kl[3])/Kl[1], 1.0 };  /* tool.cc:1561 */
         double rho = -(ray[0]*theta[0] + ray[1]*theta[1] + ray[2]*theta[2]);                    /* ModelTool.hpp:167 */
@@ -137,6 +137,7 @@ static void f_text_taps(const double Rcr[9], const double tcr[3], const double t
         double P[3] = { Rr[0]/rho + tcr[0], Rr[1]/rho + tcr[1], Rr[2]/rho + tcr[2] };
         double u = Kl[0]*P[0]/P[2] + Kl[2];
         double v = Kl[1]*P[1]/P[2] + Kl[3];
+        if (uv) { uv[2*k] = u; uv[2*k+1] = v; }
         double I = bilinear(img, w, h, u, v, NULL, NULL);
         if (sigma != 0) r[k] = ((I - mu)/sigma - ref[k])*wT; else r[k] = 0.0;
     }
@@ -144,26 +145,26 @@ static void f_text_taps(const double Rcr[9], const double tcr[3], const double t
 /* nume_BAText::operator() (include/nume_BAText.h:28-94) */
 static void f_ba_text(const double qcw_[4], const double tcw[3], const double qrw_[4], const double trw[3], const double theta[3],
                       double fu, double fv, const double Kl[4], const uint8_t *img, int w, int h, const double ref[8],
-                      double mu, double sigma, double wT, double r[8]) {
+                      double mu, double sigma, double wT, double r[8], double *uv) {
     double qcw[4], qrw[4], Rcw[9], Rrw[9], Rcr[9], tcr[3], tmp[3];
     quat_normalize(qcw_, qcw); quat_to_R(qcw, Rcw);
     quat_normalize(qrw_, qrw); quat_to_R(qrw, Rrw);
     mat3_mulT(Rcw, Rrw, Rcr);                     /* T_cr = T_cw * T_rw^-1 */
     mat3_vec(Rcr, trw, tmp);
     tcr[0] = tcw[0] - tmp[0]; tcr[1] = tcw[1] - tmp[1]; tcr[2] = tcw[2] - tmp[2];
-    f_text_taps(Rcr, tcr, theta, fu, fv, Kl, img, w, h, ref, mu, sigma, wT, r);
+    f_text_taps(Rcr, tcr, theta, fu, fv, Kl, img, w, h, ref, mu, sigma, wT, r, uv);
 }
 /* nume_PoseOptimText::operator() (include/nume_PoseOptimText.h:28-79): T_cr = T_cw * T_wr */
 static void f_pose_text(const double q_[4], const double t[3], const double Twr[12], const double theta[3],
                         double fu, double fv, const double Kl[4], const uint8_t *img, int w, int h, const double ref[8],
-                        double mu, double sigma, double wT, double r[8]) {
+                        double mu, double sigma, double wT, double r[8], double *uv) {
     double q[4], Rcw[9], Rwr[9], twr[3], Rcr[9], tcr[3], tmp[3];
     quat_normalize(q_, q); quat_to_R(q, Rcw);
     for (int i = 0; i < 3; i++) { Rwr[i*3] = Twr[i*4]; Rwr[i*3+1] = Twr[i*4+1]; Rwr[i*3+2] = Twr[i*4+2]; twr[i] = Twr[i*4+3]; }
     mat3_mul(Rcw, Rwr, Rcr);
     mat3_vec(Rcw, twr, tmp);
     tcr[0] = tmp[0] + t[0]; tcr[1] = tmp[1] + t[1]; tcr[2] = tmp[2] + t[2];
-    f_text_taps(Rcr, tcr, theta, fu, fv, Kl, img, w, h, ref, mu, sigma, wT, r);
+    f_text_taps(Rcr, tcr, theta, fu, fv, Kl, img, w, h, ref, mu, sigma, wT, r, uv);
 }
 
 /* ------------------------------------------------------------------ cv::fillPoly restatement (recalled) */
@@ -460,8 +461,8 @@ static void frozen_scene_host(const tsba_problem *p, int pt, double q[4], double
     R_to_quat(R, qq); quat_normalize(qq, q);
 }
 
-/* raw residual of one block at (pose, rho, theta) */
-static void blk_residual(const pass_t *P, const blk_t *b, const double *pose, const double *rho, const double *theta, double r[8]) {
+/* raw residual of one block at (pose, rho, theta); uv (text blocks, may be NULL): the 8 taps' pixel positions [8][2] */
+static void blk_residual_uv(const pass_t *P, const blk_t *b, const double *pose, const double *rho, const double *theta, double r[8], double *uv) {
     const tsba_problem *p = P->p; const tsba_options *o = P->o; int l = P->level;
     if (b->type == BLK_SCENE_BA || b->type == BLK_SCENE_POSE) {
         double ray[3] = { p->pt_ray[2*b->lm], p->pt_ray[2*b->lm+1], 1.0 };
@@ -477,11 +478,26 @@ static void blk_residual(const pass_t *P, const blk_t *b, const double *pose, co
         const uint8_t *img = p->img[l][b->kf]; int w = p->img_w[l], h = p->img_h[l];
         if (b->type == BLK_TEXT_BA)
             f_ba_text(pose + 7*b->kf, pose + 7*b->kf + 4, pose + 7*b->host, pose + 7*b->host + 4, theta + 3*b->lm,
-                      fuv[0], fuv[1], P->Kl, img, w, h, ref, P->mu[b->tobs], P->sigma[b->tobs], o->w_t, r);
+                      fuv[0], fuv[1], P->Kl, img, w, h, ref, P->mu[b->tobs], P->sigma[b->tobs], o->w_t, r, uv);
         else
             f_pose_text(pose + 7*b->kf, pose + 7*b->kf + 4, p->text_host_Twr + 12*b->lm, theta + 3*b->lm,
-                        fuv[0], fuv[1], P->Kl, img, w, h, ref, P->mu[b->tobs], P->sigma[b->tobs], o->w_t, r);
+                        fuv[0], fuv[1], P->Kl, img, w, h, ref, P->mu[b->tobs], P->sigma[b->tobs], o->w_t, r, uv);
     }
+}
+static void blk_residual(const pass_t *P, const blk_t *b, const double *pose, const double *rho, const double *theta, double r[8]) {
+    blk_residual_uv(P, b, pose, rho, theta, r, NULL);
+}
+
+/* A tap's pixel cell and its in/out status under bilinear()'s rule (nume_BAText.h:67-82), compared in double: a projection that
+ * is not finite compares unequal to everything and so always counts as a change. */
+static int tap_inside(int w, int h, double u, double v) {
+    return floor(u) >= 0 && floor(v) >= 0 && ceil(u) < w && ceil(v) < h;
+}
+static int tap_moved(int w, int h, const double uv0[2], const double uv1[2]) {
+    int code = 0;
+    if (!(floor(uv1[0]) == floor(uv0[0]) && floor(uv1[1]) == floor(uv0[1]))) code |= TSBA_ORACLE_TAP_CELL;
+    if (tap_inside(w, h, uv1[0], uv1[1]) != tap_inside(w, h, uv0[0], uv0[1])) code |= TSBA_ORACLE_TAP_INOUT;
+    return code;
 }
 
 /* ceres::QuaternionParameterization::ComputeJacobian: 4x3, row-major */
@@ -507,13 +523,18 @@ static void quat_plus(const double x[4], const double d[3], double o[4]) {
 /* Ceres NumericDiffCostFunction<CENTRAL> on the raw parameter blocks of a text block, then the quaternion
  * manifold: numeric_diff.h (relative_step_size 1e-6, min step sqrt(eps)).  Output tangent-space blocks. */
 static void text_jac_numeric(const pass_t *P, const blk_t *b, const double *pose, const double *rho, const double *theta,
-                             double Jt[48], double Jh[48], double Jl[24]) {
+                             double Jt[48], double Jh[48], double Jl[24], uint8_t *tap_code) {
     const tsba_problem *p = P->p;
+    const int w = p->img_w[P->level], h = p->img_h[P->level];
     size_t npose = 7*(size_t)p->n_kf, nth = 3*(size_t)p->n_text;
     double *pz = (double *)malloc(sizeof(double)*(npose + nth)); double *tz = pz + npose;
     memcpy(pz, pose, sizeof(double)*npose); memcpy(tz, theta, sizeof(double)*nth);
     const double min_step = sqrt(DBL_EPSILON);
-    double amb_t[8*7], amb_h[8*7], rp[8], rm[8];
+    double amb_t[8*7], amb_h[8*7], rp[8], rm[8], uv0[16], uvp[16], uvm[16];
+    if (tap_code) {                                 /* tap_code[k]: bit 2 = tap k out of the image unperturbed, bits 0 / 1 = some +-delta evaluation moved it */
+        blk_residual_uv(P, b, pz, rho, tz, rp, uv0);  /* to another pixel cell / across the in/out rule (TSBA_ORACLE_TAP_*) */
+        for (int k = 0; k < 8; k++) tap_code[k] = tap_inside(w, h, uv0[2*k], uv0[2*k+1]) ? 0 : TSBA_ORACLE_TAP_OUT;
+    }
     for (int which = 0; which < 3; which++) {
         double *x; int n; double *out; int ld;
         if (which == 0) { x = pz + 7*b->kf; n = 7; out = amb_t; ld = 7; }
@@ -521,9 +542,10 @@ static void text_jac_numeric(const pass_t *P, const blk_t *b, const double *pose
         else { if (b->type != BLK_TEXT_BA) continue; x = tz + 3*b->lm; n = 3; out = Jl; ld = 3; }
         for (int j = 0; j < n; j++) {
             double x0 = x[j], delta = fabs(x0)*1e-6; if (delta < min_step) delta = min_step;
-            x[j] = x0 + delta; blk_residual(P, b, pz, rho, tz, rp);
-            x[j] = x0 - delta; blk_residual(P, b, pz, rho, tz, rm);
+            x[j] = x0 + delta; blk_residual_uv(P, b, pz, rho, tz, rp, uvp);
+            x[j] = x0 - delta; blk_residual_uv(P, b, pz, rho, tz, rm, uvm);
             x[j] = x0;
+            if (tap_code) for (int k = 0; k < 8; k++) tap_code[k] |= (uint8_t)(tap_moved(w, h, uv0 + 2*k, uvp + 2*k) | tap_moved(w, h, uv0 + 2*k, uvm + 2*k));
             double inv = (1.0/delta)/2;
             for (int k = 0; k < 8; k++) out[k*ld + j] = (rp[k] - rm[k])*inv;
         }
@@ -564,8 +586,8 @@ static void chain_pose(const double drdP[3], const double Pmtc[3], const double 
 }
 
 /* residual + tangent-space Jacobian of one block.  Jt/Jh: nres x 6, Jl: nres x 3 (scene: column 0 only), row-major */
-static void blk_eval(const pass_t *P, const blk_t *b, const double *pose, const double *rho, const double *theta,
-                     double r[8], double Jt[48], double Jh[48], double Jl[24]) {
+static void blk_eval_codes(const pass_t *P, const blk_t *b, const double *pose, const double *rho, const double *theta,
+                           double r[8], double Jt[48], double Jh[48], double Jl[24], uint8_t *tap_code) {
     const tsba_problem *p = P->p; const tsba_options *o = P->o; int l = P->level;
     blk_residual(P, b, pose, rho, theta, r);
     if (!Jt) return;
@@ -588,7 +610,7 @@ static void blk_eval(const pass_t *P, const blk_t *b, const double *pose, const 
             if (b->type == BLK_SCENE_BA) Jl[3*k] = -(A[k][0]*Rm[0] + A[k][1]*Rm[1] + A[k][2]*Rm[2])/(rh*rh);
         }
     } else {
-        if (o->text_jacobian == 1) { text_jac_numeric(P, b, pose, rho, theta, Jt, Jh, Jl); return; }
+        if (o->text_jacobian == 1) { text_jac_numeric(P, b, pose, rho, theta, Jt, Jh, Jl, tap_code); return; }
         double sigma = P->sigma[b->tobs];
         if (sigma == 0) return;
         const double *fuv = p->tfeat_uv[l] + 2*b->src; const double *th = theta + 3*b->lm;
@@ -621,6 +643,11 @@ static void blk_eval(const pass_t *P, const blk_t *b, const double *pose, const 
     }
 }
 
+static void blk_eval(const pass_t *P, const blk_t *b, const double *pose, const double *rho, const double *theta,
+                     double r[8], double Jt[48], double Jh[48], double Jl[24]) {
+    blk_eval_codes(P, b, pose, rho, theta, r, Jt, Jh, Jl, NULL);
+}
+
 /* ceres::HuberLoss + Corrector (corrector.cc: rho'' <= 0 => scale residual and Jacobian by sqrt(rho')) */
 static double huber(double s, double delta, double *scale) {
     double b = delta*delta;
@@ -631,12 +658,18 @@ static double huber(double s, double delta, double *scale) {
 /* ------------------------------------------------------------------ public: eval */
 int tsba_oracle_eval(const tsba_problem *p, const tsba_options *o, int level,
                      double *resid, double *jac, double *musigma, int64_t *ns, int64_t *nt) {
+    return tsba_oracle_eval_taps(p, o, level, resid, jac, musigma, ns, nt, NULL);
+}
+int tsba_oracle_eval_taps(const tsba_problem *p, const tsba_options *o, int level,
+                          double *resid, double *jac, double *musigma, int64_t *ns, int64_t *nt, uint8_t *tap_code) {
     if (!p || !o || level < 0 || level >= p->n_levels) return TSBA_ERR_ARG;
+    if (tap_code && (!jac || o->text_jacobian != 1)) return TSBA_ERR_ARG;
     pass_t P; pass_build(&P, p, o, level);
     double *rp = resid, *jp = jac;
     for (int i = 0; i < P.nblk; i++) {
         blk_t *b = &P.blk[i]; double r[8], Jt[48], Jh[48], Jl[24];
-        blk_eval(&P, b, p->pose, p->rho, p->theta, r, jac ? Jt : NULL, Jh, Jl);
+        blk_eval_codes(&P, b, p->pose, p->rho, p->theta, r, jac ? Jt : NULL, Jh, Jl,
+                       tap_code && b->nres == 8 ? tap_code + 8*(size_t)(i - P.ns) : NULL);
         if (resid) { memcpy(rp, r, sizeof(double)*b->nres); rp += b->nres; }
         if (jac) {
             int nc = b->nres == 2 ? 13 : 15, nl = b->nres == 2 ? 1 : 3;
@@ -1185,6 +1218,23 @@ int tsba_oracle_theta_cov(const tsba_problem *p, const tsba_options *o, int leve
     return inv_sym(V, 3, cov) ? TSBA_ERR_NUMERIC : TSBA_OK;
 }
 
+/* The outlier pass's statistic of one block at (pose, rho, theta), optimizer.cc:1609-1686 / :1228-1305: on the loss-corrected
+ * residual, scene max((r_x scale / w_sx)^2, (r_y scale / w_sy)^2), text max_k |r_k scale / w_t|.  A block is flagged when it
+ * exceeds chi2_mono / chi2_text (a NaN term never counts, as in the reference's comparisons). */
+static double outlier_stat(const pass_t *P, const blk_t *b, const double *pose, const double *rho, const double *theta) {
+    const tsba_options *o = P->o; double r[8], s = 0, scale, stat = 0;
+    blk_residual(P, b, pose, rho, theta, r);
+    for (int k = 0; k < b->nres; k++) s += r[k]*r[k];
+    huber(s, b->nres == 2 ? o->huber_scene : o->huber_text, &scale);
+    if (b->nres == 2) {
+        double cx = (r[0]*scale/o->w_sx)*(r[0]*scale/o->w_sx), cy = (r[1]*scale/o->w_sy)*(r[1]*scale/o->w_sy);
+        if (cx > stat) stat = cx;
+        if (cy > stat) stat = cy;
+    } else for (int k = 0; k < 8; k++) { double a = fabs(r[k]*scale/o->w_t); if (a > stat) stat = a; }
+    return stat;
+}
+static double pass_chi2_mono(const pass_t *P, int pass) { return P->o->chi2_mono[pass] + (P->nt < 50 ? 4 : 0); }
+
 /* ------------------------------------------------------------------ one pyramid pass: LM + outlier pass */
 static int run_pass(tsba_problem *p, const tsba_options *o, int pass, tsba_report *rep, int cov_text, double *cov_out, int *cov_rc) {
     int level = o->levels[pass], max_it = o->its[pass];
@@ -1280,22 +1330,17 @@ done:
     }
     /* outlier pass on loss-corrected residuals, optimizer.cc:1609-1686 / :1228-1305 */
     if (o->outlier_scene || o->outlier_text) {
-        double chi2m = o->chi2_mono[pass]; if (P.nt < 50) chi2m += 4;
+        double chi2m = pass_chi2_mono(&P, pass);
         double chi2t = o->chi2_text[pass];
         int *bad_in_tobs = (int *)calloc((size_t)p->n_tobs + 1, sizeof(int));
         for (int i = 0; i < P.nblk; i++) {
-            const blk_t *b = &P.blk[i]; double r[8];
-            blk_residual(&P, b, x_pose, x_rho, x_th, r);
-            double s = 0; for (int k = 0; k < b->nres; k++) s += r[k]*r[k];
-            double scale; huber(s, b->nres == 2 ? o->huber_scene : o->huber_text, &scale);
+            const blk_t *b = &P.blk[i];
             if (b->nres == 2) {
                 if (!o->outlier_scene) continue;
-                double cx = (r[0]*scale/o->w_sx)*(r[0]*scale/o->w_sx), cy = (r[1]*scale/o->w_sy)*(r[1]*scale/o->w_sy);
-                if (cx > chi2m || cy > chi2m) { p->sgood[p->sobs_flag[level][b->src]] = 0; rep->n_bad_scene[pass]++; }
+                if (outlier_stat(&P, b, x_pose, x_rho, x_th) > chi2m) { p->sgood[p->sobs_flag[level][b->src]] = 0; rep->n_bad_scene[pass]++; }
             } else {
                 if (!o->outlier_text) continue;
-                int bad = 0; for (int k = 0; k < 8; k++) if (fabs(r[k]*scale/o->w_t) > chi2t) bad = 1;
-                if (bad) { p->tfgood[p->tobs_fgood_off[b->tobs] + p->tfeat_raw[level][b->src]] = 0; bad_in_tobs[b->tobs]++; rep->n_bad_tfeat[pass]++; }
+                if (outlier_stat(&P, b, x_pose, x_rho, x_th) > chi2t) { p->tfgood[p->tobs_fgood_off[b->tobs] + p->tfeat_raw[level][b->src]] = 0; bad_in_tobs[b->tobs]++; rep->n_bad_tfeat[pass]++; }
             }
         }
         if (o->outlier_text) for (int t = 0; t < p->n_tobs; t++) if (P.tobs_size[t] > 0) {
@@ -1308,6 +1353,27 @@ done:
     free(sp); free(dgp); free(yp); free(dp); free(sl); free(dgl); free(yl); free(dl); free(keep);
     neq_free(&N); pass_free(&P);
     return term == 5 ? TSBA_ERR_NUMERIC : TSBA_OK;
+}
+
+int tsba_oracle_outlier_stats(const tsba_problem *p, const tsba_options *o, int pass, const double *pose, const double *rho, const double *theta,
+                              double *s_stat, double *tf_stat, double *tobs_ratio, double thr[2]) {
+    if (!p || !o || pass < 0 || pass >= TSBA_MAX_LEVELS || o->levels[pass] < 0 || o->levels[pass] >= p->n_levels) return TSBA_ERR_ARG;
+    const int level = o->levels[pass];
+    pass_t P; pass_build(&P, p, o, level);
+    int *bad_in_tobs = (int *)calloc((size_t)p->n_tobs + 1, sizeof(int));
+    for (int i = 0; i < P.nblk; i++) {
+        const blk_t *b = &P.blk[i];
+        double st = outlier_stat(&P, b, pose, rho, theta);
+        if (b->nres == 2) { if (s_stat) s_stat[p->sobs_flag[level][b->src]] = st; }
+        else {
+            if (tf_stat) tf_stat[p->tobs_fgood_off[b->tobs] + p->tfeat_raw[level][b->src]] = st;
+            if (st > o->chi2_text[pass]) bad_in_tobs[b->tobs]++;
+        }
+    }
+    if (tobs_ratio) for (int t = 0; t < p->n_tobs; t++) if (P.tobs_size[t] > 0) tobs_ratio[t] = (double)bad_in_tobs[t]/(double)P.tobs_size[t];
+    if (thr) { thr[0] = pass_chi2_mono(&P, pass); thr[1] = o->chi2_text[pass]; }
+    free(bad_in_tobs); pass_free(&P);
+    return TSBA_OK;
 }
 
 int tsba_oracle_solve(tsba_problem *p, const tsba_options *o, tsba_report *r) {

@@ -23,6 +23,25 @@ extern "C" {
 int tsba_oracle_eval(const tsba_problem *p, const tsba_options *o, int level,
                      double *resid, double *jac, double *musigma, int64_t *ns, int64_t *nt);
 
+/* tsba_oracle_eval in numeric mode (options.text_jacobian == 1, jac != NULL; else TSBA_ERR_ARG) that also records, per tap of
+ * every text block, tap_code[nt][8]: TSBA_ORACLE_TAP_OUT if the unperturbed tap lies outside the image under the in/out rule,
+ * TSBA_ORACLE_TAP_CELL / _INOUT if any +-delta evaluation of the central differences moved it to another pixel cell
+ * (floor(u), floor(v)) / across the in/out rule.  A tap with either of the last two bits "straddles": its numeric derivative
+ * differences across a kink of the bilinear interpolation, where the analytic (one-cell) derivative is not its limit. */
+#define TSBA_ORACLE_TAP_CELL  1
+#define TSBA_ORACLE_TAP_INOUT 2
+#define TSBA_ORACLE_TAP_OUT   4
+int tsba_oracle_eval_taps(const tsba_problem *p, const tsba_options *o, int level,
+                          double *resid, double *jac, double *musigma, int64_t *ns, int64_t *nt, uint8_t *tap_code);
+
+/* The outlier pass of pass `pass` as run_pass computes it: the blocks and mu / sigma from p (flags and parameters as the pass
+ * starts), residuals at (pose, rho, theta) (where its LM loop ended).  Writes, for the flags the pass judges:
+ * s_stat[sgood index] = max((r_x scale / w_sx)^2, (r_y scale / w_sy)^2), tf_stat[tfgood index] = max_k |r_k scale / w_t|,
+ * tobs_ratio[t] = flagged features / blocks of observation t; entries the pass does not judge are left as they are.
+ * thr = (chi2_mono as applied, with +4 when the pass has fewer than 50 text blocks; chi2_text).  Any of the outputs may be NULL. */
+int tsba_oracle_outlier_stats(const tsba_problem *p, const tsba_options *o, int pass, const double *pose, const double *rho, const double *theta,
+                              double *s_stat, double *tf_stat, double *tobs_ratio, double thr[2]);
+
 /* Full solve (all pyramid passes, outlier passes, write-back into p) -- restates
  * LocalBundleAdjustment / PoseOptim / GlobalBA depending on the options. */
 int tsba_oracle_solve(tsba_problem *p, const tsba_options *o, tsba_report *r);

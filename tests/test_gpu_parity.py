@@ -18,6 +18,7 @@ from textslam_amd import synth, abi
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -80,6 +81,51 @@ def test_eval_matches_reference_style_numeric_jacobian(gpu, oracle_lib):
     en = oracle_lib.evaluate(P, o, 0)
     rel = np.abs(eg["jac_text"] - en["jac_text"]) / np.abs(en["jac_text"]).max()
     assert np.median(rel) < 1e-9 and np.mean(rel < 1e-6) > 0.995
+    # the straddle rule: every tap whose central-difference stencil stays in its pixel cell and on its side of the in/out rule, to 1e-8
+    gap = oracle_lib.straddle_gap(eg["jac_text"], oracle_lib.evaluate(P, o, 0, straddle=True))
+    assert gap["unmasked"] <= 1e-8, gap["unmasked"]
+
+
+@pytest.mark.parametrize("name", ["tiny3", "tiny11", "c4", "c3", "init_pair", "landmark_refine", "border"])
+def test_eval_numeric_jacobian_straddle_rule(gpu, oracle_lib, name):
+    """k_eval_text's analytic Jacobian against the oracle's Ceres central differences on every block type and level (the problems of
+    tests/test_oracle.py::test_text_jacobian_straddle_rule): 1e-8 of the largest entry on every tap outside the straddle mask."""
+    from test_oracle import rule_case
+    P, o, levels = rule_case(name)
+    for l in levels:
+        o.text_jacobian = 0
+        eg = gpu.evaluate(P, o, l)
+        o.text_jacobian = 1
+        en = oracle_lib.evaluate(P, o, l, straddle=True)
+        gap = oracle_lib.straddle_gap(eg["jac_text"], en)
+        print(f"{name} level {l}: {gap['n_straddle']} of {gap['n_taps']} taps straddle, unmasked gap {gap['unmasked']:.1e}")
+        assert gap["n_taps"] > 0 and gap["unmasked"] <= 1e-8, (l, gap["unmasked"])
+        if name == "border" and l > 0:
+            assert en["straddle_inout"].any()
+
+
+@pytest.mark.parametrize("name", ["tiny", "c4", "border"])
+def test_reduced_system_against_numeric_mode(gpu, oracle_lib, name):
+    """k_linearize's first linearisation (gpu.reduced_system) against the oracle's reduced system in NUMERIC mode, at every pass's level:
+    S and g no further from it than the oracle's analytic system is (tests/test_oracle.py::REDUCED_FIGURE, pinned there) plus 1e-9, the
+    GPU-versus-analytic tolerance of test_reduced_system_parity; and that figure within 2x of its measured value."""
+    from test_oracle import reduced_case, REDUCED_FIGURE
+    P, o = reduced_case(name)
+    for ps in range(o.n_passes):
+        o1 = oracle_lib.pass_options(o, ps); l = o1.levels[0]
+        ra = oracle_lib.reduced_system(P, o1, l, o.initial_radius)
+        on = oracle_lib.pass_options(o, ps); on.text_jacobian = 1
+        rn = oracle_lib.reduced_system(P, on, l, o.initial_radius)
+        gpu.upload(P, o1)
+        rg = gpu.reduced_system(o.initial_radius)
+        m = 6 * rn["nf"]
+        assert np.array_equal(np.nonzero(rg["free"])[0], np.nonzero(rn["free_idx"] >= 0)[0])
+        fig_s, fig_g = _rel(ra["S"], rn["S"]), _rel(ra["g"], rn["g"])
+        gs, gg = _rel(rg["S"][:m, :m], rn["S"]), _rel(rg["g"][:m], rn["g"])
+        print(f"{name} level {l}: S {gs:.2e} (oracle analytic {fig_s:.2e}), g {gg:.2e} ({fig_g:.2e})")
+        assert fig_s <= 2 * REDUCED_FIGURE[(name, l)][0] and fig_g <= 2 * REDUCED_FIGURE[(name, l)][1]
+        assert gs <= fig_s + 1e-9 and gg <= fig_g + 1e-9, (l, gs, fig_s, gg, fig_g)
+        assert rg["cost"] == pytest.approx(rn["cost"], rel=1e-12)
 
 
 def test_reduced_system_parity(gpu, oracle_lib):

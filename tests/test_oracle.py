@@ -90,6 +90,148 @@ def test_text_analytic_vs_ceres_numeric_diff(oracle_lib):
     rel = np.abs(Ja - Jn) / scale
     assert np.median(rel) < 1e-9
     assert np.mean(rel < 1e-6) > 0.995
+    # and every tap whose stencil stays in its pixel cell, on its side of the in/out rule, agrees to 1e-8 (the straddle rule)
+    gap = oracle_lib.straddle_gap(Ja, oracle_lib.evaluate(P, o, 0, straddle=True))
+    assert gap["unmasked"] <= 1e-8, gap["unmasked"]
+
+
+def rule_case(name):
+    """The problems the straddle rule runs over: (problem, options, levels)."""
+    if name.startswith("tiny"):
+        return synth.tiny(seed=int(name[4:])), abi.options_local(), (0, 1, 2)
+    if name == "c4":
+        return synth.config_c4(), abi.options_local(), (0, 1, 2)
+    if name == "c3":
+        return synth.config_c3(), abi.options_pose(), (0, 1, 2)
+    if name == "init_pair":
+        return synth.init_pair(seed=5), abi.options_init(), (0, 1, 2, 3)
+    if name == "landmark_refine":
+        return synth.landmark_refine(seed=9), abi.options_landmarker(), (0, 1, 2, 3)
+    return synth.border_variant(), abi.options_local(), (0, 1, 2)
+
+
+RULE_CASES = ["tiny3", "tiny11", "c4", "c3", "init_pair", "landmark_refine", "border"]
+
+
+@pytest.mark.parametrize("name", RULE_CASES)
+def test_text_jacobian_straddle_rule(oracle_lib, name):
+    """The analytic text Jacobian (pose-only, InitBA, frozen-host and window blocks) against the reference's central differences, tap by tap:
+    a tap may differ only where a +-delta evaluation moved it to another pixel cell or across the image's in/out rule (the straddle mask);
+    everywhere else 1e-8 of the largest entry (measured: <= 5.7e-9).  The border variant makes taps fall outside an image and stencils
+    step across its edge at levels 1 and 2, so the in/out rule itself is exercised."""
+    P, o, levels = rule_case(name)
+    for l in levels:
+        o.text_jacobian = 0
+        Ja = oracle_lib.evaluate(P, o, l)["jac_text"]
+        o.text_jacobian = 1
+        en = oracle_lib.evaluate(P, o, l, straddle=True)
+        gap = oracle_lib.straddle_gap(Ja, en)
+        print(f"{name} level {l}: {gap['n_straddle']} of {gap['n_taps']} taps straddle, unmasked gap {gap['unmasked']:.1e}, "
+              f"masked {gap['masked']:.1e}, {int(en['tap_out'].sum())} taps outside the image")
+        assert gap["n_taps"] > 0 and gap["unmasked"] <= 1e-8, (l, gap["unmasked"])
+        if name == "border" and l > 0:
+            assert en["tap_out"].any() and en["straddle_inout"].any()
+
+
+def _text_blocks(P, o, level):
+    """(tobs, kf, text, feature) of every text block of a pass, in the oracle's order (pass_build)."""
+    out = []
+    for t in range(P.n_tobs):
+        kf, j = int(P.tobs_kf[t]), int(P.tobs_text[t])
+        if (o.filter_good and not P.tobs_good[t]) or P.text_host[j] == kf:
+            continue
+        for f in range(P.tfeat_off[level][j], P.tfeat_off[level][j + 1]):
+            if o.filter_good and not P.tfgood[P.tobs_fgood_off[t] + P.tfeat_raw[level][f]]:
+                continue
+            out.append((t, kf, j, f))
+    return out
+
+
+@pytest.mark.parametrize("name,level", [("tiny11", 0), ("border", 1), ("border", 2)])
+def test_straddle_mask_matches_perturbed_projections(oracle_lib, name, level):
+    """The oracle's straddle mask against an independent restatement: the taps projected in numpy (synth.text_tap_uv) at every +-delta of
+    Ceres' step rule (max(|x| 1e-6, sqrt(eps)) on the raw pose / theta entries the block depends on).  A masked tap really moves to another
+    cell or across the in/out rule, an unmasked one does not."""
+    P, o, _ = rule_case(name)
+    o.text_jacobian = 1
+    ev = oracle_lib.evaluate(P, o, level, straddle=True)
+    blocks = _text_blocks(P, o, level)
+    assert len(blocks) == ev["nt"]
+    w, h = P.img[level].shape[2], P.img[level].shape[1]
+
+    def state(uv):
+        return np.floor(uv), (np.floor(uv[:, 0]) >= 0) & (np.floor(uv[:, 1]) >= 0) & (np.ceil(uv[:, 0]) < w) & (np.ceil(uv[:, 1]) < h)
+    cell = np.zeros((len(blocks), 8), bool); inout = np.zeros((len(blocks), 8), bool); out = np.zeros((len(blocks), 8), bool)
+    min_step = np.sqrt(np.finfo(np.float64).eps)
+    for i, (t, kf, j, f) in enumerate(blocks):
+        fuv = P.tfeat_uv[level][f]
+        c0, in0 = state(synth.text_tap_uv(P, level, kf, j, fuv))
+        out[i] = ~in0
+        host = int(P.text_host[j])
+        params = [("pose", kf, a) for a in range(7)]
+        if host >= 0:
+            params += [("pose", host, a) for a in range(7)] + [("theta", j, a) for a in range(3)]
+        for arr, row, a in params:
+            for sgn in (1, -1):
+                pose, theta = P.pose.reshape(-1, 7).copy(), P.theta.reshape(-1, 3).copy()
+                x = pose if arr == "pose" else theta
+                x[row, a] += sgn * max(abs(x[row, a]) * 1e-6, min_step)
+                c1, in1 = state(synth.text_tap_uv(P, level, kf, j, fuv, pose, theta))
+                cell[i] |= np.any(c1 != c0, axis=1)
+                inout[i] |= in1 != in0
+    assert np.array_equal(ev["tap_out"], out)
+    assert np.array_equal(ev["straddle"], cell | inout), (np.argwhere(ev["straddle"] != (cell | inout)))
+    assert np.array_equal(ev["straddle_inout"], inout)
+    assert ev["straddle"].any()
+
+
+# the oracle's own analytic-versus-numeric figure of the first linearisation's reduced system (rel. to the largest entry of S / g), measured
+# here; tests/test_gpu_parity.py::test_reduced_system_against_numeric_mode holds k_linearize to it.  border levels 1 / 2: one tap whose
+# stencil steps across the image edge dominates the numeric S (its central difference spans the jump of the in/out rule)
+REDUCED_FIGURE = {("tiny", 2): (3.0e-8, 3.0e-8), ("tiny", 1): (6.2e-9, 2.2e-8), ("tiny", 0): (5.7e-9, 1.2e-8),
+                  ("c4", 2): (2.8e-5, 1.0e-4), ("c4", 1): (5.7e-5, 1.9e-4), ("c4", 0): (1.8e-5, 8.8e-5),
+                  ("border", 2): (1.0, 8.3e-2), ("border", 1): (1.0, 6.8e-2), ("border", 0): (1.6e-8, 1.2e-8)}
+
+
+def reduced_case(name):
+    return {"tiny": synth.tiny, "c4": synth.config_c4, "border": synth.border_variant}[name](), abi.options_local()
+
+
+@pytest.mark.parametrize("name", ["tiny", "c4", "border"])
+def test_reduced_system_analytic_vs_numeric_figure(oracle_lib, name):
+    """The figure above stays where it was measured (within 2x): the yardstick of the GPU test cannot drift with a slip shared by the
+    kernel and the oracle's analytic Jacobian."""
+    P, o = reduced_case(name)
+    for ps in range(o.n_passes):
+        o1 = oracle_lib.pass_options(o, ps); l = o1.levels[0]
+        ra = oracle_lib.reduced_system(P, o1, l, o.initial_radius)
+        o1.text_jacobian = 1
+        rn = oracle_lib.reduced_system(P, o1, l, o.initial_radius)
+        fs = np.abs(ra["S"] - rn["S"]).max() / np.abs(rn["S"]).max()
+        fg = np.abs(ra["g"] - rn["g"]).max() / np.abs(rn["g"]).max()
+        assert ra["cost"] == rn["cost"]
+        assert fs <= 2 * REDUCED_FIGURE[(name, l)][0] and fg <= 2 * REDUCED_FIGURE[(name, l)][1], (l, fs, fg)
+
+
+def test_outlier_stats_reproduce_the_outlier_pass(oracle_lib):
+    """oracle.outlier_stats at a pass's end parameters decides exactly the flags that pass drops (C4's first pass, the pass-by-pass solve
+    equal to the one-call solve)."""
+    P, o = synth.config_c4(), abi.options_local()
+    o.text_jacobian = 1
+    N = P.copy(); rep, tr, starts = oracle_lib.solve_by_pass(N, o)
+    R = P.copy(); rep_r, tr_r = oracle_lib.solve_traced(R, o)
+    assert rep["iters"] == rep_r["iters"] and rep["cost1"] == rep_r["cost1"] and np.array_equal(N.theta, R.theta) and np.array_equal(N.tfgood, R.tfgood)
+    assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(tr, tr_r))
+    S0, E0 = starts[0], starts[1]
+    st = oracle_lib.outlier_stats(S0, oracle_lib.pass_options(o, 0), 0, end=E0)
+    judged = ~np.isnan(st["tf_stat"])
+    assert judged.sum() == rep["n_tblock"][0]
+    assert np.array_equal(E0.tfgood[judged] == 0, st["tf_stat"][judged] > st["chi2_text"])
+    sj = ~np.isnan(st["s_stat"])
+    assert np.array_equal(E0.sgood[sj] == 0, st["s_stat"][sj] > st["chi2_mono"])
+    tj = ~np.isnan(st["tobs_ratio"])
+    assert np.array_equal(E0.tobs_good[tj] == 0, st["tobs_ratio"][tj] > st["text_bad_ratio"])
+    assert (S0.tfgood != E0.tfgood).sum() == rep["n_bad_tfeat"][0] > 0
 
 
 def test_lm_converges_to_truth_noise_free(oracle_lib):

@@ -162,7 +162,7 @@ class _Plane:
 def make_problem(n_kf=20, n_pt=5000, n_text=100, seed=SEED, feats=(64, 24, 12), max_targets=5, text_targets=5,
                  frozen_frac=0.1, outlier_frac=0.05, noise_px=0.5, perturb=True, n_levels=3,
                  band=None, far_frac=0.0, n_out=3, rot_deg=0.5, trans_m=0.02, lm_rel=0.05, self_obs=True, n_fixed=3, kf_initial=None, loop=False, loop_at=0, closures=0,
-                 drop_outlier_points=False, perturb_in_camera=False):
+                 drop_outlier_points=False, perturb_in_camera=False, border=None):
     """Build a synthetic window (local BA / pose-only / global BA depending on the arguments).
 
     n_kf == 1 with frozen_frac == 1 gives the pose-only problem (every landmark hosted outside).
@@ -175,6 +175,8 @@ def make_problem(n_kf=20, n_pt=5000, n_text=100, seed=SEED, feats=(64, 24, 12), 
     perturb_in_camera: the pose perturbation as a motion of the CAMERA, T_cw' = (dR, dt) T_cw: the camera centre moves by ~trans_m wherever the keyframe is.  The
     default perturbs R_cw and t_cw separately, which turns a camera 500 m from the origin around the ORIGIN (0.2 degrees = 1.7 m at keyframe 5000 against a
     step of 0.1 m between keyframes): a start no loop correction would leave behind, and the reason the 5000-keyframe chains need hundreds of LM iterations.
+    border: (k, yaw_deg) -- window keyframe k looks yaw_deg further to the side, and a text plane counts as seen by k while its box centre
+    projects into k's image (not its whole box): planes near k's image edge stick out of it (border_variant).
     """
     rng = np.random.default_rng(seed)
     fx, fy, cx, cy = K_GENERAL_MOTION
@@ -187,6 +189,9 @@ def make_problem(n_kf=20, n_pt=5000, n_text=100, seed=SEED, feats=(64, 24, 12), 
     lobes = _lobes(n_kf, closures) if closures > 0 else []
     if closures > 0:                                          # several separate loop closures (frozen hosts outside the map are not used with it)
         cams = {k: _cam_lobes(max(k, 0), n_kf, closures) for k in range(-n_out, n_kf)}
+    if border is not None:
+        Ry = _rot_y(np.deg2rad(border[1]))
+        cams[border[0]] = (Ry @ cams[border[0]][0], Ry @ cams[border[0]][1])
     Rcw = np.stack([cams[k][0] for k in range(n_kf)])
     tcw = np.stack([cams[k][1] for k in range(n_kf)])
 
@@ -334,7 +339,11 @@ def make_problem(n_kf=20, n_pt=5000, n_text=100, seed=SEED, feats=(64, 24, 12), 
             cand = range(n_kf) if pl.host < 0 else range(pl.host + 1, n_kf)
             for k in cand:
                 u, v, z = project(k, Xw_c)
-                if np.all(z > 0.1) and u.min() >= 8 and u.max() < W - 8 and v.min() >= 8 and v.max() < H - 8:
+                if border is not None and k == border[0]:
+                    seen = np.all(z > 0.1) and 8 <= u.mean() < W - 8 and 8 <= v.mean() < H - 8
+                else:
+                    seen = np.all(z > 0.1) and u.min() >= 8 and u.max() < W - 8 and v.min() >= 8 and v.max() < H - 8
+                if seen:
                     obs.append(k)
                     if len(obs) >= text_targets:
                         break
@@ -517,6 +526,69 @@ def tiny(seed=7, n_kf=5, n_pt=60, n_text=4, **kw):
     kw.setdefault("feats", (12, 8, 6))
     kw.setdefault("text_targets", 3)
     return make_problem(n_kf, n_pt, n_text, seed, **kw)
+
+
+def text_tap_uv(P, level, kf, text, fuv, pose=None, theta=None):
+    """Pixel positions [8, 2] in keyframe kf at pyramid level `level` of the 8 taps of the text feature at host pixel fuv of plane `text`:
+    nume_BAText / nume_PoseOptimText's projection (tool.cc:1561, ModelTool.hpp:167) at the parameters pose [n_kf, 7] / theta [n_text, 3]
+    (default P's)."""
+    pose = np.asarray(P.pose if pose is None else pose, np.float64).reshape(-1, 7)
+    theta = np.asarray(P.theta if theta is None else theta, np.float64).reshape(-1, 3)
+    Kl = np.asarray(P.K, np.float64) * 0.5 ** level
+    Rc, tc = _q_to_R(pose[kf, :4]), pose[kf, 4:]
+    host = int(P.text_host[text])
+    if host >= 0:                                     # T_cr = T_cw T_rw^-1
+        Rr, tr = _q_to_R(pose[host, :4]), pose[host, 4:]
+        Rcr = Rc @ Rr.T
+        tcr = tc - Rcr @ tr
+    else:                                             # T_cr = T_cw T_wr
+        T = np.asarray(P.text_host_Twr[text], np.float64).reshape(3, 4)
+        Rcr, tcr = Rc @ T[:, :3], Rc @ T[:, 3] + tc
+    ray = np.stack([(fuv[0] + TAP_DX - Kl[2]) / Kl[0], (fuv[1] + TAP_DY - Kl[3]) / Kl[1], np.ones(8)], 1)
+    rho = -(ray @ theta[text])
+    X = ray @ Rcr.T / rho[:, None] + tcr
+    return np.stack([Kl[0] * X[:, 0] / X[:, 2] + Kl[2], Kl[1] * X[:, 1] / X[:, 2] + Kl[3]], 1)
+
+
+def border_variant(seed=7, n_text=12, kf=3, yaw_deg=16.0, edge_levels=(1, 2)):
+    """tiny() (n_text planes) with keyframe kf turned by yaw_deg (make_problem's border option): some text planes stick out of kf's image, so taps fall
+    outside it.  At every level in edge_levels, one text feature is then moved (by less than 3 pixels in its host image, its reference
+    intensities resampled) so that one of its taps in kf lies 1e-9 pixels inside the right image edge (u = w - 1): the Ceres central
+    difference of that tap steps across the image's in/out rule."""
+    P = tiny(seed=seed, n_text=n_text, border=(kf, yaw_deg))
+    edge = np.float64(1e-9)
+    for l in edge_levels:
+        w = int(P.img[l].shape[2])
+        best = None
+        for t in np.nonzero((P.tobs_kf == kf) & (P.tobs_good == 1))[0]:
+            j = int(P.tobs_text[t])
+            if P.text_host[j] < 0:
+                continue
+            for f in range(int(P.tfeat_off[l][j]), int(P.tfeat_off[l][j + 1])):
+                if not P.tfgood[P.tobs_fgood_off[t] + P.tfeat_raw[l][f]]:
+                    continue
+                uv = text_tap_uv(P, l, kf, j, P.tfeat_uv[l][f])
+                for k in range(8):
+                    d = (w - 1) - uv[k, 0]
+                    if 0 < d < 3 and (best is None or d < best[0]):
+                        best = (d, j, f, k)
+        if best is None:
+            raise RuntimeError("border_variant: no text tap near keyframe %d's right edge at level %d" % (kf, l))
+        _, j, f, k = best
+        fuv = P.tfeat_uv[l][f].copy()
+        for _ in range(20):                           # secant steps on the feature's host u
+            u0 = text_tap_uv(P, l, kf, j, fuv)[k, 0]
+            du = (text_tap_uv(P, l, kf, j, fuv + [1e-3, 0])[k, 0] - u0) / 1e-3
+            fuv[0] += ((w - 1) - edge - u0) / du
+        u = text_tap_uv(P, l, kf, j, fuv)[k, 0]
+        assert 0 < (w - 1) - u < 1e-8, u
+        host = int(P.text_host[j])
+        Kl = np.asarray(P.K) * 0.5 ** l
+        corners = np.stack([Kl[0] * P.text_box_ray[j][:, 0] + Kl[2], Kl[1] * P.text_box_ray[j][:, 1] + Kl[3]], 1)
+        mu, sg = _quad_stats(P.img[l][host], corners)
+        P.tfeat_uv[l][f] = fuv
+        P.tfeat_ref[l][f] = (_bilinear(P.img[l][host].astype(np.float64), fuv[0] + TAP_DX, fuv[1] + TAP_DY) - mu) / (sg if sg != 0 else 1.0)
+    return P.normalise()
 
 
 def init_pair(seed=SEED, n_pt=300, n_text=3):
