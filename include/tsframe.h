@@ -6,6 +6,7 @@
  *   tool::CalNormvec / GetNeighbour     /root/reference/src/tool.cc:1342-1364,1540-1566 (INTERVAL8) -> tsframe_neighbours
  *   tool::GetBoxAllPixs                 /root/reference/src/tool.cc:1264-1337     -> tsframe_box_pixels
  *   tracking::TextJudgeSingle (xn)      /root/reference/src/tracking.cc:1991-2131 -> tsframe_text_judge
+ *   tracking::TrackNewTextFeat          /root/reference/src/tracking.cc:1752-1785 -> tsframe_klt_track
  * The pyramid stays resident in HBM: tsframe_level_ptr hands the device pointers to the BA library, so the four levels of a
  * keyframe need no host round trip between GetPyrMat and the photometric residuals.
  * All functions return 0 on success, a negative TSFRAME_ERR_* otherwise; tsframe_last_error gives the text. */
@@ -82,6 +83,22 @@ int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const d
                        const double K_ref[4], const double K[4], double cos_min, int out_margin, double zncc_min,
                        int n_dete, const double *dete_xy,
                        uint8_t *pass, int32_t *reason, double *cos, double *zncc, double *box_uv, uint32_t *dete_bits);
+
+/* tracking::TrackNewTextFeat -> cv::calcOpticalFlowPyrLK (defaults: win 21, max_level 3, 30 iterations, eps 0.01, min_eig 1e-4) for
+ * all n points of all detections in ONE launch, between the resident pyramids of two contexts on the same device. */
+int tsframe_klt_track(void *prev_ctx, void *cur_ctx, int n, const float *prev_xy /*[n][2]*/,
+                      int win, int max_level, int max_iter, double eps, double min_eig,
+                      float *next_xy /*[n][2]*/, uint8_t *status /*[n]*/);
+/* prev_ctx holds the image the points were seen in (the last frame or keyframe), cur_ctx the current frame; both stay as they are: the level
+ * images are read in place, the Scharr derivatives are computed on the fly.  The arithmetic is docs/klt_recalled.md: the window sums are
+ * exact integers rounded once to fp32, everything after them is fp32 in a fixed order, so a point's result does not depend on the other
+ * points of the call.  Levels: L + 1 with L <= max_level; a level whose width or height is <= win is dropped with all coarser ones, and both
+ * contexts must hold the levels that remain.  status[i] = 1: tracked; 0: the point or its track left the image by more than the window, the
+ * patch is flat (min_eig), or the input is not finite (then next_xy = prev_xy).  OpenCV's err is not computed.
+ * TSFRAME_ERR_ARG: a NULL pointer with n > 0, contexts on different devices, level-0 sizes that differ or are not larger than win, win even
+ * or outside [3, 31], max_level outside [0, 7], max_iter outside [1, 100], eps < 0, too few resident levels.  TSFRAME_ERR_STATE: a context
+ * without an image.  n == 0 launches nothing.  The points and the results travel through cur_ctx's pinned staging block and stream: the
+ * previous frame's context must stay alive (and keep its image) until the call returns. */
 
 #ifdef __cplusplus
 }

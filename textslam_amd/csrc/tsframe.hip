@@ -322,6 +322,8 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
     }
 }
 
+#include "tsklt.h"
+
 static int ensure_host(FCtx *c, size_t bytes) {
     if (bytes <= c->h_cap) return 0;
     if (c->h_stage) hipHostFree(c->h_stage);
@@ -590,6 +592,53 @@ int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const d
         memcpy(box_uv + 8*(size_t)i, ho[i].box, 64);
     }
     if (words > 0) memcpy(dete_bits, h + o_bits, 4*(size_t)n*words);
+    return TSFRAME_OK;
+}
+
+int tsframe_klt_track(void *prev_ctx, void *cur_ctx, int n, const float *prev_xy, int win, int max_level, int max_iter, double eps, double min_eig,
+                      float *next_xy, uint8_t *status) {
+    FCtx *p = (FCtx *)prev_ctx, *c = (FCtx *)cur_ctx;
+    if (!c) return TSFRAME_ERR_ARG;
+    auto bad = [&](const char *what) { c->err = std::string("tsframe_klt_track: ") + what; return TSFRAME_ERR_ARG; };
+    if (!p) return bad("prev_ctx NULL");
+    if (n < 0) return bad("n < 0");
+    if (n > 0 && (!prev_xy || !next_xy || !status)) return bad("NULL array with n > 0");
+    if (win < 3 || win > 31 || !(win & 1)) return bad("win must be odd and in [3, 31]");
+    if (max_level < 0 || max_level > TSFRAME_MAX_LEVELS - 1) return bad("max_level outside [0, 7]");
+    if (max_iter < 1 || max_iter > 100) return bad("max_iter outside [1, 100]");
+    if (!(eps >= 0.0)) return bad("eps < 0");
+    if (n == 0) return TSFRAME_OK;
+    if (p->n_levels == 0 || c->n_levels == 0) { c->err = "tsframe_klt_track: no image set"; return TSFRAME_ERR_STATE; }
+    if (p->device != c->device) return bad("the two contexts are on different devices");
+    if (p->w[0] != c->w[0] || p->h[0] != c->h[0]) return bad("the level-0 sizes differ");
+    // the level rule: L + 1 levels, L <= max_level; level l and all coarser ones are dropped if its width or height is <= win
+    if (c->w[0] <= win || c->h[0] <= win) return bad("the level-0 image must be larger than the window");
+    int need = 1, lw = c->w[0], lh = c->h[0];
+    for (int l = 1; l <= max_level; l++) { lw = (lw + 1)/2; lh = (lh + 1)/2; if (lw <= win || lh <= win) break; need = l + 1; }
+    if (p->n_levels < need || c->n_levels < need) return bad("a context holds fewer resident levels than max_level and the image size ask for");
+    hipSetDevice(c->device);
+    KltArgs A;
+    for (int l = 0; l < TSFRAME_MAX_LEVELS; l++) {
+        const bool on = l < need;
+        A.I[l] = on ? p->plane[TSFRAME_IMG][l] : nullptr; A.J[l] = on ? c->plane[TSFRAME_IMG][l] : nullptr; A.w[l] = on ? c->w[l] : 0; A.h[l] = on ? c->h[l] : 0;
+    }
+    A.n = n; A.n_levels = need; A.win = win; A.max_iter = max_iter;
+    A.eps2 = (float)eps*(float)eps; A.min_eig = (float)min_eig;
+    // one pinned block: prev_xy || next_xy | status
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_out = al(8*(size_t)n), o_st = o_out + al(8*(size_t)n), tot = o_st + al((size_t)n);
+    int rc = ensure_work(c, tot); if (rc) return rc;
+    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    uint8_t *h = c->h_stage, *d = c->d_work;
+    memcpy(h, prev_xy, 8*(size_t)n);
+    CKF(hipMemcpyAsync(d, h, 8*(size_t)n, hipMemcpyHostToDevice, c->stream));
+    const dim3 grid((n + KLT_WAVES - 1)/KLT_WAVES), block(64*KLT_WAVES);
+    if (win*win <= 64*8) hipLaunchKernelGGL(k_klt_track<8>, grid, block, 0, c->stream, A, (const float *)d, (float *)(d + o_out), d + o_st);
+    else hipLaunchKernelGGL(k_klt_track<16>, grid, block, 0, c->stream, A, (const float *)d, (float *)(d + o_out), d + o_st);
+    CKF(hipGetLastError());
+    CKF(hipMemcpyAsync(h + o_out, d + o_out, tot - o_out, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipStreamSynchronize(c->stream));
+    memcpy(next_xy, h + o_out, 8*(size_t)n); memcpy(status, h + o_st, (size_t)n);
     return TSFRAME_OK;
 }
 

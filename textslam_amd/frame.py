@@ -5,6 +5,7 @@
   Frame.CalNormvec(level, uv, mu, std)                tool::CalNormvec          /root/reference/src/tool.cc:1342-1364 (GetNeighbour INTERVAL8)
   Frame.GetBoxAllPixs(level, vTextDete, mu, std, K)   tool::GetBoxAllPixs       /root/reference/src/tool.cc:1264-1337
   Frame.TextJudgeBatch(...)                           tracking::TextJudgeSingle /root/reference/src/tracking.cc:1991-2131 (n planes, one launch)
+  Frame.TrackKLT(prev_frame, pts, ...)                tracking::TrackNewTextFeat /root/reference/src/tracking.cc:1752-1785 (all points, one launch)
 
 No CPU fallback: without the HIP library / a GPU every call raises.
 """
@@ -15,7 +16,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libtsframe.so")
 EXPORTED_SYMBOLS = ["tsframe_create", "tsframe_destroy", "tsframe_last_error", "tsframe_set_image", "tsframe_level_size", "tsframe_level_ptr",
-                    "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_neighbours", "tsframe_box_pixels", "tsframe_text_judge"]
+                    "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_neighbours", "tsframe_box_pixels", "tsframe_text_judge", "tsframe_klt_track"]
 IMG, GRAD, GRADX, GRADY = 0, 1, 2, 3
 JUDGE_PASS, JUDGE_ORIENT, JUDGE_DEPTH, JUDGE_BOX, JUDGE_ZNCC = 0, 1, 2, 3, 4
 
@@ -42,6 +43,8 @@ def _load():
     L.tsframe_text_judge.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, ip, C.POINTER(C.c_int16), up, dp, dp, C.c_double, C.c_int, C.c_double,
                                      C.c_int, dp, up, ip, dp, dp, dp, C.POINTER(C.c_uint32)]
     L.tsframe_text_judge.restype = C.c_int
+    L.tsframe_klt_track.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_float), up]
+    L.tsframe_klt_track.restype = C.c_int
     return L
 
 
@@ -162,3 +165,14 @@ class Frame:
             j = np.arange(nd)
             out["dete"] = ((b[:, j // 32] >> (j % 32).astype(np.uint32)) & 1).astype(bool) if nd else np.zeros((n, 0), bool)
         return out
+
+    def TrackKLT(self, prev_frame, pts, win=21, max_level=3, max_iter=30, eps=0.01, min_eig=1e-4):
+        """cv::calcOpticalFlowPyrLK(prev_frame, this frame, pts) on the two resident pyramids in one launch (include/tsframe.h: tsframe_klt_track;
+        the arithmetic is docs/klt_recalled.md).  pts [n, 2] float32 level-0 positions in prev_frame, all detections concatenated.
+        Returns (next_xy float32 [n, 2], status uint8 [n])."""
+        xy = np.ascontiguousarray(pts, np.float32).reshape(-1, 2); n = len(xy)
+        nxt = np.zeros((max(n, 1), 2), np.float32); st = np.zeros(max(n, 1), np.uint8)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.tsframe_klt_track(prev_frame.ctx, self.ctx, n, xy.ctypes.data_as(fp), int(win), int(max_level), int(max_iter), float(eps),
+                                               float(min_eig), nxt.ctypes.data_as(fp), _up(st)), "tsframe_klt_track")
+        return nxt[:n], st[:n]
