@@ -157,7 +157,7 @@ typedef struct tsba_report {
     int64_t n_sblock[TSBA_MAX_LEVELS], n_tblock[TSBA_MAX_LEVELS];   /* residual blocks in the problem */
     int64_t n_resid_evals;                 /* scalar residuals evaluated, one count per LM trial step + linearisation */
     int32_t n_bad_scene[TSBA_MAX_LEVELS], n_bad_tfeat[TSBA_MAX_LEVELS], n_bad_text[TSBA_MAX_LEVELS];
-    double  t_upload_ms, t_solve_ms, t_download_ms;
+    double  t_upload_ms, t_solve_ms, t_download_ms;   /* t_solve_ms: the whole of tsba_solve -- of a pose-only solve that was run again after a give-up (poll_timeouts) both attempts */
     int32_t cov_valid;                     /* tsba_theta_optim: 1 = cov[] was written, 0 = singular information matrix (cov untouched) */
     /* How the reduced camera system S dx = -g was solved (the reference hands it to Ceres' sparse Cholesky, optimizer.cc:1833-1840, which
      * either solves it or fails the step).  Every path below is an exact solve except TSBA_SOLVER_BAND_PCG, which iterates to a relative

@@ -260,3 +260,82 @@ def test_a_device_too_small_for_the_grid_takes_the_launch_per_step_path(gpu, map
         assert small[0]["iters"] == ref[0]["iters"] and small[0]["accepted"] == ref[0]["accepted"]
         assert abs(small[0]["cost1"][0] - ref[0]["cost1"][0]) <= 1e-6*ref[0]["cost1"][0]
         assert np.array_equal(small[2][0][:, 3], ref[2][0][:, 3])                     # the same decisions
+
+
+# ---- the pose-only retry: a give-up anywhere during a k_pose_pass solve discards the answer and runs the solve again with a launch per LM step.  No test can
+# make a poll run into its bound, so tsba_debug_options.pass_launches = 2 has the host treat the first (production) attempt as abandoned.
+_REPORT_KEYS = ("status", "n_passes", "solver_path", "n_resid_evals", "iters", "accepted", "termination", "cost0", "cost1", "n_sblock", "n_tblock",
+                "n_bad_scene", "n_bad_tfeat", "n_bad_text")
+_ARRAYS = ("pose", "rho", "theta", "sgood", "tobs_good", "tfgood")
+
+
+def _pose_run(g, P, o, oneshot, upload=True, **dbg):
+    """One PoseOptim of P under the debug switches `dbg` (none: production) -> (report, the problem after the solve)."""
+    G = P.copy()
+    g.debug_set(**dbg)
+    try:
+        if oneshot:
+            rep = g.PoseOptim(G, options=o)
+        else:
+            if upload:
+                g.upload(P, o)
+            rep = g.solve(); g.download(G)
+    finally:
+        g.debug_set()
+    return rep, G
+
+
+def _same_bits(a, b):
+    for k in _REPORT_KEYS:
+        assert a[0][k] == b[0][k], (k, a[0], b[0])
+    for k in _ARRAYS:
+        assert np.array_equal(getattr(a[1], k), getattr(b[1], k)), k
+
+
+@pytest.fixture(scope="module")
+def pose_ref(gpu):
+    """config_c3 through PoseOptim, resident and one-shot: production (k_pose_pass) and a launch per LM step (pass_launches = 1, twice: the second run is warm)."""
+    P, o = synth.config_c3(), abi.options_pose()
+    ref = {}
+    for oneshot in (False, True):
+        ref[oneshot] = {"production": _pose_run(gpu, P, o, oneshot),
+                        "per_step": [_pose_run(gpu, P, o, oneshot, pass_launches=1) for _ in range(2)]}
+        _same_bits(*ref[oneshot]["per_step"])
+        assert all(r[0]["poll_timeouts"] == 0 for r in [ref[oneshot]["production"]] + ref[oneshot]["per_step"])
+        assert sum(ref[oneshot]["production"][0]["iters"]) > 0
+    return P, o, ref
+
+
+@pytest.mark.parametrize("oneshot", [False, True], ids=["resident", "oneshot"])
+def test_pose_retry_runs_a_launch_per_step_and_leaves_no_state(gpu, pose_ref, oneshot):
+    """pass_launches = 2: the first attempt is abandoned by the host, the second is k_pose_iter end to end -- the bits of a pass_launches = 1 run; the report says that
+    an attempt was abandoned (poll_timeouts == 1) and its time covers both attempts; the next production solve is the production result bit for bit."""
+    P, o, ref = pose_ref
+    per_step = ref[oneshot]["per_step"]
+    retried = _pose_run(gpu, P, o, oneshot, pass_launches=2)
+    print("t_solve_ms retried", retried[0]["t_solve_ms"], "per step", [r[0]["t_solve_ms"] for r in per_step])
+    _same_bits(retried, per_step[1])
+    assert retried[0]["poll_timeouts"] == 1
+    assert retried[0]["t_solve_ms"] >= min(r[0]["t_solve_ms"] for r in per_step)
+    after = _pose_run(gpu, P, o, oneshot, upload=False)           # (resident: on the upload the retry ran on)
+    assert after[0]["poll_timeouts"] == 0
+    _same_bits(after, ref[oneshot]["production"])
+
+
+def test_pose_retry_in_a_one_rank_local_group_returns(pose_ref):
+    """A context joined to local_group_create(1) holds the group's device token (a plain mutex) for the whole of tsba_solve: a retry that entered tsba_solve again
+    would wait for it for ever.  The call runs on a daemon thread, so that a deadlock fails the assertion instead of stopping the session."""
+    from textslam_amd.optimizer import Optimizer, local_group_create, local_group_destroy
+    P, o, ref = pose_ref
+    out = {}
+
+    def run():
+        g = Optimizer(0); group = local_group_create(1)
+        g.comm_init_local(group, 0, 1)
+        out["retried"] = _pose_run(g, P, o, False, pass_launches=2)
+        local_group_destroy(group); g.close()
+    th = threading.Thread(target=run, daemon=True)
+    th.start(); th.join(timeout=30)
+    assert not th.is_alive(), "tsba_solve did not return within 30 s"
+    assert out["retried"][0]["poll_timeouts"] == 1
+    _same_bits(out["retried"], ref[False]["per_step"][1])
