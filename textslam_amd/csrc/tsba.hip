@@ -13,6 +13,9 @@
 //                      one wave per (KF, text) observation of up to 64 photometric blocks
 //   k_mid     per landmark V, b and the host-pose column of W; per pair the host-side products
 //   k_postlin pose diagonal / gradient, Jacobi scaling, cost, gradient tolerance
+// Windows on one GPU (at most SCHUR_KEEP_KF keyframes) run a trial as FOUR launches: k_schur_t<4> (assembly; one more workgroup takes the full decision on the
+// previous trial: new state, poses' rows, trace) | k_solve_back (solver + back-substitution) | k_linearize at the candidate | k_mid (+ its decision block: the light
+// decision on this trial -- accept / reject, radius, current linearisation -- left in W.dec for the next k_schur_t<4>); k_decide only behind a pass's last trial.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -697,7 +700,7 @@ static int upload_impl(void *ctx, const tsba_problem *p, const tsba_options *o, 
     AL(W.partial, 2*(size_t)c->nb_back_max);
     AL(W.posepart, 2*((size_t)p->n_kf/21 + 2));
     AL(W.cntpart, 2*(mx_cnt/4 + mx_cnt/256 + 4));
-    AL(W.st, 2); c->st_base = W.st;
+    AL(W.st, 2); c->st_base = W.st; AL(W.dec, 1);
     W.st_next = (W.dp_poll && p->n_kf <= SCHUR_KEEP_KF) ? W.st + 1 : nullptr;        // windows on one GPU: k_schur_t takes the previous trial's decision itself (the two copies of the state swap roles after that launch)
     AL(c->cov_log, 6*TSBA_MAX_LEVELS);
     flush_run(c);
@@ -906,6 +909,10 @@ static void mid_blocks(const Ctx *c, const LevelDev &D, int &nb_pt, int &nb_tx, 
 static int pose_parts(const Ctx *c) { return c->n_kf > 126 ? (c->n_kf + 20)/21 : 0; }    // k_pose_sums workgroups (0: the pose sums stay in k_postlin / k_decide)
 // pairs with a dozen scene blocks (large maps): four pairs per wave
 static bool lin_small_pairs(const Ctx *c, const LevelDev &D) { return !c->dbg.no_small_pairs && D.n_pair > 0 && (long long)D.n_sc <= 24LL*D.n_pair; }
+static bool fused_decisions(const Ctx *c, const LevelDev &D);
+// windows on one GPU with one-wave k_mid blocks: a speculative k_mid launch carries the decision block (decision_block, tsba_kernels_lin.h) and the k_schur_t<4>
+// behind it reads the record it leaves (SchurDec.on = 3).  tsba_debug_options.trial_launches = 1 / 2 (128-thread blocks, k_lin_mid) keep the decision inside k_schur_t (on = 1)
+static bool decision_in_mid(const Ctx *c, const LevelDev &D) { return fused_decisions(c, D) && mid_threads(c) == 64; }
 static void launch_linearize(Ctx *c, const LevelDev &D, int spec, bool skip_postlin = false) {      // skip_postlin: windows -- the first k_schur_t of the pass does k_postlin's work (SchurDec.on = 2)
     struct XL { Ctx *c; size_t x0; ~XL() { c->x_lin = c->x_acc - x0; } } xl{c, c->x_acc};
     Work &W = c->W;
@@ -926,9 +933,13 @@ static void launch_linearize(Ctx *c, const LevelDev &D, int spec, bool skip_post
         else if (lin_small_pairs(c, D)) LAUNCHK((k_linearize<MODE_FULL, 4>), dim3((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + D.n_tg + 7)/8)*8), dim3(LIN_T), 0, c->stream, W, D, spec);
         else LAUNCHK((k_linearize<MODE_FULL, 1>), dim3((((D.n_pair + LIN_NWV - 1)/LIN_NWV + D.n_tg + 7)/8)*8), dim3(LIN_T), 0, c->stream, W, D, spec);
     }
-    if (mid_threads(c) == MID_TW) LAUNCHK((k_mid<MID_TW, 6, MID_PR_MIN>), dim3(nb_pt + nb_tx + nb_pr), dim3(MID_TW), 0, c->stream, W, D, nb_pt, nb_tx, spec);
-    else if (mid_threads(c) == 64) LAUNCHK((k_mid<64, 6, MID_PR_MIN>), dim3(nb_pt + nb_tx + nb_pr), dim3(64), 0, c->stream, W, D, nb_pt, nb_tx, spec);
-    else LAUNCHK((k_mid<256, 4, MID_PR_MIN>), dim3(nb_pt + nb_tx + nb_pr), dim3(256), 0, c->stream, W, D, nb_pt, nb_tx, spec);
+    const MidDec md0{0, 0, 0, tsba_options{}};
+    if (mid_threads(c) == MID_TW) LAUNCHK((k_mid<MID_TW, 6, MID_PR_MIN>), dim3(nb_pt + nb_tx + nb_pr), dim3(MID_TW), 0, c->stream, W, D, nb_pt, nb_tx, spec, md0);
+    else if (mid_threads(c) == 64) {                  // (a speculative launch: + the decision block, which takes the trial's light decision for the next k_schur_t<4>)
+        const int dec_on = spec && decision_in_mid(c, D) ? 1 : 0;
+        LAUNCHK((k_mid<64, 6, MID_PR_MIN>), dim3(nb_pt + nb_tx + nb_pr + dec_on), dim3(64), 0, c->stream, W, D, nb_pt, nb_tx, spec,
+                dec_on ? MidDec{1, nb_pr, back_blocks_pt(c->n_pt) + back_blocks_tx(c->n_text) + nb_kf, c->opt} : md0);
+    } else LAUNCHK((k_mid<256, 4, MID_PR_MIN>), dim3(nb_pt + nb_tx + nb_pr), dim3(256), 0, c->stream, W, D, nb_pt, nb_tx, spec, md0);
     const int multi = is_multi(c);
     const int npp = pose_parts(c);
     if (multi) {
@@ -952,7 +963,7 @@ static void launch_schur(Ctx *c, const LevelDev &D, int multi, SchurDec dec = Sc
         if (D.n_tg > 0) LAUNCHK(k_schur_quad<true>, dim3(nq + ng), dim3(64), 0, c->stream, c->W, D, multi, nq, ng);
         else LAUNCHK(k_schur_quad<false>, dim3(nq + ng), dim3(64), 0, c->stream, c->W, D, multi, nq, ng);
     } else if (c->n_kf > 126) LAUNCHK(k_schur_t<1>, dim3(D.n_sb + c->n_kf), dim3(64), 0, c->stream, c->W, D, multi, 0, SchurDec{0, 0, 0, tsba_options{}});
-    else LAUNCHK(k_schur_t<4>, dim3(D.n_sb + c->n_kf), dim3(256), 0, c->stream, c->W, D, multi, 0, dec);
+    else LAUNCHK(k_schur_t<4>, dim3(D.n_sb + c->n_kf + (dec.on == 3 ? 1 : 0)), dim3(256), 0, c->stream, c->W, D, multi, 0, dec);      // (on = 3: + the workgroup of the full decision)
     if (D.far_B > 0 && D.n_far > 0) {            // the blocks of E (what couples different clusters of a landmark): the same kernels on the fb_* lists, stored to W.Sfar
         LevelDev E = D;
         E.n_sb = D.n_far; E.sb_a = D.far_a; E.sb_b = D.far_b; E.sb_pab = D.fb_pab; E.sb_pba = D.fb_pba; E.sb_far = D.fb_id;
@@ -1394,7 +1405,7 @@ static void launch_step(Ctx *c, const LevelDev &D, bool decide_prev = false, boo
     const int bb_pt = back_blocks_pt(c->n_pt), bb_tx = back_blocks_tx(c->n_text), nb_all = bb_pt + bb_tx + nb_kf;      // k_back's blocks
     const bool fused_decide = fused_decisions(c, D);
     if (fused_decide && (decide_prev || first_fused)) {     // (first_fused: the pass's first trial -- workgroup 0 of the assembly does k_postlin's work on the first linearisation, nobody decides anything)
-        launch_schur(c, D, 0, SchurDec{decide_prev ? 1 : 2, nb_all, nb_pt + nb_tx + nb_pr, c->opt});
+        launch_schur(c, D, 0, SchurDec{decide_prev ? (decision_in_mid(c, D) ? 3 : 1) : 2, nb_all, nb_pt + nb_tx + nb_pr, c->opt});
         std::swap(W.st, W.st_next);                 // from here on the launches see the state that launch wrote
     } else launch_schur(c, D, (int)is_multi(c));
     if (is_multi(c)) {                             // one exchange per LM trial: the reduced normal equations

@@ -744,6 +744,26 @@ __device__ __forceinline__ void mid_lds_fence() {           // order this wave's
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 #define PT_PAIRN 6                          // entries of L.pt_pair4 per point
+// One row of a pair's sums on a lane of k_mid's one-wave pair block: the scene blocks' value *a0 plus the pair's text groups [tq0, tq1) of `row` IN ORDER, eight groups in
+// flight (a lane that holds no sum -- on = false -- adds zeros).  In two halves, so that a caller can put the first requests of several rows in flight together.
+// mid_block (lane 27: the pair's cost) and decision_block share them: the decision block forms the candidate's cost partials with this very expression.
+__device__ __forceinline__ void pair_row_load(const double *a0, const double *row, const int tq0, const int ntg, double &m0, double g8[8]) {
+    m0 = *a0;
+#pragma unroll
+    for (int u = 0; u < 8; u++) g8[u] = ntg > 0 ? row[min(tq0 + u, ntg - 1)] : 0.0;
+}
+__device__ __forceinline__ double pair_row_sum(const double m0, double g8[8], const double *row, const int tq0, const int tq1, const int ntg, const bool on) {
+    double m = m0;
+#pragma unroll
+    for (int u = 0; u < 8; u++) m += (on && tq0 + u < tq1) ? g8[u] : 0.0;
+    for (int q0 = tq0 + 8; q0 < tq1; q0 += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) g8[u] = row[min(q0 + u, ntg - 1)];
+#pragma unroll
+        for (int u = 0; u < 8; u++) m += (on && q0 + u < tq1) ? g8[u] : 0.0;
+    }
+    return m;
+}
 // MID_PR lanes per pair (4.  16 was measured on C4 -- ~90 pairs at a level, up to ~20 text groups each --: 8.65 against 7.63 us: two more shuffle steps over 27 values and
 // stores predicated sixteen ways cost a lone wave more than the group loop's extra round trip; tools/mid_stamps.sh)
 template <int NT, int U, int MID_PR>
@@ -912,19 +932,9 @@ __device__ __forceinline__ void mid_block(const Work &W, const LevelDev &L, cons
             const bool isM = k < 27, isS = k < 28, isR = k >= 32 && k < 41;
             const double *row = isM ? B.tgM + (size_t)k*ntg : B.tgCost;
             const double *a0 = isM ? B.pairM + (size_t)k*L.n_pair + p : (isR ? &PAIRR(B, p, k - 32, L.n_pair) : B.pairCost + p);
-            double g8[8];
-            const double m0 = *a0;
-#pragma unroll
-            for (int u = 0; u < 8; u++) g8[u] = ntg > 0 ? row[min(tq0 + u, ntg - 1)] : 0.0;
-            double m = m0;
-#pragma unroll
-            for (int u = 0; u < 8; u++) m += (isS && tq0 + u < tq1) ? g8[u] : 0.0;
-            for (int q0 = tq0 + 8; q0 < tq1; q0 += 8) {
-#pragma unroll
-                for (int u = 0; u < 8; u++) g8[u] = row[min(q0 + u, ntg - 1)];
-#pragma unroll
-                for (int u = 0; u < 8; u++) m += (isS && q0 + u < tq1) ? g8[u] : 0.0;
-            }
+            double g8[8], m0;
+            pair_row_load(a0, row, tq0, ntg, m0, g8);
+            const double m = pair_row_sum(m0, g8, row, tq0, tq1, ntg, isS);
             if (k == 27) cs = m;
             if (k < 27) { xs[k] = m; B.pairOut[(size_t)k*L.n_pair + p] = m; }
             if (isR) xs[k] = ph_ >= 0 ? m : 0.0;
@@ -1046,9 +1056,107 @@ __device__ __forceinline__ void mid_block(const Work &W, const LevelDev &L, cons
 #endif
 }
 #define MID_TW LIN_T                         // (128 with LIN_TPL = 4)
+// ---- windows on one GPU, one-wave blocks: the DECISION BLOCK of a speculative k_mid launch -- one more wave in front of the launch's point / plane / pair blocks.
+// The next k_schur_t<4> takes the decision on this trial (accept / reject, trust region: lm_decide), and none of its assembling workgroups can request a slot
+// record before it knows which linearisation is current and what the radius is.  Everything that part of the decision is made of exists when this launch
+// starts: the candidate's costs (k_linearize: pairCost, tgCost), the step and model-change partials (k_solve_back: W.partial) and the state with its failure
+// flag (*W.st: the state that k_schur_t will see).  So this wave takes the "light" decision in the shadow of the launch's other blocks (which are bound by
+// their two round trips and do not need it) and leaves the outcome in W.dec; the state is NOT written -- the full decision (gradient maximum, |x|^2, the
+// gradient-tolerance exit, the new state, the trace) stays in k_schur_t, with one workgroup that assembles nothing.
+// Same bits as postlin_fused + lm_decide by construction: the cost partial of pair block k is what mid_block leaves in lmpart[3 k + 2] (pair_row_load /
+// pair_row_sum on lane 27; the block's other lanes and the point / plane blocks contribute +0.0), virtual thread t of postlin_fused's 256 adds the entries
+// t, t + 256, ... in that order, lane l carries the virtual threads l, l + 64, l + 128, l + 192 and adds them (r[l] + r[l+64]) + (r[l+128] + r[l+192]), then wave_sum1.
+template <class S> __device__ __forceinline__ double lm_decide(S &s, double cost, double step2, double mcc, double gmax_c, double xn_c, const tsba_options &o);      // (tsba_kernels_step.h)
+struct MidDec { int on, nb_pr, nb_back; tsba_options o; };      // on: the launch has a decision block (block 0, dispatched first: the point / plane / pair blocks follow from block 1); nb_back: k_solve_back's partials
+#define DEC_STAGE 16                        // cost values per lane the decision block stages through LDS: windows of up to 1024 pairs + text groups at a level (C4: ~900)
+__device__ __forceinline__ void decision_block(const Work &W, const LevelDev &L, const int nb_pt, const int nb_tx, const MidDec &md, double *dcs /* [64*DEC_STAGE] */) {
+#ifdef MID_STAMPS                           // (tools/mid_stamps.sh: W.dbg[44] cycles to the state, [45] to the record's store, [46] blocks)
+    const long long ds_t0 = clock64();
+#endif
+    const int lane = threadIdx.x, nb0 = nb_pt + nb_tx, nb_lm = nb0 + md.nb_pr, nb_back = md.nb_back, np = L.n_pair, ntg = L.n_tg, nv = np + ntg;
+    // ONE round trip: the state, the static text-group ranges of this lane's pair blocks, this lane's step / model-change partials -- and the costs (pairCost | tgCost)
+    // of BOTH linearisation buffers, lane-contiguous: which one holds the candidate is in the state, and waiting for it would be a second, dependent round trip
+    // (2 x 7 KB on C4).  The candidate's then cross through LDS, where the pairs' in-order sums cost LDS latencies.  A level with more than 64 DEC_STAGE pairs + text
+    // groups takes them from memory behind the state instead: the same sums, two round trips and a pair's scattered groups more.
+    const bool staged = nv <= 64*DEC_STAGE;
+    int r0[4], r1[4]; double ps[4], pm[4], v0[DEC_STAGE], v1[DEC_STAGE];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int k = lane + 64*q, pc = min(max(k - nb0, 0), max(np - 1, 0)), kb = min(k, max(nb_back - 1, 0));
+        r0[q] = np > 0 ? L.pair_tg_off[pc] : 0; r1[q] = np > 0 ? L.pair_tg_off[pc + 1] : 0;
+        ps[q] = W.partial[2*kb]; pm[q] = W.partial[2*kb + 1];
+    }
+    if (staged && nv > 0) {                                     // (uniform)
+#pragma unroll
+        for (int u = 0; u < DEC_STAGE; u++) {
+            const int i = min(lane + 64*u, nv - 1);
+            v0[u] = i < np ? W.lb[0].pairCost[i] : W.lb[0].tgCost[i - np]; v1[u] = i < np ? W.lb[1].pairCost[i] : W.lb[1].tgCost[i - np];
+        }
+    }
+    LmState s = *W.st;
+    if (s.done) return;                                         // (a finished pass: k_schur_t returns on the state, nobody reads the record)
+#ifdef MID_STAMPS
+    if (lane == 0) atomicAdd((unsigned long long *)&W.dbg[44], (unsigned long long)(clock64() - ds_t0));
+#endif
+    const LinBuf &B = W.lb[s.lcur ^ 1];
+    const double *pcost = B.pairCost, *tcost = B.tgCost;
+    if (staged) {
+        if (nv > 0) {
+#pragma unroll
+            for (int u = 0; u < DEC_STAGE; u++) if (lane + 64*u < nv) dcs[lane + 64*u] = (s.lcur ^ 1) ? v1[u] : v0[u];
+        }
+        mid_lds_fence();
+        pcost = dcs; tcost = dcs + np;
+    }
+    double cost[4] = {0.0, 0.0, 0.0, 0.0}, step2[4] = {0.0, 0.0, 0.0, 0.0}, mcc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 4; q++) if (lane + 64*q < nb_back) { step2[q] += ps[q]; mcc[q] += pm[q]; }
+    for (int k0 = 256; k0 < nb_back; k0 += 256) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) { const int k = k0 + lane + 64*q; if (k < nb_back) { step2[q] += W.partial[2*k]; mcc[q] += W.partial[2*k + 1]; } }
+    }
+    // the candidate's cost partials: four k_mid blocks per lane, the pair blocks' first requests in flight together
+    for (int k0 = 0; k0 < nb_lm; k0 += 256) {
+        double m0[4], g8[4][8];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int k = k0 + lane + 64*q, pc = min(max(k - nb0, 0), max(np - 1, 0));
+            if (k0 > 0 && np > 0) { r0[q] = L.pair_tg_off[pc]; r1[q] = L.pair_tg_off[pc + 1]; }
+            if (np > 0 && k0 + 64*q + 63 >= nb0 && k0 + 64*q < nb_lm) pair_row_load(pcost + pc, tcost, r0[q], ntg, m0[q], g8[q]);      // (uniform: this quarter of the wave holds a pair block)
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int k = k0 + lane + 64*q;
+            double c = 0.0;                                     // (a point or a plane block's cost partial)
+            if (k >= nb0 && k < nb_lm) c = pair_row_sum(m0[q], g8[q], tcost, r0[q], r1[q], ntg, true) + 0.0;      // (+ 0.0: the block's other lanes in mid_block's wave reduction)
+            if (k < nb_lm) cost[q] += c;
+        }
+    }
+    const double cost_ = wave_sum1((cost[0] + cost[1]) + (cost[2] + cost[3]));
+    const double step2_ = wave_sum1((step2[0] + step2[1]) + (step2[2] + step2[3]));
+    const double mcc_ = wave_sum1((mcc[0] + mcc[1]) + (mcc[2] + mcc[3]));
+    if (lane == 0) {
+        const int lcur0 = s.lcur;
+        s.lin_done = 0;
+        lm_decide(s, cost_, step2_, mcc_, __builtin_inf(), 0.0, md.o);      // (on this wave's private copy of the state; no gradient-tolerance exit from the light decision)
+        LmDec *d = W.dec;
+        d->radius = s.radius; d->done = s.done; d->lcur = s.lcur; d->fresh = s.lcur != lcur0;
+#ifdef MID_STAMPS
+        atomicAdd((unsigned long long *)&W.dbg[45], (unsigned long long)(clock64() - ds_t0)); atomicAdd((unsigned long long *)&W.dbg[46], 1ull);
+#endif
+    }
+}
 template <int NT, int U, int PR>
-__global__ __launch_bounds__(NT) void k_mid(Work W, LevelDev L, int nb_pt, int nb_tx, int spec) {
+__global__ __launch_bounds__(NT) void k_mid(Work W, LevelDev L, int nb_pt, int nb_tx, int spec, MidDec md) {
     __shared__ double red[NT < 80 ? 80 : NT];
+    if constexpr (NT == 64) {
+        __shared__ double dcs[64*DEC_STAGE];
+        if (md.on) {
+            if (blockIdx.x == 0) { decision_block(W, L, nb_pt, nb_tx, md, dcs); return; }
+            mid_block<NT, U, PR>(W, L, nb_pt, nb_tx, spec, (int)blockIdx.x - 1, true, red);
+            return;
+        }
+    }
     mid_block<NT, U, PR>(W, L, nb_pt, nb_tx, spec, (int)blockIdx.x, true, red);
 }
 

@@ -12,6 +12,10 @@
 // gradient rows), applies the Ceres rules to its private copy of the state and goes on with the outcome; workgroup 0 also stores the rows and writes the
 // new state to W.st_next (the host passes that copy as W.st from the next launch on).  k_decide as a launch of its own was 9.0 us + a gap per trial;
 // inside this launch its round trip runs next to the list fetches of the assembly.
+// dec.on:  0 no decision here (large maps, several GPUs: k_decide) | 2 the pass's first trial: workgroup 0 does k_postlin's work | 1 every workgroup takes the light
+// decision itself and workgroup 0 the full one (128-thread k_mid blocks: tsba_debug_options.trial_launches = 1 / 2) | 3 PRODUCTION: the light decision was taken by the
+// decision block of the k_mid launch before this one (tsba_kernels_lin.h) -- the assembling and gradient workgroups read its record (W.dec) with the state and start from
+// a decided state; one more workgroup (grid n_sb + n_kf + 1) takes the full decision, stores the state, the poses' rows and the trace, and assembles nothing.
 struct SchurDec { int on, nb_back, nb_lm; tsba_options o; };
 template <class S> __device__ __forceinline__ double lm_decide(S &s, double cost, double step2, double mcc, double gmax_c, double xn_c, const tsba_options &o);
 __device__ __forceinline__ void lm_decide_publish(const Work &W, const LmState &s, double cost, double mcc_half, double verdict);
@@ -51,6 +55,8 @@ __global__ __launch_bounds__(64*SCHUR_NW) void k_schur_t(Work W, LevelDev L, int
             pre.t0 = L.pose_t_off[pre.a]; pre.t1 = L.pose_t_off[pre.a+1]; pre.h0 = L.pose_h_off[pre.a]; pre.h1 = L.pose_h_off[pre.a+1];
         }
     }
+    LmDec rec = LmDec{0.0, 0, 0, 0, 0};                         // (dec.on == 3: the light decision's record, requested with the state and the block's own entries)
+    if constexpr (SCHUR_NW == 4) { if (dec.on == 3) rec = *W.dec; }
     LmState *st = W.st;
     if (st->done) {                                             // (a finished pass: the launches the host still had in flight -- the other copy of the state has to say so too)
         if (SCHUR_NW == 4 && dec.on && blockIdx.x == 0 && threadIdx.x == 0) { const LmState s = *st; lm_state_store(W.st_next, s); }
@@ -108,26 +114,38 @@ __global__ __launch_bounds__(64*SCHUR_NW) void k_schur_t(Work W, LevelDev L, int
         // L2 at once: 18 - 24 k cycles of a 38 k-cycle kernel, tools/mid_stamps.sh) only decides the gradient-tolerance exit, which workgroup 0 keeps -- a
         // workgroup that misses it assembles a block nobody reads.  The rows a workgroup needs of the accepted candidate (its pose's damping / gradient) it
         // forms itself from the ranges it reads anyway, with the arithmetic of postlin_fused.
+        // dec.on == 3 (one-wave k_mid blocks): the light decision was taken by the decision block of the k_mid launch before this one (decision_block,
+        // tsba_kernels_lin.h) and its outcome is in W.dec, requested above with the state: the assembling and gradient workgroups sum nothing and decide nothing --
+        // with the stage-2 list indices there they go straight to the record gather.  The FULL decision is taken by a workgroup of its own behind them (grid
+        // n_sb + n_kf + 1) that assembles nothing: in front of workgroup 0's block it set the kernel's time.  Its accept / reject, radius and buffer are the
+        // record's bits: the same sums in the same order.  dec.on == 1 (128-thread k_mid blocks, tsba_debug_options.trial_launches = 1 / 2): as in round 6.
         double o5[5];
-        const bool full = blockIdx.x == 0;
+        const bool rec_on = dec.on == 3;
+        const bool full = rec_on ? (int)blockIdx.x == L.n_sb + W.n_kf : blockIdx.x == 0;
+        if (rec_on && !full) {
+            if (rec.done) return;
+            lcur_ = rec.lcur; radius_ = rec.radius; fresh = rec.fresh != 0;
+        } else {
         // (Measured and dropped: the block's tail -- pose-pair products / gradient row -- formed for BOTH outcomes before the decision, in flight with its partials.
         // A diagonal block's 36 lanes read 36 different rows of the pair products with every request: 2 x 48 requests x 36 cache lines through one compute
         // unit's vector cache cost 9 k cycles in front of the decision against the 4.5 k they take behind the gather: 15.9 against 14.0 us.)
         postlin_fused(W, L, W.lb[lcur_ ^ 1], W.pose[st->cur ^ 1], false, dec.nb_lm, dec.nb_back, lds, lds + 5*256, o5, 0, full, nullptr, !full);
-        if (blockIdx.x == 0 && W.dp_poll) for (int k = threadIdx.x; k <= W.N; k += SCHUR_T) W.dp[k] = __builtin_nan("");     // (k_solve_back: "not there yet")
+        if (full && W.dp_poll) for (int k = threadIdx.x; k <= W.N; k += SCHUR_T) W.dp[k] = __builtin_nan("");     // (k_solve_back: "not there yet")
         if (threadIdx.x == 0) {
             LmState s = *st;
             s.lin_done = 0;
             const double verdict = lm_decide(s, o5[2], o5[3], o5[4], full ? o5[0] : __builtin_inf(), full ? o5[1] : 0.0, dec.o);      // (no gradient-tolerance exit from the light decision)
             dsh_i[0] = s.done; dsh_i[1] = s.lcur; dsh_i[2] = s.lcur != lcur_; dsh_r = s.radius;
-            if (blockIdx.x == 0) {                               // the new state, every field but step_fail (zero since k_mid of the last trial; the workgroups of this launch may raise it)
+            if (full) {                                          // the new state, every field but step_fail (zero since k_mid of the last trial; the workgroups of this launch may raise it)
                 lm_state_store(W.st_next, s);
                 lm_decide_publish(W, s, o5[2], s.model_change, verdict);
             }
         }
+        if (rec_on) return;                                     // (the workgroup of the full decision assembles nothing)
         __syncthreads();
         if (dsh_i[0]) return;
         lcur_ = dsh_i[1]; radius_ = dsh_r; fresh = dsh_i[2] != 0;
+        }
         st = W.st_next;                                         // (where this trial's failure flag lives)
     } }
     // (b0 > 0: large maps take the S blocks through k_schur_quad and only the gradient part here, a grid of a multiple of 8 workgroups in

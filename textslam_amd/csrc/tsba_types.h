@@ -15,6 +15,11 @@ struct LmState {
     long long n_lin, n_cost;
 };
 
+// What the decision block of k_mid's launch (windows on one GPU, one-wave blocks: decision_block, tsba_kernels_lin.h) leaves for the assembling and gradient
+// workgroups of the NEXT k_schur_t<4> (SchurDec.on = 3): the outcome of the trial's accept / reject decision as far as the assembly depends on it -- the pass is
+// over, the linearisation that is current, whether that is the candidate just accepted, the trust-region radius.  The state itself is not touched by it.
+struct LmDec { double radius; int done, lcur, fresh, pad; };
+
 struct LevelDev {            // device copies of HostPlan + per-level inputs
     int level, n_sc, n_pair, n_tg, n_pslot, n_tslot, n_sb, n_tfeat, bw_rows;      // bw_rows: rows of S below a pose block that can be non-zero
     double K[4];             // K_l
@@ -109,7 +114,9 @@ struct Work {                // device work buffers (sized for the largest level
     int *cntpart;                       // per k_participation workgroup: active scene blocks, active text blocks
     double *posepart;                   // large maps: per k_pose_sums workgroup (21 poses): gradient max, |x|^2
     unsigned int *poll0;                // ts_poll_giveups at the start of the solve (k_reset_state)
-    LmState *st, *st_next;              // st_next (windows, single GPU; else null): the copy of the state that k_schur_t writes when it takes the previous trial's decision itself -- the host swaps the two after that launch
+    LmState *st, *st_next;              // st_next (windows, single GPU; else null): the copy of the state that k_schur_t writes when it takes the previous trial's decision itself (one workgroup that assembles
+                                        // nothing, or -- SchurDec.on = 1 -- workgroup 0) -- the host swaps the two after that launch
+    LmDec *dec;                         // (with st_next) the light decision's record: written by the decision block of a speculative k_mid launch, read by the k_schur_t<4> behind it
     PoseState *pst; double *ppart;      // pose-only path (tsba_pose.h): double-buffered state, [2][G][28] partial sums
     // band + long-range blocks, preconditioned conjugate gradients (tsba_pcg.h): the blocks outside the band [n_far][36] (rows: the earlier keyframe),
     // the iteration's vectors in the compressed row space of S, per-workgroup partial sums [2][workgroups], double-buffered scalars, statistics
