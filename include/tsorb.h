@@ -80,6 +80,24 @@ int tsorb_match_set_features(void *ctx, const float *kp6, const uint8_t *desc, i
 int tsorb_match_search(void *ctx, int nq, const float *qxy, const float *qr, const int32_t *qlev, const uint8_t *qdesc, int max_cand,
                        int32_t *cand_idx, int32_t *cand_dist, int32_t *cand_cnt, int32_t *best_idx, int32_t *best_dist, int32_t *best_dist2);
 
+/* ---- Text features of a frame.
+ * frame::FeatExtracText (src/frame.cc:334-355): for each of n_dete detection quads (level-0 pixels, double x, y; truncated like cv::Point)
+ * cv::ORB::create()->detect on the frame masked to the quad (tool::GetMask) and ->compute on the frame itself, OpenCV 3.3 defaults;
+ * docs/cvorb_recalled.md is the arithmetic.  frame = index in the resident batch (after tsorb_extract_batch / tsorb_upload + tsorb_run).
+ * nfeatures: 500 is the drop-in value.  kp [n_dete][cap][6] = x, y, size, angle, response (Harris), octave; desc [n_dete][cap][32];
+ * count [n_dete].  A detection with more than cap keypoints: TSORB_ERR_ARG with count[] complete and nothing written for that detection.
+ * Only the first count[d] rows of a detection's arrays are written.  The resident batch (scene keypoints, descriptors, pyramid, match grid) is
+ * left as it was.  TSORB_ERR_ARG also for: a NULL pointer with n_dete > 0, frame outside the batch or no batch resident, nfeatures < 1, cap < 1,
+ * a quad coordinate that is not finite (or beyond 2^30), level 0 larger than 640 x 480.  n_dete == 0 launches nothing.
+ * Two deliberate differences from OpenCV, both in docs/cvorb_recalled.md:
+ *   ties   OpenCV's retainBest(n) keeps the points at or above the response of whatever std::nth_element left at position n - 1, which depends on
+ *          the standard library; here a cut keeps EVERY point whose response is >= the n-th largest response (the superset of all those outcomes);
+ *   order  OpenCV's order inside a level is what nth_element and partition left; here it is level-major and, inside a level, raster order of the
+ *          level coordinates (y, then x).
+ * The -3-px boundary test of frame.cc:244 (tool::BoundFeatDele_T) stays with the caller. */
+int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad /*[n_dete][4][2]*/, int nfeatures, int cap,
+                       float *kp, uint8_t *desc, int32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,183 @@
+"""tsorb_text_extract on the device: bit-equal to the CPU restatement (tests/cvorb_ref.py, docs/cvorb_recalled.md) on the shared fixture -- count, order, the six
+keypoint fields as fp32 bit patterns, every descriptor byte --, every detection independent of the others in the call, the resident batch untouched, the
+capacity rule, every argument error, and the adapter's two ways of calling from C++."""
+import ctypes as C
+import os
+import struct
+import subprocess
+import sys
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cvorb_ref as R                                                 # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ex320():
+    """The 320 x 240 fixture image resident as frame 0 (the scene extraction's upload)."""
+    from textslam_amd.orbextractor import ORBextractor
+    ex = ORBextractor()
+    ex.extract_batch(R.fixture_image())
+    return ex
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _same(got, ref, what):
+    assert len(got) == len(ref), what
+    for d, ((kp, de), (rkp, rde)) in enumerate(zip(got, ref)):
+        n_bits = int((_bits(kp) != _bits(rkp)).any(1).sum()) if kp.shape == rkp.shape else -1
+        n_desc = int((de != rde).any(1).sum()) if de.shape == rde.shape else -1
+        print("%s detection %d: %d keypoints (restatement %d), per level %s, rows differing in a keypoint bit %d, in a descriptor byte %d"
+              % (what, d, len(kp), len(rkp), np.bincount(rkp[:, 5].astype(int), minlength=8).tolist(), n_bits, n_desc))
+        assert kp.dtype == np.float32 and de.dtype == np.uint8 and kp.shape == rkp.shape and de.shape == rde.shape, (what, d)
+        assert np.array_equal(_bits(kp), _bits(rkp)), (what, d)
+        assert np.array_equal(de, rde), (what, d)
+
+
+@pytest.mark.parametrize("nfeatures", [500, 60, 30])
+def test_bit_equal_to_the_restatement_320(ex320, nfeatures):
+    img, ref, _ = R.reference("320", nfeatures)
+    got = ex320.extract_text(0, R.QUADS_320, nfeatures)
+    _same(got, ref, "320 x 240, nfeatures %d," % nfeatures)
+    assert len(got[3][0]) == 0 and min(len(g[0]) for g in got[:3]) > 0          # the quad inside the 31-px border: no keypoint
+
+
+@pytest.mark.parametrize("nfeatures", [500, 60])
+def test_bit_equal_to_the_restatement_200(nfeatures):
+    from textslam_amd.orbextractor import ORBextractor
+    img, ref, _ = R.reference("200", nfeatures)
+    ex = ORBextractor(nlevels=4)                                       # (the scene extractor's own pyramid needs fewer levels on 200 x 150; cv::ORB's eight do not depend on it)
+    ex.extract_batch(img)
+    got = ex.extract_text(0, R.QUADS_200, nfeatures)
+    _same(got, ref, "200 x 150, nfeatures %d," % nfeatures)
+    lv = np.concatenate([g[0][:, 5] for g in got])
+    assert lv.max() == 4 and (lv == 4).any()                           # levels 5 - 7 contribute nothing, level 4 (96 x 72) does
+
+
+def test_detections_are_independent(ex320):
+    all4 = ex320.extract_text(0, R.QUADS_320, 500)
+    again = ex320.extract_text(0, R.QUADS_320, 500)
+    rev = ex320.extract_text(0, R.QUADS_320[::-1], 500)[::-1]
+    for d in range(4):
+        alone = ex320.extract_text(0, R.QUADS_320[d:d + 1], 500)[0]
+        for other in (again[d], rev[d], alone):
+            assert all4[d][0].tobytes() == other[0].tobytes() and all4[d][1].tobytes() == other[1].tobytes(), d
+    many = ex320.extract_text(0, np.concatenate([R.QUADS_320] * 5), 60)          # 20 detections, then fewer again: the scratch grows and is reused
+    few = ex320.extract_text(0, R.QUADS_320, 60)
+    for d in range(20):
+        assert many[d][0].tobytes() == few[d % 4][0].tobytes() and many[d][1].tobytes() == few[d % 4][1].tobytes(), d
+
+
+def test_resident_batch_unchanged(ex320):
+    rng = np.random.default_rng(11)
+    before = ex320.download()[0]
+    ex320.match_set_frame(0, (0.0, 320.0, 0.0, 240.0))
+    q = rng.choice(len(before[0]), 40, replace=False)
+    qxy = before[0][q, :2] + rng.uniform(-3, 3, (40, 2)).astype(np.float32)
+    args = (qxy, np.full(40, 12.0, np.float32), None, before[1][q])
+    m0 = ex320.match_search(*args)
+    lev0 = [ex320.debug_level(0, l).copy() for l in range(8)]
+    ex320.extract_text(0, R.QUADS_320, 500)
+    ex320.extract_text(0, R.QUADS_320[:1], 60)
+    m1 = ex320.match_search(*args)
+    after = ex320.download()[0]
+    assert before[0].tobytes() == after[0].tobytes() and before[1].tobytes() == after[1].tobytes()
+    assert all(m0[k].tobytes() == m1[k].tobytes() for k in m0)
+    assert all(np.array_equal(a, ex320.debug_level(0, l)) for l, a in enumerate(lev0))
+
+
+def _raw(ex, frame=0, n=None, quads=R.QUADS_320, nfeatures=500, cap=600, kp=True, desc=True, cnt=True, ctx=True):
+    quads = None if quads is None else np.ascontiguousarray(quads, np.float64)
+    n = (0 if quads is None else len(quads.reshape(-1, 4, 2))) if n is None else n
+    rows = max(n, 1)
+    o_kp = np.full((rows, max(cap, 1), 6), 7.0, np.float32); o_de = np.full((rows, max(cap, 1), 32), 0x5a, np.uint8); o_cn = np.full(rows, -77, np.int32)
+    rc = ex.lib.tsorb_text_extract(ex.ctx if ctx else None, frame, n, None if quads is None else quads.ctypes.data_as(C.POINTER(C.c_double)), nfeatures, cap,
+                                   o_kp.ctypes.data_as(C.POINTER(C.c_float)) if kp else None, o_de.ctypes.data_as(C.POINTER(C.c_uint8)) if desc else None,
+                                   o_cn.ctypes.data_as(C.POINTER(C.c_int32)) if cnt else None)
+    return rc, o_kp, o_de, o_cn
+
+
+def test_capacity(ex320):
+    img, ref, _ = R.reference("320", 500)
+    counts = [len(r[0]) for r in ref]
+    cap = counts[2] + 3                                                # enough for detection 2 (and 3), not for 0 and 1
+    assert counts[0] > cap and counts[1] > cap and counts[2] <= cap
+    rc, kp, de, cn = _raw(ex320, cap=cap)
+    assert rc == -1 and "cap" in ex320.lib.tsorb_last_error(ex320.ctx).decode()
+    assert cn.tolist() == counts                                       # complete counts
+    for d in (0, 1):
+        assert np.all(kp[d] == 7.0) and np.all(de[d] == 0x5a)          # nothing written for a detection that does not fit
+    for d in (2, 3):
+        assert np.array_equal(_bits(kp[d, :counts[d]]), _bits(ref[d][0])) and np.array_equal(de[d, :counts[d]], ref[d][1])
+        assert np.all(kp[d, counts[d]:] == 7.0) and np.all(de[d, counts[d]:] == 0x5a)      # and only count rows for one that does
+    rc, kp, de, cn = _raw(ex320, cap=max(counts))                      # exactly enough
+    assert rc == 0 and cn.tolist() == counts
+
+
+def test_arguments_and_edges(ex320):
+    from textslam_amd.orbextractor import ORBextractor, TsorbError
+    untouched = lambda r: bool(np.all(r[1] == 7.0) and np.all(r[2] == 0x5a) and np.all(r[3] == -77))
+    r = _raw(ex320); assert r[0] == 0 and not untouched(r)
+    r = _raw(ex320, n=0); assert r[0] == 0 and untouched(r)            # n_dete == 0: nothing to do
+    r = _raw(ex320, n=0, quads=None, kp=False, desc=False, cnt=False); assert r[0] == 0
+    nan = R.QUADS_320.copy(); nan[1, 2, 0] = np.nan
+    inf = R.QUADS_320.copy(); inf[0, 0, 1] = -np.inf
+    cases = [("ctx NULL", dict(ctx=False)), ("quad NULL", dict(quads=None, n=2)), ("kp NULL", dict(kp=False)), ("desc NULL", dict(desc=False)), ("count NULL", dict(cnt=False)),
+             ("frame -1", dict(frame=-1)), ("frame 1 of a batch of 1", dict(frame=1)), ("n_dete < 0", dict(n=-1)), ("nfeatures 0", dict(nfeatures=0)), ("cap 0", dict(cap=0)),
+             ("NaN corner", dict(quads=nan)), ("infinite corner", dict(quads=inf))]
+    for name, kw in cases:
+        r = _raw(ex320, **kw)
+        assert r[0] == -1 and untouched(r), name
+        if kw.get("ctx", True):
+            assert "tsorb_text_extract" in ex320.lib.tsorb_last_error(ex320.ctx).decode(), name
+    fresh = ORBextractor()                                             # no batch resident
+    r = _raw(fresh); assert r[0] == -1 and untouched(r)
+    fresh.upload(R.fixture_image())                                    # uploaded but not run: level 0 is not in place yet
+    r = _raw(fresh); assert r[0] == -1 and untouched(r)
+    big = ORBextractor(); big.extract_batch(np.pad(R.fixture_image(), ((0, 240), (0, 328)), mode="reflect"))     # 648 x 480: level 0 larger than 640 x 480
+    r = _raw(big); assert r[0] == -1 and untouched(r) and "640" in big.lib.tsorb_last_error(big.ctx).decode()
+    with pytest.raises(TsorbError):
+        fresh.extract_text(0, R.QUADS_320)
+    # edges: a zero-area quad (one pixel of mask: a lone bright pixel is a FAST corner, at every level it survives), a quad off the frame, the whole
+    # frame; after the errors the context still answers
+    zero = [[100.4, 100.9]] * 4
+    off = [[-90, -50], [-20, -50], [-20, -8], [-90, -8]]
+    got = ex320.extract_text(0, [zero, off, R.FULL_320], 500)
+    ref = R.Frame(R.fixture_image()).extract([zero, off, R.FULL_320], 500)
+    _same(got, ref, "edge quads,")
+    assert len(got[0][0]) <= 2 and len(got[1][0]) == 0 and got[1][0].shape == (0, 6) and got[1][1].shape == (0, 32) and len(got[2][0]) >= 400
+    assert ex320.extract_text(0, np.zeros((0, 4, 2))) == []
+    one = ex320.extract_text(0, R.QUADS_320[:1], 1)[0]                 # nfeatures 1: the quotas are 0 but for the last level
+    assert len(one[0]) >= 1 and (one[0][:, 5] == 7).all()
+
+
+def test_adapter_from_cxx(tmp_path, ex320):
+    exe = str(tmp_path / "text_orb_from_cxx")
+    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "adapter"),
+                           "-I" + os.path.join(ROOT, "tests", "cxx"), "-o", exe, os.path.join(ROOT, "tests", "cxx", "text_orb_from_cxx.cpp"),
+                           "-L" + os.path.join(ROOT, "textslam_amd"), "-ltsorb", "-L/opt/rocm/lib",
+                           "-Wl,-rpath," + os.path.join(ROOT, "textslam_amd"), "-Wl,-rpath,/opt/rocm/lib"])
+    img = R.fixture_image()
+    inp, outp = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(inp, "wb") as f:
+        f.write(struct.pack("<iiii", img.shape[1], img.shape[0], 8, len(R.QUADS_320)))
+        f.write(img.tobytes()); f.write(np.ascontiguousarray(R.QUADS_320, np.float64).tobytes())
+    res = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "text orb from C++: ok" in res.stdout, res.stdout
+    got = ex320.extract_text(0, R.QUADS_320, 500)                      # the Python mirror
+    raw = open(outp, "rb").read()
+    off = 0
+    for d in range(len(R.QUADS_320)):
+        (n,) = struct.unpack_from("<i", raw, off); off += 4
+        kp = np.frombuffer(raw, np.float32, 6 * n, off).reshape(n, 6); off += 24 * n
+        de = np.frombuffer(raw, np.uint8, 32 * n, off).reshape(n, 32); off += 32 * n
+        assert n == len(got[d][0]) and np.array_equal(_bits(kp), _bits(got[d][0])) and np.array_equal(de, got[d][1]), d
+    assert off == len(raw)

@@ -1448,6 +1448,8 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
     if (lane == 0) { cand_cnt[q] = nc; best_idx[q] = bi; best_dist[q] = bd; best_dist2[q] = bd2; }
 }
 
+#include "tscvorb.h"
+
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
     int nfeatures = 1000, nlevels = 8, ini_th = 20, min_th = 7; float scale = 1.2f;
@@ -1461,13 +1463,15 @@ struct OCtx {
     // the SLAM front-end calls once per frame with the same geometry: buffers and pinned staging are kept between calls
     MatchDev M; bool m_set = false; void *m_buf = nullptr; size_t m_cap = 0; void *m_feat = nullptr; size_t m_feat_cap = 0;   // search grid of the current frame
     void *mq_dev = nullptr, *mq_host = nullptr; size_t mq_cap = 0;
+    bool ran = false;                                                           // the resident batch has been through tsorb_run (its level 0 is in place)
+    CvoDev CV; int cv_w = 0, cv_h = 0, cv_nd = 0; void *cv_geo = nullptr, *cv_det = nullptr, *cv_sel = nullptr, *cv_pin = nullptr; size_t cv_sel_cap = 0, cv_pin_cap = 0;   // tsorb_text_extract's scratch, kept between calls
     int key[5] = {0, 0, 0, 0, 0}; uint8_t *h_img = nullptr; void *h_out = nullptr; size_t h_img_sz = 0, h_out_sz = 0;
 };
 static int cv_round_f(float v) { return (int)lrintf(v); }
 #define OCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); return TSORB_ERR_DEVICE; } } while (0)
 template <typename T> static int oalloc(OCtx *c, T **p, size_t n) { void *q = nullptr; if (hipMalloc(&q, std::max<size_t>(n, 1)*sizeof(T)) != hipSuccess) { c->err = "hipMalloc failed"; return TSORB_ERR_DEVICE; }
     c->allocs.push_back(q); *p = (T *)q; return 0; }
-static void ofree(OCtx *c) { hipStreamSynchronize(c->stream); for (void *p : c->allocs) hipFree(p); c->allocs.clear(); c->uploaded = false; c->key[0] = 0; c->m_set = false;
+static void ofree(OCtx *c) { hipStreamSynchronize(c->stream); for (void *p : c->allocs) hipFree(p); c->allocs.clear(); c->uploaded = false; c->ran = false; c->key[0] = 0; c->m_set = false;
     if (c->h_img) hipHostFree(c->h_img); if (c->h_out) hipHostFree(c->h_out); c->h_img = nullptr; c->h_out = nullptr; c->h_img_sz = c->h_out_sz = 0; }
 
 extern "C" {
@@ -1502,6 +1506,7 @@ int tsorb_create(void **ctx, int nfeatures, float scale, int nlevels, int ini_th
 }
 int tsorb_destroy(void *ctx) { OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG; hipSetDevice(c->device); ofree(c);
     if (c->h_fb) hipHostFree(c->h_fb);
+    if (c->cv_geo) hipFree(c->cv_geo); if (c->cv_det) hipFree(c->cv_det); if (c->cv_sel) hipFree(c->cv_sel); if (c->cv_pin) hipHostFree(c->cv_pin);
     if (c->m_buf) hipFree(c->m_buf); if (c->m_feat) hipFree(c->m_feat); if (c->mq_dev) hipFree(c->mq_dev); if (c->mq_host) hipHostFree(c->mq_host);
     hipStreamDestroy(c->stream); delete c; return TSORB_OK; }
 const char *tsorb_last_error(void *ctx) { return ctx ? ((OCtx *)ctx)->err.c_str() : "null ctx"; }
@@ -1514,6 +1519,7 @@ int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride
     OCtx *c = (OCtx *)ctx; if (!c || !imgs || n < 1 || w < 64 || h < 64 || stride < w || cap < 1) return TSORB_ERR_ARG;
     hipSetDevice(c->device);
     c->out_on_host = false;                                  // (until the next run)
+    c->ran = false;
     if (c->uploaded && c->key[0] == n && c->key[1] == w && c->key[2] == h && c->key[3] == stride && c->key[4] == cap) {
         // same geometry as the previous call: only the pixels travel (pinned staging, one asynchronous copy)
         memcpy(c->h_img, imgs, (size_t)n*h*stride);
@@ -1640,7 +1646,7 @@ int tsorb_run(void *ctx) {
     if (few) hipLaunchKernelGGL(k_orient_describe, dim3((D.n*D.slots_per_frame*32 + 255)/256), dim3(256), 0, c->stream, D);      // a few frames: orientation inside the descriptor launch
     else hipLaunchKernelGGL(k_describe, dim3((D.n*D.slots_per_frame*32 + 255)/256), dim3(256), 0, c->stream, D);
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    c->out_on_host = few;
+    c->out_on_host = few; c->ran = true;
     if (*(volatile int *)c->h_fb) {             // a level the LDS quadtree could not hold (counted as empty so far): the serial pass, then orientation and descriptors again with its keypoints in place
         c->fallbacks++;
         hipLaunchKernelGGL(k_octree_serial, dim3(D.n*D.nlevels), dim3(64), 0, c->stream, D);
@@ -1754,6 +1760,105 @@ int tsorb_match_search(void *ctx, int nq, const float *qxy, const float *qr, con
     if (best_dist) memcpy(best_dist, tail + 2*(size_t)nq, 4*(size_t)nq);
     if (best_dist2) memcpy(best_dist2, tail + 3*(size_t)nq, 4*(size_t)nq);
     return TSORB_OK;
+}
+
+// ---- frame::FeatExtracText: cv::ORB detect on the masked frame + compute on the frame, every detection of a frame in one call (tscvorb.h)
+int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int nfeatures, int cap, float *kp, uint8_t *desc, int32_t *count) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_text_extract: ") + m; return TSORB_ERR_ARG; };
+    if (!c->uploaded || !c->ran) return bad("no batch resident (tsorb_extract_batch, or tsorb_upload + tsorb_run, first)");
+    OrbDev &D = c->D;
+    if (frame < 0 || frame >= D.n) return bad("frame outside the resident batch");
+    if (n_dete < 0) return bad("n_dete < 0");
+    if (nfeatures < 1) return bad("nfeatures < 1");
+    if (cap < 1) return bad("cap < 1");
+    if (D.w > CVO_MAX_W || D.h > CVO_MAX_H) return bad("level 0 larger than 640 x 480");
+    if (n_dete == 0) return TSORB_OK;
+    if (!quad || !kp || !desc || !count) return bad("NULL pointer");
+    for (int i = 0; i < 8*n_dete; i++) if (!std::isfinite(quad[i]) || fabs(quad[i]) > 1073741824.0) return bad("quad coordinate not finite (or beyond 2^30)");
+    hipSetDevice(c->device);
+    CvoDev &C = c->CV;
+    const int nd = n_dete;
+    // ---- geometry: cv::ORB's levels, quotas, tiles (docs/cvorb_recalled.md); the planes shared by the detections
+    if (c->cv_w != D.w || c->cv_h != D.h) {
+        if (c->cv_geo) hipFree(c->cv_geo); if (c->cv_det) hipFree(c->cv_det); c->cv_geo = c->cv_det = nullptr; c->cv_nd = 0; c->cv_w = c->cv_h = 0;
+        memset(&C, 0, sizeof(C)); C.w = D.w; C.h = D.h;
+        size_t off = 0, boff = 0; int t0 = 0, rt = 0;
+        for (int l = 0; l < CVO_NL; l++) { CvoLevel &G = C.L[l];
+            G.scale = (float)pow((double)1.2f, (double)l); G.inv = 1.f/G.scale;
+            G.w = cv_round_f((float)D.w/G.scale); G.h = cv_round_f((float)D.h/G.scale);
+            G.ntx = (G.w + CVO_TS - 1)/CVO_TS; G.nty = (G.h + CVO_TS - 1)/CVO_TS; G.tile0 = t0; t0 += G.ntx*G.nty;
+            G.boff = boff; boff += (size_t)G.w*G.h;
+            if (l > 0) { G.off = off; off += (size_t)G.w*G.h; G.xt_off = rt; rt += 2*((G.w + 1) & ~1); G.yt_off = rt; rt += 4*G.h;
+                G.rsx = 1.0/((double)G.w/(double)C.L[l-1].w); G.rsy = 1.0/((double)G.h/(double)C.L[l-1].h); } }
+        C.ntiles = t0; C.m_stride = (off + 15) & ~(size_t)15;
+        const size_t bU = C.m_stride, bB = (boff + 15) & ~(size_t)15;
+        OCK(hipMalloc(&c->cv_geo, bU + bB + sizeof(int)*(size_t)rt));
+        C.U = (uint8_t *)c->cv_geo; C.B = C.U + bU; C.rtab = (int *)(C.B + bB);
+        memcpy(C.umax, c->umax, sizeof(C.umax)); memcpy(C.gk, c->gk, sizeof(C.gk));
+        hipLaunchKernelGGL(k_cvo_tab, dim3(CVO_NL - 1), dim3(256), 0, c->stream, C);
+        c->cv_w = D.w; c->cv_h = D.h;
+    }
+    {   // cv::ORB's quota per level for this call's nfeatures
+        const float factor = (float)(1.0/(double)1.2f);
+        float nf = nfeatures*(1 - factor)/(1 - (float)pow((double)factor, (double)CVO_NL)); int sum = 0;
+        for (int l = 0; l < CVO_NL - 1; l++) { C.L[l].quota = cv_round_f(nf); sum += C.L[l].quota; nf *= factor; }
+        C.L[CVO_NL - 1].quota = std::max(nfeatures - sum, 0);
+    }
+    const size_t NT = (size_t)C.ntiles;
+    if (c->cv_nd < nd) {
+        if (c->cv_det) hipFree(c->cv_det); c->cv_det = nullptr; c->cv_nd = 0;
+        const size_t per = 4*(size_t)MS_MASK_WORDS + 16*CVO_NL + C.m_stride + 2*4*NT*CVO_TCAP + 4*NT + 4*(size_t)CVO_NL*CVO_MAX_H + 4*CVO_NL + 8*CVO_NL;
+        OCK(hipMalloc(&c->cv_det, per*(size_t)nd)); c->cv_nd = nd;
+    }
+    {   uint8_t *p = (uint8_t *)c->cv_det; const size_t n = (size_t)c->cv_nd;          // (arrays sized for the largest call so far)
+        C.mask = (unsigned *)p; p += 4*(size_t)MS_MASK_WORDS*n; C.dfoot = (int *)p; p += 16*(size_t)CVO_NL*n; C.M = p; p += C.m_stride*n;
+        C.tkp = (uint32_t *)p; p += 4*NT*CVO_TCAP*n; C.tkey = (uint32_t *)p; p += 4*NT*CVO_TCAP*n; C.tcnt = (int *)p; p += 4*NT*n;
+        C.rowoff = (int *)p; p += 4*(size_t)CVO_NL*CVO_MAX_H*n; C.lvlcnt = (int *)p; p += 4*(size_t)CVO_NL*n; C.thr = (uint32_t *)p; }
+    const size_t need_sel = sizeof(float4)*(size_t)nd*cap;
+    if (c->cv_sel_cap < need_sel) { if (c->cv_sel) hipFree(c->cv_sel); c->cv_sel = nullptr; c->cv_sel_cap = 0; OCK(hipMalloc(&c->cv_sel, need_sel)); c->cv_sel_cap = need_sel; }
+    C.sel = (float4 *)c->cv_sel;
+    // ---- one pinned block: [corners | footprints] in, [count | kp | desc] out
+    const size_t b_in = 160*(size_t)nd, b_cnt = ((4*(size_t)nd + 15)/16)*16, b_kp = 24*(size_t)nd*cap, b_desc = 32*(size_t)nd*cap, tot = b_in + b_cnt + b_kp + b_desc;
+    if (c->cv_pin_cap < tot) { if (c->cv_pin) hipHostFree(c->cv_pin); c->cv_pin = nullptr; c->cv_pin_cap = 0; OCK(hipHostMalloc(&c->cv_pin, tot, hipHostMallocDefault)); c->cv_pin_cap = tot; }
+    char *h = (char *)c->cv_pin, *dp = nullptr;
+    { void *hd = nullptr; OCK(hipHostGetDevicePointer(&hd, c->cv_pin, 0)); dp = (char *)hd; }
+    int *h_quad = (int *)h, *h_foot = (int *)(h + 32*(size_t)nd);
+    for (int d = 0; d < nd; d++) {
+        int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
+        for (int k = 0; k < 4; k++) { const int x = (int)quad[8*d + 2*k], y = (int)quad[8*d + 2*k + 1];         // cv::Point(double, double): truncation
+            h_quad[8*d + 2*k] = x; h_quad[8*d + 2*k + 1] = y; x0 = std::min(x0, x); x1 = std::max(x1, x); y0 = std::min(y0, y); y1 = std::max(y1, y); }
+        // the footprint: the corners' bounding box inside the frame, then level by level every pixel whose two source columns / rows can touch the footprint
+        // above (with a pixel to spare on either side; an empty footprint is 1, 1, 0, 0)
+        int *F = h_foot + 32*(size_t)d;
+        x0 = std::max(x0, 0); y0 = std::max(y0, 0); x1 = std::min(x1, C.w - 1); y1 = std::min(y1, C.h - 1);
+        bool empty = x0 > x1 || y0 > y1;
+        for (int l = 0; l < CVO_NL; l++) {
+            if (l > 0 && !empty) { const CvoLevel &G = C.L[l];
+                x0 = std::max(0, (int)floor((x0 - 1.0)/G.rsx) - 1); x1 = std::min(G.w - 1, (int)ceil((x1 + 1.0)/G.rsx) + 1);
+                y0 = std::max(0, (int)floor((y0 - 1.0)/G.rsy) - 1); y1 = std::min(G.h - 1, (int)ceil((y1 + 1.0)/G.rsy) + 1);
+                empty = x0 > x1 || y0 > y1; }
+            F[4*l] = empty ? 1 : x0; F[4*l + 1] = empty ? 1 : y0; F[4*l + 2] = empty ? 0 : x1; F[4*l + 3] = empty ? 0 : y1;
+        }
+    }
+    C.nd = nd; C.cap = cap;
+    C.img0 = D.pyr + (size_t)frame*D.pyr_frame + D.L[0].pyr_off + (size_t)EDGE*D.L[0].bw + EDGE; C.pitch0 = D.L[0].bw;
+    C.quad = (const int *)dp; C.foot = (const int *)(dp + 32*(size_t)nd);
+    C.o_cnt = (int *)(dp + b_in); C.o_kp = (float *)(dp + b_in + b_cnt); C.o_desc = (uint8_t *)(dp + b_in + b_cnt + b_kp);
+    hipLaunchKernelGGL(k_cvo_mask, dim3(nd), dim3(256), 0, c->stream, C);
+    for (int l = 1; l < CVO_NL; l++) hipLaunchKernelGGL(k_cvo_resize, dim3((C.L[l].w + 63)/64, (C.L[l].h + 3)/4, 1 + nd), dim3(256), 0, c->stream, C, l);
+    hipLaunchKernelGGL(k_cvo_blur, dim3(C.ntiles), dim3(256), 0, c->stream, C);
+    hipLaunchKernelGGL(k_cvo_fast, dim3(C.ntiles, nd), dim3(256), 0, c->stream, C);
+    hipLaunchKernelGGL(k_cvo_select, dim3(CVO_NL, nd), dim3(256), 0, c->stream, C);
+    hipLaunchKernelGGL(k_cvo_place, dim3(C.ntiles, nd), dim3(CVO_TCAP), 0, c->stream, C);
+    hipLaunchKernelGGL(k_cvo_describe, dim3(CVO_DESC_BLOCKS, nd), dim3(256), 0, c->stream, C);
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    const int *o_cnt = (const int *)(h + b_in); const char *o_kp = h + b_in + b_cnt, *o_desc = h + b_in + b_cnt + b_kp;
+    int rc = TSORB_OK;
+    for (int d = 0; d < nd; d++) { const int n = o_cnt[d]; count[d] = n;
+        if (n > cap) { rc = bad("a detection has more keypoints than cap (count[] is complete, nothing written for it)"); continue; }
+        memcpy(kp + 6*(size_t)d*cap, o_kp + 24*(size_t)d*cap, 24*(size_t)n); memcpy(desc + 32*(size_t)d*cap, o_desc + 32*(size_t)d*cap, 32*(size_t)n); }
+    return rc;
 }
 
 } // extern "C"

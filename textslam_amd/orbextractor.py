@@ -12,7 +12,8 @@ _lib = None
 
 EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_get_levels", "tsorb_get_scale_factors",
                     "tsorb_get_features_per_level", "tsorb_extract_batch", "tsorb_upload", "tsorb_run", "tsorb_download",
-                    "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search"]
+                    "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
+                    "tsorb_text_extract"]
 
 
 class TsorbError(RuntimeError):
@@ -43,6 +44,8 @@ def load_library():
         L.tsorb_match_set_frame.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]
         L.tsorb_match_set_features.argtypes = [vp, fp, up, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]
         L.tsorb_match_search.argtypes = [vp, C.c_int, fp, fp, ip, up, C.c_int, ip, ip, ip, ip, ip, ip]
+        L.tsorb_text_extract.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, fp, up, ip]
+        L.tsorb_text_extract.restype = C.c_int
         _lib = L
     return _lib
 
@@ -138,6 +141,22 @@ class ORBextractor:
                                                 None if qlev_p is None else ip_(qlev_p), qdesc.ctypes.data_as(C.POINTER(C.c_uint8)), max_cand,
                                                 ip_(ci), ip_(cd), ip_(cc), ip_(bi), ip_(bd), ip_(bd2)), "tsorb_match_search")
         return dict(cand_idx=ci, cand_dist=cd, cand_cnt=cc, best_idx=bi, best_dist=bd, best_dist2=bd2)
+
+    # ---- text features (frame::FeatExtracText: cv::ORB detect on the masked frame + compute on the frame, docs/cvorb_recalled.md)
+    def extract_text(self, frame, quads, nfeatures=500, cap=None):
+        """Text features of frame `frame` of the resident batch for every detection quad in one call.  quads [n, 4, 2] (x, y in level-0 pixels).
+        Returns a list of (keypoints [k, 6] = x, y, size, angle, Harris response, octave ; descriptors [k, 32]), one pair per detection: level-major,
+        raster order inside a level.  cap = rows per detection (default: nfeatures + 64 for the ties a cut keeps); a detection with more raises."""
+        quads = np.ascontiguousarray(quads, np.float64).reshape(-1, 4, 2)
+        n = quads.shape[0]
+        cap = int(nfeatures) + 64 if cap is None else int(cap)
+        kp = np.zeros((n, max(cap, 1), 6), np.float32)
+        desc = np.zeros((n, max(cap, 1), 32), np.uint8)
+        cnt = np.zeros(max(n, 1), np.int32)
+        self._check(self.lib.tsorb_text_extract(self.ctx, int(frame), n, quads.ctypes.data_as(C.POINTER(C.c_double)), int(nfeatures), cap,
+                                                kp.ctypes.data_as(C.POINTER(C.c_float)), desc.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                cnt.ctypes.data_as(C.POINTER(C.c_int32))), "tsorb_text_extract")
+        return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy()) for i in range(n)]
 
     def debug_fast_shape(self, shape=-1):
         """Diagnostics: the shape of the FAST launches (include/tsorb.h); -1 = chosen by the batch size."""
