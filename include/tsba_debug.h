@@ -80,6 +80,13 @@ typedef struct tsba_debug_options {
     int32_t lds_poison;        // 1 / 2 / 3: before every launch of tsba_solve the LDS of every compute unit is filled with NaNs / 1e300 / 0x5a bytes (what another context's kernels may leave there): results must not change
 } tsba_debug_options;
 int  tsba_debug_set(void *ctx, const tsba_debug_options *d);   /* d == NULL: back to production behaviour; applies to the next upload */
+/* Host only: the layout of the reduced system an upload chooses (csrc/tsba_layout.h) for a map of n_kf keyframes whose levels have a band of at most
+ * bw_rows rows, with a ring plan (the loop starting at keyframe ring_k0) or without, on several ranks (multi) or one; d == NULL: production
+ * behaviour, else its band_parts / sep_solver / no_band_stream.  out[12]: [0] LDS solver  [1] band storage  [2] columns stored right of the diagonal + 1
+ * [3] doubles per band row  [4] streaming band solver  [5] interiors P (1: one workgroup streams down the band)  [6] separator system by cyclic
+ * reduction  [7] partitioned  [8] separator labels  [9] solved as a ring (ghost rows)  [10] interiors in the loop  [11] packed row width of the ranks'
+ * exchange.  Returns 0, or TSBA_ERR_STATE where an upload refuses the ring plan (no partitioned solver with cyclic reduction for it). */
+int  tsba_debug_solver_layout(int n_kf, int bw_rows, int ring, int ring_k0, int multi, const tsba_debug_options *d, int32_t out[12]);
 
 
 /* The reduced system of the first linearisation as 6x6 blocks keyed by KEYFRAME pairs, whatever the storage behind it (band rows in any

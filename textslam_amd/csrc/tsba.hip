@@ -29,6 +29,7 @@
 #include <map>
 #include <condition_variable>
 #include <atomic>
+#include <functional>
 #include <dlfcn.h>
 #include <rccl/rccl.h>      // types only: the library is dlopen()ed by tsba_comm_init, single-GPU use never touches RCCL
 #include "../../include/tsba.h"
@@ -50,6 +51,7 @@
 #include "tsba_bandms.h"
 #include "tsba_bandsv.h"
 #include "tsba_bandmx.h"
+#include "tsba_layout.h"
 #include "tsba_pcg.h"
 #include "tsba_wb.h"
 #include "tsba_pose.h"
@@ -116,6 +118,7 @@ struct Ctx {
     // RCCL (global BA sharded over the GPUs of one node): one process per GPU, communicator created by tsba_comm_init
     bool pose_only = false;                       // one keyframe, every landmark frozen in its host: the fused pose-only LM kernel applies
     double *S_alloc = nullptr; size_t S_count = 0;
+    SolverLayout lay{};                             // what choose_solver_layout (tsba_layout.h) decided for this upload; the fields below are its copies where the solvers read them
     int S_up = CH_NB;                               // band storage: columns stored right of the diagonal + 1
     bool S_stale = true;                            // band storage: entries of another pass may be left in S (cleared before the next assembly)
     double *S_xchg = nullptr; int xchg_wp = 0;      // multi-GPU, band storage: packed band rows for the exchange (k_band_pack)
@@ -243,6 +246,11 @@ static int dev_upload(Ctx *c, const T **out, const T *src, size_t n) {
     return 0;
 }
 template <typename T>
+static int dev_upload_or_zeros(Ctx *c, const T **out, const T *src, size_t n) {       // an optional array of the problem: zeros where the caller passes none
+    std::vector<T> z; if (!src) { z.assign(n, T(0)); src = z.data(); }
+    return dev_upload(c, out, src, n);
+}
+template <typename T>
 static int dev_upload_vec(Ctx *c, const T **out, const std::vector<T> &v) { return dev_upload(c, out, v.data(), v.size()); }
 
 static void join_planners(Ctx *c) { for (auto &t : c->planners) if (t.joinable()) t.join(); c->planners.clear(); }
@@ -354,6 +362,12 @@ int tsba_destroy(void *ctx) {
 int tsba_abi_version(void) { return TSBA_ABI_VERSION; }
 const char *tsba_last_error(void *ctx) { return ctx ? ((Ctx *)ctx)->err.c_str() : "null ctx"; }
 
+// the pyramid levels the passes use, each once, in the order of the first pass that uses it
+static std::vector<int> levels_used(const tsba_options *o, int n_levels) {
+    std::vector<int> used; std::vector<char> seen(n_levels, 0);
+    for (int q = 0; q < o->n_passes; q++) if (!seen[o->levels[q]]) { seen[o->levels[q]] = 1; used.push_back(o->levels[q]); }
+    return used;
+}
 // Every index the plan builder and the kernels dereference is range-checked here, once, in O(problem size): a bad index from the
 // adapter becomes TSBA_ERR_ARG instead of a host out-of-bounds read or a GPU memory fault (the library never aborts the process).
 static int check_problem(Ctx *c, const tsba_problem *p, const tsba_options *o) {
@@ -385,10 +399,8 @@ static int check_problem(Ctx *c, const tsba_problem *p, const tsba_options *o) {
         }
         if (p->tobs_fgood_off[p->n_tobs] > 0 && !p->tfgood) return bad("tfgood is null");
     }
-    std::vector<char> seen(p->n_levels, 0);
     std::vector<int32_t> maxraw;
-    for (int i = 0; i < o->n_passes; i++) {
-        const int l = o->levels[i]; if (seen[l]) continue; seen[l] = 1;
+    for (const int l : levels_used(o, p->n_levels)) {
         const int ns = p->n_sobs[l];
         if (ns < 0) return bad("n_sobs < 0");
         if (ns > 0) {
@@ -418,74 +430,93 @@ static int check_problem(Ctx *c, const tsba_problem *p, const tsba_options *o) {
 }
 
 static int stage_level(Ctx *c, const tsba_problem *p, int l, double *t_plan, double *t_img);
-// lazy: the caller (a one-shot entry point) runs the solve right away and keeps *p alive until it returns -- on small windows only the first
-// pass's level is staged here, the others when their pass begins (tsba_solve), so that the coarse passes run on the device while the host
-// still builds and stages the plan of level 0 (the largest: ~1 ms of a 20-keyframe window's cold call)
-static int upload_impl(void *ctx, const tsba_problem *p, const tsba_options *o, bool lazy) {
-    Ctx *c = (Ctx *)ctx; if (!c) return TSBA_ERR_ARG;
-    hipSetDevice(c->device);
-    int rc = check_problem(c, p, o); if (rc) return rc;
-    const bool tdbg = c->dbg.verbose != 0;
-    auto tu0 = std::chrono::steady_clock::now(); double t_plan = 0.0, t_img = 0.0;
-    free_problem(c);
-    auto tu1 = std::chrono::steady_clock::now();
+// ---- the upload, stage by stage: upload_impl at the end is the list of calls, and every stage says what it leaves behind.  The slabs are bump allocators and
+// dev_upload joins consecutive staged ranges into one host-to-device copy: the ORDER of the dev_upload / dev_alloc calls across the stages, sizes included, is
+// part of the behaviour -- it fixes every buffer's address and the number of copies in front of the first kernel.
+#define UP(dst, src, n) do { const int rc_ = dev_upload(c, &(dst), (src), (size_t)(n)); if (rc_) return rc_; } while (0)
+#define UPZ(dst, src, n) do { const int rc_ = dev_upload_or_zeros(c, &(dst), (src), (size_t)(n)); if (rc_) return rc_; } while (0)
+#define AL(dst, n) do { const int rc_ = dev_alloc(c, &(dst), (size_t)(n)); if (rc_) return rc_; } while (0)
+typedef std::chrono::steady_clock UpClock;
+static double ms_between(UpClock::time_point a, UpClock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+struct UploadTimes { UpClock::time_point t0, t1; double plan = 0.0, img = 0.0; bool verbose = false; };      // tsba_debug_options.verbose: the timing line
+struct PlannerJoiner { Ctx *c; bool armed; ~PlannerJoiner() { if (armed) join_planners(c); } };             // on the error returns
+struct PlanStart { bool defer = false, single_frame = false; std::function<void()> first_plan; };          // first_plan: a deferring call's first level, built on the calling thread
+// sizes of the buffers that every level shares: what the levels on the device hold, what a level staged later can hold at most
+struct LevelMax { size_t pair = 1, tg = 1, pslot = 1, tslot = 1, cnt = 1, pose_grid = 1;
+    void take(const LevelMax &m) { pair = std::max(pair, m.pair); tg = std::max(tg, m.tg); pslot = std::max(pslot, m.pslot); tslot = std::max(tslot, m.tslot);
+                                   cnt = std::max(cnt, m.cnt); pose_grid = std::max(pose_grid, m.pose_grid); } };
+static LevelMax level_size(const LevelDev &D) {
+    LevelMax m; m.pair = (size_t)D.n_pair; m.tg = (size_t)D.n_tg; m.pslot = (size_t)D.n_pslot; m.tslot = (size_t)D.n_tslot; m.cnt = (size_t)D.n_sc + D.n_tg; m.pose_grid = (size_t)pose_grid(D);
+    return m;
+}
+static LevelMax level_capacity(const tsba_problem *p, int l) {
+    const size_t nsc = (size_t)p->n_sobs[l], ntg = (size_t)p->n_tobs; size_t npf = 0;
+    if (p->tfeat_off[l]) for (int q = 0; q < p->n_tobs; q++) { const int j = p->tobs_text[q]; npf += (size_t)(p->tfeat_off[l][j + 1] - p->tfeat_off[l][j]); }
+    LevelMax m; m.pair = std::min((size_t)p->n_kf*((size_t)p->n_kf + 1), nsc + ntg); m.tg = ntg; m.pslot = nsc + (size_t)p->n_pt; m.tslot = ntg + (size_t)p->n_text; m.cnt = nsc + ntg;
+    m.pose_grid = (nsc + 255)/256 + (npf + 31)/32 + 1;
+    return m;
+}
+static int max_band_rows(const Ctx *c) { int bw = 0; for (int l = 0; l < c->n_levels; l++) if (c->lev_built[l]) bw = std::max(bw, c->lev[l].bw_rows); return bw; }
+
+// leaves the context's copy of the options (returned; a rank's shard set), the counts and the scalars of Work
+static const tsba_options *begin_upload(Ctx *c, const tsba_problem *p, const tsba_options *o) {
     c->opt = *o;
     if (c->world > 1) { c->opt.lm_shard = c->rank; c->opt.lm_nshard = c->world; }
     o = &c->opt;
     c->n_kf = p->n_kf; c->n_pt = p->n_pt; c->n_text = p->n_text; c->n_tobs = p->n_tobs; c->n_sgood = p->n_sgood; c->n_levels = p->n_levels;
     c->n_tfgood = p->n_tobs > 0 ? p->tobs_fgood_off[p->n_tobs] : 0;
+    c->nb_back_max = back_blocks_pt(p->n_pt) + back_blocks_tx(p->n_text) + (p->n_kf + 255)/256;      // k_back's blocks (at least k_mid's landmark blocks)
     Work &W = c->W; memset(&W, 0, sizeof(W));
     W.n_kf = p->n_kf; W.n_pt = p->n_pt; W.n_text = p->n_text; W.n_tobs = p->n_tobs; W.N = 6*p->n_kf;
     for (int k = 0; k < 4; k++) W.K0[k] = p->K[k];
     W.w_sx = o->w_sx; W.w_sy = o->w_sy; W.w_t = o->w_t; W.huber_s = o->huber_scene; W.huber_t = o->huber_text;
     W.filter_good = o->filter_good; W.min_diag = o->min_diagonal; W.max_diag = o->max_diagonal;
     W.rank = c->rank; W.world = c->world;
-    // the per-level plans are independent of each other and of the uploads below: one host thread per level builds them while this
-    // thread stages the parameter / observation arrays (C4: 1.6 ms of plan construction in sequence -> the largest level, overlapped)
+    return o;
+}
+// leaves the plan of every level the passes use under way: on a host thread of its own, built already (single-frame problems), or as first_plan.
+// The per-level plans are independent of each other and of the uploads that follow: one host thread per level builds them while the calling
+// thread stages the parameter / observation arrays (C4: 1.6 ms of plan construction in sequence -> the largest level, overlapped)
+static PlanStart start_plans(Ctx *c, const tsba_problem *p, const tsba_options *o, bool lazy, UploadTimes &T) {
     c->hplan.resize(p->n_levels); c->lev.resize(p->n_levels); c->lev_built.assign(p->n_levels, 0); c->lev_planned.assign(p->n_levels, 0);
     c->planners.clear(); c->planners.resize(p->n_levels);
-    std::vector<std::thread> &planners = c->planners;
-    struct Joiner { Ctx *c; bool armed; ~Joiner() { if (armed) join_planners(c); } } joiner{c, true};   // on the error returns
-    int n_lev_used = 0; { std::vector<char> sn(p->n_levels, 0); for (int q = 0; q < o->n_passes; q++) if (!sn[o->levels[q]]) { sn[o->levels[q]] = 1; n_lev_used++; } }
-    const bool small_window = solve_lds_doubles(W.N)*sizeof(double) <= 160*1024 - 64;
+    for (int l = 0; l < TSBA_MAX_LEVELS; l++) { c->plan_done[l].store(0); c->lev_wait[l] = 0; }
+    const std::vector<int> used = levels_used(o, p->n_levels); const int n_lev = (int)used.size();
+    PlanStart S;
     // (round 6: also the single-frame problems of tsba_pose_optim -- the plans of the later passes' levels are built and staged while the first pass runs)
     // (round 6: a single-frame problem with every landmark frozen -- tsba_pose_optim, per frame -- has a plan that is a copy of its input: written down directly
     // on this thread for every level (build_plan_single_frame, microseconds), no plan threads, every level staged before the solve)
-    const bool single_frame = plan_is_single_frame(p, o) && c->dbg.host_pair_lists != 1;
-    const bool defer = lazy && small_window && n_lev_used > 1 && !is_multi(c) && !single_frame;
-    for (int l = 0; l < TSBA_MAX_LEVELS; l++) { c->plan_done[l].store(0); c->lev_wait[l] = 0; }
-    std::function<void()> first_plan;
-    {   auto tp0 = std::chrono::steady_clock::now();
-        std::vector<char> seen(p->n_levels, 0);
-        const int n_lev = n_lev_used;
-        const bool reorder = !c->dbg.no_kf_reorder;
-        // ring maps (one loop closure): a single-level, single-GPU solve through the partitioned solver with the cyclic-reduction separator tree
-        const int ring_max = (n_lev == 1 && !c->dbg.no_ring && !c->dbg.no_band_stream && c->dbg.sep_solver != 1 && c->dbg.sep_solver != 3 && c->dbg.band_parts != 1) ? CR_SMAX/6 : 0;
-        // maps with long-range coupling (several loop closures, points seen again much later): band + blocks outside it, preconditioned conjugate gradients
-        const int far_max = (n_lev == 1 && c->dbg.far_solver != 1 && !c->dbg.no_band_stream && (!c->dbg.no_ring || c->dbg.far_solver >= 2)) ? CR_SMAX/6 : 0;     // (no_ring asks for the reordering path)
-        const bool far_force = c->dbg.far_solver == 2 || c->dbg.far_solver == 3;
-        // the point slot pairs by S block are built on the device (tsba_devplan.h) -- since round 4 on maps of more than 126 keyframes (2 M pairs: 9 of the plan's 21 ms), since round 6 on
-        // windows as well: they are the largest part of a window's plan (C4 level 2: 0.18 of 0.5 ms on the calling thread of a one-shot call, level 0: 0.7 of 1.5 ms), the three small
-        // launches that build them cost the pass ~15 us, the lists are the same entries in the same order (same bits: test_schur_lists_built_on_the_device_equal_the_host_lists)
-        // (... on problems of at least 4096 scene observations: below, the three launches cost a level more than the host's lists -- InitBA's pair, a landmark's refinement, a plane's:
-        // 15 us per level of calls that take 1.3 - 2.3 ms in launch-bound trials of ~32 us; tsba_debug_options.host_pair_lists = 2 asks for the device lists at any size)
-        const bool dev_pairs = p->n_kf > 1 && c->dbg.host_pair_lists != 1 && (c->dbg.host_pair_lists == 2 || p->n_sobs[0] >= 4096);
-        for (int ps = o->n_passes - 1; ps >= 0; ps--) { const int l = o->levels[ps]; if (seen[l]) continue;
-            bool later = false; for (int q = 0; q < ps; q++) later |= o->levels[q] == l;       // (a level used by an earlier pass is started with that pass)
-            if (later) continue;
-            seen[l] = 1;
-            HostPlan *H = &c->hplan[l];
-            c->lev_planned[l] = 1;
-            std::atomic<int> *done = &c->plan_done[l];
-            // the levels of the later passes first (the largest plans); a deferring call builds the first pass's (small) plan on this thread:
-            // it is needed at once, and a thread's start costs as much as that plan
-            if (single_frame) { build_plan_single_frame(p, o, l, *H); done->store(1); continue; }
-            if (defer && ps == 0) { first_plan = [=]() { build_plan(p, o, l, *H, tdbg, reorder, ring_max, far_max, far_force, dev_pairs); done->store(1); }; continue; }    // (built below, behind the problem arrays' copy)
-            planners[l] = std::thread([p, o, l, H, tdbg, reorder, ring_max, far_max, far_force, dev_pairs, done]() { build_plan(p, o, l, *H, tdbg, reorder, ring_max, far_max, far_force, dev_pairs); done->store(1, std::memory_order_release); }); }
-        t_plan += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
-    }
-#define UP(dst, src, n) do { rc = dev_upload(c, &(dst), (src), (size_t)(n)); if (rc) return rc; } while (0)
-#define AL(dst, n) do { rc = dev_alloc(c, &(dst), (size_t)(n)); if (rc) return rc; } while (0)
+    S.single_frame = plan_is_single_frame(p, o) && c->dbg.host_pair_lists != 1;
+    S.defer = lazy && lds_solver_fits(c->W.N) && n_lev > 1 && !is_multi(c) && !S.single_frame;      // small windows only
+    const auto tp0 = UpClock::now();
+    const bool tdbg = T.verbose, reorder = !c->dbg.no_kf_reorder;
+    // ring maps (one loop closure): a single-level, single-GPU solve through the partitioned solver with the cyclic-reduction separator tree
+    const int ring_max = (n_lev == 1 && !c->dbg.no_ring && !c->dbg.no_band_stream && c->dbg.sep_solver != 1 && c->dbg.sep_solver != 3 && c->dbg.band_parts != 1) ? CR_SMAX/6 : 0;
+    // maps with long-range coupling (several loop closures, points seen again much later): band + blocks outside it, preconditioned conjugate gradients
+    const int far_max = (n_lev == 1 && c->dbg.far_solver != 1 && !c->dbg.no_band_stream && (!c->dbg.no_ring || c->dbg.far_solver >= 2)) ? CR_SMAX/6 : 0;     // (no_ring asks for the reordering path)
+    const bool far_force = c->dbg.far_solver == 2 || c->dbg.far_solver == 3;
+    // the point slot pairs by S block are built on the device (tsba_devplan.h) -- since round 4 on maps of more than 126 keyframes (2 M pairs: 9 of the plan's 21 ms), since round 6 on
+    // windows as well: they are the largest part of a window's plan (C4 level 2: 0.18 of 0.5 ms on the calling thread of a one-shot call, level 0: 0.7 of 1.5 ms), the three small
+    // launches that build them cost the pass ~15 us, the lists are the same entries in the same order (same bits: test_schur_lists_built_on_the_device_equal_the_host_lists)
+    // (... on problems of at least 4096 scene observations: below, the three launches cost a level more than the host's lists -- InitBA's pair, a landmark's refinement, a plane's:
+    // 15 us per level of calls that take 1.3 - 2.3 ms in launch-bound trials of ~32 us; tsba_debug_options.host_pair_lists = 2 asks for the device lists at any size)
+    const bool dev_pairs = p->n_kf > 1 && c->dbg.host_pair_lists != 1 && (c->dbg.host_pair_lists == 2 || p->n_sobs[0] >= 4096);
+    for (int i = n_lev - 1; i >= 0; i--) {         // (a level is started with the first pass that uses it)
+        const int l = used[(size_t)i];
+        HostPlan *H = &c->hplan[l];
+        c->lev_planned[l] = 1;
+        std::atomic<int> *done = &c->plan_done[l];
+        // the levels of the later passes first (the largest plans); a deferring call builds the first pass's (small) plan on this thread:
+        // it is needed at once, and a thread's start costs as much as that plan
+        if (S.single_frame) { build_plan_single_frame(p, o, l, *H); done->store(1); continue; }
+        if (S.defer && i == 0) { S.first_plan = [=]() { build_plan(p, o, l, *H, tdbg, reorder, ring_max, far_max, far_force, dev_pairs); done->store(1); }; continue; }    // (built by stage_levels, behind the problem arrays' copy)
+        c->planners[l] = std::thread([p, o, l, H, tdbg, reorder, ring_max, far_max, far_force, dev_pairs, done]() { build_plan(p, o, l, *H, tdbg, reorder, ring_max, far_max, far_force, dev_pairs); done->store(1, std::memory_order_release); }); }
+    T.plan += ms_between(tp0, UpClock::now());
+    return S;
+}
+// leaves the parameters (and their restart copies), the landmark and observation arrays and the per-problem work arrays on the slabs
+static int upload_problem_arrays(Ctx *c, const tsba_problem *p) {
+    Work &W = c->W;
     const double *cd; const uint8_t *cu;
     UP(cd, p->pose, 7*(size_t)p->n_kf); c->pose0 = (double *)cd;
     UP(cd, p->rho, p->n_pt); c->rho0 = (double *)cd;
@@ -493,14 +524,13 @@ static int upload_impl(void *ctx, const tsba_problem *p, const tsba_options *o, 
     UP(cu, p->sgood, p->n_sgood); c->sgood0 = (uint8_t *)cu;
     UP(cu, p->tobs_good, p->n_tobs); c->tobs_good0 = (uint8_t *)cu;
     UP(cu, p->tfgood, c->n_tfgood); c->tfgood0 = (uint8_t *)cu;
-    std::vector<uint8_t> ki(p->n_kf, 0); if (p->kf_initial) memcpy(ki.data(), p->kf_initial, p->n_kf);
-    UP(cu, ki.data(), p->n_kf); c->kf_initial = (uint8_t *)cu;
+    UPZ(cu, p->kf_initial, p->n_kf); c->kf_initial = (uint8_t *)cu;
     for (int b = 0; b < 2; b++) { AL(W.pose[b], 7*(size_t)p->n_kf); AL(W.rho[b], p->n_pt); AL(W.theta[b], 3*(size_t)p->n_text); }
     AL(W.sgood, p->n_sgood); AL(W.tobs_good, p->n_tobs); AL(W.tfgood, c->n_tfgood);
     UP(W.pt_ray, p->pt_ray, 2*(size_t)p->n_pt); UP(W.pt_host, p->pt_host, p->n_pt);
-    { std::vector<double> z; const double *src = p->pt_host_Trw; if (!src) { z.assign(12*(size_t)p->n_pt, 0.0); src = z.data(); } UP(W.pt_Trw, src, 12*(size_t)p->n_pt); }
+    UPZ(W.pt_Trw, p->pt_host_Trw, 12*(size_t)p->n_pt);
     UP(W.text_host, p->text_host, p->n_text);
-    { std::vector<double> z; const double *src = p->text_host_Twr; if (!src) { z.assign(12*(size_t)p->n_text, 0.0); src = z.data(); } UP(W.text_Twr, src, 12*(size_t)p->n_text); }
+    UPZ(W.text_Twr, p->text_host_Twr, 12*(size_t)p->n_text);
     UP(W.text_box, p->text_box_ray, 8*(size_t)p->n_text);
     UP(W.tobs_kf, p->tobs_kf, p->n_tobs); UP(W.tobs_text, p->tobs_text, p->n_tobs); UP(W.tobs_fgood_off, p->tobs_fgood_off, (size_t)p->n_tobs + 1);
     AL(c->musig2[0], 2*(size_t)p->n_tobs); AL(c->musig2[1], 2*(size_t)p->n_tobs); c->musig_sel = 0; W.musig = c->musig2[0];
@@ -508,216 +538,218 @@ static int upload_impl(void *ctx, const tsba_problem *p, const tsba_options *o, 
     AL(c->lin_ticket, 2); c->lin_base = 0;                         // (slab memory: zero)
     AL(W.kf_in, p->n_kf); AL(W.kf_const, p->n_kf); AL(W.act_pt, p->n_pt); AL(W.act_tx, p->n_text);
     AL(W.fidx, p->n_kf); AL(W.nfree, 2); AL(W.dbg, 64); AL(W.trace, 4*(size_t)TSBA_TRACE_CAP*TSBA_MAX_LEVELS); AL(W.LDbuf, 32*((size_t)p->n_kf + BAND_BW_MAX/6 + 1));     // (+ the ghost blocks of a ring map)
-    // ---- plane cache (tsba_problem.kf_id): the keyframes of this call get their slots; the planes of those not seen before are staged and copied
+    return 0;
+}
+// plane cache (tsba_problem.kf_id): leaves every keyframe of this call with a slot (ic_slot); the planes of those not seen before are staged and copied.
+// A failed call leaves no half state: no slot marked full without its planes
+static int assign_plane_cache(Ctx *c, const tsba_problem *p, const tsba_options *o) {
     std::vector<int> &ic_slot = c->ic_slot; ic_slot.clear();
-    bool &use_img_cache = c->use_img_cache; use_img_cache = false;
-    if (p->kf_id && !o->img_on_device && o->use_text && p->n_tobs > 0 && p->n_kf <= TSBA_IMG_CACHE_KF) {
-        Ctx::ImgCache &IC = c->ic;
-        unsigned mask = 0; size_t off = 0, lo[TSBA_MAX_LEVELS] = {0,0,0,0}; bool same = IC.dev != nullptr;
-        { std::vector<char> seen(p->n_levels, 0);
-          for (int ps = 0; ps < o->n_passes; ps++) { const int l = o->levels[ps]; if (seen[l] || !p->img[l]) continue; seen[l] = 1; mask |= 1u << l; }
-          for (int l = 0; l < p->n_levels; l++) if (mask >> l & 1) { lo[l] = off; off += ((size_t)p->img_w[l]*p->img_h[l] + 255) & ~(size_t)255;
-              same = same && IC.w[l] == p->img_w[l] && IC.h[l] == p->img_h[l]; } }
-        same = same && IC.lvl_mask == mask && IC.slot == off;
-        if (mask && off) {
-            if (!same) {                                     // new geometry (or first use): an empty cache of TSBA_IMG_CACHE_KF slots
-                hipStreamSynchronize(c->stream);
-                if (IC.dev) { hipFree(IC.dev); IC.dev = nullptr; }
-                if (hipMalloc((void **)&IC.dev, off*TSBA_IMG_CACHE_KF) != hipSuccess) { IC.dev = nullptr; set_err(c, "hipMalloc (plane cache)"); return TSBA_ERR_DEVICE; }
-                IC.slot = off; IC.lvl_mask = mask;
-                for (int l = 0; l < TSBA_MAX_LEVELS; l++) { IC.lvl_off[l] = lo[l]; IC.w[l] = l < p->n_levels ? p->img_w[l] : 0; IC.h[l] = l < p->n_levels ? p->img_h[l] : 0; }
-                for (int q = 0; q < TSBA_IMG_CACHE_KF; q++) { IC.id[q] = 0; IC.used[q] = 0; IC.full[q] = false; }
-            }
-            for (int l = 0; l < p->n_levels; l++) if (mask >> l & 1) for (int k = 0; k < p->n_kf; k++)      // before any slot changes hands: a failed call must not leave a slot marked full without its planes
-                if (!p->img[l][k]) { set_err(c, "null image pointer"); return TSBA_ERR_ARG; }
-            IC.tick++;
-            ic_slot.assign((size_t)p->n_kf, -1);
-            std::vector<int> miss;
-            for (int k = 0; k < p->n_kf; k++) { for (int q = 0; q < TSBA_IMG_CACHE_KF; q++) if (IC.full[q] && IC.id[q] == p->kf_id[k]) { ic_slot[(size_t)k] = q; IC.used[q] = IC.tick; break; }
-                if (ic_slot[(size_t)k] < 0) miss.push_back(k); }
-            for (int k : miss) { int best = -1;              // least recently used slot that this call does not use
-                for (int q = 0; q < TSBA_IMG_CACHE_KF; q++) if (IC.used[q] != IC.tick && (best < 0 || !IC.full[q] || (IC.full[best] && IC.used[q] < IC.used[best]))) { best = q; if (!IC.full[q]) break; }
-                IC.id[best] = p->kf_id[k]; IC.full[best] = true; IC.used[best] = IC.tick; ic_slot[(size_t)k] = best; }
-            IC.hits += p->n_kf - (long long)miss.size(); IC.misses += (long long)miss.size();
-            if (!miss.empty()) {
-                const size_t need = miss.size()*off;
-                if (IC.stage_cap < need) { if (IC.stage) hipHostFree(IC.stage); IC.stage = nullptr; IC.stage_cap = 0;
-                    if (hipHostMalloc((void **)&IC.stage, need, hipHostMallocDefault) != hipSuccess) { IC.stage = nullptr;
-                        for (int k : miss) IC.full[ic_slot[(size_t)k]] = false;          // (their planes were never copied)
-                        set_err(c, "hipHostMalloc (plane cache staging)"); return TSBA_ERR_DEVICE; }
-                    IC.stage_cap = need; }
-                for (size_t m = 0; m < miss.size(); m++) { const int k = miss[m];
-                    for (int l = 0; l < p->n_levels; l++) if (mask >> l & 1) memcpy(IC.stage + m*off + lo[l], p->img[l][k], (size_t)p->img_w[l]*p->img_h[l]);
-                    hipMemcpyAsync(IC.dev + (size_t)ic_slot[(size_t)k]*off, IC.stage + m*off, off, hipMemcpyHostToDevice, c->stream); }
-            }
-            use_img_cache = true;
-        }
+    c->use_img_cache = false;
+    if (!(p->kf_id && !o->img_on_device && o->use_text && p->n_tobs > 0 && p->n_kf <= TSBA_IMG_CACHE_KF)) return 0;
+    Ctx::ImgCache &IC = c->ic;
+    unsigned mask = 0; size_t off = 0, lo[TSBA_MAX_LEVELS] = {0,0,0,0}; bool same = IC.dev != nullptr;
+    for (int l : levels_used(o, p->n_levels)) if (p->img[l]) mask |= 1u << l;
+    for (int l = 0; l < p->n_levels; l++) if (mask >> l & 1) { lo[l] = off; off += ((size_t)p->img_w[l]*p->img_h[l] + 255) & ~(size_t)255;
+        same = same && IC.w[l] == p->img_w[l] && IC.h[l] == p->img_h[l]; }
+    same = same && IC.lvl_mask == mask && IC.slot == off;
+    if (!mask || !off) return 0;
+    if (!same) {                                     // new geometry (or first use): an empty cache of TSBA_IMG_CACHE_KF slots
+        hipStreamSynchronize(c->stream);
+        if (IC.dev) { hipFree(IC.dev); IC.dev = nullptr; }
+        if (hipMalloc((void **)&IC.dev, off*TSBA_IMG_CACHE_KF) != hipSuccess) { IC.dev = nullptr; set_err(c, "hipMalloc (plane cache)"); return TSBA_ERR_DEVICE; }
+        IC.slot = off; IC.lvl_mask = mask;
+        for (int l = 0; l < TSBA_MAX_LEVELS; l++) { IC.lvl_off[l] = lo[l]; IC.w[l] = l < p->n_levels ? p->img_w[l] : 0; IC.h[l] = l < p->n_levels ? p->img_h[l] : 0; }
+        for (int q = 0; q < TSBA_IMG_CACHE_KF; q++) { IC.id[q] = 0; IC.used[q] = 0; IC.full[q] = false; }
     }
-    // ---- per-level plans
-    if (first_plan) {                              // a deferring call: the first pass's plan on this thread, while the problem arrays (and a new keyframe's planes) cross the bus
+    for (int l = 0; l < p->n_levels; l++) if (mask >> l & 1) for (int k = 0; k < p->n_kf; k++)      // before any slot changes hands: a failed call must not leave a slot marked full without its planes
+        if (!p->img[l][k]) { set_err(c, "null image pointer"); return TSBA_ERR_ARG; }
+    IC.tick++;
+    ic_slot.assign((size_t)p->n_kf, -1);
+    std::vector<int> miss;
+    for (int k = 0; k < p->n_kf; k++) { for (int q = 0; q < TSBA_IMG_CACHE_KF; q++) if (IC.full[q] && IC.id[q] == p->kf_id[k]) { ic_slot[(size_t)k] = q; IC.used[q] = IC.tick; break; }
+        if (ic_slot[(size_t)k] < 0) miss.push_back(k); }
+    for (int k : miss) { int best = -1;              // least recently used slot that this call does not use
+        for (int q = 0; q < TSBA_IMG_CACHE_KF; q++) if (IC.used[q] != IC.tick && (best < 0 || !IC.full[q] || (IC.full[best] && IC.used[q] < IC.used[best]))) { best = q; if (!IC.full[q]) break; }
+        IC.id[best] = p->kf_id[k]; IC.full[best] = true; IC.used[best] = IC.tick; ic_slot[(size_t)k] = best; }
+    IC.hits += p->n_kf - (long long)miss.size(); IC.misses += (long long)miss.size();
+    if (!miss.empty()) {
+        const size_t need = miss.size()*off;
+        if (IC.stage_cap < need) { if (IC.stage) hipHostFree(IC.stage); IC.stage = nullptr; IC.stage_cap = 0;
+            if (hipHostMalloc((void **)&IC.stage, need, hipHostMallocDefault) != hipSuccess) { IC.stage = nullptr;
+                for (int k : miss) IC.full[ic_slot[(size_t)k]] = false;          // (their planes were never copied)
+                set_err(c, "hipHostMalloc (plane cache staging)"); return TSBA_ERR_DEVICE; }
+            IC.stage_cap = need; }
+        for (size_t m = 0; m < miss.size(); m++) { const int k = miss[m];
+            for (int l = 0; l < p->n_levels; l++) if (mask >> l & 1) memcpy(IC.stage + m*off + lo[l], p->img[l][k], (size_t)p->img_w[l]*p->img_h[l]);
+            hipMemcpyAsync(IC.dev + (size_t)ic_slot[(size_t)k]*off, IC.stage + m*off, off, hipMemcpyHostToDevice, c->stream); }
+    }
+    c->use_img_cache = true;
+    return 0;
+}
+// leaves on the device the levels the solve needs before it starts -- all of them, unless the call defers: then the first pass's only, the others are staged when
+// their pass begins (stage_p) -- and in *mx what the buffers shared by all levels must hold
+static int stage_levels(Ctx *c, const tsba_problem *p, const tsba_options *o, const PlanStart &S, LevelMax *mx, UploadTimes &T) {
+    if (S.first_plan) {                              // a deferring call: the first pass's plan on this thread, while the problem arrays (and a new keyframe's planes) cross the bus
         flush_run(c);
-        auto tp0 = std::chrono::steady_clock::now(); first_plan();
-        t_plan += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count(); }
-    size_t mx_pair = 1, mx_tg = 1, mx_pslot = 1, mx_tslot = 1, mx_cnt = 1;
-    for (int ps = 0; ps < o->n_passes; ps++) {
-        const int l = o->levels[ps]; if (c->lev_built[l]) continue;
-        if (defer && ps > 0) {                     // staged when its pass begins: buffers by what the level can hold at most
-            const size_t nsc = (size_t)p->n_sobs[l], ntg = (size_t)p->n_tobs;
-            mx_pair = std::max(mx_pair, std::min((size_t)p->n_kf*((size_t)p->n_kf + 1), nsc + ntg)); mx_tg = std::max(mx_tg, ntg);
-            mx_pslot = std::max(mx_pslot, nsc + (size_t)p->n_pt); mx_tslot = std::max(mx_tslot, ntg + (size_t)p->n_text); mx_cnt = std::max(mx_cnt, nsc + ntg);
-            continue; }
-        rc = stage_level(c, p, l, &t_plan, &t_img); if (rc) return rc;
-        const LevelDev &D = c->lev[l];
-        mx_pair = std::max(mx_pair, (size_t)D.n_pair); mx_tg = std::max(mx_tg, (size_t)D.n_tg);
-        mx_pslot = std::max(mx_pslot, (size_t)D.n_pslot); mx_tslot = std::max(mx_tslot, (size_t)D.n_tslot); mx_cnt = std::max(mx_cnt, (size_t)D.n_sc + D.n_tg);
+        const auto tp0 = UpClock::now(); S.first_plan();
+        T.plan += ms_between(tp0, UpClock::now()); }
+    const std::vector<int> used = levels_used(o, p->n_levels);
+    for (size_t i = 0; i < used.size(); i++) {
+        const int l = used[i];
+        if (S.defer && i > 0) { mx->take(level_capacity(p, l)); continue; }
+        const int rc = stage_level(c, p, l, &T.plan, &T.img); if (rc) return rc;
+        mx->take(level_size(c->lev[l]));
     }
-    c->stage_p = defer ? p : nullptr;
-    c->nb_back_max = back_blocks_pt(p->n_pt) + back_blocks_tx(p->n_text) + (p->n_kf + 255)/256;      // k_back's blocks (at least k_mid's landmark blocks)
-    {   bool po = p->n_kf == 1;
-        for (int j = 0; po && j < p->n_pt; j++) po = p->pt_host[j] < 0;
-        for (int j = 0; po && j < p->n_text; j++) po = p->text_host[j] < 0;
-        c->pose_only = po && !c->dbg.no_pose_kernel;
-        W.pst = nullptr; W.ppart = nullptr;
-        if (c->pose_only) {
-            size_t gmax = 1;
-            for (int l = 0; l < p->n_levels; l++) {
-                if (c->lev_built[l]) gmax = std::max(gmax, (size_t)pose_grid(c->lev[l]));
-                else if (c->lev_planned[l]) {                // a level staged later (deferred): its grid is bounded by what the level can hold
-                    size_t npf = 0;
-                    if (p->tfeat_off[l]) for (int q = 0; q < p->n_tobs; q++) { const int j = p->tobs_text[q]; npf += (size_t)(p->tfeat_off[l][j + 1] - p->tfeat_off[l][j]); }
-                    gmax = std::max(gmax, ((size_t)p->n_sobs[l] + 255)/256 + (npf + 31)/32 + 1); } }
-            AL(W.pst, 2); AL(W.ppart, 3*28*gmax);
-        } }
+    c->stage_p = S.defer ? p : nullptr;
+    return 0;
+}
+// decides the fused pose-only path (one keyframe, every landmark frozen in its host) and leaves its state and per-workgroup partial sums
+static int alloc_pose_buffers(Ctx *c, const tsba_problem *p, const LevelMax &mx) {
+    Work &W = c->W;
+    c->pose_only = p->n_kf == 1 && every_landmark_frozen(p) && !c->dbg.no_pose_kernel;
+    W.pst = nullptr; W.ppart = nullptr;
+    if (c->pose_only) { AL(W.pst, 2); AL(W.ppart, 3*28*mx.pose_grid); }
+    return 0;
+}
+// leaves the two linearisation buffers (current / candidate) and the Jacobi scaling
+static int alloc_lin_buffers(Ctx *c, const tsba_problem *p, const LevelMax &mx) {
+    Work &W = c->W;
     for (int b = 0; b < 2; b++) {
         LinBuf &B = W.lb[b];
-        AL(B.pairM, 27*mx_pair); AL(B.pairCost, mx_pair); AL(B.pairR, 9*mx_pair); AL(B.pairOut, 90*mx_pair);
-        AL(B.tgM, 27*mx_tg); AL(B.tgCost, mx_tg);
-        AL(B.w_pt, PT_REC*mx_pslot); AL(B.vdb_pt, PT_VDB*(size_t)p->n_pt);
-        AL(B.w_tx, TX_REC*mx_tslot); AL(B.V_tx, 6*(size_t)p->n_text); AL(B.b_tx, 3*(size_t)p->n_text); AL(B.dgs_tx, 3*(size_t)p->n_text);
+        AL(B.pairM, 27*mx.pair); AL(B.pairCost, mx.pair); AL(B.pairR, 9*mx.pair); AL(B.pairOut, 90*mx.pair);
+        AL(B.tgM, 27*mx.tg); AL(B.tgCost, mx.tg);
+        AL(B.w_pt, PT_REC*mx.pslot); AL(B.vdb_pt, PT_VDB*(size_t)p->n_pt);
+        AL(B.w_tx, TX_REC*mx.tslot); AL(B.V_tx, 6*(size_t)p->n_text); AL(B.b_tx, 3*(size_t)p->n_text); AL(B.dgs_tx, 3*(size_t)p->n_text);
         AL(B.Hd, W.N); AL(B.bp, W.N); AL(B.bp_loc, W.N); AL(B.dgs_p, W.N);
-        AL(B.lmpart, 3*((size_t)p->n_pt/64 + (size_t)p->n_text/2 + mx_pair + 8));      // (one partial per k_mid block, at its smallest block size)      // (one partial per k_mid block: at most n_pt / 128 + n_text / 128 + pairs / 128 + 3, and nb_back_max >= n_pt / 64 + n_text / 16)
+        AL(B.lmpart, 3*((size_t)p->n_pt/64 + (size_t)p->n_text/2 + mx.pair + 8));      // (one partial per k_mid block, at its smallest block size)      // (one partial per k_mid block: at most n_pt / 128 + n_text / 128 + pairs / 128 + 3, and nb_back_max >= n_pt / 64 + n_text / 16)
     }
     AL(W.sig_pt, p->n_pt); AL(W.sig_tx, 3*(size_t)p->n_text); AL(W.sig_p, W.N);
     AL(W.cb, 2*(size_t)W.N + 8); AL(W.cbm, 1);
-    {   // reduced camera matrix: dense for the LDS solver; for the large-system Cholesky only its band (rows overlap in a skewed
-        // view: S(i,j) = base[i*(LDB-1) + j], LDB = band + 96 columns of the diagonal block's upper triangle, where the inverse
-        // diagonal factors are kept) -- 80 MB instead of 7.2 GB at 5000 keyframes, and what the ranks all-reduce
-        const int use_lds_ = solve_lds_doubles(W.N)*sizeof(double) <= 160*1024 - 64;        // (as solve_lds_bytes)
-        W.dp_poll = use_lds_ && !is_multi(c) && !c->pose_only && (c->dbg.solve_variant == 0 || c->dbg.solve_variant == 5);        // solver and back-substitution in one launch (k_solve_back)
-        if (W.dp_poll) {                           // ... whose workgroups poll the solver's: only where the whole grid is resident at once (else k_solve_t + k_back + k_decide)
-            const int nb_all_ = back_blocks_pt(p->n_pt) + back_blocks_tx(p->n_text) + (p->n_kf + 255)/256;
-            const int ldsb_ = std::max((int)(solve_lds_doubles(W.N)*sizeof(double)), (int)((768 + W.N + 2)*sizeof(double)));
-            ATTR(k_solve_back<true>, ldsb_);
-            if (!grid_resident(c, (const void *)k_solve_back<true>, SOLVE_THREADS, (size_t)ldsb_, 1 + (nb_all_ + 2)/3)) W.dp_poll = 0;
-        }
-        int bwmax = 0; for (int l = 0; l < p->n_levels; l++) if (c->lev_built[l]) bwmax = std::max(bwmax, c->lev[l].bw_rows);
-        // band storage: row i holds the columns [i - Wb, i + up) (skewed view S(i, j) = base[i (LDB - 1) + j]).  The blocked Cholesky of
-        // tsba_chol.h writes 96-wide blocks on both sides of the diagonal (up = CH_NB, Wb = band + CH_NB - 1); the streaming / partitioned
-        // solvers read the band only (up = 6: the diagonal pose block is stored square) -- 72 instead of 251 columns per row at a band of
-        // 60, and the band is cleared before every Schur assembly (60 MB per LM trial at 5000 keyframes with the wide rows)
-        const bool stream_ok = bwmax >= 6 && bwmax <= BAND_BW_MAX && band_chunk_blocks(bwmax) > 0 && !c->dbg.no_band_stream;
-        int ring = 0, ring_k0 = 0; for (int l = 0; l < p->n_levels; l++) if (c->lev_built[l] && c->hplan[l].ring) { ring = 1; ring_k0 = c->hplan[l].ring_k0; }     // (a ring plan is only built for single-level solves)
-        int ring_G = 0;
-        const size_t nrow = (size_t)W.N + (ring ? bwmax : 0);                                                 // + the ghost rows of the first separator
-        c->S_up = stream_ok ? 6 : CH_NB;
-        const size_t LDB = stream_ok ? (size_t)bwmax + 12 : (size_t)bwmax + 2*CH_NB - 1;
-        if (use_lds_ || (size_t)bwmax + 2*CH_NB - 1 >= (size_t)W.N) { c->S_count = (size_t)(W.N + 1)*W.N; AL(c->S_alloc, c->S_count); W.S = c->S_alloc; W.ldS = W.N; W.band = 0; }
-        else { c->S_count = nrow*LDB + LDB; AL(c->S_alloc, c->S_count); W.S = c->S_alloc + (LDB - c->S_up); W.ldS = (int)LDB - 1; W.band = 1; }
-        W.ring = 0; W.ring_g = 0; W.ring_b = 0; W.ring_k0 = -1;
-        c->Lcol = nullptr; c->band_stream = 0; c->sep_cr = false;
-        if (W.band && stream_ok) {
-            AL(c->Lcol, ((size_t)p->n_kf + bwmax/6 + 1)*bwmax*6); c->band_stream = 1;
-            // substructuring: P interiors on P workgroups + a separator system (again a band, 2 bw - 6 wide)
-            // number of interiors: the interiors run in parallel (n_kf / P blocks each, ~3.5 us per block, 5 us once the border makes the
-            // panel waves take two rounds), the separator system is sequential again ((P - 1) B blocks at ~4.5 us, 5.5 us when its band
-            // exceeds 115 rows): the sum is smallest near sqrt(n_kf t_f / (B t_s))
-            const int Bq = bwmax/6;
-            const double t_f = bwmax > 57 ? 5.0 : 3.5, t_s = 2*bwmax - 6 > 115 ? 5.5 : 4.5;
-            int P = (int)lround(sqrt((double)p->n_kf*t_f/((double)std::max(Bq, 1)*t_s)));
-            bool want_cr = false;
-            if (bwmax <= CR_SMAX && c->dbg.sep_solver != 1) {
-                // separator system by cyclic reduction (tsba_bandcre.h): its cost grows with log2(P) only (~45 us per level: one elimination
-                // and one back-substitution launch; 130 us with the three kernels of round 1), so many more, shorter interiors pay.
-                // Measured at 5000 keyframes / band 10 (ms per 20-iteration solve): P = 64 / 80 / 96 / 112 / 127 / 150 -> 20.6 / 20.3 / 19.4 /
-                // 18.6 / 18.0 / 18.8 (150: an eighth level)
-                double best = 1e300; int bestP = P;
-                for (int q = 4; q <= BANDP_MAXP; q++) {
-                    if ((p->n_kf - (q - 1)*Bq)/q < 2*Bq + 2) break;          // (the kernels need 2 B + 2 blocks per interior; until round 6 this loop stopped at 2 B + 8 -- C5: 11 interiors, 9.39 ms; 13: 8.76 ms, tools/diag/gpu_sweep_parts.py)
-                    int lev = 1; for (int hh = 1; hh < q - 1; hh <<= 1) lev++;
-                    const double cost = (double)p->n_kf/q*t_f + 45.0*lev;
-                    if (cost < best) { best = cost; bestP = q; }
-                }
-                // (few, long interiors -- some hundred keyframes -- are still cheaper with the sequential separator solve: compare)
-                const int Ps = std::max(1, std::min(P, BANDP_MAXP));
-                const double cost_seq = (double)p->n_kf/Ps*t_f + (double)(Ps - 1)*Bq*t_s;
-                if (best < cost_seq) { P = bestP; want_cr = true; }
-            }
-            if (c->dbg.sep_solver >= 2 && bwmax <= CR_SMAX) want_cr = true;
-            if (c->dbg.band_parts > 0) P = c->dbg.band_parts;
-            P = std::max(1, std::min(P, BANDP_MAXP));
-            if (ring) {                       // ring: a power of two interiors in the loop (the separator tree ends in its first separator and the ghost), cyclic reduction only
-                const int cap = c->dbg.band_parts > 0 ? c->dbg.band_parts : 128, nloop = p->n_kf - ring_k0;
-                int Pr = 4; while (2*Pr <= cap && (nloop - 2*Pr*Bq)/(2*Pr) >= 2*Bq + 8) Pr *= 2;
-                ring_G = Pr;
-                int Pt = 0;                   // a tail before the loop: interiors of about the loop's size
-                if (ring_k0 > 0) { const int ql = (nloop - Pr*Bq)/Pr; Pt = std::max(1, std::min(std::min(RING_OFF - 1, BANDP_MAXP - Pr), (ring_k0 + ql/2)/(ql + Bq)));
-                    while (Pt > 1 && (ring_k0 - (Pt - 1)*Bq)/Pt < 2*Bq + 8) Pt--; }
-                P = Pr + Pt; want_cr = true;
-            }
-            while (!ring && P > 1 && (p->n_kf - (P - 1)*Bq)/P < ((c->dbg.band_parts > 0 || want_cr) ? 2*Bq + 2 : 4*Bq + 4)) P--;     // (2 B + 2: the least the kernels take; the sequential separator solve pays only for interiors of a few bands)
-            if (P > 1 && bandp_chunk_blocks(bwmax) > 0 && 2*bwmax - 6 <= BAND_BW_MAX && band_chunk_blocks(2*bwmax - 6) > 0) {
-                const int nsepb = cr_mmax(ring, P, ring_G);                     // separator labels (ring: the last one is the ghost of the loop's first separator)
-                const int nsep = nsepb*bwmax, bws = 2*bwmax - 6;
-                c->nsep_ld = nsep;
-                AL(c->Lb, ((size_t)p->n_kf + bwmax/6 + 1)*bwmax*6); AL(c->Tbuf, (size_t)P*((size_t)4*bwmax*bwmax + 2*bwmax));
-                AL(c->Bpart, (size_t)P*BANDP_NS*((size_t)bwmax*bwmax + bwmax));
-                c->sep_cr = want_cr && P >= 4;
-                if (c->sep_cr) { AL(c->Ssep, cr_pool_blocks(nsepb)*(size_t)bwmax*bwmax); AL(c->CRcontrib, (size_t)nsepb*cre_contrib_doubles(bwmax)); AL(c->CRfac, (size_t)nsepb*cre_rec_doubles(bwmax)); AL(c->CRgate, (size_t)(nsepb + 2)*TSBA_CRE_KMAX); c->cre_epoch = 0; }
-                else AL(c->Ssep, (size_t)nsep*nsep + nsep);
-                AL(c->Lcol_sep, (size_t)(nsep/6 + 1)*bws*6);
-                Work &Ws = c->Wsep; memset(&Ws, 0, sizeof(Ws));
-                Ws.N = nsep; Ws.n_kf = 0; Ws.S = c->Ssep; Ws.ldS = nsep; Ws.band = 1; Ws.st = nullptr;       // (st is set at launch: W.st is allocated below)
-                AL(Ws.Sy, nsep); AL(Ws.g, nsep); AL(Ws.dp, nsep); AL(Ws.LDbuf, 32*(size_t)(nsep/6 + 1)); AL(Ws.nfree, 1); AL(Ws.fidx, 1);
-                c->band_parts = P;
-                W.ring = (ring && c->sep_cr) ? 1 : 0; W.ring_g = ring_G; W.ring_b = bwmax/6; W.ring_k0 = W.ring ? ring_k0 : -1;
-            } else c->band_parts = 1;
-        }
-        if (ring && !W.ring) { set_err(c, "ring-shaped map: the partitioned band solver is not available for this plan"); return TSBA_ERR_STATE; }
-        AL(W.Sy, W.N + BAND_BW_MAX);                            // (+ the ghost rows of a ring map)
-        c->far_B = 0; c->n_far = 0; c->pcg_parts = 0;
-        for (int l = 0; l < p->n_levels; l++) if (c->lev_built[l] && c->lev[l].far_B > 0) { c->far_B = c->lev[l].far_B; c->n_far = std::max(c->n_far, c->lev[l].n_far); }
-        if (c->far_B > 0) {
-            if (!W.band || !c->band_stream) { set_err(c, "map with long-range coupling: the band solvers are not available for this plan"); return TSBA_ERR_STATE; }
-            c->pcg_parts = (p->n_kf + 31)/32;
-            AL(W.Sfar, 36*(size_t)std::max(c->n_far, 1));
-            AL(W.pc_x, W.N); AL(W.pc_r, W.N); AL(W.pc_p[0], W.N); AL(W.pc_p[1], W.N); AL(W.pc_q, W.N); AL(W.pc_g0, W.N);
-            AL(W.pc_part, 5*(size_t)c->pcg_parts + 16 + 144); AL(W.pcs, 2); AL(W.pc_stat, 8);       // (pc_part: + partial r.z per interior of the solve phase, tsba_bandsv.h)
-        }
-        c->S_xchg = nullptr; c->xchg_wp = 0;
-        if (W.band && is_multi(c)) { c->xchg_wp = std::min(W.N, bwmax + 6); AL(c->S_xchg, ((size_t)W.N + bwmax)*c->xchg_wp); }
+    return 0;
+}
+// the layout of the reduced system for the levels on the device (a ring plan is only built for single-level solves)
+static SolverLayout upload_layout(const Ctx *c) {
+    int ring = 0, ring_k0 = 0; for (int l = 0; l < c->n_levels; l++) if (c->lev_built[l] && c->hplan[l].ring) { ring = 1; ring_k0 = c->hplan[l].ring_k0; }
+    return choose_solver_layout(c->n_kf, max_band_rows(c), ring, ring_k0, is_multi(c), c->dbg);
+}
+// leaves S (dense or band) and the buffers of the solver the layout names: the streaming band solver's factor, the partitioned solver's interiors and separator system
+static int alloc_reduced_system(Ctx *c, const tsba_problem *p, const SolverLayout &L) {
+    Work &W = c->W; const int bw = L.bw_rows;
+    c->lay = L;
+    W.dp_poll = L.use_lds && !is_multi(c) && !c->pose_only && (c->dbg.solve_variant == 0 || c->dbg.solve_variant == 5);        // solver and back-substitution in one launch (k_solve_back)
+    if (W.dp_poll) {                           // ... whose workgroups poll the solver's: only where the whole grid is resident at once (else k_solve_t + k_back + k_decide)
+        const int ldsb = std::max((int)(solve_lds_doubles(W.N)*sizeof(double)), (int)((768 + W.N + 2)*sizeof(double)));
+        ATTR(k_solve_back<true>, ldsb);
+        if (!grid_resident(c, (const void *)k_solve_back<true>, SOLVE_THREADS, (size_t)ldsb, 1 + (c->nb_back_max + 2)/3)) W.dp_poll = 0;
     }
+    c->S_up = L.S_up; c->S_count = L.S_count; AL(c->S_alloc, c->S_count);
+    if (!L.band) { W.S = c->S_alloc; W.ldS = W.N; W.band = 0; }
+    else { W.S = c->S_alloc + (L.LDB - L.S_up); W.ldS = (int)L.LDB - 1; W.band = 1; }
+    W.ring = 0; W.ring_g = 0; W.ring_b = 0; W.ring_k0 = -1;
+    c->Lcol = nullptr; c->band_stream = L.band_stream; c->sep_cr = L.sep_cr != 0; c->band_parts = L.P;
+    if (L.band_stream) AL(c->Lcol, ((size_t)p->n_kf + bw/6 + 1)*bw*6);
+    if (L.partitioned) {                       // substructuring: P interiors on P workgroups + a separator system (again a band, 2 bw - 6 wide)
+        const int P = L.P, nsep = L.nsep;
+        c->nsep_ld = nsep;
+        AL(c->Lb, ((size_t)p->n_kf + bw/6 + 1)*bw*6); AL(c->Tbuf, (size_t)P*((size_t)4*bw*bw + 2*bw));
+        AL(c->Bpart, (size_t)P*BANDP_NS*((size_t)bw*bw + bw));
+        if (L.sep_cr) { AL(c->Ssep, cr_pool_blocks(L.nsepb)*(size_t)bw*bw); AL(c->CRcontrib, (size_t)L.nsepb*cre_contrib_doubles(bw)); AL(c->CRfac, (size_t)L.nsepb*cre_rec_doubles(bw)); AL(c->CRgate, (size_t)(L.nsepb + 2)*TSBA_CRE_KMAX); c->cre_epoch = 0; }
+        else AL(c->Ssep, (size_t)nsep*nsep + nsep);
+        AL(c->Lcol_sep, (size_t)(nsep/6 + 1)*L.bws*6);
+        Work &Ws = c->Wsep; memset(&Ws, 0, sizeof(Ws));
+        Ws.N = nsep; Ws.n_kf = 0; Ws.S = c->Ssep; Ws.ldS = nsep; Ws.band = 1; Ws.st = nullptr;       // (st is set at launch: W.st is allocated by alloc_step_buffers)
+        AL(Ws.Sy, nsep); AL(Ws.g, nsep); AL(Ws.dp, nsep); AL(Ws.LDbuf, 32*(size_t)(nsep/6 + 1)); AL(Ws.nfree, 1); AL(Ws.fidx, 1);
+        W.ring = L.ring; W.ring_g = L.ring_G; W.ring_b = bw/6; W.ring_k0 = L.ring_k0;
+    }
+    if (L.err) { set_err(c, "ring-shaped map: the partitioned band solver is not available for this plan"); return L.err; }
+    AL(W.Sy, W.N + BAND_BW_MAX);                            // (+ the ghost rows of a ring map)
+    return 0;
+}
+// leaves the conjugate-gradient buffers of a map with long-range coupling (tsba_pcg.h) and the packed band rows that several ranks exchange
+static int alloc_pcg(Ctx *c, const tsba_problem *p, const SolverLayout &L) {
+    Work &W = c->W;
+    c->far_B = 0; c->n_far = 0; c->pcg_parts = 0;
+    for (int l = 0; l < p->n_levels; l++) if (c->lev_built[l] && c->lev[l].far_B > 0) { c->far_B = c->lev[l].far_B; c->n_far = std::max(c->n_far, c->lev[l].n_far); }
+    if (c->far_B > 0) {
+        if (!W.band || !c->band_stream) { set_err(c, "map with long-range coupling: the band solvers are not available for this plan"); return TSBA_ERR_STATE; }
+        c->pcg_parts = (p->n_kf + 31)/32;
+        AL(W.Sfar, 36*(size_t)std::max(c->n_far, 1));
+        AL(W.pc_x, W.N); AL(W.pc_r, W.N); AL(W.pc_p[0], W.N); AL(W.pc_p[1], W.N); AL(W.pc_q, W.N); AL(W.pc_g0, W.N);
+        AL(W.pc_part, 5*(size_t)c->pcg_parts + 16 + 144); AL(W.pcs, 2); AL(W.pc_stat, 8);       // (pc_part: + partial r.z per interior of the solve phase, tsba_bandsv.h)
+    }
+    c->S_xchg = nullptr; c->xchg_wp = L.xchg_wp;
+    if (L.xchg_wp) AL(c->S_xchg, ((size_t)W.N + L.bw_rows)*L.xchg_wp);
+    return 0;
+}
+// leaves the buffers of an LM step: gradient, pose and landmark steps, the kernels' partial sums, the two copies of the LM state
+static int alloc_step_buffers(Ctx *c, const tsba_problem *p, const LevelMax &mx) {
+    Work &W = c->W;
     AL(W.g, W.N); AL(W.dp, W.N + 2); AL(W.dl_pt, p->n_pt); AL(W.dl_tx, 3*(size_t)p->n_text);
     AL(W.partial, 2*(size_t)c->nb_back_max);
     AL(W.posepart, 2*((size_t)p->n_kf/21 + 2));
-    AL(W.cntpart, 2*(mx_cnt/4 + mx_cnt/256 + 4));
+    AL(W.cntpart, 2*(mx.cnt/4 + mx.cnt/256 + 4));
     AL(W.st, 2); c->st_base = W.st; AL(W.dec, 1);
     W.st_next = (W.dp_poll && p->n_kf <= SCHUR_KEEP_KF) ? W.st + 1 : nullptr;        // windows on one GPU: k_schur_t takes the previous trial's decision itself (the two copies of the state swap roles after that launch)
     AL(c->cov_log, 6*TSBA_MAX_LEVELS);
+    return 0;
+}
+// leaves the last staged bytes on their way and the problem marked uploaded.  A resident upload ends synchronised; a one-shot call goes straight on to the solve on
+// the same stream: nothing touches the staged bytes before free_problem's synchronisation at the next upload
+static int finish_upload(Ctx *c, bool lazy, const UploadTimes &T, PlannerJoiner &joiner) {
     flush_run(c);
-    auto tu2 = std::chrono::steady_clock::now();
-    // (a one-shot call goes straight on to the solve on the same stream: nothing touches the staged bytes before free_problem's synchronisation at the next upload)
+    const auto t2 = UpClock::now();
     c->upload_pending = false;
     if (lazy && c->ev_upload && (!c->stage_p || c->copy_stream)) { if (c->stage_p) { hipEventRecord(c->ev_upload, c->stream); c->upload_pending = true; } }
     else if (hipStreamSynchronize(c->stream) != hipSuccess) { set_err(c, "upload sync failed"); return TSBA_ERR_DEVICE; }
-    if (tdbg) { auto tu3 = std::chrono::steady_clock::now(); auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "[tsba_upload] free %.2f ms, host total %.2f ms (waiting for the plan threads %.2f ms, image section %.2f ms), final sync %.2f ms\n", ms(tu0, tu1), ms(tu1, tu2), t_plan, t_img, ms(tu2, tu3)); }
+    if (T.verbose) fprintf(stderr, "[tsba_upload] free %.2f ms, host total %.2f ms (waiting for the plan threads %.2f ms, image section %.2f ms), final sync %.2f ms\n",
+                           ms_between(T.t0, T.t1), ms_between(T.t1, t2), T.plan, T.img, ms_between(t2, UpClock::now()));
     c->uploaded = true;
     joiner.armed = false;                          // (deferred levels: their plan threads are joined by stage_level / free_problem)
     if (!c->stage_p) join_planners(c);
     return TSBA_OK;
 }
+// lazy: the caller (a one-shot entry point) runs the solve right away and keeps *p alive until it returns -- on small windows only the first
+// pass's level is staged here, the others when their pass begins (tsba_solve), so that the coarse passes run on the device while the host
+// still builds and stages the plan of level 0 (the largest: ~1 ms of a 20-keyframe window's cold call)
+static int upload_impl(void *ctx, const tsba_problem *p, const tsba_options *o, bool lazy) {
+    Ctx *c = (Ctx *)ctx; if (!c) return TSBA_ERR_ARG;
+    hipSetDevice(c->device);
+    int rc = check_problem(c, p, o); if (rc) return rc;
+    UploadTimes T; T.verbose = c->dbg.verbose != 0; T.t0 = UpClock::now();
+    free_problem(c);
+    T.t1 = UpClock::now();
+    o = begin_upload(c, p, o);
+    PlannerJoiner joiner{c, true};
+    const PlanStart plans = start_plans(c, p, o, lazy, T);
+    if ((rc = upload_problem_arrays(c, p))) return rc;
+    if ((rc = assign_plane_cache(c, p, o))) return rc;
+    LevelMax mx;
+    if ((rc = stage_levels(c, p, o, plans, &mx, T))) return rc;      // (the first plan behind the problem arrays and the plane cache: a deferring call overlaps their copy)
+    if ((rc = alloc_pose_buffers(c, p, mx))) return rc;
+    if ((rc = alloc_lin_buffers(c, p, mx))) return rc;
+    const SolverLayout L = upload_layout(c);
+    if ((rc = alloc_reduced_system(c, p, L))) return rc;
+    if ((rc = alloc_pcg(c, p, L))) return rc;
+    if ((rc = alloc_step_buffers(c, p, mx))) return rc;
+    return finish_upload(c, lazy, T, joiner);
+}
 int tsba_upload(void *ctx, const tsba_problem *p, const tsba_options *o) { return upload_impl(ctx, p, o, false); }
 
+// leaves D.img: the table of the level's image planes -- staged here, resident already (tsframe_level_ptr), or in the keyframes' slots of the plane cache
+static int stage_level_images(Ctx *c, const tsba_problem *p, int l, LevelDev &D) {
+    std::vector<const uint8_t *> ptrs(p->n_kf, nullptr);
+    const size_t npx = (size_t)p->img_w[l]*p->img_h[l];
+    for (int k = 0; k < p->n_kf; k++) {                 // through the pinned staging mirror: one copy for the whole level
+        if (!p->img[l][k]) { set_err(c, "null image pointer"); return TSBA_ERR_ARG; }
+        if (c->opt.img_on_device) { ptrs[k] = p->img[l][k]; continue; }   // resident pyramid plane (tsframe_level_ptr): used in place
+        if (c->use_img_cache) { ptrs[k] = c->ic.dev + (size_t)c->ic_slot[(size_t)k]*c->ic.slot + c->ic.lvl_off[l]; continue; }   // the keyframe's slot of the plane cache (filled by the upload)
+        UP(ptrs[k], p->img[l][k], npx);
+    }
+    const uint8_t *const *dptr = nullptr;
+    UP(dptr, (const uint8_t *const *)ptrs.data(), ptrs.size());
+    D.img = (const uint8_t *const *)dptr;
+    return 0;
+}
 // One pyramid level onto the device: the plan's lists (its host thread is joined here), the level's reference features, the table of image planes.
 static int stage_level(Ctx *c, const tsba_problem *p, int l, double *t_plan, double *t_img) {
     const tsba_options *o = &c->opt; int rc;
@@ -762,20 +794,7 @@ static int stage_level(Ctx *c, const tsba_problem *p, int l, double *t_plan, dou
         UP(D.tfeat_uv, p->tfeat_uv[l], 2*(size_t)p->n_tfeat[l]); UP(D.tfeat_ref, p->tfeat_ref[l], 8*(size_t)p->n_tfeat[l]);
     } else { std::vector<int32_t> z((size_t)p->n_text + 1, 0); UP(D.tfeat_off, z.data(), z.size()); }
     auto ti0 = std::chrono::steady_clock::now();
-    if (o->use_text && p->n_tobs > 0 && p->img[l]) {
-        std::vector<const uint8_t *> ptrs(p->n_kf, nullptr);
-        size_t npx = (size_t)p->img_w[l]*p->img_h[l];
-        const bool cached = c->use_img_cache;
-        for (int k = 0; k < p->n_kf; k++) {                 // through the pinned staging mirror: one copy for the whole level
-            if (!p->img[l][k]) { set_err(c, "null image pointer"); return TSBA_ERR_ARG; }
-            if (o->img_on_device) { ptrs[k] = p->img[l][k]; continue; }   // resident pyramid plane (tsframe_level_ptr): used in place
-            if (cached) { ptrs[k] = c->ic.dev + (size_t)c->ic_slot[(size_t)k]*c->ic.slot + c->ic.lvl_off[l]; continue; }   // the keyframe's slot of the plane cache (filled by the upload)
-            rc = dev_upload(c, &ptrs[k], p->img[l][k], npx); if (rc) return rc;
-        }
-        const uint8_t *const *dptr = nullptr;
-        rc = dev_upload(c, &dptr, (const uint8_t *const *)ptrs.data(), ptrs.size()); if (rc) return rc;
-        D.img = (const uint8_t *const *)dptr;
-    }
+    if (o->use_text && p->n_tobs > 0 && p->img[l]) { rc = stage_level_images(c, p, l, D); if (rc) return rc; }
     if (t_img) *t_img += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti0).count();
     if (c->stage_async || H.dev_pt_pairs >= 0) flush_run(c);        // (a level staged with the upload: its bytes leave with the upload's last copy -- one copy for all levels of a single-frame call)
     if (H.dev_pt_pairs >= 0 && D.n_sb > 0) {                       // (after the copies it reads, on the stream they went over)
@@ -789,6 +808,9 @@ static int stage_level(Ctx *c, const tsba_problem *p, int l, double *t_plan, dou
     c->lev_built[l] = 1;
     return TSBA_OK;
 }
+#undef UP
+#undef UPZ
+#undef AL
 // during a solve: levels of later passes whose plans are complete go to the device now, over the copy stream, next to the running pass
 static int stage_ahead(Ctx *c, int ps) {
     if (!c->stage_p) return TSBA_OK;
@@ -953,9 +975,8 @@ static void launch_linearize(Ctx *c, const LevelDev &D, int spec, bool skip_post
     if (!spec && !skip_postlin) LAUNCHK(k_postlin, dim3(1), dim3(256), 0, c->stream, W, D, c->opt.gradient_tolerance, nb_pt + nb_tx + nb_pr, multi, npp);
 }
 static int solve_lds_bytes(Ctx *c, int *use_lds) {
-    size_t bytes = solve_lds_doubles(c->W.N)*sizeof(double);                                // worst case: every pose free
-    *use_lds = bytes <= 160*1024 - 64;                                                      // gfx950: 160 KB of LDS per workgroup
-    return *use_lds ? (int)bytes : 0;
+    *use_lds = lds_solver_fits(c->W.N);
+    return *use_lds ? (int)(solve_lds_doubles(c->W.N)*sizeof(double)) : 0;
 }
 static void launch_schur(Ctx *c, const LevelDev &D, int multi, SchurDec dec = SchurDec{0, 0, 0, tsba_options{}}) {
     if (c->n_kf > 126 && !c->dbg.no_schur_quad) {               // large maps: four S blocks per wave, then one wave per pose for the reduced gradient
@@ -2001,6 +2022,15 @@ void tsba_debug_bandp_part_ring(int nb, int B, int Pmax, int p, int *out5) { con
 // ring with a tail: nf free poses, the loop starts at free row row0; out8 = P, a, b, has_left, has_right, G, Pt, label of the left separator
 void tsba_debug_bandp_part_ring2(int nf, int row0, int B, int Pmax, int Gmax, int p, int *out8) { const BandpPart r = bandp_part_ring(nf, row0, B, Pmax, Gmax, p);
     out8[0] = r.P; out8[1] = r.a; out8[2] = r.b; out8[3] = r.has_left; out8[4] = r.has_right; out8[5] = r.G; out8[6] = r.Pt; out8[7] = r.lblL; }
+// the layout an upload would choose (tests/test_solver_layout.py).  A ring is taken as the plan builder makes one (tsba_plan.h): a band of 1 .. CR_SMAX / 6 pose
+// blocks, a loop of at least four interiors of 3 B + 2 blocks and their separators
+int tsba_debug_solver_layout(int n_kf, int bw_rows, int ring, int ring_k0, int multi, const tsba_debug_options *d, int32_t out[12]) {
+    if (!out || n_kf < 1 || bw_rows < 0 || ring_k0 < 0 || ring_k0 >= n_kf) return TSBA_ERR_ARG;
+    if (ring && (bw_rows < 6 || bw_rows > CR_SMAX || n_kf - ring_k0 < 4*(3*(bw_rows/6) + 2) + bw_rows/6)) return TSBA_ERR_ARG;
+    const SolverLayout L = choose_solver_layout(n_kf, bw_rows, ring != 0, ring_k0, multi != 0, d ? *d : tsba_debug_options{});
+    const int32_t v[12] = { L.use_lds, L.band, L.S_up, (int32_t)L.LDB, L.band_stream, L.P, L.sep_cr, L.partitioned, L.nsepb, L.ring, L.ring_G, L.xchg_wp };
+    memcpy(out, v, sizeof(v)); return L.err;
+}
 int tsba_debug_sv_lmax(int n_kf, int B, int Pmax) { return sv_lmax_of(n_kf, B, Pmax); }      // the bound the solve phase sizes its LDS with (tests/test_band_partition.py)
 void tsba_debug_bandp_part(int nb, int B, int Pmax, int p, int *out5) { const BandpPart r = bandp_part(nb, B, Pmax, p); out5[0] = r.P; out5[1] = r.a; out5[2] = r.b; out5[3] = r.has_left; out5[4] = r.has_right; }
 long long tsba_debug_cr_blk_index(int mmax, int br, int bc) { return (long long)cr_blk_index(mmax, br, bc); }

@@ -205,9 +205,8 @@ int tsba_text_label_image(void *ctx, int kf, int level, float *out) {
 int tsba_debug_solver_info(void *ctx, int32_t *out, int n) {
     Ctx *c = (Ctx *)ctx; if (!c || !out || n < 16) return TSBA_ERR_ARG;
     if (!c->uploaded) return TSBA_ERR_STATE;
-    int use_lds; solve_lds_bytes(c, &use_lds);
-    int bwmax = 0; for (int l = 0; l < c->n_levels; l++) if (c->lev_built[l]) bwmax = std::max(bwmax, c->lev[l].bw_rows);
-    out[0] = use_lds; out[1] = c->W.band; out[2] = c->band_stream; out[3] = c->band_stream ? c->band_parts : 0; out[4] = c->sep_cr ? 1 : 0; out[5] = bwmax;
+    const SolverLayout &L = c->lay;                      // (band rows: of the levels on the device NOW -- a deferring call stages the later passes' during its solve)
+    out[0] = L.use_lds; out[1] = L.band; out[2] = L.band_stream; out[3] = L.band_stream ? L.P : 0; out[4] = L.sep_cr; out[5] = max_band_rows(c);
     out[6] = lin_small_pairs(c, c->lev[c->opt.levels[0]]) ? 1 : 0; out[7] = c->pose_only ? 1 : 0; out[8] = c->n_kf > 126 ? 1 : 0;
     out[9] = c->world; out[10] = c->rank;
     { const LevelDev &D0 = c->lev[c->opt.levels[0]]; out[11] = D0.n_pair; out[12] = D0.n_sb; out[13] = D0.n_sc; out[14] = D0.n_pslot; out[15] = D0.kf_order ? 1 : 0; }

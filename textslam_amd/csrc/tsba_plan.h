@@ -287,12 +287,12 @@ struct BucketPlacer {
 // arrives at exactly these lists through its generic passes (candidate keys, bucket placements, slot pairs: 0.03 - 0.07 ms per level, on threads of their own in
 // a one-shot call); here they are written down directly -- a copy of the input arrays -- in a few microseconds on the calling thread, so that a one-shot
 // tsba_pose_optim call plans and stages all its levels before the solve (round 6; tests/test_band_partition.py compares the checksum over every list with build_plan's).
-inline bool plan_is_single_frame(const tsba_problem *p, const tsba_options *o) {
-    if (p->n_kf != 1 || o->lm_nshard > 1) return false;
+inline bool every_landmark_frozen(const tsba_problem *p) {          // every point and plane has its host outside the problem
     for (int j = 0; j < p->n_pt; j++) if (p->pt_host[j] >= 0) return false;
     for (int j = 0; j < p->n_text; j++) if (p->text_host[j] >= 0) return false;
     return true;
 }
+inline bool plan_is_single_frame(const tsba_problem *p, const tsba_options *o) { return p->n_kf == 1 && o->lm_nshard <= 1 && every_landmark_frozen(p); }
 inline void build_plan_single_frame(const tsba_problem *p, const tsba_options *o, int L, HostPlan &P) {
     P.recycle(); P.level = L;
     const int n_pt = p->n_pt, n_text = p->n_text, n_sc = p->n_sobs[L], n_tg = o->use_text ? p->n_tobs : 0, n_pair = (n_sc > 0 || n_tg > 0) ? 1 : 0;

@@ -192,6 +192,7 @@ __device__ __forceinline__ void solve_backsub_wave(double *A, double *LD, int n,
 
 #define SOLVE_DIAG_NB 96                     // diagonal block of the large-system Cholesky (tsba_chol.h)
 static size_t solve_lds_doubles(int N) { return (size_t)rowoff(N + 1) + 16 + (size_t)SOLVE_LD*(N/6) + 36*SOLVE_PW + 8; }
+static bool lds_solver_fits(int N) { return solve_lds_doubles(N)*sizeof(double) <= 160*1024 - 64; }      // gfx950: 160 KB of LDS per workgroup; N: worst case, every pose free
 static size_t solve_diag_lds_doubles() { return solve_lds_doubles(SOLVE_DIAG_NB) + rowoff(SOLVE_DIAG_NB + 1) + SOLVE_DIAG_NB + 36*(SOLVE_DIAG_NB/6) + 16; }
 
 

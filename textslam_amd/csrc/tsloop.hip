@@ -385,7 +385,7 @@ int tsloop_optimize_loop(void *ctx, tsloop_graph_problem *p, const tsloop_option
     W.LDbuf = (double *)(d + o_LD); W.fidx = (int *)(d + o_sfidx); W.nfree = (int *)(d + o_nfree); W.dbg = (long long *)(d + o_dbg); W.st = (LmState *)(d + o_st);
     // ---- solver selection as in the BA library
     const size_t lds_small = solve_lds_doubles(n6)*sizeof(double);
-    const bool use_lds = lds_small <= 160*1024 - 64;
+    const bool use_lds = lds_solver_fits(n6);
     const int lds_diag = (int)(solve_diag_lds_doubles()*sizeof(double)), lds_panel = (CH_NB + 64)*(CH_NB + 1)*(int)sizeof(double), lds_upd = 2*64*(CH_NB + 1)*(int)sizeof(double),
               lds_bs = (CH_NB*(CH_NB + 1) + 2*CH_NB + 8*CH_NB)*(int)sizeof(double);
     if (use_lds) CKL(hipFuncSetAttribute((const void *)k_solve_t<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
