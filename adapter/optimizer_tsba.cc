@@ -2,13 +2,15 @@
 //
 // Lives in the TextSLAM tree next to src/optimizer.cc and replaces the bodies of the six BA / pose methods of src/optimizer.h:57-66
 // (signatures, callers -- tracking.cc:447,521,561,833,839, loopClosing.cc:589 -- and the host-side bookkeeping stay as they are):
-// each body is gather (adapter/tsba_gather.hpp) -> one C-ABI call -> scatter -> the reference's own UpdateTrackedText* call.
+// each body is gather (adapter/tsba_gather.hpp) -> one C-ABI call -> scatter -> the reference's own UpdateTrackedText* call, which takes the labels at the
+// detection centres (adapter/tsba_text_labels.hpp: const vector<float> &vLabel, INTEGRATION.md "The text label image") instead of the label image.
 // OptimizeSim3 / OptimizeLoop map onto include/tsloop.h the same way.  Build: add this file instead of the Pyr*
 // methods, -I<this repo>/include -I<this repo>/adapter, link -ltsba.  Not compiled by this repository (needs TextSLAM + Eigen +
 // OpenCV); the gather / scatter templates it instantiates are compiled and tested here through tests/cxx/abi_from_cxx.cpp.
 #include <optimizer.h>
 #include "tsba.h"
 #include "tsba_gather.hpp"
+#include "tsba_text_labels.hpp"
 #include "textslam_traits.hpp"
 
 namespace TextSLAM {
@@ -19,8 +21,8 @@ namespace {
 // One context per calling THREAD: TextSLAM's tracking, mapping and loop-closing threads call these methods concurrently (tracking.cc:447-561,
 // loopClosing.cc:589) and a tsba context serves one caller at a time (include/tsba.h).  thread_local keeps this file free of header changes;
 // with a header change the context would be a member of the optimizer object guarded like its other state.
-// The holder destroys the context when its thread exits (slabs, plane cache of 64 pyramid slots and streams go with it).  The label image below
-// reads the state of the last solve OF THE CALLING THREAD: UpdateTrackedTextBA runs on the thread that ran the BA (optimizer.cc:322-326), as here.
+// The holder destroys the context when its thread exits (slabs, plane cache of 64 pyramid slots and streams go with it).  The labels below
+// read the state of the last solve OF THE CALLING THREAD: UpdateTrackedTextBA runs on the thread that ran the BA (optimizer.cc:322-326), as here.
 struct CtxHolder { void *ctx = nullptr; ~CtxHolder() { if (ctx) tsba_destroy(ctx); } };
 void *tsba_ctx() { static thread_local CtxHolder h;
     if (!h.ctx && tsba_abi_version() != TSBA_ABI_VERSION) { std::cerr << "libtsba.so: ABI version " << tsba_abi_version() << ", this adapter was built against " << TSBA_ABI_VERSION << std::endl; exit(-1); }
@@ -33,8 +35,6 @@ void k_of(const Mat33 &K, double out[4]) { out[0] = K(0, 0); out[1] = K(1, 1); o
 // downloaded the LAST ACCEPTED state and the flags of the passes that ran (tsba.hip: one_shot returns the status after tsba_download), so
 // the scatter below writes a consistent state -- as Ceres leaves the parameter blocks at the best iterate.  Everything else is an error.
 bool failed(int rc, const char *what) { if (rc != TSBA_OK && rc != TSBA_ERR_NUMERIC) { std::cerr << what << ": " << tsba_last_error(tsba_ctx()) << std::endl; return true; } return false; }
-// label image of keyframe `kf` for the state left by the last solve: the TextLabelImg of ShowBAReproj_TextBox (optimizer.cc:2508-2582)
-cv::Mat label_image(int kf, const cv::Size &size) { cv::Mat lab(size, CV_32F); tsba_text_label_image(tsba_ctx(), kf, 0, (float *)lab.data); return lab; }
 }
 
 void optimizer::LocalBundleAdjustment(map *mpMap, vector<keyframe *> vKFs, const BAStatus &STATE) {
@@ -50,9 +50,10 @@ void optimizer::LocalBundleAdjustment(map *mpMap, vector<keyframe *> vKFs, const
     if (failed(tsba_local_ba(tsba_ctx(), &P.p, &o, &rep), "tsba_local_ba")) return;
     tsba_adapter::scatter_map<TT>(P, vKFs, vMapPts, vMapTexts, /*poses*/true, /*flags*/true);                               // :292-326
     keyframe *KFCur = vKFs[vKFs.size() - 1];
-    cv::Mat ImgTextLabel = label_image((int)vKFs.size() - 1, KFCur->vFrameImg[0].size());
+    vector<float> vLabel;                                                                                                   // the label image at the detection centres
+    if (failed(tsba_adapter::labels_at_centres(tsba_ctx(), (int)vKFs.size() - 1, KFCur->vTextDeteCenter, vLabel), "tsba_text_label_at")) return;
     vector<int> vIdxGOOD2Raw = GetNewIdxForTextState(KFCur->vObvText, TEXTGOOD);
-    UpdateTrackedTextBA(KFCur->vObvText, vIdxGOOD2Raw, ImgTextLabel, KFCur, false);                                         // :328-329
+    UpdateTrackedTextBA(KFCur->vObvText, vIdxGOOD2Raw, vLabel, KFCur, false);                                               // :328-329
 }
 
 void optimizer::GlobalBA(map *mpMap) {
@@ -81,11 +82,14 @@ void optimizer::OptimizeLandmarker(map *mpMap) {
     tsba_report rep;
     if (failed(tsba_local_ba(tsba_ctx(), &P.p, &o, &rep), "tsba_local_ba(landmarker)")) return;
     tsba_adapter::scatter_map<TT>(P, vKFs, vMapPts, vMapTexts, /*poses stay*/false, true);                                // :543-556
-    for (int back = 2; back >= 1; back--) {                                                                                // the two newest keyframes, :558-561
+    vector<int> kfs2; vector<const vector<Vec2> *> centres2;                                                              // the two newest keyframes, :558-561: their labels in one call
+    for (int back = 2; back >= 1; back--) { kfs2.push_back((int)vKFs.size() - back); centres2.push_back(&vKFs[vKFs.size() - back]->vTextDeteCenter); }
+    vector<vector<float> > vLabels;
+    if (failed(tsba_adapter::labels_at_centres(tsba_ctx(), kfs2, centres2, vLabels), "tsba_text_label_at")) return;
+    for (int back = 2; back >= 1; back--) {
         keyframe *KF = vKFs[vKFs.size() - back];
-        cv::Mat lab = label_image((int)vKFs.size() - back, KF->vFrameImg[0].size());
         vector<int> vIdx = GetNewIdxForTextState(KF->vObvText, TEXTGOOD);
-        UpdateTrackedTextBA(KF->vObvText, vIdx, lab, KF, false);
+        UpdateTrackedTextBA(KF->vObvText, vIdx, vLabels[2 - back], KF, false);
     }
 }
 
@@ -104,8 +108,9 @@ void optimizer::PoseOptim(frame &F) {
     tsba_adapter::scatter_pose<TT>(P, F);                                                                                 // :188-190
     vector<TextObservation *> TextObjs;
     for (size_t i = 0; i < F.vObvText.size(); i++) if (F.vObvText[i]->obj->STATE == TEXTGOOD) TextObjs.push_back(F.vObvText[i]);
-    cv::Mat ImgTextLabel = label_image(0, F.vFrameImg[0].size());
-    UpdateTrackedTextPOSE(TextObjs, ImgTextLabel, F);                                                                      // :192
+    vector<float> vLabel;
+    if (failed(tsba_adapter::labels_at_centres(tsba_ctx(), 0, F.vTextDeteCenter, vLabel), "tsba_text_label_at")) return;
+    UpdateTrackedTextPOSE(TextObjs, vLabel, F);                                                                            // :192
 }
 
 void optimizer::InitBA(keyframe *F1, keyframe *F2) {
@@ -116,8 +121,9 @@ void optimizer::InitBA(keyframe *F1, keyframe *F2) {
     tsba_report rep;
     if (failed(tsba_local_ba(tsba_ctx(), &P.p, &o, &rep), "tsba_local_ba(init)")) return;
     tsba_adapter::scatter_init<TT>(P, *F1, *F2);                                                                          // :119-129
-    cv::Mat ImgTextLabel = label_image(1, F2->vFrameImg[0].size());
-    UpdateTrackedTextBA(F2->vObvText, ImgTextLabel, F2, true);                                                             // :131
+    vector<float> vLabel;
+    if (failed(tsba_adapter::labels_at_centres(tsba_ctx(), 1, F2->vTextDeteCenter, vLabel), "tsba_text_label_at")) return;
+    UpdateTrackedTextBA(F2->vObvText, vLabel, F2, true);                                                                   // :131
 }
 
 bool optimizer::ThetaOptimMultiFs(const frame &F, mapText *&obj) {

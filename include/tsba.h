@@ -248,8 +248,22 @@ int  tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const 
  * tool::TextBoxWithFill / GetTextLabelMask, src/tool.cc:2103-2166): background -1, then every text observation of the keyframe,
  * in the order of tobs_*, fills its projected quad (cv::Point truncation, cv::fillPoly scan conversion) with its rank among the
  * keyframe's observations; later quads overwrite earlier ones.  out: img_h[level] * img_w[level] floats (the CV_32F Mat that
- * optimizer::UpdateTrackedTextBA, optimizer.cc:2246-2386, reads).  The drawing of box outlines / ids stays in the host. */
+ * optimizer::UpdateTrackedTextBA, optimizer.cc:2246-2386, reads).  The drawing of box outlines / ids stays in the host.
+ * It remains for that drawing half (a whole label image to show) and for tests; what UpdateTrackedText* need of the image -- its value at the
+ * detection centres -- comes from tsba_text_label_at below, without the image. */
 int  tsba_text_label_image(void *ctx, int kf, int level, float *out);
+
+/* label[i] = the value tsba_text_label_image(ctx, kf[i], level, ...) has at pixel (px[2i], px[2i+1]): the rank, among keyframe kf[i]'s text
+ * observations in tobs order, of the LAST one whose projected quad (cv::Point truncation, cv::fillPoly) contains the pixel; -1 where none
+ * does, and -1 for a pixel outside the level image (the reference reads out of bounds there; same decision as tsframe_text_judge).
+ * Any mix of keyframes in one call, one launch; nothing image-sized is written, allocated or copied.  State of the last solve on this context,
+ * left unchanged.  n == 0 launches nothing.
+ *   errors: TSBA_ERR_STATE without an uploaded problem; TSBA_ERR_ARG for n < 0, a NULL pointer with n > 0, a kf[i] outside [0, n_kf), a level that is
+ *     not uploaded or has no image geometry.  Nothing is written on error.
+ *   transfers: queries and labels go through a pinned block of the context that grows on demand: one host-to-device copy, one launch, one
+ *     device-to-host copy, one synchronisation.  No 640 x 480 limit: there is no mask.
+ * No struct changed for it: TSBA_ABI_VERSION stays 5. */
+int  tsba_text_label_at(void *ctx, int level, int n, const int32_t *kf, const int32_t *px /*[n][2]*/, int32_t *label /*[n]*/);
 
 /* ---- staged calls (bench / repeated solves with the problem resident in HBM) ---- */
 int  tsba_upload  (void *ctx, const tsba_problem *p, const tsba_options *o);

@@ -126,6 +126,7 @@ struct Ctx {
     int band_parts = 1; double *Lb = nullptr, *Tbuf = nullptr, *Bpart = nullptr, *Ssep = nullptr, *Lcol_sep = nullptr, *CRcontrib = nullptr, *CRfac = nullptr; int *CRgate = nullptr; int cre_epoch = 0; int nsep_ld = 0; Work Wsep;   // partitioned band solver (tsba_bandp.h)
     double *Lcol = nullptr; int band_stream = 0;  // streaming band solver (tsba_band.h): L by block column; 1 = every built level fits it     // storage behind W.S (dense or band)
     float *lbl_dev = nullptr, *lbl_host = nullptr; size_t lbl_cap = 0;   // text label image staging
+    int32_t *lat_dev = nullptr, *lat_host = nullptr; size_t lat_cap = 0;   // tsba_text_label_at: queries (kf [cap] | px [cap][2]) and labels [cap], device and pinned; grows on demand
     unsigned long long *hprog = nullptr; unsigned int pass_seq = 0;   // pinned progress word written by k_postlin / k_decide
     std::vector<struct Slab> slabs; int cur_slab = 0;
     int run_slab = 0; size_t run_off = 0, run_len = 0;   // pending contiguous host-to-device range
@@ -345,6 +346,7 @@ int tsba_destroy(void *ctx) {
     if (c->comm && c->p_destroy) c->p_destroy(c->comm);
     hipHostFree(c->st_host); hipFree(c->st_log); if (c->hprog) hipHostFree(c->hprog);
     if (c->lbl_dev) hipFree(c->lbl_dev); if (c->lbl_host) hipHostFree(c->lbl_host);
+    if (c->lat_dev) hipFree(c->lat_dev); if (c->lat_host) hipHostFree(c->lat_host);
     if (c->ic.dev) hipFree(c->ic.dev); if (c->ic.stage) hipHostFree(c->ic.stage);
     if (c->tb_dev) hipFree(c->tb_dev); if (c->tb_host) hipHostFree(c->tb_host); if (c->tb_out) hipHostFree(c->tb_out);
     if (c->ms_alloc) hipFree(c->ms_alloc);

@@ -196,6 +196,32 @@ int tsba_text_label_image(void *ctx, int kf, int level, float *out) {
     return TSBA_OK;
 }
 
+// The label image's values at n pixels (k_label_at): queries and labels through one pinned block (kf [n] | px [n][2] | label [n]) -- one copy in, one launch,
+// one copy out, one synchronisation; nothing image-sized anywhere, so no limit on the level's size.
+int tsba_text_label_at(void *ctx, int level, int n, const int32_t *kf, const int32_t *px, int32_t *label) {
+    Ctx *c = (Ctx *)ctx; if (!c || n < 0) return TSBA_ERR_ARG;
+    if (!c->uploaded) { set_err(c, "no problem uploaded"); return TSBA_ERR_STATE; }
+    if (level < 0 || level >= c->n_levels || !c->lev_built[level]) { set_err(c, "tsba_text_label_at: level out of range or not uploaded"); return TSBA_ERR_ARG; }
+    const LevelDev &D = c->lev[level];
+    if (D.img_w <= 0 || D.img_h <= 0) { set_err(c, "tsba_text_label_at: no image geometry for this level"); return TSBA_ERR_ARG; }
+    if (n == 0) return TSBA_OK;
+    if (!kf || !px || !label) { set_err(c, "tsba_text_label_at: NULL argument"); return TSBA_ERR_ARG; }
+    for (int i = 0; i < n; i++) if (kf[i] < 0 || kf[i] >= c->n_kf) { set_err(c, "tsba_text_label_at: keyframe out of range"); return TSBA_ERR_ARG; }
+    hipSetDevice(c->device);
+    const size_t nq = (size_t)n;
+    if (c->lat_cap < nq) { if (c->lat_dev) hipFree(c->lat_dev); if (c->lat_host) hipHostFree(c->lat_host); c->lat_dev = c->lat_host = nullptr; c->lat_cap = 0;
+        const size_t cap = std::max<size_t>(64, nq + nq/2);
+        CK(hipMalloc((void **)&c->lat_dev, 4*cap*sizeof(int32_t))); CK(hipHostMalloc((void **)&c->lat_host, 4*cap*sizeof(int32_t), hipHostMallocDefault)); c->lat_cap = cap; }
+    memcpy(c->lat_host, kf, nq*sizeof(int32_t)); memcpy(c->lat_host + nq, px, 2*nq*sizeof(int32_t));
+    CK(hipMemcpyAsync(c->lat_dev, c->lat_host, 3*nq*sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_label_at, dim3((unsigned)((nq + LBA_WAVES - 1)/LBA_WAVES)), dim3(64*LBA_WAVES), 0, c->stream, c->W, n, c->lat_dev, c->lat_dev + nq,
+                       D.img_w, D.img_h, D.K[0], D.K[1], D.K[2], D.K[3], c->lat_dev + 3*nq);
+    CK(hipMemcpyAsync(c->lat_host + 3*nq, c->lat_dev + 3*nq, nq*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    CK(hipStreamSynchronize(c->stream)); CK(hipGetLastError());
+    memcpy(label, c->lat_host + 3*nq, nq*sizeof(int32_t));
+    return TSBA_OK;
+}
+
 // which kernels the uploaded problem runs through (so that a test can assert that it exercises the path it means to):
 // out[0] reduced system in LDS (k_solve_t / k_solve_col)   [1] band storage   [2] streaming band solver   [3] interiors P
 // [4] separator system by cyclic reduction   [5] band rows   [6] four pairs per wave in the linearisation of the first pass's level

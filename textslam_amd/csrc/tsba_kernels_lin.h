@@ -385,6 +385,29 @@ __global__ __launch_bounds__(MS_THREADS) void k_musigma(Work W, LevelDev L) {
 // tool.cc:2103-2166): background -1, then every text observation of the keyframe in observation order fills its projected quad
 // with its rank; later quads overwrite earlier ones, so ONE workgroup walks the observations sequentially (a keyframe sees a few
 // dozen planes) and only the rasterisation of each quad is parallel.
+// The corners of text plane j (host h) projected into keyframe kf and truncated as cv::Point(double, double) does.  ONE piece of machine code for k_label and
+// k_label_at (this translation unit contracts FMAs): inlined twice, the two could disagree on a corner that lies within an ulp of an integer.
+struct LabelQuad { int xy[8]; };
+__device__ __noinline__ LabelQuad label_quad(const double *pose, const double *theta, const double *text_Twr, const double *text_box, int kf, int j, int h,
+                                             double fx, double fy, double cx, double cy) {
+    LabelQuad q;
+    Pose C; load_pose(pose + 7*kf, C);
+    PairT T;
+    if (h >= 0) { Pose Hs; load_pose(pose + 7*h, Hs); pair_from_poses(C, Hs, T); }
+    else pair_from_Twr(C, text_Twr + 12*j, T);
+    const double th[3] = { theta[3*j], theta[3*j+1], theta[3*j+2] };
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const double mx = text_box[(j*4 + b)*2], my = text_box[(j*4 + b)*2 + 1];
+        const double invz = -(mx*th[0] + my*th[1] + th[2]);
+        double m[3] = { mx, my, 1.0 }, Rm[3]; mat3_vec(T.Rcr, m, Rm);
+        const double X = Rm[0]/invz + T.tq[0] + C.t[0], Y = Rm[1]/invz + T.tq[1] + C.t[1], Z = Rm[2]/invz + T.tq[2] + C.t[2];
+        const double cu = fx*X/Z + cx, cv = fy*Y/Z + cy;
+        q.xy[2*b] = (int)cu; q.xy[2*b+1] = (int)cv;               // cv::Point(double, double): truncation
+    }
+    return q;
+}
+
 #define LBL_THREADS 1024
 __global__ __launch_bounds__(LBL_THREADS) void k_label(Work W, int kf, int w, int hh, double fx, double fy, double cx, double cy, float *out) {
     __shared__ unsigned mask[MS_MASK_WORDS];
@@ -397,19 +420,10 @@ __global__ __launch_bounds__(LBL_THREADS) void k_label(Work W, int kf, int w, in
         if (W.tobs_kf[t] != kf) continue;                   // (uniform)
         const int j = W.tobs_text[t], h = W.text_host[j];
         if (tid == 0) {
-            Pose C; load_pose(pose + 7*kf, C);
-            PairT T;
-            if (h >= 0) { Pose Hs; load_pose(pose + 7*h, Hs); pair_from_poses(C, Hs, T); }
-            else pair_from_Twr(C, W.text_Twr + 12*j, T);
-            const double th[3] = { theta[3*j], theta[3*j+1], theta[3*j+2] };
+            const LabelQuad q = label_quad(pose, theta, W.text_Twr, W.text_box, kf, j, h, fx, fy, cx, cy);
             int xMin = w, xMax = -1, yMin = hh, yMax = -1;
             for (int b = 0; b < 4; b++) {
-                const double mx = W.text_box[(j*4 + b)*2], my = W.text_box[(j*4 + b)*2 + 1];
-                const double invz = -(mx*th[0] + my*th[1] + th[2]);
-                double m[3] = { mx, my, 1.0 }, Rm[3]; mat3_vec(T.Rcr, m, Rm);
-                const double X = Rm[0]/invz + T.tq[0] + C.t[0], Y = Rm[1]/invz + T.tq[1] + C.t[1], Z = Rm[2]/invz + T.tq[2] + C.t[2];
-                const double cu = fx*X/Z + cx, cv = fy*Y/Z + cy;
-                const int iu = (int)cu, iv = (int)cv;                 // cv::Point(double, double): truncation
+                const int iu = q.xy[2*b], iv = q.xy[2*b+1];
                 s_xy[2*b] = iu; s_xy[2*b+1] = iv;
                 xMin = min(xMin, iu); xMax = max(xMax, iu); yMin = min(yMin, iv); yMax = max(yMax, iv);
             }
@@ -429,6 +443,37 @@ __global__ __launch_bounds__(LBL_THREADS) void k_label(Work W, int kf, int w, in
         rank++;
         __syncthreads();
     }
+}
+
+// ---- the same labels at n pixels, without the image (what UpdateTrackedText* read of it: the detection centres, optimizer.cc:2251-2257).  One wave per query
+// q = (keyframe, x, y): the wave walks the text observations 64 at a time; a lane whose observation belongs to the keyframe has rank = matches in the chunks
+// before (base) + matches below it in this chunk's ballot, projects its quad (label_quad) and tests the pixel (quad_covers).  Later quads overwrite earlier ones
+// in the image: the label is the LARGEST covering rank.  Reads the state of the last solve, writes label[] only.
+#define LBA_WAVES 4
+__global__ __launch_bounds__(64*LBA_WAVES) void k_label_at(Work W, int n, const int *q_kf, const int *q_px, int w, int hh, double fx, double fy, double cx, double cy, int *label) {
+    const int lane = threadIdx.x & 63, qi = blockIdx.x*LBA_WAVES + (threadIdx.x >> 6);
+    if (qi >= n) return;                                    // (uniform in the wave)
+    const int kf = q_kf[qi], x = q_px[2*qi], y = q_px[2*qi+1];
+    int best = -1;
+    if (x >= 0 && x < w && y >= 0 && y < hh) {              // (uniform in the wave)
+        const double *pose = W.pose[W.st->cur], *theta = W.theta[W.st->cur];
+        int base = 0;
+        for (int t0 = 0; t0 < W.n_tobs; t0 += 64) {
+            const int t = t0 + lane;
+            const bool mine = t < W.n_tobs && W.tobs_kf[t] == kf;
+            const unsigned long long bal = __ballot(mine);
+            if (mine) {
+                const int rank = base + __popcll(bal & ((1ull << lane) - 1ull));
+                const int j = W.tobs_text[t];
+                const LabelQuad c = label_quad(pose, theta, W.text_Twr, W.text_box, kf, j, W.text_host[j], fx, fy, cx, cy);
+                if (quad_covers(c.xy, w, hh, x, y)) best = rank;             // (a lane's ranks grow from chunk to chunk)
+            }
+            base += __popcll(bal);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
+    }
+    if (lane == 0) label[qi] = best;
 }
 
 // ---- linearisation / cost.  grid = n_pair (scene waves) + n_tg (text waves), 64 threads each.

@@ -38,6 +38,8 @@ def load_library():
     L.tsba_upload.argtypes = [vp, C.POINTER(TsbaProblem), C.POINTER(TsbaOptions)]
     L.tsba_solve.argtypes = [vp, C.POINTER(TsbaReport)]
     L.tsba_text_label_image.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.tsba_text_label_at.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.tsba_text_label_at.restype = C.c_int
     L.tsba_download.argtypes = [vp, C.POINTER(TsbaProblem)]
     L.tsba_eval.argtypes = [vp, C.POINTER(TsbaProblem), C.POINTER(TsbaOptions), C.c_int, dp, dp, dp,
                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -80,6 +82,7 @@ EXPORTED_SYMBOLS = [
     "tsba_abi_version", "tsba_create", "tsba_destroy", "tsba_last_error",
     "tsba_default_options_init", "tsba_default_options_landmarker", "tsba_default_options_theta",
     "tsba_local_ba", "tsba_pose_optim", "tsba_global_ba", "tsba_theta_optim", "tsba_theta_optim_batch", "tsba_text_label_image",
+    "tsba_text_label_at",
     "tsba_upload", "tsba_solve", "tsba_download", "tsba_eval", "tsba_time_linearize",
     "tsba_comm_unique_id", "tsba_comm_load", "tsba_comm_init", "tsba_comm_init_local", "tsba_local_group_create", "tsba_local_group_destroy",
     "tsba_debug_set", "tsba_debug_reduced_system",
@@ -183,6 +186,21 @@ class Optimizer:
         (the TextLabelImg of optimizer::ShowBAReproj_TextBox)."""
         out = np.zeros(shape, np.float32)
         self._check(self.lib.tsba_text_label_image(self.ctx, int(kf), int(level), out.ctypes.data_as(C.POINTER(C.c_float))), "tsba_text_label_image")
+        return out
+
+    def TextLabelAt(self, level: int, kf, px):
+        """The label image's values at n pixels without the image (tsba_text_label_at): kf [n] (or one keyframe for all), px [n, 2] integer
+        (x, y) at pyramid level `level` -> int32 [n]: the rank of the last text observation of kf[i] whose quad covers the pixel, -1 where none
+        does or the pixel lies outside the level image.  State of the last solve; one launch for any mix of keyframes."""
+        px = np.ascontiguousarray(np.asarray(px, np.int32).reshape(-1, 2))
+        n = px.shape[0]
+        kf = np.asarray(kf, np.int32).reshape(-1)
+        kf = np.ascontiguousarray(np.broadcast_to(kf, (n,)) if kf.size == 1 else kf)
+        if kf.shape[0] != n:
+            raise ValueError("TextLabelAt: %d keyframes for %d pixels" % (kf.shape[0], n))
+        out = np.full(n, -1, np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.tsba_text_label_at(self.ctx, int(level), n, kf.ctypes.data_as(ip), px.ctypes.data_as(ip), out.ctypes.data_as(ip)), "tsba_text_label_at")
         return out
 
     def _one_shot(self, fn, prob, o, what):
