@@ -34,6 +34,10 @@ extern "C" {
 #endif
 
 #define TSBA_MAX_LEVELS 4
+/* Largest width / height of an image level of a text-bearing problem: tsba_upload, tsba_local_ba, tsba_pose_optim, tsba_theta_optim and tsba_theta_optim_batch
+ * return TSBA_ERR_ARG above it.  A level of up to 640 x 480 pixels keeps a projected text box's fill mask whole in LDS; a larger one builds it in row bands
+ * (same mu / sigma bits, same label image).  tsorb_text_extract (include/tsorb.h) is the one text path still capped at a 640 x 480 level 0. */
+#define TSBA_MAX_IMAGE_DIM 8192
 #define TSBA_NTAP 8            /* INTERVAL8 pattern, tool.cc:1550-1561 */
 
 /* error codes */
@@ -226,8 +230,8 @@ int  tsba_theta_optim(void *ctx, tsba_problem *p, const tsba_options *o, int tex
  * LM solve, passes, report and covariance, exactly as n calls of tsba_theta_optim on single-plane problems would (within rounding: same iterations and
  * terminations).  cov: [n][9], row i written only where reps[i].cov_valid == 1.  reps: [n].
  *   shape of every probs[i], checked before anything runs: n_text == 1 and 0 <= text_host[0] < n_kf; n_pt == 0 and every n_sobs[l] == 0; every
- *     kf_initial[k] == 1; every tobs_text == 0; every level that o->levels[] uses exists (image of at most 640 x 480 = MS_MASK_WORDS x 32 pixels,
- *     the general path's limit).
+ *     kf_initial[k] == 1; every tobs_text == 0; every level that o->levels[] uses exists (image of at most TSBA_MAX_IMAGE_DIM pixels per
+ *     side, the general path's limit).
  *   options: one shared o with use_text == 1, filter_good == 0, outlier_scene == outlier_text == 0 (tsba_default_options_theta: PyrThetaOptim filters
  *     nothing and runs no outlier pass); huber_text is honoured (1e300 = no loss).
  *   errors: any violation returns TSBA_ERR_ARG and writes nothing; tsba_last_error names the problem index and the reason.  n == 0 returns TSBA_OK.
@@ -251,7 +255,7 @@ int  tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const 
  * optimizer::UpdateTrackedTextBA, optimizer.cc:2246-2386, reads).  The drawing of box outlines / ids stays in the host.
  * It remains for that drawing half (a whole label image to show) and for tests; what UpdateTrackedText* need of the image -- its value at the
  * detection centres -- comes from tsba_text_label_at below, without the image. */
-int  tsba_text_label_image(void *ctx, int kf, int level, float *out);
+int  tsba_text_label_image(void *ctx, int kf, int level, float *out);   /* any level size the upload accepted (up to TSBA_MAX_IMAGE_DIM per side) */
 
 /* label[i] = the value tsba_text_label_image(ctx, kf[i], level, ...) has at pixel (px[2i], px[2i+1]): the rank, among keyframe kf[i]'s text
  * observations in tobs order, of the LAST one whose projected quad (cv::Point truncation, cv::fillPoly) contains the pixel; -1 where none
@@ -261,7 +265,7 @@ int  tsba_text_label_image(void *ctx, int kf, int level, float *out);
  *   errors: TSBA_ERR_STATE without an uploaded problem; TSBA_ERR_ARG for n < 0, a NULL pointer with n > 0, a kf[i] outside [0, n_kf), a level that is
  *     not uploaded or has no image geometry.  Nothing is written on error.
  *   transfers: queries and labels go through a pinned block of the context that grows on demand: one host-to-device copy, one launch, one
- *     device-to-host copy, one synchronisation.  No 640 x 480 limit: there is no mask.
+ *     device-to-host copy, one synchronisation.  No mask, so nothing depends on the level's size.
  * No struct changed for it: TSBA_ABI_VERSION stays 5. */
 int  tsba_text_label_at(void *ctx, int level, int n, const int32_t *kf, const int32_t *px /*[n][2]*/, int32_t *label /*[n]*/);
 

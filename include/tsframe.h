@@ -74,7 +74,8 @@ int tsframe_box_pixels(void *ctx, int level, const double *quad, double mu, doub
  * this frame.  cos_min: the reference passes 0 (its int parameter truncates the callers' 0.5), so 0 is the drop-in value; out_margin >= 0;
  * zncc_min <= -2 skips the ZNCC test.  dete_xy[n_dete][2] = vTextDeteCenter (level 0); with dete_bits non-NULL, bit j of plane i's
  * (n_dete + 31) / 32 words is set when the plane passed and detection j lies in its projected quad (cv::fillPoly on a label image of
- * the level-0 size, which must be at most 640 x 480; a centre outside that image is not associated).
+ * the level-0 size, whatever that size is: up to 640 x 480 the filled mask is built, above it every rounded centre is tested against the same fill
+ * without one; a centre outside that image is not associated).
  * Out, per plane: pass (1 / 0), reason (TSFRAME_JUDGE_*), cos, zncc (NaN when not computed or fewer than 2 pixels, -100 for a constant
  * vector, as the reference), box_uv[8] = the four projected corners (always all four).  n == 0 launches nothing.  The resident planes
  * are read in place and left unchanged. */

@@ -79,6 +79,11 @@ static void lds_poison_hook(hipStream_t st) {
 }
 #define LAUNCHK(kern, grid, block, lds, st, ...) do { lds_poison_hook(st); hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__); } while (0)
 // ------------------------------------------------------------------------------------------------ host side
+// a kernel with a mu / sigma part, in the instantiation for the level's geometry: BIG where the level's bit mask does not fit MS_MASK_WORDS (musigma_core)
+static inline bool ms_big(int w, int h) { return (size_t)w*(size_t)h > (size_t)MS_MASK_WORDS*32; }
+static inline bool ms_big(const LevelDev &D) { return ms_big(D.img_w, D.img_h); }
+#define LAUNCHK_MS(big, kern, ...) do { if (big) LAUNCHK(kern<true>, __VA_ARGS__); else LAUNCHK(kern<false>, __VA_ARGS__); } while (0)
+static inline bool image_dims_ok(int w, int h) { return w > 0 && h > 0 && w <= TSBA_MAX_IMAGE_DIM && h <= TSBA_MAX_IMAGE_DIM; }
 static int pose_grid(const LevelDev &D) { return std::max(1, (D.n_sc + 255)/256 + (D.n_pf + 31)/32); }    // workgroups of k_pose_iter
 struct Ctx {
     int device = 0;
@@ -426,7 +431,7 @@ static int check_problem(Ctx *c, const tsba_problem *p, const tsba_options *o) {
                 if (maxraw[p->tobs_text[t]] >= p->tobs_fgood_off[t+1] - p->tobs_fgood_off[t]) return bad("tfeat_raw exceeds the observation's flag span");
         }
         if (o->use_text && p->n_tobs > 0)
-            if (!p->img[l] || p->img_w[l] <= 0 || p->img_h[l] <= 0 || p->img_w[l]*p->img_h[l] > MS_MASK_WORDS*32) { set_err(c, "missing image level or image larger than 640x480"); return TSBA_ERR_ARG; }
+            if (!p->img[l] || !image_dims_ok(p->img_w[l], p->img_h[l])) { set_err(c, "missing image level or image side above TSBA_MAX_IMAGE_DIM (" + std::to_string(TSBA_MAX_IMAGE_DIM) + ")"); return TSBA_ERR_ARG; }
     }
     return 0;
 }
@@ -916,7 +921,7 @@ static void launch_pass_init(Ctx *c, const LevelDev &D, int pass) {
     else LAUNCHK(k_gauge, dim3(1), dim3(64), 0, c->stream, W, (const uint8_t *)c->kf_initial, o.state, ncp, D.kf_order);
     if (D.far_B > 0 && D.far_rec) { const int ne = D.n_far_ent;      // the blocks outside the band by keyframe, with the other keyframe's row (the gauge is fixed now)
         if (ne > 0) LAUNCHK(k_far_rows, dim3((ne + 255)/256), dim3(256), 0, c->stream, W, D, ne); }
-    if (D.n_tg > 0) LAUNCHK(k_musigma, dim3(D.n_tg), dim3(MS_THREADS), 0, c->stream, W, D);
+    if (D.n_tg > 0) LAUNCHK_MS(ms_big(D), k_musigma, dim3(D.n_tg), dim3(MS_THREADS), 0, c->stream, W, D);
 }
 // k_mid's blocks: 256 landmarks / pairs each.  tsba_debug_options.trial_launches = 1 / 2 (the k_lin_mid experiment and its comparison partner): 128 (MID_TW: what a
 // workgroup of the linearisation can take over)
@@ -1494,7 +1499,7 @@ static int pose_pass(Ctx *c, int ps, PassCarry &carry) {
     const tsba_options &o = c->opt; const LevelDev &D = c->lev[o.levels[ps]]; const int G = pose_grid(D);
     const bool one_launch = !carry.per_step && grid_resident(c, (const void *)k_pose_pass, POSE_WG, 0, G);
     c->W.hprog = c->hprog; c->W.pass_seq = ++c->pass_seq;                 // (k_pose_begin: k_pass_reset + k_participation + k_gauge + k_musigma in one launch)
-    LAUNCHK(k_pose_begin, dim3(D.n_tg + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial,
+    LAUNCHK_MS(ms_big(D), k_pose_begin, dim3(D.n_tg + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial,
             one_launch ? c->W.ppart : (double *)nullptr, 3*28*G, carry.log_pending ? c->st_log + ps - 1 : (LmState *)nullptr);
     int k_last = -1;                                     // (k_pose_pass leaves the final state in pst[0])
     if (one_launch) LAUNCHK(k_pose_pass, dim3(G), dim3(POSE_WG), 0, c->stream, c->W, D, o, G, o.its[ps]);
@@ -1531,7 +1536,7 @@ static int window_pass(Ctx *c, int ps, PassCarry &carry) {
     c->W.hprog = c->hprog; c->W.pass_seq = ++c->pass_seq; c->W.trace_pass = ps;
     // (at most PB_WG workgroups walk k_participation's npb blocks: every arrival at the ticket is a device-wide fence and an atomic on one word -- 30 - 40 ns each, one after the other: tools/ticket_bench.hip)
     const int npb = (D.n_sc + 255)/256 + (D.n_tg + 3)/4, nwg = std::min(npb, PB_WG), n_ms = carry.ms_ahead == ps ? 0 : D.n_tg;
-    LAUNCHK(k_pass_begin, dim3(nwg + n_ms), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial, o.state,
+    LAUNCHK_MS(ms_big(D), k_pass_begin, dim3(nwg + n_ms), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial, o.state,
                        npb, nwg, n_ms, carry.log_pending ? c->st_log + ps - 1 : (LmState *)nullptr, c->ticket);
     // k_postlin (the first linearisation's scaling, cost, gradient test: 8.6 us of one workgroup) inside the first trial's assembly
     int rc = lm_trials(c, D, ps, o.its[ps] > 0 && c->dbg.trial_launches != 3); if (rc) return rc;
@@ -1540,7 +1545,7 @@ static int window_pass(Ctx *c, int ps, PassCarry &carry) {
     const LevelDev *Dn = ln >= 0 && c->lev_built[ln] && window_fast(c, c->lev[ln], carry.per_step) && c->lev[ln].n_tg > 0 ? &c->lev[ln] : nullptr;
     if (Dn) { rc = level_ready(c, ln); if (rc) return rc; }      // (staged over the copy stream during this pass's trials: long since there)
     const int n_msn = Dn ? Dn->n_tg : 0;
-    LAUNCHK(k_pass_end, dim3((nb_out + 3)/4 + n_msn + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, Dn ? *Dn : D, nb_out, n_msn, c->musig2[c->musig_sel ^ 1],
+    LAUNCHK_MS(Dn && ms_big(*Dn), k_pass_end, dim3((nb_out + 3)/4 + n_msn + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, Dn ? *Dn : D, nb_out, n_msn, c->musig2[c->musig_sel ^ 1],
                        o.chi2_mono[ps], o.chi2_text[ps], o.text_bad_ratio, o.outlier_scene, o.outlier_text);
     if (Dn) { c->musig_sel ^= 1; c->W.musig = c->musig2[c->musig_sel]; carry.ms_ahead = ps + 1; }
     record_cov(c, ps);
@@ -1788,7 +1793,7 @@ static int theta_batch_check(Ctx *c, tsba_problem *const *probs, int n, const ts
         for (int ps = 0; ps < o->n_passes; ps++) {
             const int l = o->levels[ps];
             if (l >= p->n_levels) return bad(i, "level " + std::to_string(l) + " of the options does not exist");
-            if (!p->img[l] || p->img_w[l] <= 0 || p->img_h[l] <= 0 || p->img_w[l]*p->img_h[l] > MS_MASK_WORDS*32) return bad(i, "missing image level or image larger than 640x480");
+            if (!p->img[l] || !image_dims_ok(p->img_w[l], p->img_h[l])) return bad(i, "missing image level or image side above TSBA_MAX_IMAGE_DIM (" + std::to_string(TSBA_MAX_IMAGE_DIM) + ")");
             if (!p->tfeat_off[l] || p->tfeat_off[l][0] != 0 || p->tfeat_off[l][1] < 0 || p->tfeat_off[l][1] > p->n_tfeat[l]
                 || (p->tfeat_off[l][1] > 0 && (!p->tfeat_uv[l] || !p->tfeat_ref[l]))) return bad(i, "bad reference features");
             for (int t = 0; t < p->n_tobs; t++) if (!p->img[l][p->tobs_kf[t]]) return bad(i, "NULL image plane");
@@ -1868,7 +1873,10 @@ int tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const t
     auto t1 = std::chrono::steady_clock::now();
     ThArgs A; A.hdr = (const ThHdr *)(db + o_hdr); A.obs = (const ThObs *)(db + o_obs); A.fuv = (const double *)(db + o_uv); A.fref = (const double *)(db + o_ref);
     A.scr = (double *)(db + o_scr); A.out = (ThOut *)(db + o_out);
-    LAUNCHK(k_theta_batch<THETA_WG>, dim3(n), dim3(THETA_WG), 0, c->stream, A, *o);
+    bool big = false;                                              // (one launch walks every pass's level: BIG if any of them needs it)
+    for (int i = 0; i < n; i++) for (int ps = 0; ps < o->n_passes; ps++) big = big || ms_big(probs[i]->img_w[o->levels[ps]], probs[i]->img_h[o->levels[ps]]);
+    void (*const kern)(ThArgs, tsba_options) = big ? k_theta_batch<THETA_WG, true> : k_theta_batch<THETA_WG, false>;
+    LAUNCHK(kern, dim3(n), dim3(THETA_WG), 0, c->stream, A, *o);
     CK(hipGetLastError());
     CK(hipMemcpyAsync(c->tb_out, db + o_out, sizeof(ThOut)*n, hipMemcpyDeviceToHost, c->stream));
     CK(hipStreamSynchronize(c->stream));

@@ -245,7 +245,10 @@ __global__ __launch_bounds__(1024) void k_gauge_par(Work W, const uint8_t *kf_in
 // sum the 256 bins through block_sum<NT>: the slots past 255 add +0.0, so every NT gives the bits of NT = 256).  pc: the observing pose, ph: the host
 // pose (h_in) or its T_wr (3x4), th: the plane, (mx, my): box corner tid & 3.  Returns n < 2 (no moments: mu = sigma = 0) as false; *mu / *sigma in
 // every thread otherwise.  LDS: mask [MS_MASK_WORDS], hist [256], s_xy [8], s_bb [4], s_c [16], s_red [NT].
-template <int NT>
+// BIG = false: w hh <= MS_MASK_WORDS*32, the whole level's mask in LDS.  BIG = true: any size -- the mask is built and read in bands of B = MS_MASK_WORDS*32 / w rows
+// that start at the box's clamped yMin (raster_quad_rows: the full image's fill, a window of its rows), so a box no taller than B rows costs one band.  The moments
+// come from the integer histogram: the same bits whatever the order of the pixels and however they are banded.
+template <int NT, bool BIG>
 __device__ __forceinline__ bool musigma_core(const double pc[7], const double ph[12], bool h_in, const double th[3], double mx, double my,
                                              const double K[4], int w, int hh, const uint8_t *img,
                                              unsigned *mask, unsigned *hist, int *s_xy, int *s_bb, int *s_c, double *s_red, double *mu_out, double *sig_out
@@ -287,6 +290,36 @@ __device__ __forceinline__ bool musigma_core(const double pc[7], const double ph
         s_bb[0] = xMin; s_bb[1] = xMax; s_bb[2] = yMin; s_bb[3] = yMax;
     }
     MS_STAMP(1);                                              // (corners projected)
+    if constexpr (BIG) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        const int xMin = s_bb[0], xMax = s_bb[1], yMin = s_bb[2], yMax = s_bb[3];
+        const int bw = xMax - xMin + 1, B = (MS_MASK_WORDS*32)/w;
+        if (bw > 0)
+            for (int yb = yMin; yb <= yMax; yb += B) {
+                const int ye = min(yb + B, yMax + 1), bh = ye - yb;
+                for (int k = tid; k < (bh*w + 31) >> 5; k += NT) mask[k] = 0;
+                __syncthreads();
+                raster_quad_rows(mask, s_xy, w, hh, yb, ye, tid, NT);
+                __syncthreads();
+                const int npx = bw*bh, dx = NT % bw, dy = NT / bw;
+                int x = tid % bw, y = tid / bw;
+                for (int k0 = tid; k0 < npx; k0 += 4*NT) {
+                    int bit[4]; bool in[4]; unsigned px[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        bit[u] = y*w + xMin + x;                      // (band-relative: the image's pixel is yb w further)
+                        in[u] = k0 + u*NT < npx && (mask[bit[u] >> 5] & (1u << (bit[u] & 31)));
+                        x += dx; y += dy; if (x >= bw) { x -= bw; y++; }
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) px[u] = in[u] ? img[yb*w + bit[u]] : 0u;
+#pragma unroll
+                    for (int u = 0; u < 4; u++) if (in[u]) atomicAdd(&hist[px[u]], 1u);
+                }
+                __syncthreads();
+            }
+    } else {
     for (int k = tid; k < min((w*hh + 31) >> 5, MS_MASK_WORDS); k += NT) mask[k] = 0;
     if (tid < 256) hist[tid] = 0;
     __syncthreads();
@@ -320,6 +353,7 @@ __device__ __forceinline__ bool musigma_core(const double pc[7], const double ph
     }
     __syncthreads();
     MS_STAMP(4);                                              // (histogram)
+    }
     const double hv = tid < 256 ? (double)hist[tid] : 0.0;
     double cnt = hv, sum = hv*(double)tid;
     double n = block_sum<NT>(cnt, s_red), sm = block_sum<NT>(sum, s_red);
@@ -334,6 +368,7 @@ __device__ __forceinline__ bool musigma_core(const double pc[7], const double ph
 // ---- mu / sigma of a projected text box: tool::GetProjText x4 + tool::CalTextinfo (src/tool.cc:1178-1262,1655-1728)
 // with cv::fillPoly's scan conversion (boundary Bresenham lines + 16.16 fixed-point scanline spans).  One workgroup per
 // (KF, text) observation; the polygon mask of the clamped bounding box lives in LDS as a bit field.
+template <bool BIG>
 __device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, const int g, const double *pose, const double *theta) {
     __shared__ unsigned mask[MS_MASK_WORDS];
     __shared__ unsigned hist[256];
@@ -364,7 +399,7 @@ __device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, con
     MS_STAMP(0);                                              // (operands there)
     __shared__ int s_c[16];
     double mu, sigma;
-    const bool ok = musigma_core<MS_THREADS>(pc, ph, h >= 0, th, mx, my, L.K, L.img_w, L.img_h, img, mask, hist, s_xy, s_bb, s_c, s_red, &mu, &sigma
+    const bool ok = musigma_core<MS_THREADS, BIG>(pc, ph, h >= 0, th, mx, my, L.K, L.img_w, L.img_h, img, mask, hist, s_xy, s_bb, s_c, s_red, &mu, &sigma
 #ifdef MID_STAMPS
                                              , dbg, us_t0
 #endif
@@ -377,8 +412,9 @@ __device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, con
 #endif
 }
 
+template <bool BIG>
 __global__ __launch_bounds__(MS_THREADS) void k_musigma(Work W, LevelDev L) {
-    musigma_wg(W, L, blockIdx.x, W.pose[W.st->cur], W.theta[W.st->cur]);
+    musigma_wg<BIG>(W, L, blockIdx.x, W.pose[W.st->cur], W.theta[W.st->cur]);
 }
 
 // ---- text label image of one keyframe (optimizer::ShowBAReproj_TextBox -> tool::TextBoxWithFill, optimizer.cc:2508-2582,
@@ -408,7 +444,10 @@ __device__ __noinline__ LabelQuad label_quad(const double *pose, const double *t
     return q;
 }
 
+// BIG (a level above MS_MASK_WORDS*32 pixels): every quad in bands of MS_MASK_WORDS*32 / w rows from its clamped yMin (raster_quad_rows); out[] keeps the full
+// image's index, only the mask's bit is relative to the band.
 #define LBL_THREADS 1024
+template <bool BIG>
 __global__ __launch_bounds__(LBL_THREADS) void k_label(Work W, int kf, int w, int hh, double fx, double fy, double cx, double cy, float *out) {
     __shared__ unsigned mask[MS_MASK_WORDS];
     __shared__ int s_xy[8], s_bb[4];
@@ -428,6 +467,27 @@ __global__ __launch_bounds__(LBL_THREADS) void k_label(Work W, int kf, int w, in
                 xMin = min(xMin, iu); xMax = max(xMax, iu); yMin = min(yMin, iv); yMax = max(yMax, iv);
             }
             s_bb[0] = max(xMin, 0); s_bb[1] = min(xMax, w - 1); s_bb[2] = max(yMin, 0); s_bb[3] = min(yMax, hh - 1);
+        }
+        if constexpr (BIG) {
+            __syncthreads();
+            const int x0 = s_bb[0], x1 = s_bb[1], y0 = s_bb[2], y1 = s_bb[3];
+            const int bw = x1 - x0 + 1, B = (MS_MASK_WORDS*32)/w;
+            for (int yb = y0; yb <= y1; yb += B) {
+                const int ye = min(yb + B, y1 + 1), bh = ye - yb;
+                for (int k = tid; k < (bh*w + 31) >> 5; k += LBL_THREADS) mask[k] = 0;
+                __syncthreads();
+                raster_quad_rows(mask, s_xy, w, hh, yb, ye, tid, LBL_THREADS);
+                __syncthreads();
+                if (bw > 0)
+                    for (int k = tid; k < bw*bh; k += LBL_THREADS) {
+                        const int x = x0 + k % bw, y = k / bw, bit = y*w + x;
+                        if (mask[bit >> 5] & (1u << (bit & 31))) out[(yb + y)*w + x] = (float)rank;
+                    }
+                __syncthreads();
+            }
+            rank++;
+            __syncthreads();
+            continue;
         }
         for (int k = tid; k < MS_MASK_WORDS; k += LBL_THREADS) mask[k] = 0;
         __syncthreads();

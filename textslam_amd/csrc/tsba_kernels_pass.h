@@ -36,10 +36,11 @@ __device__ __forceinline__ void gauge_wave_body(const Work &W, const uint8_t *kf
 #define PB_WG 128                           // workgroups that walk k_participation's blocks in k_pass_begin.  Round 6: 24 -> 128 (C4 level 0: 215 blocks, nine in turn per workgroup at ~2 us
                                             // each were the kernel once mu / sigma stopped being it: 20.7 us at 24, 15.9 at 48, 14.4 at 72, 13.6 at 128; the ticket's 128 arrivals cost ~4 us of that)
 #endif
+template <bool BIG>
 __global__ __launch_bounds__(MS_THREADS) void k_pass_begin(Work W, LevelDev L, double radius0, int max_it, const uint8_t *kf_initial, int state,
                                                            int npb, int nwg, int n_ms, LmState *log_prev, int *ticket) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (b >= nwg) { if (b - nwg < n_ms) musigma_wg(W, L, b - nwg, W.pose[W.st->cur], W.theta[W.st->cur]); return; }
+    if (b >= nwg) { if (b - nwg < n_ms) musigma_wg<BIG>(W, L, b - nwg, W.pose[W.st->cur], W.theta[W.st->cur]); return; }
     for (int vb = b; vb < npb; vb += nwg) { participation_wg(W, L, vb, 1); __syncthreads(); }       // (k_participation's block vb: its partial counts go to cntpart[vb])
     __shared__ int s_last; __shared__ int s_cnt2[2];
     if (tid == 0) { __threadfence(); s_last = atomicAdd(ticket, 1) == nwg - 1; s_cnt2[0] = 0; s_cnt2[1] = 0; }
@@ -63,12 +64,13 @@ __global__ __launch_bounds__(MS_THREADS) void k_pass_begin(Work W, LevelDev L, d
 }
 
 // nb_out: k_outlier's blocks of this pass ((n_sc + 63)/64 + n_tg; 0: no outlier pass).  n_ms: text observations of the NEXT pass's level Ln whose mu / sigma
-// go to ms_next (0: there is no next pass, or its level is not on the device yet -- k_pass_begin computes them then)
+// go to ms_next (0: there is no next pass, or its level is not on the device yet -- k_pass_begin computes them then).  BIG: the geometry of Ln, not of L
+template <bool BIG>
 __global__ __launch_bounds__(MS_THREADS) void k_pass_end(Work W, LevelDev L, LevelDev Ln, int nb_out, int n_ms, double *ms_next,
                                                          double chi2_mono, double chi2_text, double bad_ratio, int do_scene, int do_text) {
     const int b = blockIdx.x, tid = threadIdx.x, nbo = (nb_out + 3) >> 2;
     if (b < nbo) { const int ob = 4*b + (tid >> 6); if (ob < nb_out) outlier_wave(W, L, ob, tid & 63, chi2_mono, chi2_text, bad_ratio, do_scene, do_text, nullptr); return; }
-    if (b < nbo + n_ms) { Work Wn = W; Wn.musig = ms_next; musigma_wg(Wn, Ln, b - nbo, W.pose[W.st->cur], W.theta[W.st->cur]); return; }
+    if (b < nbo + n_ms) { Work Wn = W; Wn.musig = ms_next; musigma_wg<BIG>(Wn, Ln, b - nbo, W.pose[W.st->cur], W.theta[W.st->cur]); return; }
     for (int k = tid; k < W.n_kf; k += MS_THREADS) W.kf_in[k] = 0;
     for (int k = tid; k < W.n_pt; k += MS_THREADS) W.act_pt[k] = 0;
     for (int k = tid; k < W.n_text; k += MS_THREADS) W.act_tx[k] = 0;

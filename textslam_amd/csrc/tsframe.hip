@@ -226,6 +226,8 @@ __device__ __forceinline__ double judge_sample(const uint8_t *__restrict__ img, 
     return I;
 }
 
+// BIG (a level-0 image above MS_MASK_WORDS*32 pixels): no mask -- every rounded centre is tested with quad_covers, the same fill's point membership.
+template <bool BIG>
 __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restrict__ img, JudgeArgs A, const JudgePlane *__restrict__ planes,
                                                          const int *__restrict__ pix_off, const short *__restrict__ pix_uv,
                                                          const uint8_t *__restrict__ pix_inten, const double *__restrict__ dete_xy,
@@ -302,6 +304,19 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
     // 4. detection association (tracking.cc:2116-2128): label image = the quad filled by cv::fillPoly; centre (round(u), round(v)), half away from zero
     if (dete_bits && A.dete_words > 0) {
         unsigned *bits = dete_bits + (size_t)p*A.dete_words;
+        if constexpr (BIG) {
+            for (int k = tid; k < A.dete_words; k += JUDGE_NT) {
+                unsigned word = 0;
+                if (reason == TSFRAME_JUDGE_PASS)
+                    for (int j = 32*k; j < min(32*k + 32, A.n_dete); j++) {
+                        const double ru = round(dete_xy[2*j]), rv = round(dete_xy[2*j + 1]);
+                        if (!(ru >= 0.0 && ru <= (double)(A.w0 - 1) && rv >= 0.0 && rv <= (double)(A.h0 - 1))) continue;
+                        if (quad_covers(s_xy, A.w0, A.h0, (int)ru, (int)rv)) word |= 1u << (j & 31);
+                    }
+                bits[k] = word;
+            }
+            return;
+        }
         if (reason == TSFRAME_JUDGE_PASS) {
             for (int k = tid; k < (A.w0*A.h0 + 31) >> 5; k += JUDGE_NT) s_u.mask[k] = 0;
             __syncthreads();
@@ -558,7 +573,6 @@ int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const d
     if (c->n_levels == 0) { c->err = "tsframe_text_judge: no image set"; return TSFRAME_ERR_STATE; }
     if (level >= c->n_levels) { c->err = "tsframe_text_judge: level not built"; return TSFRAME_ERR_STATE; }
     const int words = dete_bits ? (n_dete + 31)/32 : 0;
-    if (words > 0 && (size_t)c->w[0]*c->h[0] > (size_t)MS_MASK_WORDS*32) return bad("detection association needs a level-0 image of at most 640 x 480 pixels");
     hipSetDevice(c->device);
     JudgeArgs A;
     A.w = c->w[level]; A.h = c->h[level]; A.w0 = c->w[0]; A.h0 = c->h[0]; A.margin = out_margin; A.n_dete = n_dete; A.dete_words = words;
@@ -580,9 +594,14 @@ int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const d
     memcpy(h + o_off, pix_off, 4*((size_t)n + 1));
     if (npix) { memcpy(h + o_uv, pix_uv, 4*npix); memcpy(h + o_in, pix_inten, npix); }
     CKF(hipMemcpyAsync(d, h, o_out, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_text_judge, dim3(n), dim3(JUDGE_NT), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], A, (const JudgePlane *)(d + o_pl),
-                       (const int *)(d + o_off), (const short *)(d + o_uv), (const uint8_t *)(d + o_in), (const double *)(d + o_dx),
-                       (JudgeOut *)(d + o_out), words > 0 ? (unsigned *)(d + o_bits) : nullptr);
+    if (words > 0 && (size_t)c->w[0]*c->h[0] > (size_t)MS_MASK_WORDS*32)       // the association's mask is level-0 sized: above it, point tests instead
+        hipLaunchKernelGGL(k_text_judge<true>, dim3(n), dim3(JUDGE_NT), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], A, (const JudgePlane *)(d + o_pl),
+                           (const int *)(d + o_off), (const short *)(d + o_uv), (const uint8_t *)(d + o_in), (const double *)(d + o_dx),
+                           (JudgeOut *)(d + o_out), (unsigned *)(d + o_bits));
+    else
+        hipLaunchKernelGGL(k_text_judge<false>, dim3(n), dim3(JUDGE_NT), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], A, (const JudgePlane *)(d + o_pl),
+                           (const int *)(d + o_off), (const short *)(d + o_uv), (const uint8_t *)(d + o_in), (const double *)(d + o_dx),
+                           (JudgeOut *)(d + o_out), words > 0 ? (unsigned *)(d + o_bits) : nullptr);
     CKF(hipGetLastError());
     CKF(hipMemcpyAsync(h + o_out, d + o_out, tot - o_out, hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream));

@@ -6,6 +6,7 @@ points hosted in their first observer; planar text patches with a band-limited t
 into every keyframe through the true plane-induced homography, so that photometric residuals
 vanish at ground truth.  Pure numpy, deterministic for a given seed.
 """
+import contextlib
 import numpy as np
 from .abi import BAProblem, MAX_LEVELS
 
@@ -14,6 +15,23 @@ SEED = 20240926
 TAP_DX = np.array([0, 2, 1, 0, -1, -2, -1, 0], np.float64)      # tool.cc:1550-1557 (INTERVAL8)
 TAP_DY = np.array([0, 0, -1, -2, -1, 0, 1, 2], np.float64)
 W, H = 640, 480
+
+
+@contextlib.contextmanager
+def camera(width, height, K):
+    """The camera of the problems made inside the block: image size width x height and intrinsics K = (fx, fy, cx, cy) instead of the 640 x 480
+    GeneralMotion camera.  Every generator of this module reads W, H and K_GENERAL_MOTION when it is called; they are restored on exit, so
+    problems made outside the block are what they were."""
+    global W, H, K_GENERAL_MOTION
+    K = np.asarray(K, np.float64).reshape(4).copy()
+    if int(width) < 2 or int(height) < 2:
+        raise ValueError("camera: width and height must be at least 2")
+    saved = (W, H, K_GENERAL_MOTION)
+    W, H, K_GENERAL_MOTION = int(width), int(height), K
+    try:
+        yield
+    finally:
+        W, H, K_GENERAL_MOTION = saved
 
 
 def _rot_y(a):
