@@ -15,7 +15,7 @@
 //   k_postlin pose diagonal / gradient, Jacobi scaling, cost, gradient tolerance
 // Windows on one GPU (at most SCHUR_KEEP_KF keyframes) run a trial as FOUR launches: k_schur_t<4> (assembly; one more workgroup takes the full decision on the
 // previous trial: new state, poses' rows, trace) | k_solve_back (solver + back-substitution) | k_linearize at the candidate | k_mid (+ its decision block: the light
-// decision on this trial -- accept / reject, radius, current linearisation -- left in W.dec for the next k_schur_t<4>); k_decide only behind a pass's last trial.
+// decision on this trial -- accept / reject, radius, current linearisation -- left in W.dec for the next k_schur_t<4>); a pass's last trial is decided by one workgroup of k_pass_end (k_decide's body; k_decide as a launch on every other path).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -939,6 +939,8 @@ static int pose_parts(const Ctx *c) { return c->n_kf > 126 ? (c->n_kf + 20)/21 :
 // pairs with a dozen scene blocks (large maps): four pairs per wave
 static bool lin_small_pairs(const Ctx *c, const LevelDev &D) { return !c->dbg.no_small_pairs && D.n_pair > 0 && (long long)D.n_sc <= 24LL*D.n_pair; }
 static bool fused_decisions(const Ctx *c, const LevelDev &D);
+// tsba_debug_options.trial_launches = 4: production's launches with the text lanes of k_linearize projecting every tap twice (lin_body<.., REDO>: the carried projection's partner)
+static bool lin_redo(const Ctx *c) { return c->dbg.trial_launches == 4; }
 // windows on one GPU with one-wave k_mid blocks: a speculative k_mid launch carries the decision block (decision_block, tsba_kernels_lin.h) and the k_schur_t<4>
 // behind it reads the record it leaves (SchurDec.on = 3).  tsba_debug_options.trial_launches = 1 / 2 (128-thread blocks, k_lin_mid) keep the decision inside k_schur_t (on = 1)
 static bool decision_in_mid(const Ctx *c, const LevelDev &D) { return fused_decisions(c, D) && mid_threads(c) == 64; }
@@ -959,8 +961,12 @@ static void launch_linearize(Ctx *c, const LevelDev &D, int spec, bool skip_post
     }
     if (D.n_pair + D.n_tg > 0) {
         if (lin_small_pairs(c, D) && D.n_tg == 0) LAUNCHK((k_linearize<MODE_FULL, 4, false>), dim3((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + 7)/8)*8), dim3(LIN_T), 0, c->stream, W, D, spec);
-        else if (lin_small_pairs(c, D)) LAUNCHK((k_linearize<MODE_FULL, 4>), dim3((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + D.n_tg + 7)/8)*8), dim3(LIN_T), 0, c->stream, W, D, spec);
-        else LAUNCHK((k_linearize<MODE_FULL, 1>), dim3((((D.n_pair + LIN_NWV - 1)/LIN_NWV + D.n_tg + 7)/8)*8), dim3(LIN_T), 0, c->stream, W, D, spec);
+        else if (lin_small_pairs(c, D)) { const dim3 g((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + D.n_tg + 7)/8)*8);
+            if (lin_redo(c)) LAUNCHK((k_linearize<MODE_FULL, 4, true, true>), g, dim3(LIN_T), 0, c->stream, W, D, spec);
+            else LAUNCHK((k_linearize<MODE_FULL, 4>), g, dim3(LIN_T), 0, c->stream, W, D, spec); }
+        else { const dim3 g((((D.n_pair + LIN_NWV - 1)/LIN_NWV + D.n_tg + 7)/8)*8);
+            if (lin_redo(c)) LAUNCHK((k_linearize<MODE_FULL, 1, true, true>), g, dim3(LIN_T), 0, c->stream, W, D, spec);
+            else LAUNCHK((k_linearize<MODE_FULL, 1>), g, dim3(LIN_T), 0, c->stream, W, D, spec); }
     }
     const MidDec md0{0, 0, 0, tsba_options{}};
     if (mid_threads(c) == MID_TW) LAUNCHK((k_mid<MID_TW, 6, MID_PR_MIN>), dim3(nb_pt + nb_tx + nb_pr), dim3(MID_TW), 0, c->stream, W, D, nb_pt, nb_tx, spec, md0);
@@ -1406,7 +1412,7 @@ static void launch_solve_full(Ctx *c, const LevelDev &D) {
     LAUNCHK(k_pcg_finish, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, it);
 }
 
-// a trial's decision is taken by the NEXT trial's k_schur_t (the last trial's by k_decide after the loop): windows on one GPU without blocks outside the band
+// a trial's decision is taken by the NEXT trial's k_schur_t (the last trial's by k_decide after the loop, or -- window_pass, decision_in_mid -- by a workgroup of k_pass_end): windows on one GPU without blocks outside the band
 static bool fused_decisions(const Ctx *c, const LevelDev &D) { return c->W.st_next != nullptr && D.far_B <= 0; }
 // ... and there a pass begins and ends with one launch each (k_pass_begin, k_pass_end).  window_fast_ctx: what the context alone says, for a level that is not on the device yet (only inside a one-shot call: W.st_next is this problem's)
 static bool window_fast_ctx(const Ctx *c, bool per_step) { return c->W.st_next != nullptr && c->n_kf <= 64 && !is_multi(c) && !c->pose_only && !per_step; }
@@ -1518,14 +1524,18 @@ static int pose_pass(Ctx *c, int ps, PassCarry &carry) {
     return stage_ahead(c, ps);                           // (one-shot calls: the later passes' levels, over the copy stream while this pass runs)
 }
 // the LM trials of a window's or a map's pass behind its begin-launch: the first linearisation, up to its[ps] trials, and (fused_decisions) the decision on the last one
-static int lm_trials(Ctx *c, const LevelDev &D, int ps, bool fuse_first) {
+// end_decides (window_pass): where the trials' k_mid launches carry the decision block, the last trial's decision is left to a workgroup of k_pass_end (*end_decides = true)
+static int lm_trials(Ctx *c, const LevelDev &D, int ps, bool fuse_first, bool *end_decides = nullptr) {
     launch_linearize(c, D, 0, fuse_first); int n_trials = 0;
     for (int it = 0; it < c->opt.its[ps]; it++) {
         if (converged(c, it) && !(fuse_first && n_trials == 0)) break;
         launch_step(c, D, n_trials > 0, fuse_first && n_trials == 0); n_trials++;
         if (it >= 1) { const int rc = stage_ahead(c, ps); if (rc) return rc; }      // (with two iterations queued the device does not run dry while the host stages)
     }
-    if (n_trials > 0 && fused_decisions(c, D)) launch_decide(c, D);
+    if (n_trials > 0 && fused_decisions(c, D)) {
+        if (end_decides && decision_in_mid(c, D) && (c->dbg.trial_launches == 0 || lin_redo(c))) *end_decides = true;
+        else launch_decide(c, D);
+    }
     return TSBA_OK;
 }
 // windows on one GPU (window_fast): k_pass_begin | trials, the first one's assembly doing k_postlin's work | k_pass_end (tsba_kernels_pass.h)
@@ -1539,14 +1549,18 @@ static int window_pass(Ctx *c, int ps, PassCarry &carry) {
     LAUNCHK_MS(ms_big(D), k_pass_begin, dim3(nwg + n_ms), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial, o.state,
                        npb, nwg, n_ms, carry.log_pending ? c->st_log + ps - 1 : (LmState *)nullptr, c->ticket);
     // k_postlin (the first linearisation's scaling, cost, gradient test: 8.6 us of one workgroup) inside the first trial's assembly
-    int rc = lm_trials(c, D, ps, o.its[ps] > 0 && c->dbg.trial_launches != 3); if (rc) return rc;
+    bool end_decides = false;
+    int rc = lm_trials(c, D, ps, o.its[ps] > 0 && c->dbg.trial_launches != 3, &end_decides); if (rc) return rc;
     // the outlier pass, the NEXT pass's mu / sigma (when its level is on the device already) and the clearing of the participation arrays in one launch
     const int nb_out = (o.outlier_scene || o.outlier_text) && D.n_sc + D.n_tg > 0 ? (D.n_sc + 63)/64 + D.n_tg : 0, ln = ps + 1 < o.n_passes ? o.levels[ps + 1] : -1;
     const LevelDev *Dn = ln >= 0 && c->lev_built[ln] && window_fast(c, c->lev[ln], carry.per_step) && c->lev[ln].n_tg > 0 ? &c->lev[ln] : nullptr;
     if (Dn) { rc = level_ready(c, ln); if (rc) return rc; }      // (staged over the copy stream during this pass's trials: long since there)
     const int n_msn = Dn ? Dn->n_tg : 0;
-    LAUNCHK_MS(Dn && ms_big(*Dn), k_pass_end, dim3((nb_out + 3)/4 + n_msn + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, Dn ? *Dn : D, nb_out, n_msn, c->musig2[c->musig_sel ^ 1],
-                       o.chi2_mono[ps], o.chi2_text[ps], o.text_bad_ratio, o.outlier_scene, o.outlier_text);
+    PassDec pd{0, 0, 0, tsba_options{}};                 // (+ the workgroup of the last trial's decision, in front: k_decide's arguments)
+    if (end_decides) { int nb_pt, nb_tx, nb_pr; mid_blocks(c, D, nb_pt, nb_tx, nb_pr);
+        pd = PassDec{1, back_blocks_pt(c->n_pt) + back_blocks_tx(c->n_text) + (c->n_kf + 255)/256, nb_pt + nb_tx + nb_pr, c->opt}; }
+    LAUNCHK_MS(Dn && ms_big(*Dn), k_pass_end, dim3(pd.on + (nb_out + 3)/4 + n_msn + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, Dn ? *Dn : D, nb_out, n_msn, c->musig2[c->musig_sel ^ 1],
+                       o.chi2_mono[ps], o.chi2_text[ps], o.text_bad_ratio, o.outlier_scene, o.outlier_text, pd);
     if (Dn) { c->musig_sel ^= 1; c->W.musig = c->musig2[c->musig_sel]; carry.ms_ahead = ps + 1; }
     record_cov(c, ps);
     carry.log_pending = true;                            // (kept by the next pass's k_pass_begin, or by k_solve_end)

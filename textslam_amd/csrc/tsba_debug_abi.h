@@ -163,8 +163,12 @@ int tsba_time_linearize(void *ctx, int level, int n, double *avg_ms, double *alg
     CK(hipEventRecord(c->ev0, c->stream));
     for (int k = 0; k < n; k++) {
         if (lin_small_pairs(c, D) && D.n_tg == 0) hipLaunchKernelGGL((k_linearize<MODE_FULL, 4, false>), dim3((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + 7)/8)*8), dim3(LIN_T), 0, c->stream, c->W, D, 0);
-        else if (lin_small_pairs(c, D)) hipLaunchKernelGGL((k_linearize<MODE_FULL, 4>), dim3((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + D.n_tg + 7)/8)*8), dim3(LIN_T), 0, c->stream, c->W, D, 0);
-        else hipLaunchKernelGGL((k_linearize<MODE_FULL, 1>), dim3((((D.n_pair + LIN_NWV - 1)/LIN_NWV + D.n_tg + 7)/8)*8), dim3(LIN_T), 0, c->stream, c->W, D, 0);
+        else if (lin_small_pairs(c, D)) { const dim3 g((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + D.n_tg + 7)/8)*8);
+            if (lin_redo(c)) hipLaunchKernelGGL((k_linearize<MODE_FULL, 4, true, true>), g, dim3(LIN_T), 0, c->stream, c->W, D, 0);
+            else hipLaunchKernelGGL((k_linearize<MODE_FULL, 4>), g, dim3(LIN_T), 0, c->stream, c->W, D, 0); }
+        else { const dim3 g((((D.n_pair + LIN_NWV - 1)/LIN_NWV + D.n_tg + 7)/8)*8);
+            if (lin_redo(c)) hipLaunchKernelGGL((k_linearize<MODE_FULL, 1, true, true>), g, dim3(LIN_T), 0, c->stream, c->W, D, 0);
+            else hipLaunchKernelGGL((k_linearize<MODE_FULL, 1>), g, dim3(LIN_T), 0, c->stream, c->W, D, 0); }
     }
     CK(hipEventRecord(c->ev1, c->stream));
     CK(hipEventSynchronize(c->ev1));

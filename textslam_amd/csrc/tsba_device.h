@@ -132,8 +132,20 @@ TS_DEV void scene_residual(const PairT &T, const double tc[3], double mx, double
 }
 
 // INTERVAL8 pattern, src/tool.cc:1550-1557
-__device__ __constant__ double TAP_DX[8] = { 0, 2, 1, 0, -1, -2, -1, 0 };
-__device__ __constant__ double TAP_DY[8] = { 0, 0, -1, -2, -1, 0, 1, 2 };
+#define TAP_DX_LIST { 0, 2, 1, 0, -1, -2, -1, 0 }
+#define TAP_DY_LIST { 0, 0, -1, -2, -1, 0, 1, 2 }
+__device__ __constant__ double TAP_DX[8] = TAP_DX_LIST;
+__device__ __constant__ double TAP_DY[8] = TAP_DY_LIST;
+// the same offsets as immediates, for a tap index that is known at compile time up to a select (k_linearize's text lanes: a table entry indexed by the lane is a
+// vector load from constant memory with its round trip in front of the projection)
+TS_DEV constexpr double tap_dx_imm(int kt) { return kt == 1 ? 2.0 : kt == 2 ? 1.0 : kt == 4 ? -1.0 : kt == 5 ? -2.0 : kt == 6 ? -1.0 : 0.0; }
+TS_DEV constexpr double tap_dy_imm(int kt) { return kt == 2 ? -1.0 : kt == 3 ? -2.0 : kt == 4 ? -1.0 : kt == 6 ? 1.0 : kt == 7 ? 2.0 : 0.0; }
+namespace tap_imm_check {
+constexpr double dx[8] = TAP_DX_LIST, dy[8] = TAP_DY_LIST;
+constexpr bool same(int k = 0) { return k == 8 || (dx[k] == (k == 1 ? 2.0 : k == 2 ? 1.0 : k == 4 ? -1.0 : k == 5 ? -2.0 : k == 6 ? -1.0 : 0.0)
+                                                   && dy[k] == (k == 2 ? -1.0 : k == 3 ? -2.0 : k == 4 ? -1.0 : k == 6 ? 1.0 : k == 7 ? 2.0 : 0.0) && same(k + 1)); }
+static_assert(same(), "tap_dx_imm / tap_dy_imm are TAP_DX / TAP_DY");
+}
 
 // bilinear tap with the reference's in/out rule (nume_BAText.h:67-82) + bilinear gradient
 TS_DEV double bilinear_tap(const uint8_t *__restrict__ img, int w, int h, double u, double v, double &gu, double &gv) {
@@ -153,24 +165,24 @@ TS_DEV double bilinear_tap(const uint8_t *__restrict__ img, int w, int h, double
 }
 
 // one photometric tap, split so that the image fetches of all taps of a feature can be in flight together:
-//   tap_fetch   projects the tap and loads its 2x2 pixel neighbourhood (zeros outside the image: same rule as bilinear_tap)
-//   text_tap_px redoes the (cheap, bit-identical) projection and finishes residual, target-pose row (6), theta row (3)
+//   tap_fetch     projects the tap and loads its 2x2 pixel neighbourhood (zeros outside the image: same rule as bilinear_tap)
+//   text_tap_eval finishes residual, target-pose row (6), theta row (3) from the projection's values and the pixel quad
+//   text_tap_px   = the projection redone (cheap, bit-identical) + text_tap_eval: for a caller that kept nothing of tap_fetch's projection
+//   tap_fetch_keep / text_tap_kept: k_linearize's text lanes -- the fetch hands out what the evaluation cannot rebuild in a few instructions (1/s, 1/z, u, v: the two
+//                 reciprocals and everything behind them); the evaluation rebuilds Rm, Pm, P from those and (mx, my) with tap_project's own expressions
 struct TapPx { int I00, I01, I10, I11; };
 TS_DEV void tap_project(const PairT &T, const double tc[3], const double th[3], double mx, double my,
-                        double fx, double fy, double cx, double cy, double Rm[3], double &is, double Pm[3], double P[3], double &u, double &v) {
+                        double fx, double fy, double cx, double cy, double Rm[3], double &is, double Pm[3], double P[3], double &iz, double &u, double &v) {
     const double s = -(mx*th[0] + my*th[1] + th[2]);         // rho(m) = -m^T theta, ModelTool.hpp:167
     const double m[3] = { mx, my, 1.0 };
     mat3_vec(T.Rcr, m, Rm);
     is = ts_rcp(s);
     Pm[0] = Rm[0]*is + T.tq[0]; Pm[1] = Rm[1]*is + T.tq[1]; Pm[2] = Rm[2]*is + T.tq[2];
     P[0] = Pm[0] + tc[0]; P[1] = Pm[1] + tc[1]; P[2] = Pm[2] + tc[2];
-    const double iz = ts_rcp(P[2]);                          // one reciprocal for both coordinates (and the Jacobian)
+    iz = ts_rcp(P[2]);                                       // one reciprocal for both coordinates (and the Jacobian)
     u = fx*P[0]*iz + cx; v = fy*P[1]*iz + cy;
 }
-TS_DEV TapPx tap_fetch(const PairT &T, const double tc[3], const double th[3], double mx, double my,
-                       double fx, double fy, double cx, double cy, const uint8_t *__restrict__ img, int w, int h) {
-    double Rm[3], is, Pm[3], P[3], u, v;
-    tap_project(T, tc, th, mx, my, fx, fy, cx, cy, Rm, is, Pm, P, u, v);
+TS_DEV TapPx tap_quad(double u, double v, const uint8_t *__restrict__ img, int w, int h) {
     TapPx px = { 0, 0, 0, 0 };
     const double uf = floor(u), vf = floor(v);
     const int iu = (int)uf, iv = (int)vf;
@@ -185,11 +197,20 @@ TS_DEV TapPx tap_fetch(const PairT &T, const double tc[3], const double th[3], d
     px.I10 = r1 & 0xff; px.I11 = in_u ? (r1 >> 8) : 0;
     return px;
 }
-TS_DEV double text_tap_px(const PairT &T, const double tc[3], const double th[3], double mx, double my,
-                          double fx, double fy, double cx, double cy, const TapPx &px, int w, int h,
-                          double mu, double sigma, double inv_sigma, double ref, double wT, bool want_j, double jt[6], double jl[3]) {
-    double Rm[3], is, Pm[3], P[3], u, v;
-    tap_project(T, tc, th, mx, my, fx, fy, cx, cy, Rm, is, Pm, P, u, v);
+TS_DEV TapPx tap_fetch_keep(const PairT &T, const double tc[3], const double th[3], double mx, double my,
+                            double fx, double fy, double cx, double cy, const uint8_t *__restrict__ img, int w, int h, double &is, double &iz, double &u, double &v) {
+    double Rm[3], Pm[3], P[3];
+    tap_project(T, tc, th, mx, my, fx, fy, cx, cy, Rm, is, Pm, P, iz, u, v);
+    return tap_quad(u, v, img, w, h);
+}
+TS_DEV TapPx tap_fetch(const PairT &T, const double tc[3], const double th[3], double mx, double my,
+                       double fx, double fy, double cx, double cy, const uint8_t *__restrict__ img, int w, int h) {
+    double is, iz, u, v;
+    return tap_fetch_keep(T, tc, th, mx, my, fx, fy, cx, cy, img, w, h, is, iz, u, v);
+}
+TS_DEV double text_tap_eval(const double Rm[3], double is, const double Pm[3], const double P[3], double iz, double u, double v, double mx, double my,
+                            double fx, double fy, const TapPx &px, int w, int h,
+                            double mu, double inv_sigma, double ref, double wT, bool want_j, double jt[6], double jl[3]) {
     double gu = 0.0, gv = 0.0, I = 0.0;
     const double uf = floor(u), vf = floor(v);
     const int iu = (int)uf, iv = (int)vf;
@@ -202,8 +223,7 @@ TS_DEV double text_tap_px(const PairT &T, const double tc[3], const double th[3]
     }
     const double r = ((I - mu)*inv_sigma - ref)*wT;         // nume_BAText.h:86-87
     if (want_j) {
-        const double Px = P[0], Py = P[1], Pz = P[2];
-        double iz = ts_rcp(Pz);
+        const double Px = P[0], Py = P[1];
         double g0 = wT*inv_sigma*gu, g1 = wT*inv_sigma*gv;
         double a[3] = { g0*fx*iz, g1*fy*iz, -(g0*fx*Px + g1*fy*Py)*iz*iz };
         jt[0] = 2.0*(Pm[1]*a[2] - Pm[2]*a[1]); jt[1] = 2.0*(Pm[2]*a[0] - Pm[0]*a[2]); jt[2] = 2.0*(Pm[0]*a[1] - Pm[1]*a[0]);
@@ -212,6 +232,23 @@ TS_DEV double text_tap_px(const PairT &T, const double tc[3], const double th[3]
         jl[0] = c*mx; jl[1] = c*my; jl[2] = c;
     }
     return r;
+}
+TS_DEV double text_tap_px(const PairT &T, const double tc[3], const double th[3], double mx, double my,
+                          double fx, double fy, double cx, double cy, const TapPx &px, int w, int h,
+                          double mu, double sigma, double inv_sigma, double ref, double wT, bool want_j, double jt[6], double jl[3]) {
+    double Rm[3], is, Pm[3], P[3], iz, u, v;
+    tap_project(T, tc, th, mx, my, fx, fy, cx, cy, Rm, is, Pm, P, iz, u, v);
+    return text_tap_eval(Rm, is, Pm, P, iz, u, v, mx, my, fx, fy, px, w, h, mu, inv_sigma, ref, wT, want_j, jt, jl);
+}
+TS_DEV double text_tap_kept(const PairT &T, const double tc[3], double mx, double my, double is, double iz, double u, double v,
+                            double fx, double fy, const TapPx &px, int w, int h,
+                            double mu, double inv_sigma, double ref, double wT, double jt[6], double jl[3]) {
+    const double m[3] = { mx, my, 1.0 };
+    double Rm[3], Pm[3], P[3];
+    mat3_vec(T.Rcr, m, Rm);                                  // (as tap_project)
+    Pm[0] = Rm[0]*is + T.tq[0]; Pm[1] = Rm[1]*is + T.tq[1]; Pm[2] = Rm[2]*is + T.tq[2];
+    P[0] = Pm[0] + tc[0]; P[1] = Pm[1] + tc[1]; P[2] = Pm[2] + tc[2];
+    return text_tap_eval(Rm, is, Pm, P, iz, u, v, mx, my, fx, fy, px, w, h, mu, inv_sigma, ref, wT, true, jt, jl);
 }
 TS_DEV double text_tap(const PairT &T, const double tc[3], const double th[3], double mx, double my,
                        double fx, double fy, double cx, double cy, const uint8_t *__restrict__ img, int w, int h,

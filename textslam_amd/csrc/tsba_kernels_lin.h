@@ -596,7 +596,9 @@ __device__ __forceinline__ void wave_sum_groups16_mw(const double *acc, double *
 #define LIN_NWV (LIN_T/64)
 #define MID_U 4                          // slot records of a point that k_mid keeps in flight per round trip
 // TEXT = false: levels without text planes (the reference's GlobalBA): the scene path alone needs far fewer registers than the text path.
-template <int MODE, int PPW = 1, bool TEXT = true>
+// REDO (tsba_debug_options.trial_launches = 4: the bit-identity partner of the carried projection): the text lanes' evaluation loop projects every tap again, behind
+// the lane-indexed table loads of its offsets, as it did until the fetch loop started to hand its projection on.
+template <int MODE, int PPW = 1, bool TEXT = true, bool REDO = false>
 __device__ __forceinline__ void lin_body(const Work &W, const LevelDev &L, const int spec) {
     // spec = 0: linearise at x (pass start); spec = 1: speculative linearisation at the LM candidate, into the other LinBuf
     const LmState *st = W.st;
@@ -754,28 +756,47 @@ __device__ __forceinline__ void lin_body(const Work &W, const LevelDev &L, const
                 }
                 const uint8_t good = in ? (W.filter_good ? W.tfgood[fg + raw] : (uint8_t)1) : (uint8_t)0;   // in flight with the pixel fetches
                 // the pixel-pair fetches of all the thread's taps in flight before the first residual; the quads wait in LDS so that
-                // the residual loop can stay rolled (unrolled, its live state does not fit 256 VGPRs and spills to scratch)
+                // the residual loop can stay rolled (unrolled, its live state does not fit 256 VGPRs and spills to scratch).
+                // Each tap is projected ONCE: what the evaluation cannot rebuild in a few instructions -- (mx, my), 1/s, 1/z, u, v: 6 doubles a tap -- waits in the
+                // wave's transpose area `reg` (28 doubles per lane, idle until the reduction behind the tap loop; a lane touches its own column only, and a later
+                // chunk's values are parked after the previous chunk's transposes have read theirs: LDS accesses of one wave stay in order).  The taps' offsets are
+                // immediates (tap_dx_imm: a select per lane of the feature), not lane-indexed loads from the constant tables.
+                static_assert(6*TPL <= 28, "the parked projections of a lane's taps fit its column of the transpose area");
 #pragma unroll
                 for (int k = 0; k < TPL; k++) {
-                    const int kt = TPL*tp + k;
-                    const double mx = (fu + TAP_DX[kt] - L.K[2])*ifx, my = (fv + TAP_DY[kt] - L.K[3])*ify;   // tool.cc:1561
-                    const TapPx q = tap_fetch(T, C.t, th, mx, my, L.K[0], L.K[1], L.K[2], L.K[3], img, L.img_w, L.img_h);
+                    double dx, dy;
+                    if constexpr (REDO) { const int kt = TPL*tp + k; dx = TAP_DX[kt]; dy = TAP_DY[kt]; }
+                    else {
+                        dx = tap_dx_imm(k); dy = tap_dy_imm(k);
+#pragma unroll
+                        for (int q = 1; q < LPF; q++) if (tp == q) { dx = tap_dx_imm(TPL*q + k); dy = tap_dy_imm(TPL*q + k); }
+                    }
+                    const double mx = (fu + dx - L.K[2])*ifx, my = (fv + dy - L.K[3])*ify;   // tool.cc:1561
+                    double is, iz, u, v;
+                    const TapPx q = tap_fetch_keep(T, C.t, th, mx, my, L.K[0], L.K[1], L.K[2], L.K[3], img, L.img_w, L.img_h, is, iz, u, v);
                     s_px[k*LIN_T + tid] = (unsigned)q.I00 | ((unsigned)q.I01 << 8) | ((unsigned)q.I10 << 16) | ((unsigned)q.I11 << 24);
+                    if constexpr (!REDO) { double *pk = reg + 6*k*65 + lane; pk[0] = mx; pk[65] = my; pk[2*65] = is; pk[3*65] = iz; pk[4*65] = u; pk[5*65] = v; }
                 }
                 LIN_STAMP(1);                                   // (operands there, the taps' pixel quads requested)
                 double s = 0.0;
 #pragma unroll 1
                 for (int k = 0; k < TPL; k++) {
-                    const int kt = TPL*tp + k;
-                    const double mx = (fu + TAP_DX[kt] - L.K[2])*ifx, my = (fv + TAP_DY[kt] - L.K[3])*ify;
                     const unsigned q4 = s_px[k*LIN_T + tid];
                     const TapPx pxk = { (int)(q4 & 0xff), (int)((q4 >> 8) & 0xff), (int)((q4 >> 16) & 0xff), (int)(q4 >> 24) };
                     double rf = refv[0];
 #pragma unroll
                     for (int q = 1; q < TPL; q++) if (k == q) rf = refv[q];
-                    double jt[6], jl[3];
-                    double r = text_tap_px(T, C.t, th, mx, my, L.K[0], L.K[1], L.K[2], L.K[3], pxk, L.img_w, L.img_h,
-                                           mu, sigma, inv_sigma, rf, W.w_t, true, jt, jl);
+                    double jt[6], jl[3], r;
+                    if constexpr (REDO) {
+                        const int kt = TPL*tp + k;
+                        const double mx = (fu + TAP_DX[kt] - L.K[2])*ifx, my = (fv + TAP_DY[kt] - L.K[3])*ify;
+                        r = text_tap_px(T, C.t, th, mx, my, L.K[0], L.K[1], L.K[2], L.K[3], pxk, L.img_w, L.img_h,
+                                        mu, sigma, inv_sigma, rf, W.w_t, true, jt, jl);
+                    } else {
+                        const double *pk = reg + 6*k*65 + lane;
+                        r = text_tap_kept(T, C.t, pk[0], pk[65], pk[2*65], pk[3*65], pk[4*65], pk[5*65], L.K[0], L.K[1], pxk, L.img_w, L.img_h,
+                                          mu, inv_sigma, rf, W.w_t, jt, jl);
+                    }
                     s += r*r;
                     int q = 0;
 #pragma unroll
@@ -828,8 +849,8 @@ __device__ __forceinline__ void lin_body(const Work &W, const LevelDev &L, const
     }
 }
 
-template <int MODE, int PPW = 1, bool TEXT = true>
-__global__ __launch_bounds__(LIN_T, TEXT ? 2 : 3) void k_linearize(Work W, LevelDev L, int spec) { lin_body<MODE, PPW, TEXT>(W, L, spec); }
+template <int MODE, int PPW = 1, bool TEXT = true, bool REDO = false>
+__global__ __launch_bounds__(LIN_T, TEXT ? 2 : 3) void k_linearize(Work W, LevelDev L, int spec) { lin_body<MODE, PPW, TEXT, REDO>(W, L, spec); }
 
 // ---- per landmark: V, b, host column of W (= -sum Q^T w);  per pair: host-side products.  256-thread blocks.
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -1245,7 +1266,7 @@ __device__ __forceinline__ void decision_block(const Work &W, const LevelDev &L,
         s.lin_done = 0;
         lm_decide(s, cost_, step2_, mcc_, __builtin_inf(), 0.0, md.o);      // (on this wave's private copy of the state; no gradient-tolerance exit from the light decision)
         LmDec *d = W.dec;
-        d->radius = s.radius; d->done = s.done; d->lcur = s.lcur; d->fresh = s.lcur != lcur0;
+        d->radius = s.radius; d->done = s.done; d->lcur = s.lcur; d->fresh = s.lcur != lcur0; d->cur = s.cur;
 #ifdef MID_STAMPS
         atomicAdd((unsigned long long *)&W.dbg[45], (unsigned long long)(clock64() - ds_t0)); atomicAdd((unsigned long long *)&W.dbg[46], 1ull);
 #endif

@@ -7,7 +7,8 @@
 //   k_pass_begin   workgroups [0, nwg): k_participation's blocks, taken in turn (good flags -> which landmarks / keyframes take part, block counts); the LAST of them to finish
 //                  (ticket) keeps the previous pass's final state for the report, resets the LM state and fixes the gauge (k_gauge_wave's ballots);
 //                  workgroups [nwg, nwg + n_ms): the text observations' mu / sigma (k_musigma) -- unless the previous pass's k_pass_end has computed them
-//   k_pass_end     the outlier pass (four of k_outlier's waves per workgroup)  |  mu / sigma of the NEXT pass's level at the final parameters of this one
+//   k_pass_end     one workgroup that takes the decision on the pass's last trial (k_decide's body; windows with the decision block in k_mid's launch)  |  the outlier pass
+//                  (four of k_outlier's waves per workgroup)  |  mu / sigma of the NEXT pass's level at the final parameters of this one
 //                  (into the other of two buffers: the outlier pass still reads this level's)  |  one workgroup that clears the participation arrays
 //   k_solve_end    the passes' final states -> pinned host memory (no copy engine, no staging)
 //
@@ -57,6 +58,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_pass_begin(Work W, LevelDev L, d
         s->done = 0; s->need_lin = 1; s->first = 1; s->it = 0; s->accepted = 0; s->term = 0; s->invalid = 0; s->max_it = max_it;
         s->step_fail = 0; s->lcur = 0; s->lin_done = 0; s->pad2 = 0;
         s->ns_active = s_cnt2[0]; s->nt_active = s_cnt2[1]; s->n_bad_scene = 0; s->n_bad_tfeat = 0; s->n_bad_text = 0;
+        if (W.dec) W.dec->cur = s->cur;                        // (k_pass_end reads `cur` from the record: a pass that is over before a decision block writes it accepts nothing)
         if (W.hprog) { *W.hprog = (unsigned long long)W.pass_seq << 32; __threadfence_system(); }
         *ticket = 0;
     }
@@ -65,12 +67,20 @@ __global__ __launch_bounds__(MS_THREADS) void k_pass_begin(Work W, LevelDev L, d
 
 // nb_out: k_outlier's blocks of this pass ((n_sc + 63)/64 + n_tg; 0: no outlier pass).  n_ms: text observations of the NEXT pass's level Ln whose mu / sigma
 // go to ms_next (0: there is no next pass, or its level is not on the device yet -- k_pass_begin computes them then).  BIG: the geometry of Ln, not of L
+// pd.on (windows whose k_mid launches carry the decision block): workgroup 0 takes the FULL decision on the pass's last trial -- k_decide's body, on the state in
+// place -- and the other roles follow from workgroup 1.  They need the decision's outcome only as far as `cur` goes (the final parameters), and that is in the
+// record the last trial's decision block left (W.dec: the same sums in the same order as the full decision, so the same accept / reject); they read no field of
+// the state that the decision writes -- nt_active and the outlier counters (atomics) are not among them.  A pass that ended before its last queued trial: the
+// decision workgroup returns on `done` as k_decide does, and the record's `cur` is the final state's (no decision block has written it since).
+struct PassDec { int on, nb_back, nb_lm; tsba_options o; };
 template <bool BIG>
 __global__ __launch_bounds__(MS_THREADS) void k_pass_end(Work W, LevelDev L, LevelDev Ln, int nb_out, int n_ms, double *ms_next,
-                                                         double chi2_mono, double chi2_text, double bad_ratio, int do_scene, int do_text) {
-    const int b = blockIdx.x, tid = threadIdx.x, nbo = (nb_out + 3) >> 2;
-    if (b < nbo) { const int ob = 4*b + (tid >> 6); if (ob < nb_out) outlier_wave(W, L, ob, tid & 63, chi2_mono, chi2_text, bad_ratio, do_scene, do_text, nullptr); return; }
-    if (b < nbo + n_ms) { Work Wn = W; Wn.musig = ms_next; musigma_wg<BIG>(Wn, Ln, b - nbo, W.pose[W.st->cur], W.theta[W.st->cur]); return; }
+                                                         double chi2_mono, double chi2_text, double bad_ratio, int do_scene, int do_text, PassDec pd) {
+    static_assert(MS_THREADS == 256, "the decision workgroup is k_decide's: 256 threads");
+    if (pd.on && blockIdx.x == 0) { decide_body(W, L, pd.nb_back, pd.nb_lm, pd.o, 0, 0); return; }
+    const int b = (int)blockIdx.x - (pd.on ? 1 : 0), tid = threadIdx.x, nbo = (nb_out + 3) >> 2;
+    if (b < nbo) { const int ob = 4*b + (tid >> 6); if (ob < nb_out) outlier_wave(W, L, ob, tid & 63, chi2_mono, chi2_text, bad_ratio, do_scene, do_text, nullptr, pd.on ? W.dec->cur : -1); return; }
+    if (b < nbo + n_ms) { Work Wn = W; Wn.musig = ms_next; const int cur = pd.on ? W.dec->cur : W.st->cur; musigma_wg<BIG>(Wn, Ln, b - nbo, W.pose[cur], W.theta[cur]); return; }
     for (int k = tid; k < W.n_kf; k += MS_THREADS) W.kf_in[k] = 0;
     for (int k = tid; k < W.n_pt; k += MS_THREADS) W.act_pt[k] = 0;
     for (int k = tid; k < W.n_text; k += MS_THREADS) W.act_tx[k] = 0;

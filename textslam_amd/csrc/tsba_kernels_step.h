@@ -255,8 +255,9 @@ __device__ __forceinline__ void lm_decide_publish(const Work &W, const LmState &
         t[0] = verdict < 0.0 ? __longlong_as_double(0x7ff8000000000000LL) : (cost == cost ? cost : 1.7976931348623157e308); t[1] = mcc_half; t[2] = s.radius; t[3] = verdict; }
     if (W.hprog) { *W.hprog = ((unsigned long long)W.pass_seq << 32) | ((unsigned long long)s.it << 1) | (s.done ? 1u : 0u); __threadfence_system(); }
 }
-// ---- step quality and trust-region update (Ceres 1.x TrustRegionMinimizer / LevenbergMarquardtStrategy semantics)
-__global__ __launch_bounds__(256) void k_decide(Work W, LevelDev L, int nb_back, int nb_lm, tsba_options o, int multi, int npp) {
+// ---- step quality and trust-region update (Ceres 1.x TrustRegionMinimizer / LevenbergMarquardtStrategy semantics): one workgroup of 256 threads, on the state in place --
+// k_decide as a launch of its own, or the decision workgroup of k_pass_end behind a window's last trial (tsba_kernels_pass.h)
+__device__ __forceinline__ void decide_body(const Work &W, const LevelDev &L, int nb_back, int nb_lm, const tsba_options &o, int multi, int npp) {
     LmState *st = W.st;
     if (W.dp_poll) for (int k = threadIdx.x; k <= W.N; k += 256) W.dp[k] = __builtin_nan("");       // (k_solve_back: "not there yet" for the blocks that poll the next step)
     if (st->done) return;
@@ -290,6 +291,7 @@ __global__ __launch_bounds__(256) void k_decide(Work W, LevelDev L, int nb_back,
     W.dbg[32] = s1_ - s0_; W.dbg[33] = s2_ - s1_; W.dbg[34] = s3_ - s2_; W.dbg[35] = clock64() - s3_;
 #endif
 }
+__global__ __launch_bounds__(256) void k_decide(Work W, LevelDev L, int nb_back, int nb_lm, tsba_options o, int multi, int npp) { decide_body(W, L, nb_back, nb_lm, o, multi, npp); }
 
 // ================================================================== multi-GPU (global BA sharded by landmark over RCCL)
 // stage A: local sums into the all-reduce buffer hb = [Hd | bp | scal] and gm.  spec: candidate LinBuf (also folds the
@@ -358,9 +360,9 @@ __global__ void k_kfin_multi(Work W) {               // kf_in was summed over ra
 // (one wave of 64 lanes per block b: k_outlier launches a workgroup per wave, k_pass_end -- tsba_kernels_pass.h -- four waves per workgroup next to
 // other roles)
 __device__ __forceinline__ void outlier_wave(const Work &W, const LevelDev &L, const int b, const int lane, double chi2_mono, double chi2_text, double bad_ratio,
-                                             int do_scene, int do_text, const PoseState *pfin) {
+                                             int do_scene, int do_text, const PoseState *pfin, const int cur_in = -1) {
     LmState *st = W.st;
-    const int selc = pfin ? 0 : st->cur;
+    const int selc = pfin ? 0 : cur_in >= 0 ? cur_in : st->cur;      // (cur_in: k_pass_end with the decision workgroup beside it -- the state's `cur` is being written)
     const double *pose = pfin ? pfin->x : W.pose[selc], *rho = W.rho[selc], *theta = W.theta[selc];
     if (st->nt_active < 50) chi2_mono += 4.0;
     const int nb_sc = (L.n_sc + 63) >> 6;

@@ -18,7 +18,9 @@ struct LmState {
 // What the decision block of k_mid's launch (windows on one GPU, one-wave blocks: decision_block, tsba_kernels_lin.h) leaves for the assembling and gradient
 // workgroups of the NEXT k_schur_t<4> (SchurDec.on = 3): the outcome of the trial's accept / reject decision as far as the assembly depends on it -- the pass is
 // over, the linearisation that is current, whether that is the candidate just accepted, the trust-region radius.  The state itself is not touched by it.
-struct LmDec { double radius; int done, lcur, fresh, pad; };
+// cur: the parameter buffer that is current after the decision -- for k_pass_end behind the pass's last trial, whose outlier / mu-sigma workgroups run beside
+// the workgroup that writes the decided state (k_pass_begin sets it to the state's, for a pass whose decision block never gets to write the record).
+struct LmDec { double radius; int done, lcur, fresh, cur; };
 
 struct LevelDev {            // device copies of HostPlan + per-level inputs
     int level, n_sc, n_pair, n_tg, n_pslot, n_tslot, n_sb, n_tfeat, bw_rows;      // bw_rows: rows of S below a pose block that can be non-zero
