@@ -3,6 +3,7 @@
  * Replaces, on the device and bit-exactly (integer image arithmetic; fp64 sampling without FMA contraction):
  *   frame::GetPyrMat                    /root/reference/src/frame.cc:178-204     -> tsframe_set_image
  *   tool::GetPyramidPts (text, scene)   /root/reference/src/tool.cc:564-710,862-980 -> tsframe_pyramid_pts
+ *   frame::TextFeaProc (its loop)       src/frame.cc:359-370, with the scene call src/tracking.cc:420 (also :333-334, :494) -> tsframe_pyramid_pts_batch
  *   tool::CalNormvec / GetNeighbour     /root/reference/src/tool.cc:1342-1364,1540-1566 (INTERVAL8) -> tsframe_neighbours
  *   tool::GetBoxAllPixs                 /root/reference/src/tool.cc:1264-1337     -> tsframe_box_pixels
  *   tracking::TextJudgeSingle (xn)      /root/reference/src/tracking.cc:1991-2131 -> tsframe_text_judge
@@ -43,6 +44,24 @@ int tsframe_get_level(void *ctx, int level, int which, uint8_t *out);
  * u, v: level coordinates; idx: IdxToRaw; inten: bilinear intensity on the level image; in: the bilinear sample was inside. */
 int tsframe_pyramid_pts(void *ctx, int mode, const float *xy, int n, const double *box, const double *inv_scale,
                         int32_t *level_off, double *u, double *v, int32_t *idx, double *inten, uint8_t *in);
+
+/* tool::GetPyramidPts for all feature sets of a frame (every text detection of frame::TextFeaProc, and the scene observations) in ONE kernel
+ * launch.  Set i: mode[i] (0 text / 1 scene), its n_i = xy_off[i+1] - xy_off[i] raw features xy[xy_off[i] ..], box[i][4] (read for mode-0 sets only;
+ * box may be NULL without one); inv_scale[n_levels].  With L = the context's n_levels, set i owns the elements [xy_off[i]*L, xy_off[i+1]*L) of u, v,
+ * idx, inten and in, and row i of level_off[n_set][L + 1]; inside that range the contents and their order, the level_off row (relative to the set's
+ * base) and idx (relative to the set's first feature) are exactly what tsframe_pyramid_pts writes for that set alone, so a loop over the single
+ * call can be swapped for this one.  The sets are independent of each other.  The inputs go to the device as one block through the pinned
+ * staging, one kernel runs (one workgroup per set and level, whatever n_set and n_levels are), the results come back in one copy.
+ * n_set == 0 returns TSFRAME_OK without reading any pointer; with n_set > 0 and no feature at all nothing is launched and level_off is zeroed.
+ * TSFRAME_ERR_ARG (tsframe_last_error names this function and, where it applies, the set): a NULL pointer where data is needed, n_set < 0, a mode
+ * other than 0 or 1, xy_off[0] != 0 or a decreasing xy_off, more than INT32_MAX / n_levels features, a set whose grid is degenerate at some level
+ * (cw < 1 or ch < 1: an empty box) as in the single call, and a coordinate of xy, of a mode-0 box or of inv_scale that is not finite or above
+ * 2^20 in magnitude.  That last bound keeps the cell index inside an int on the device and in the CPU restatement alike; the single call does not
+ * check it.  TSFRAME_ERR_STATE: no image set.  On any error nothing is launched and no output array is touched. */
+int tsframe_pyramid_pts_batch(void *ctx, int n_set, const int32_t *mode /*[n_set], 0 text / 1 scene*/,
+                              const int32_t *xy_off /*[n_set + 1]*/, const float *xy /*[xy_off[n_set]][2]*/,
+                              const double *box /*[n_set][4], read for mode-0 sets only*/, const double *inv_scale /*[n_levels]*/,
+                              int32_t *level_off /*[n_set][n_levels + 1]*/, double *u, double *v, int32_t *idx, double *inten, uint8_t *in);
 
 /* tool::CalNormvec -> GetNeighbour(INTERVAL8) on the resident level image: for n features (uv, level coordinates) the 8 neighbour
  * intensities, raw and (I - mu) / sigma; in[j] = inside flag of the last tap (what the reference leaves in feat->IN).

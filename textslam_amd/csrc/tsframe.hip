@@ -338,6 +338,7 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
 }
 
 #include "tsklt.h"
+#include "tspts.h"
 
 static int ensure_host(FCtx *c, size_t bytes) {
     if (bytes <= c->h_cap) return 0;
@@ -352,6 +353,25 @@ static int ensure_work(FCtx *c, size_t bytes) {
     c->d_work = nullptr; c->d_cap = 0;
     CKF(hipMalloc((void **)&c->d_work, bytes));
     c->d_cap = bytes; return 0;
+}
+
+// the cell grid of level l >= 1 for a set of n raw features (host doubles, the reference's expressions: tool.cc:599-616 / :898-907), shared by
+// tsframe_pyramid_pts and tsframe_pyramid_pts_batch; false: degenerate (cw < 1 or ch < 1)
+static bool pts_grid(const FCtx *c, int mode, int n, const double *box, int l, double s, GridDev &g) {
+    const size_t ncell = (size_t)((double)n*s*s + (mode == 0 ? 100 : 500));
+    g.mode = mode; g.s = s; g.x0 = 0.0; g.y0 = 0.0;
+    if (mode == 0) {
+        const double pminx = box[0]*s, pminy = box[1]*s, pmaxx = box[2]*s, pmaxy = box[3]*s;
+        const double WH = (pmaxx - pminx)/(pmaxy - pminy);
+        g.ch = (int)sqrt((double)ncell/WH); g.cw = (int)sqrt((double)ncell*WH);
+        g.fx = (pmaxx - pminx)/(double)g.cw; g.fy = (pmaxy - pminy)/(double)g.ch;
+        g.x0 = pminx; g.y0 = pminy;
+    } else {
+        const double WH = (double)c->w[l]/(double)c->h[l];
+        g.ch = (int)sqrt((double)ncell/WH); g.cw = (int)sqrt((double)ncell*WH);
+        g.fx = (double)c->w[l]/(double)g.cw; g.fy = (double)c->h[l]/(double)g.ch;
+    }
+    return g.cw >= 1 && g.ch >= 1;
 }
 
 extern "C" {
@@ -425,25 +445,11 @@ int tsframe_pyramid_pts(void *ctx, int mode, const float *xy, int n, const doubl
     if (c->n_levels == 0) { c->err = "no image set"; return TSFRAME_ERR_STATE; }
     hipSetDevice(c->device);
     const int L = c->n_levels; const size_t cap = (size_t)n*L;
-    // grids (host doubles, the reference's expressions: tool.cc:599-616 / :898-907)
+    // grids (pts_grid)
     std::vector<GridDev> G(L); size_t max_cell = 1;
     for (int l = 1; l < L; l++) {
-        const double s = inv_scale[l];
-        const size_t ncell = (size_t)((double)n*s*s + (mode == 0 ? 100 : 500));
-        GridDev g; g.mode = mode; g.s = s; g.x0 = 0.0; g.y0 = 0.0;
-        if (mode == 0) {
-            const double pminx = box[0]*s, pminy = box[1]*s, pmaxx = box[2]*s, pmaxy = box[3]*s;
-            const double WH = (pmaxx - pminx)/(pmaxy - pminy);
-            g.ch = (int)sqrt((double)ncell/WH); g.cw = (int)sqrt((double)ncell*WH);
-            g.fx = (pmaxx - pminx)/(double)g.cw; g.fy = (pmaxy - pminy)/(double)g.ch;
-            g.x0 = pminx; g.y0 = pminy;
-        } else {
-            const double WH = (double)c->w[l]/(double)c->h[l];
-            g.ch = (int)sqrt((double)ncell/WH); g.cw = (int)sqrt((double)ncell*WH);
-            g.fx = (double)c->w[l]/(double)g.cw; g.fy = (double)c->h[l]/(double)g.ch;
-        }
-        if (g.cw < 1 || g.ch < 1) { c->err = "degenerate feature grid (empty box?)"; return TSFRAME_ERR_ARG; }
-        G[l] = g; max_cell = std::max(max_cell, (size_t)g.cw*g.ch);
+        if (!pts_grid(c, mode, n, box, l, inv_scale[l], G[l])) { c->err = "degenerate feature grid (empty box?)"; return TSFRAME_ERR_ARG; }
+        max_cell = std::max(max_cell, (size_t)G[l].cw*G[l].ch);
     }
     // device scratch: xy | sel | cnt, level_off | u | v | inten | idx | in
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -471,6 +477,88 @@ int tsframe_pyramid_pts(void *ctx, int mode, const float *xy, int n, const doubl
     const size_t m = (size_t)level_off[L];
     memcpy(u, c->h_stage + o_u, 8*m); memcpy(v, c->h_stage + o_v, 8*m); memcpy(inten, c->h_stage + o_I, 8*m);
     memcpy(idx, c->h_stage + o_idx, 4*m); memcpy(in, c->h_stage + o_in, m);
+    return TSFRAME_OK;
+}
+
+int tsframe_pyramid_pts_batch(void *ctx, int n_set, const int32_t *mode, const int32_t *xy_off, const float *xy, const double *box, const double *inv_scale,
+                              int32_t *level_off, double *u, double *v, int32_t *idx, double *inten, uint8_t *in) {
+    FCtx *c = (FCtx *)ctx;
+    if (!c) return TSFRAME_ERR_ARG;
+    auto bad = [&](const std::string &what) { c->err = "tsframe_pyramid_pts_batch: " + what; return TSFRAME_ERR_ARG; };
+    auto at_set = [](const char *what, int i) { return std::string(what) + " (set " + std::to_string(i) + ")"; };
+    if (n_set < 0) return bad("n_set < 0");
+    if (n_set == 0) return TSFRAME_OK;
+    if (!mode || !xy_off || !inv_scale || !level_off) return bad("NULL mode / xy_off / inv_scale / level_off");
+    if (c->n_levels == 0) { c->err = "tsframe_pyramid_pts_batch: no image set"; return TSFRAME_ERR_STATE; }
+    const int L = c->n_levels;
+    const double lim = 1048576.0;                                // 2^20: keeps the cell index inside an int, here and in the CPU restatement
+    auto wild = [lim](double x) { return !(fabs(x) <= lim); };   // (NaN and infinities included)
+    for (int l = 0; l < L; l++) if (wild(inv_scale[l])) return bad("inv_scale not finite or above 2^20 in magnitude");
+    if (xy_off[0] != 0) return bad("xy_off[0] != 0");
+    bool any_text = false;
+    for (int i = 0; i < n_set; i++) {
+        if (mode[i] != 0 && mode[i] != 1) return bad(at_set("mode is neither 0 nor 1", i));
+        if (xy_off[i + 1] < xy_off[i]) return bad(at_set("xy_off decreasing", i));
+        any_text |= mode[i] == 0;
+    }
+    const size_t total = (size_t)xy_off[n_set];
+    if (total > (size_t)(INT32_MAX / L)) return bad("more than INT32_MAX / n_levels features");
+    if (any_text && !box) return bad("box NULL with a text set");
+    if (total > 0 && (!xy || !u || !v || !idx || !inten || !in)) return bad("NULL array with features");
+    for (size_t k = 0; k < 2*total; k++)
+        if (wild((double)xy[k])) {
+            int i = 0; while (xy_off[i + 1] <= (int32_t)(k/2)) i++;
+            return bad(at_set("coordinate not finite or above 2^20 in magnitude", i));
+        }
+    // jobs: one per (set, level), level-major inside a set; the grids are the single call's (pts_grid)
+    std::vector<PtsJob> jobs((size_t)n_set*L);
+    size_t sel_ints = 0;
+    for (int i = 0; i < n_set; i++) {
+        const int n = xy_off[i + 1] - xy_off[i];
+        const double *bx = mode[i] == 0 ? box + 4*(size_t)i : nullptr;
+        if (bx) for (int k = 0; k < 4; k++) if (wild(bx[k])) return bad(at_set("box not finite or above 2^20 in magnitude", i));
+        for (int l = 0; l < L; l++) {
+            PtsJob &J = jobs[(size_t)i*L + l];
+            J.G = GridDev{mode[i], 1, 1, 1.0, 0, 0, 1, 1};
+            if (l > 0 && !pts_grid(c, mode[i], n, bx, l, inv_scale[l], J.G)) return bad(at_set("degenerate feature grid (empty box?)", i));
+            const size_t ncell = (size_t)J.G.cw*(size_t)J.G.ch;
+            if (ncell > (size_t)INT32_MAX) return bad(at_set("feature grid above 2^31 cells", i));
+            J.img = c->plane[TSFRAME_IMG][l]; J.grad = c->plane[TSFRAME_GRAD][l]; J.w = c->w[l]; J.h = c->h[l];
+            J.level = l; J.xy0 = xy_off[i]; J.n = n; J.out0 = xy_off[i]*L + l*n;
+            J.sel_off = -1;
+            if (l > 0 && n > 0 && ncell > PTS_LDS_CELLS) { J.sel_off = (long long)sel_ints; sel_ints += ncell; }
+        }
+    }
+    if (total == 0) { memset(level_off, 0, sizeof(int32_t)*(size_t)n_set*(L + 1)); return TSFRAME_OK; }
+    hipSetDevice(c->device);
+    // one block, inputs then outputs: jobs | xy || cnt | u | v | inten | idx | in; then the large grids' scratch (device only)
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t cap = total*L, nj = jobs.size();
+    const size_t o_xy = al(sizeof(PtsJob)*nj), o_cnt = o_xy + al(8*total), o_u = o_cnt + al(4*nj), o_v = o_u + al(8*cap), o_I = o_v + al(8*cap),
+                 o_idx = o_I + al(8*cap), o_in = o_idx + al(4*cap), tot = o_in + al(cap);
+    int rc = ensure_work(c, tot + 4*sel_ints); if (rc) return rc;
+    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    uint8_t *h = c->h_stage, *d = c->d_work;
+    memcpy(h, jobs.data(), sizeof(PtsJob)*nj); memcpy(h + o_xy, xy, 8*total);
+    CKF(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_pts_batch, dim3((unsigned)nj), dim3(PTS_NT), 0, c->stream, (const PtsJob *)d, (const float *)(d + o_xy), (int *)(d + tot), (int *)(d + o_cnt),
+                       (double *)(d + o_u), (double *)(d + o_v), (int *)(d + o_idx), (double *)(d + o_I), d + o_in);
+    CKF(hipGetLastError());
+    CKF(hipMemcpyAsync(h + o_cnt, d + o_cnt, tot - o_cnt, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipStreamSynchronize(c->stream));
+    // copy-out: level l of set i lies at out0 = xy_off[i]*L + l*n_i with cnt entries; packed behind the set's base, as the single call leaves it
+    const int *cnt = (const int *)(h + o_cnt);
+    for (int i = 0; i < n_set; i++) {
+        int32_t *lo = level_off + (size_t)i*(L + 1);
+        const size_t base = (size_t)xy_off[i]*L;
+        lo[0] = 0;
+        for (int l = 0; l < L; l++) {
+            const size_t src = (size_t)jobs[(size_t)i*L + l].out0, dst = base + (size_t)lo[l], m = std::min((size_t)cnt[(size_t)i*L + l], (size_t)(xy_off[i + 1] - xy_off[i]));
+            memcpy(u + dst, h + o_u + 8*src, 8*m); memcpy(v + dst, h + o_v + 8*src, 8*m); memcpy(inten + dst, h + o_I + 8*src, 8*m);
+            memcpy(idx + dst, h + o_idx + 4*src, 4*m); memcpy(in + dst, h + o_in + src, m);
+            lo[l + 1] = lo[l] + (int32_t)m;
+        }
+    }
     return TSFRAME_OK;
 }
 

@@ -2,6 +2,7 @@
 
   Frame.GetPyrMat(img, iScaleLevels)                  frame::GetPyrMat          /root/reference/src/frame.cc:178-204
   Frame.GetPyramidPts(...) / GetPyramidPtsScene(...)  tool::GetPyramidPts       /root/reference/src/tool.cc:564-710, 862-980
+  Frame.GetPyramidPtsBatch(sets, vInvScalefactor)     the loop of frame::TextFeaProc src/frame.cc:359-370 (+ the scene set), one launch
   Frame.CalNormvec(level, uv, mu, std)                tool::CalNormvec          /root/reference/src/tool.cc:1342-1364 (GetNeighbour INTERVAL8)
   Frame.GetBoxAllPixs(level, vTextDete, mu, std, K)   tool::GetBoxAllPixs       /root/reference/src/tool.cc:1264-1337
   Frame.TextJudgeBatch(...)                           tracking::TextJudgeSingle /root/reference/src/tracking.cc:1991-2131 (n planes, one launch)
@@ -11,14 +12,24 @@ No CPU fallback: without the HIP library / a GPU every call raises.
 """
 import ctypes as C
 import os
+import re
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libtsframe.so")
 EXPORTED_SYMBOLS = ["tsframe_create", "tsframe_destroy", "tsframe_last_error", "tsframe_set_image", "tsframe_level_size", "tsframe_level_ptr",
-                    "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_neighbours", "tsframe_box_pixels", "tsframe_text_judge", "tsframe_klt_track"]
+                    "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_pyramid_pts_batch", "tsframe_neighbours", "tsframe_box_pixels", "tsframe_text_judge", "tsframe_klt_track"]
 IMG, GRAD, GRADX, GRADY = 0, 1, 2, 3
 JUDGE_PASS, JUDGE_ORIENT, JUDGE_DEPTH, JUDGE_BOX, JUDGE_ZNCC = 0, 1, 2, 3, 4
+
+
+def _csrc_define(header, name):
+    text = open(os.path.join(_HERE, "csrc", header)).read()
+    return int(re.search(r"^#define\s+%s\s+(\d+)" % name, text, re.M).group(1))
+
+
+# cells of a (set, level) grid that tsframe_pyramid_pts_batch keeps in LDS; a larger grid goes to the device scratch (csrc/tspts.h)
+PTS_LDS_CELLS = _csrc_define("tspts.h", "PTS_LDS_CELLS")
 
 
 class FrameError(RuntimeError):
@@ -38,6 +49,8 @@ def _load():
     L.tsframe_level_ptr.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.tsframe_get_level.argtypes = [vp, C.c_int, C.c_int, up]
     L.tsframe_pyramid_pts.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, dp, dp, ip, dp, dp, ip, dp, up]
+    L.tsframe_pyramid_pts_batch.argtypes = [vp, C.c_int, ip, ip, C.POINTER(C.c_float), dp, dp, ip, dp, dp, ip, dp, up]
+    L.tsframe_pyramid_pts_batch.restype = C.c_int
     L.tsframe_neighbours.argtypes = [vp, C.c_int, dp, C.c_int, C.c_double, C.c_double, dp, dp, up]
     L.tsframe_box_pixels.argtypes = [vp, C.c_int, dp, C.c_double, C.c_double, C.c_int, ip, ip, ip, dp, dp]
     L.tsframe_text_judge.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, ip, C.POINTER(C.c_int16), up, dp, dp, C.c_double, C.c_int, C.c_double,
@@ -108,6 +121,31 @@ class Frame:
 
     def GetPyramidPtsScene(self, vObvRaw, vInvScalefactor):
         return self._pts(1, vObvRaw, None, vInvScalefactor)
+
+    def GetPyramidPtsBatch(self, sets, vInvScalefactor):
+        """tool::GetPyramidPts for every feature set of the frame in one launch (include/tsframe.h: tsframe_pyramid_pts_batch).
+        sets = [(mode, xy, box-or-None)]: mode 0 = text (box = (PMin.x, PMin.y, PMax.x, PMax.y)), 1 = scene.  Returns one dict per set, the same
+        as GetPyramidPts / GetPyramidPtsScene give for that set alone."""
+        ns = len(sets); nl = self.n_levels
+        inv = np.ascontiguousarray(vInvScalefactor, np.float64); assert len(inv) == nl
+        xys = [np.ascontiguousarray(s[1], np.float32).reshape(-1, 2) for s in sets]
+        mode = np.array([s[0] for s in sets], np.int32).reshape(ns)
+        off = np.zeros(ns + 1, np.int32); off[1:] = np.cumsum([len(a) for a in xys])
+        xy = np.concatenate(xys) if ns else np.zeros((0, 2), np.float32)
+        box = np.zeros((max(ns, 1), 4)); tot = int(off[ns]); cap = max(1, tot*nl)
+        for i, s in enumerate(sets):
+            if s[2] is not None:
+                box[i] = np.asarray(s[2], np.float64).reshape(4)
+        lo = np.zeros((max(ns, 1), nl + 1), np.int32); u = np.zeros(cap); v = np.zeros(cap); idx = np.zeros(cap, np.int32); I = np.zeros(cap); inn = np.zeros(cap, np.uint8)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.tsframe_pyramid_pts_batch(self.ctx, ns, mode.ctypes.data_as(ip), off.ctypes.data_as(ip), xy.ctypes.data_as(C.POINTER(C.c_float)), _dp(box),
+                                                       _dp(inv), lo.ctypes.data_as(ip), _dp(u), _dp(v), idx.ctypes.data_as(ip), _dp(I), _up(inn)),
+                    "tsframe_pyramid_pts_batch")
+        out = []
+        for i in range(ns):
+            b = int(off[i])*nl; e = b + int(lo[i, nl])
+            out.append({"level_off": lo[i].copy(), "u": u[b:e], "v": v[b:e], "idx": idx[b:e], "inten": I[b:e], "in": inn[b:e]})
+        return out
 
     def CalNormvec(self, level, uv, mu, std):
         """Returns (neighbourInten [n, 8], neighbourNInten [n, 8], IN [n]); std == 0 raises (the reference returns false)."""
