@@ -991,6 +991,7 @@ static int solve_lds_bytes(Ctx *c, int *use_lds) {
     *use_lds = lds_solver_fits(c->W.N);
     return *use_lds ? (int)(solve_lds_doubles(c->W.N)*sizeof(double)) : 0;
 }
+static int chol_subst_lds_bytes() { return (CH_NB*(CH_NB + 1) + 2*CH_NB + 8*CH_NB)*(int)sizeof(double); }      // k_chol_fwd, k_chol_backsub
 static void launch_schur(Ctx *c, const LevelDev &D, int multi, SchurDec dec = SchurDec{0, 0, 0, tsba_options{}}) {
     if (c->n_kf > 126 && !c->dbg.no_schur_quad) {               // large maps: four S blocks per wave, then one wave per pose for the reduced gradient
         const int nq = D.n_sb > 0 ? (((D.n_sb + 3)/4 + 7)/8)*8 : 0, ng = ((c->n_kf + 7)/8)*8;           // (multiples of 8 workgroups: the kernel's XCD-aware mappings)
@@ -1034,383 +1035,19 @@ static int set_solver_attrs(Ctx *c) {
 #define MX_ATTR(SS) ATTR(k_mx_cre_fwd<SS>, 156*1024); ATTR(k_mx_cre_root<SS>, 156*1024); ATTR(k_mx_cre_back<SS>, 156*1024);
         MX_ATTR(36) MX_ATTR(42) MX_ATTR(48) MX_ATTR(54) MX_ATTR(60) MX_ATTR(66)
 #undef MX_ATTR
-        ATTR(k_sv_fwd_int<1>, 156*1024);
-        ATTR(k_sv_fwd_int<2>, 156*1024);
-        ATTR(k_sv_back_int<1>, 156*1024);
-        ATTR(k_sv_back_int<2>, 156*1024);
-        ATTR(k_sv_tree_back<1>, 150*1024);
-        ATTR(k_sv_tree_back<2>, 150*1024);
-        ATTR(k_bandp_backsub<1>, 156*1024);
-        ATTR(k_bandp_backsub<2>, 156*1024);
-        ATTR(k_band_backsub<1>, 156*1024);
-        ATTR(k_band_backsub<2>, 156*1024);
-        ATTR(k_band_backsub<3>, 156*1024);
+        ATTR(k_sv_fwd_int<1>, 156*1024); ATTR(k_sv_fwd_int<2>, 156*1024);
+        ATTR(k_sv_back_int<1>, 156*1024); ATTR(k_sv_back_int<2>, 156*1024);
+        ATTR(k_sv_tree_back<1>, 150*1024); ATTR(k_sv_tree_back<2>, 150*1024);
+        ATTR(k_bandp_backsub<1>, 156*1024); ATTR(k_bandp_backsub<2>, 156*1024);
+        ATTR(k_band_backsub<1>, 156*1024); ATTR(k_band_backsub<2>, 156*1024); ATTR(k_band_backsub<3>, 156*1024);
         ATTR(k_solve_t<true>, (int)(solve_diag_lds_doubles()*sizeof(double)));
         ATTR(k_chol_panel, (CH_NB + 64)*(CH_NB + 1)*(int)sizeof(double));
         ATTR(k_chol_update, 2*64*(CH_NB + 1)*(int)sizeof(double));
-        ATTR(k_chol_backsub, (CH_NB*(CH_NB + 1) + 2*CH_NB + 8*CH_NB)*(int)sizeof(double));
-        ATTR(k_chol_fwd, (CH_NB*(CH_NB + 1) + 2*CH_NB + 8*CH_NB)*(int)sizeof(double));
+        ATTR(k_chol_backsub, chol_subst_lds_bytes()); ATTR(k_chol_fwd, chol_subst_lds_bytes());
     }
     return 0;
 }
-static void launch_dense_chol(Ctx *c, Work &W, int bw);
-// dense solve of the reduced camera system: LDS kernel for small windows, multi-workgroup blocked Cholesky otherwise
-static bool ms_available(const Ctx *c);
-static int sv_reserve(Ctx *c);
-static void launch_sv_prepare(Ctx *c, double *xreset);
-static void launch_solve(Ctx *c) {
-    Work &W = c->W;
-    c->sv_prepared = false;
-    int use_lds; int lds = solve_lds_bytes(c, &use_lds);
-    if (use_lds) {                                  // small windows: one workgroup, S in LDS.  solve_variant 1: the two-panel-wave schedule of tsba_solve.h (A/B runs)
-        const size_t la = solve_la_lds_doubles(W.N)*sizeof(double);
-        if ((c->dbg.solve_variant == 1 || c->dbg.solve_variant == 2) && la <= 160*1024 - 64) LAUNCHK(k_solve_la, dim3(1), dim3(SOLVE_THREADS), (int)la, c->stream, W, c->dbg.solve_variant == 2 ? 0 : 1);
-        else if (c->dbg.solve_variant == 4) LAUNCHK((k_solve_t<false, false>), dim3(1), dim3(SOLVE_THREADS), lds, c->stream, W, 0);      // (the diagonal blocks through the LDS scratch: A/B and bit-identity runs)
-        else LAUNCHK(k_solve_t<false>, dim3(1), dim3(SOLVE_THREADS), lds, c->stream, W, 0);
-        return; }
-    if (c->band_stream && c->band_parts > 1) {      // partitioned: interiors in parallel + separator system (tsba_bandp.h)
-        const int bwp = std::max(6, c->cur_bw_rows), cbp = bandp_chunk_blocks(bwp), P = c->band_parts;
-        const int bwsep = 2*bwp - 6, cbs = band_chunk_blocks(bwsep);
-        Work &Ws = c->Wsep; Ws.st = W.st; Ws.ldS = (P - 1)*bwp; Ws.N = (P - 1)*bwp;
-        if (!c->sep_cr) hipMemsetAsync(c->Ssep, 0, sizeof(double)*((size_t)Ws.ldS*Ws.ldS + Ws.ldS), c->stream);
-        LAUNCHK(k_bandp_factor, dim3(P), dim3(BANDP_T), (int)(bandp_lds_doubles(bwp, cbp)*sizeof(double)), c->stream, W, bwp, cbp, P, c->Lcol, c->Lb, c->Tbuf);
-        if (c->sep_cr && (W.ring || (c->dbg.sep_solver != 3 && c->dbg.sep_solver != 4)))      // block pool: border products + separator assembly in one launch (4: the three launches, for A/B runs)
-            LAUNCHK(k_bandp_sepf, dim3(W.ring ? P + 1 : P - 1), dim3(BSF_T), (int)(bandp_sepf_lds_doubles()*sizeof(double)), c->stream, W, bwp, P, (const double *)c->Tbuf, (const double *)c->Lb, c->Ssep, Ws.g, Ws.nfree);
-        else {
-        hipMemsetAsync(c->Bpart, 0, sizeof(double)*(size_t)P*BANDP_NS*((size_t)bwp*bwp + bwp), c->stream);        // (slices of short interiors stay empty)
-        LAUNCHK(k_bandp_border, dim3(P, BANDP_NS), dim3(256), (int)((2*(size_t)BANDP_JC*bwp*6 + 6*BANDP_JC)*sizeof(double)), c->stream, W, bwp, P, (const double *)c->Lb, c->Bpart);
-        LAUNCHK(k_bandp_sep, dim3(P - 1), dim3(256), 0, c->stream, W, bwp, P, (const double *)c->Tbuf, (const double *)c->Bpart, c->Ssep, Ws.ldS, Ws.g, Ws.nfree, (int)c->sep_cr);
-        }
-        if (c->sep_cr) {                  // separator system by block cyclic reduction (tsba_bandcr.h): log2(P - 1) levels
-            const int mmax = cr_mmax(W.ring, P, W.ring_g);
-            int mlev = mmax;                  // levels h < mlev.  Ring: the loop's separators need h <= G/2 (the root and the ghost are merged at the root, no level for them),
-            if (W.ring) { mlev = W.ring_g;    // a tail's separator RING_OFF - j the level of the lowest set bit of j (j < the number of tail interiors)
-                for (int hh = 1; hh < P - W.ring_g; hh <<= 1) mlev = std::max(mlev, 2*hh); }
-            const int lab0 = W.ring && P > W.ring_g ? RING_OFF - (P - W.ring_g) + 1 : 0;          // lowest separator label (a ring with a tail counts down from RING_OFF)
-            const int lp = (int)(cr_pivot_lds_doubles(bwp)*sizeof(double)), lu = (int)(cr_update_lds_doubles(bwp)*sizeof(double)), lb = (int)(cr_back_lds_doubles(bwp)*sizeof(double));
-            int htop = 1;
-            if (c->dbg.sep_solver != 3 || W.ring) {      // one launch per level (tsba_bandcre.h); 3: the pivot / update / back kernels of tsba_bandcr.h
-                const int le = (int)(cre_elim_lds_doubles(bwp)*sizeof(double)), lbk = (int)(cre_back_lds_doubles(bwp)*sizeof(double));
-                c->cre_epoch++;                                   // (this factorisation's ordinal: what the K workgroups of a pivot tell each other they have loaded for, k_cre_elim)
-                auto pivots = [&](int h, int &kb) { kb = lab0/(2*h); const int klast = (mmax - 1 - h)/(2*h); return std::max(0, klast - kb + 1); };     // pivots (2 k + 1) h, k = kb ..
-                for (int h = 1; h < mlev; h <<= 1) {
-                    int kb; const int npiv = pivots(h, kb); if (npiv <= 0) { htop = h; continue; }
-                    const int K = std::max(1, std::min(TSBA_CRE_KMAX, 224/npiv));     // workgroups per pivot (they share its product and stores)
-                    LAUNCHK(k_cre_elim, dim3(npiv*K), dim3(CRE_T), le, c->stream, W, Ws, bwp, P, h, 0, K, kb, c->CRcontrib, c->CRfac, c->CRgate, c->cre_epoch); htop = h; }
-                LAUNCHK(k_cre_elim, dim3(1), dim3(CRE_T), le, c->stream, W, Ws, bwp, P, 0, W.ring ? 2 : 1, 1, 0, c->CRcontrib, c->CRfac, c->CRgate, c->cre_epoch);
-                // back substitution: a launch per level -- or one launch through the inverse factors and products of the solve phase (k_sv_linv + k_cre_back_tree)
-                // where the iterative path needs those anyway (maps with long-range blocks) or the tree is deep enough to pay for k_sv_linv (28 us at 48-row
-                // separators against 10.5 us per level)
-                if ((c->far_B > 0 || (htop >= 32 && bwp <= 60)) && ms_available(c) && !(c->dbg.sv_per_level & 2) && c->dbg.pcg_refactor != 1 && mmax >= 2 && grid_resident(c, (const void *)k_cre_back_tree, SV_CT, 0, mmax - 1) && sv_reserve(c) == TSBA_OK) {
-                    launch_sv_prepare(c, Ws.Sy);
-                    LAUNCHK(k_cre_back_tree, dim3(mmax - 1), dim3(SV_CT), 0, c->stream, W, Ws, bwp, P, (const double *)c->CRfac, c->sv);
-                } else
-                for (int h = htop; h >= 1; h >>= 1) { int kb; const int npiv = pivots(h, kb); if (npiv > 0) LAUNCHK(k_cre_back, dim3(npiv), dim3(CRE_BT), lbk, c->stream, W, Ws, bwp, P, h, kb, (const double *)c->CRfac); }
-            } else {
-            for (int h = 1; h < mmax; h <<= 1) {
-                const int npiv = (mmax + 2*h - 1)/(2*h);           // >= the pivots (2k + 1) h < m; workgroups past the end return
-                LAUNCHK(k_cr_pivot, dim3(npiv), dim3(CR_T), lp, c->stream, W, Ws, bwp, P, h, 0);
-                LAUNCHK(k_cr_update, dim3(2*npiv + 1), dim3(CR_T), lu, c->stream, W, Ws, bwp, P, h, npiv);
-                htop = h;
-            }
-            LAUNCHK(k_cr_pivot, dim3(1), dim3(CR_T), lp, c->stream, W, Ws, bwp, P, 0, 1);
-            LAUNCHK(k_cr_back, dim3(1), dim3(CR_T), lb, c->stream, W, Ws, bwp, P, 0, 1);
-            for (int h = htop; h >= 1; h >>= 1)
-                LAUNCHK(k_cr_back, dim3((mmax + 2*h - 1)/(2*h)), dim3(CR_T), lb, c->stream, W, Ws, bwp, P, h, 0);
-            }
-        } else {
-        const int ldss = (int)(band_lds_doubles(bwsep, cbs)*sizeof(double)), nus = (bwsep + 63)/64;
-        LAUNCHK(k_band_solve, dim3(1), dim3(SOLVE_THREADS), ldss, c->stream, Ws, bwsep, cbs, c->Lcol_sep);
-        if (nus <= 1) LAUNCHK(k_band_backsub<1>, dim3(1), dim3(BAND_BS_T), ldss, c->stream, Ws, bwsep, (const double *)c->Lcol_sep);
-        else if (nus == 2) LAUNCHK(k_band_backsub<2>, dim3(1), dim3(BAND_BS_T), ldss, c->stream, Ws, bwsep, (const double *)c->Lcol_sep);
-        else LAUNCHK(k_band_backsub<3>, dim3(1), dim3(BAND_BS_T), ldss, c->stream, Ws, bwsep, (const double *)c->Lcol_sep);
-        }
-        const int nup = (bwp + 63)/64, ldsp = (int)((2*(size_t)BAND_CK*(2*(size_t)bwp*6 + 32) + 6*BAND_RINGB + 2*bwp + 64)*sizeof(double));
-        if (nup <= 1) LAUNCHK(k_bandp_backsub<1>, dim3(P), dim3(BAND_BS_T), ldsp, c->stream, W, bwp, P, (const double *)c->Lcol, (const double *)c->Lb, (const double *)Ws.Sy);
-        else LAUNCHK(k_bandp_backsub<2>, dim3(P), dim3(BAND_BS_T), ldsp, c->stream, W, bwp, P, (const double *)c->Lcol, (const double *)c->Lb, (const double *)Ws.Sy);
-        LAUNCHK(k_bandp_dp, dim3((W.n_kf + 255)/256), dim3(256), 0, c->stream, W);
-        return;
-    }
-    if (c->band_stream) {                                          // narrow band: one workgroup streams down the band (tsba_band.h)
-        const int bws = std::max(6, c->cur_bw_rows), cb = band_chunk_blocks(bws);
-        if (c->dbg.verbose) fprintf(stderr, "[launch_solve] band stream bw %d cb %d lds %zu B\n", bws, cb, band_lds_doubles(bws, cb)*sizeof(double));
-        LAUNCHK(k_band_solve, dim3(1), dim3(SOLVE_THREADS), (int)(band_lds_doubles(bws, cb)*sizeof(double)), c->stream, W, bws, cb, c->Lcol);
-        const int nu = (bws + 63)/64, ldsb = (int)(band_lds_doubles(bws, cb)*sizeof(double));      // tasks per lane of the back substitution
-        if (nu <= 1) LAUNCHK(k_band_backsub<1>, dim3(1), dim3(BAND_BS_T), ldsb, c->stream, W, bws, (const double *)c->Lcol);
-        else if (nu == 2) LAUNCHK(k_band_backsub<2>, dim3(1), dim3(BAND_BS_T), ldsb, c->stream, W, bws, (const double *)c->Lcol);
-        else LAUNCHK(k_band_backsub<3>, dim3(1), dim3(BAND_BS_T), ldsb, c->stream, W, bws, (const double *)c->Lcol);
-        return;
-    }
-    launch_dense_chol(c, W, std::min(c->cur_bw_rows, W.N));
-}
-// multi-workgroup blocked Cholesky (tsba_chol.h) of the system in `W` (band bound bw rows below a pose block; bw = N: dense)
-static void launch_dense_chol(Ctx *c, Work &W, int bw) {
-    const int N = W.N;                                             // worst case: every keyframe free
-    LAUNCHK(k_chol_rhs, dim3((N + 255)/256), dim3(256), 0, c->stream, W);
-    const int lds_diag = (int)(solve_diag_lds_doubles()*sizeof(double));
-    const int lds_panel = (CH_NB + 64)*(CH_NB + 1)*(int)sizeof(double);
-    const int lds_upd = 2*64*(CH_NB + 1)*(int)sizeof(double);
-    for (int j0 = 0; j0 < N; j0 += CH_NB) {
-        LAUNCHK(k_solve_t<true>, dim3(1), dim3(SOLVE_THREADS), lds_diag, c->stream, W, j0);
-        // the host only knows the worst case n = N; a shorter last block (nb < NB) still has the rhs row below it
-        const int wr = std::max(0, std::min(bw, N - (j0 + 6)));        // band rows below the block, + 1 for the rhs row
-        LAUNCHK(k_chol_panel, dim3(wr/64 + 1), dim3(CH_T), lds_panel, c->stream, W, j0, bw);
-        const int nt = (wr + 1 + 63)/64;
-        if (wr > 0) LAUNCHK(k_chol_update, dim3(nt*(nt + 1)/2), dim3(CH_T), lds_upd, c->stream, W, j0, bw);
-    }
-    const int lds_bs = (CH_NB*(CH_NB + 1) + 2*CH_NB + 8*CH_NB)*(int)sizeof(double);
-    LAUNCHK(k_chol_backsub, dim3(1), dim3(1024), lds_bs, c->stream, W, bw);
-}
-
-// ---- solve phase of the partitioned band solver for T right-hand sides (tsba_bandms.h): needs the factor of the last launch_solve of this level
-static bool ms_available(const Ctx *c) { return c->band_stream && c->band_parts > 1 && c->sep_cr && !c->W.ring && c->dbg.sep_solver != 3; }
-static int ms_reserve(Ctx *c, int T) {           // buffers for T columns (kept until a larger request or another problem size)
-    const size_t n6 = (size_t)c->W.N, labels = (size_t)cr_mmax(0, c->band_parts, 0) + 1, sdim = (size_t)std::max(6, c->cur_bw_rows);
-    const size_t per = 4*n6 + 6*labels*sdim, need = per*(size_t)T*sizeof(double);
-    if (need > c->ms_bytes) { if (c->ms_alloc) { hipStreamSynchronize(c->stream); hipFree(c->ms_alloc); } c->ms_alloc = nullptr; c->ms_bytes = 0;
-        if (hipMalloc((void **)&c->ms_alloc, need) != hipSuccess) { set_err(c, "hipMalloc (multi-right-hand-side buffers)"); return TSBA_ERR_DEVICE; }
-        c->ms_bytes = need; }
-    double *q = c->ms_alloc; MsBuf &M = c->ms; M.T = T;
-    M.R = q; q += n6*T; M.Wm = q; q += n6*T; M.V = q; q += n6*T; M.X = q; q += n6*T;
-    M.G = q; q += labels*sdim*T; M.Z = q; q += labels*sdim*T; M.Xs = q; q += labels*sdim*T; M.Cg = q; q += 2*labels*sdim*T; M.G2 = q;
-    c->ms_cap = T;
-    return TSBA_OK;
-}
-static void launch_ms_solve(Ctx *c, bool mx = false) {            // M.R -> M.X.  mx: the separators in product form (tsba_bandmx.h) -- c->sv holds the inverse factors of this factorisation
-    Work &W = c->W; const MsBuf &M = c->ms;
-    const int bwp = std::max(6, c->cur_bw_rows), P = c->band_parts, B = bwp/6, ncg = (M.T + 63)/64;
-    Work &Ws = c->Wsep; Ws.st = W.st;
-    mx = mx && bwp >= 36 && bwp <= MX_SMAX && bwp % 6 == 0;
-    const size_t ldsf = ms_cre_lds_doubles(bwp, 1)*sizeof(double), ldsb = (ms_cre_lds_doubles(bwp, 3) + 8*(size_t)(bwp + 2))*sizeof(double), ldsx = mx_lds_doubles(bwp)*sizeof(double);
-    LAUNCHK(k_ms_fwd_int, dim3(P, ncg), dim3(64), 0, c->stream, W, bwp, P, (const double *)c->Lcol, M);
-    LAUNCHK(k_ms_sep_rhs, dim3(P - 1, ncg), dim3(64*B), 0, c->stream, W, bwp, P, (const double *)c->Lcol, (const double *)c->Lb, M);
-    const int mmax = cr_mmax(0, P, 0);
-    auto pivots = [&](int h, int &kb) { kb = 0; const int klast = (mmax - 1 - h)/(2*h); return mmax - 1 - h < 0 ? 0 : std::max(0, klast + 1); };
-    int htop = 0;
-    const double *Li = c->sv.Li, *Lid = c->sv.Lid;
-    // (the product-form kernels are instantiated per separator size: compile-time loop bounds and LDS offsets)
-#define MX_CASES(CALL) switch (bwp) { case 36: CALL(36) break; case 42: CALL(42) break; case 48: CALL(48) break; case 54: CALL(54) break; case 60: CALL(60) break; case 66: CALL(66) break; default: break; }
-    for (int h = 1; h < mmax; h <<= 1) { int kb; const int npiv = pivots(h, kb); if (npiv <= 0) continue;
-        if (mx) {
-#define MX_FWD(SS) LAUNCHK(k_mx_cre_fwd<SS>, dim3(npiv, ncg), dim3(MX_T), ldsx, c->stream, W, Ws, bwp, P, h, kb, M, Li, Lid);
-            MX_CASES(MX_FWD)
-#undef MX_FWD
-        } else LAUNCHK(k_ms_cre_fwd, dim3(npiv, ncg), dim3(MS_CT), ldsf, c->stream, W, Ws, bwp, P, h, kb, (const double *)c->CRfac, M);
-        htop = h; }
-    if (mx) {
-#define MX_ROOT(SS) LAUNCHK(k_mx_cre_root<SS>, dim3(1, ncg), dim3(MX_T), ldsx, c->stream, W, bwp, P, M, Li, Lid);
-        MX_CASES(MX_ROOT)
-#undef MX_ROOT
-    } else LAUNCHK(k_ms_cre_root, dim3(1, ncg), dim3(256), ldsf, c->stream, W, Ws, bwp, P, (const double *)c->CRfac, M);
-    for (int h = htop; h >= 1; h >>= 1) { int kb; const int npiv = pivots(h, kb);
-        if (npiv <= 0) continue;
-        if (mx) {
-#define MX_BACK(SS) LAUNCHK(k_mx_cre_back<SS>, dim3(npiv, ncg), dim3(MX_T), ldsx, c->stream, W, Ws, bwp, P, h, kb, M, Li);
-            MX_CASES(MX_BACK)
-#undef MX_BACK
-        } else LAUNCHK(k_ms_cre_back, dim3(npiv, ncg), dim3(MS_CT), ldsb, c->stream, W, Ws, bwp, P, h, kb, (const double *)c->CRfac, M); }
-#undef MX_CASES
-    LAUNCHK(k_ms_back_border, dim3(P, ncg), dim3(BB_T), 0, c->stream, W, bwp, P, (const double *)c->Lb, M);
-    LAUNCHK(k_ms_back_int, dim3(P, ncg), dim3(64), 0, c->stream, W, bwp, P, (const double *)c->Lcol, M);
-}
-
-// ---- the same for ONE right-hand side (tsba_bandsv.h): x = M^-1 (rs * r) into c->sv.X.  launch_sv_prepare once per factorisation (the
-// separators' inverse factors), then any number of launch_sv_solve
-static int sv_reserve(Ctx *c) {
-    const size_t n6 = ((size_t)c->W.N + 1) & ~(size_t)1, labels = (size_t)cr_mmax(0, c->band_parts, 0) + 1, sdim = (size_t)std::max(6, c->cur_bw_rows);
-    const size_t need = (4*n6 + 7*labels*sdim + 3*labels*sdim*sdim)*sizeof(double);
-    if (need > c->sv_bytes) { if (c->sv_alloc) { hipStreamSynchronize(c->stream); hipFree(c->sv_alloc); } c->sv_alloc = nullptr; c->sv_bytes = 0;
-        if (hipMalloc((void **)&c->sv_alloc, need) != hipSuccess) { set_err(c, "hipMalloc (solve-phase buffers)"); return TSBA_ERR_DEVICE; }
-        c->sv_bytes = need; }
-    double *q = c->sv_alloc; MsBuf &M = c->sv; M.T = 1;
-    M.Li = q; q += labels*sdim*sdim; M.Pp = q; q += 2*labels*sdim*sdim;
-    M.R = q; q += n6; M.Wm = q; q += n6; M.V = q; q += n6; M.X = q; q += n6;
-    M.G = q; q += labels*sdim; M.Z = q; q += labels*sdim; M.Xs = q; q += labels*sdim; M.Cg = q; q += 2*labels*sdim; M.G2 = q; q += labels*sdim; M.Lid = q;
-    return TSBA_OK;
-}
-// bound of an interior's length in pose blocks (bandp_part: the device partitions the FREE poses -- at most n_kf -- into at most band_parts interiors of at
-// least 2 B + 2 blocks; where it has to take fewer interiors they stay below twice that)
-static int sv_lmax_of(int n_kf, int B, int P) { return std::max(n_kf/std::max(1, P) + 2, 5*B + 8); }
-static int sv_lmax(const Ctx *c) { return sv_lmax_of(c->n_kf, std::max(6, c->cur_bw_rows)/6, c->band_parts); }
-static void launch_sv_prepare(Ctx *c, double *xreset) {
-    const int bwp = std::max(6, c->cur_bw_rows), P = c->band_parts, mmax = cr_mmax(0, P, 0);
-    if (mmax > 0) LAUNCHK(k_sv_linv, dim3(mmax), dim3(SV_LT), sv_linv_lds_doubles(bwp)*sizeof(double), c->stream, c->W, bwp, P, (const double *)c->CRfac, (const double *)c->Ssep, c->sv, xreset);
-    c->sv_prepared = true;
-}
-static void launch_sv_solve(Ctx *c, const double *r, double rs, const double *rdot = nullptr, double *rz_part = nullptr, SvUpd upd = SvUpd{0, 0, 0, 0}) {
-    Work &W = c->W; const MsBuf &M = c->sv;
-    const int bwp = std::max(6, c->cur_bw_rows), P = c->band_parts, B = bwp/6, lmax = sv_lmax(c);
-    Work &Ws = c->Wsep; Ws.st = W.st;
-    const size_t ldf = sv_fwd_lds_doubles(B)*sizeof(double), ldb = sv_back_lds_doubles(B, lmax)*sizeof(double);
-    const int mmax = cr_mmax(0, P, 0);
-    auto pivots = [&](int h) { const int klast = (mmax - 1 - h)/(2*h); return mmax - 1 - h < 0 ? 0 : std::max(0, klast + 1); };
-    int htop = 0;
-    for (int h = 1; h < mmax; h <<= 1) if (pivots(h) > 0) htop = h;
-    // the highest level has one pivot (3 h >= 2 h >= the number of separators): its forward step, the root and its back substitution are one workgroup's work
-    const bool fuse_top = htop > 0 && pivots(htop) == 1;
-    const bool tb_fits = B <= 10 ? grid_resident(c, (const void *)k_sv_tree_back<1>, SV_T, ldb, P) : grid_resident(c, (const void *)k_sv_tree_back<2>, SV_T, ldb, P);
-    const int tree = fuse_top && !(c->dbg.sv_per_level & 1) && grid_resident(c, (const void *)k_sv_cre_tree, SV_CT, 0, mmax - 1);           // the whole tree in one launch (k_sv_cre_tree): its workgroups poll each other
-    if (B <= 10) LAUNCHK(k_sv_fwd_int<1>, dim3(P), dim3(SV_T), ldf, c->stream, W, bwp, P, (const double *)c->Lcol, (const double *)c->Lb, r, rs, M, tree, upd);
-    else LAUNCHK(k_sv_fwd_int<2>, dim3(P), dim3(SV_T), ldf, c->stream, W, bwp, P, (const double *)c->Lcol, (const double *)c->Lb, r, rs, M, tree, upd);
-    const bool tree_back = tree && !(c->dbg.sv_per_level & 8) && tb_fits;        // ... and the interiors' back substitution in the tree's launch (k_sv_tree_back)
-    if (tree_back) {
-        if (B <= 10) LAUNCHK(k_sv_tree_back<1>, dim3(P), dim3(SV_T), ldb, c->stream, W, bwp, P, htop, lmax, (const double *)c->Lcol, (const double *)c->Lb, M, rdot, rz_part);
-        else LAUNCHK(k_sv_tree_back<2>, dim3(P), dim3(SV_T), ldb, c->stream, W, bwp, P, htop, lmax, (const double *)c->Lcol, (const double *)c->Lb, M, rdot, rz_part);
-        return; }
-    if (tree) LAUNCHK(k_sv_cre_tree, dim3(mmax - 1), dim3(SV_CT), 0, c->stream, W, Ws, bwp, P, htop, M);
-    else {
-        for (int h = 1; h <= htop; h <<= 1) { const int npiv = pivots(h); if (npiv <= 0 || (fuse_top && h == htop)) continue;
-            LAUNCHK(k_sv_cre_fwd, dim3(npiv), dim3(SV_CT), 0, c->stream, W, Ws, bwp, P, h, 0, M); }
-        if (fuse_top) LAUNCHK(k_sv_cre_top, dim3(1), dim3(SV_CT), 0, c->stream, W, Ws, bwp, P, htop, M);
-        else LAUNCHK(k_sv_cre_root, dim3(1), dim3(SV_CT), 0, c->stream, W, bwp, P, M);
-        for (int h = htop; h >= 1; h >>= 1) { const int npiv = pivots(h);
-            if (npiv > 0 && !(fuse_top && h == htop)) LAUNCHK(k_sv_cre_back, dim3(npiv), dim3(SV_CT), 0, c->stream, W, Ws, bwp, P, h, 0, M); }
-    }
-    if (B <= 10) LAUNCHK(k_sv_back_int<1>, dim3(P), dim3(SV_T), ldb, c->stream, W, bwp, P, lmax, (const double *)c->Lcol, (const double *)c->Lb, M, rdot, rz_part);
-    else LAUNCHK(k_sv_back_int<2>, dim3(P), dim3(SV_T), ldb, c->stream, W, bwp, P, lmax, (const double *)c->Lcol, (const double *)c->Lb, M, rdot, rz_part);
-}
-
-// The reduced system of one LM trial: a direct solve, or -- band + long-range blocks -- conjugate gradients preconditioned with the band
-// solver (tsba_pcg.h).  The host enqueues iteration k only once the device has reached iteration k - 2 (pinned progress word), so a solve
-// that converges wastes two iterations of empty launches; every rank of a sharded run iterates on its own copy of the summed system.
-static bool pcg_finished(const Ctx *c, unsigned int seq, int it) {      // true: the device reported convergence (or the end of the pass); else waits until it is within two iterations of `it`
-    if (!c->hprog || it < 2) return false;
-    const auto tw = std::chrono::steady_clock::now();
-    for (int spin = 0;; spin++) {
-        const unsigned long long w = ((volatile unsigned long long *)c->hprog)[1];
-        if ((unsigned int)(w >> 32) == seq) { if (w & 1) return true; if ((int)((w & 0xffffffffu) >> 1) + 2 >= it) return false; }
-        PlanPool::cpu_relax();
-        if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - tw > std::chrono::seconds(5)) return false;      // never hang on it
-    }
-}
-static void launch_solve_full(Ctx *c, const LevelDev &D) {
-    launch_solve(c);
-    if (D.far_B <= 0) return;
-    Work &W = c->W;
-    const int nbp = c->pcg_parts, B = std::max(6, c->cur_bw_rows)/6;
-    const int nmv = (c->n_kf + PCG_MW - 1)/PCG_MW, pq_off = 3*nbp + 8;          // the matvec's workgroups (a wave per keyframe) and where their partial p.q go (nmv <= 2 nbp)
-    const int cap = c->dbg.pcg_max_it > 0 ? c->dbg.pcg_max_it : 200;
-    const double tol = c->dbg.pcg_tol_exp > 0 ? pow(10.0, -(double)c->dbg.pcg_tol_exp) : 1e-10, tol2 = tol*tol;
-    const unsigned int seq = ++c->pcg_seq;
-    // the inverse factors of the separators (k_sv_linv), once per factorisation: the single-vector solve phase and the product form of the many-column one use them
-    const bool svok = ms_available(c) && c->dbg.pcg_refactor != 1 && sv_reserve(c) == TSBA_OK;       // (pcg_refactor = 3: as 0 with r.z by its own kernel, for A/B runs)
-    if (svok && !c->sv_prepared) launch_sv_prepare(c, nullptr);       // (the direct solve of a chain has run it already: its back substitution uses the same products)
-    // Enlarged conjugate gradients on the many-column solve phase of the band solver (ECG_T columns per application of M^-1): an option (pcg_block = 2).
-    // It halves the iterations where the coupling outside the band is a few hundred blocks (outlying eigenvalues, captured 32 at a time), but an
-    // application costs 0.8 ms at 5000 keyframes against 0.13 ms of the single-vector solve phase (tsba_bandsv.h) -- measured when the single-vector
-    // iteration still re-ran the factorisation (0.57 ms), ms per solve single / enlarged: two loop closures 410 / 303, 1 % long-range points 247 / 320
-    const bool want_block = c->dbg.pcg_block == 2;
-    if (ms_available(c) && want_block && ms_reserve(c, std::max(ECG_T, c->ms_cap)) == TSBA_OK) {
-        const int nch = (c->n_kf + ECG_CH - 1)/ECG_CH; const size_t n6 = (size_t)W.N;
-        const size_t need = (2*n6*ECG_T + (size_t)nch*2*(ECG_T*ECG_T + 1) + 4*(size_t)ECG_T*ECG_T + 4*ECG_T + 16)*sizeof(double);
-        bool ok = true;
-        if (need > c->ecg_bytes) { if (c->ecg_alloc) { hipStreamSynchronize(c->stream); hipFree(c->ecg_alloc); } c->ecg_alloc = nullptr; c->ecg_bytes = 0;
-            ok = hipMalloc((void **)&c->ecg_alloc, need) == hipSuccess; if (ok) c->ecg_bytes = need; }
-        if (ok) {
-            EcgBuf &E = c->ecg; double *q = c->ecg_alloc;
-            E.P = q; q += n6*ECG_T; E.Q = q; q += n6*ECG_T; E.part = q; q += (size_t)nch*2*(ECG_T*ECG_T + 1); E.Cm = q; q += ECG_T*ECG_T; E.Lm = q; q += ECG_T*ECG_T + ECG_T;
-            E.Y = q; q += ECG_T*ECG_T; E.y1 = q; q += ECG_T; E.scal = q; E.nchunk = nch;
-            const int Tk = c->ms.T; c->ms.T = ECG_T; const MsBuf M = c->ms;
-            LAUNCHK(k_ecg_begin, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, M);
-            launch_ms_solve(c, svok);
-            LAUNCHK(k_ecg_gram, dim3(nch), dim3(256), 0, c->stream, W, (const double *)M.X, (const double *)M.X, (const double *)nullptr, (const double *)M.R, (const double *)M.X, E);
-            LAUNCHK(k_ecg_small, dim3(1), dim3(1024), 0, c->stream, W, E, 0, 0, seq, tol2);
-            LAUNCHK(k_ecg_update, dim3(nbp), dim3(256), 0, c->stream, W, M, E, 2, 1);
-            int it = 0;
-            for (; it < cap; it++) {
-                if (pcg_finished(c, seq, it)) break;
-                LAUNCHK(k_ecg_matvec, dim3(nbp), dim3(256), 0, c->stream, W, D, B, E);
-                LAUNCHK(k_ecg_gram, dim3(nch), dim3(256), 0, c->stream, W, (const double *)E.P, (const double *)E.Q, (const double *)M.R, (const double *)nullptr, (const double *)nullptr, E);
-                LAUNCHK(k_ecg_small, dim3(1), dim3(1024), 0, c->stream, W, E, 1, it, seq, tol2);
-                LAUNCHK(k_ecg_update, dim3(nbp), dim3(256), 0, c->stream, W, M, E, 1, 0);
-                launch_ms_solve(c, svok);
-                LAUNCHK(k_ecg_gram, dim3(nch), dim3(256), 0, c->stream, W, (const double *)E.Q, (const double *)M.X, (const double *)nullptr, (const double *)M.R, (const double *)M.X, E);
-                LAUNCHK(k_ecg_small, dim3(1), dim3(1024), 0, c->stream, W, E, 2, it, seq, tol2);
-                LAUNCHK(k_ecg_update, dim3(nbp), dim3(256), 0, c->stream, W, M, E, 2, 0);
-            }
-            LAUNCHK(k_ecg_finish, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, it);
-            c->ms.T = Tk;
-            return;
-        }
-    }
-    // Loop closures (E touches a few dozen keyframes): the band solve corrected by the low-rank part exactly (tsba_wb.h) is the preconditioner --
-    // set up once per trial (one solve phase with k columns, the k x k matrix), then a band solve and a k x k Cholesky per application
-    bool wb = D.n_wb > 0 && ms_available(c) && c->dbg.far_solver != 3 && ms_reserve(c, std::max(6*D.n_wb, c->ms_cap)) == TSBA_OK;
-    const int kk = 6*D.n_wb;
-    if (wb) {
-        const size_t need = (3*(size_t)kk*kk + 2*(size_t)kk + (size_t)W.N + ((size_t)kk + 1)*kk + 4*(size_t)kk + 64 + 2*(size_t)D.n_wb + 16)*sizeof(double);
-        if (need > c->wb_bytes) { if (c->wb_alloc) { hipStreamSynchronize(c->stream); hipFree(c->wb_alloc); } c->wb_alloc = nullptr; c->wb_bytes = 0;
-            if (hipMalloc((void **)&c->wb_alloc, need) == hipSuccess) c->wb_bytes = need; else wb = false; }
-    }
-    double *K2 = nullptr;
-    if (wb) {
-        WbBuf &Bw = c->wb; double *q = c->wb_alloc;
-        Bw.k = kk; Bw.n_u = D.n_wb; Bw.wb_kf = D.wb_kf; Bw.wb_idx = D.wb_idx;
-        Bw.Gm = q; q += (size_t)kk*kk; Bw.T1 = q; q += (size_t)kk*kk; K2 = q; q += (size_t)kk*kk; Bw.xu = q; q += kk; Bw.vu = q; q += kk; Bw.z = q; q += W.N;
-        Work &Wk = c->Wk; memset(&Wk, 0, sizeof(Wk));
-        Wk.N = kk; Wk.n_kf = D.n_wb; Wk.ldS = kk; Wk.band = 0; Wk.st = W.st;
-        Wk.S = q; q += ((size_t)kk + 1)*kk; Wk.Sy = q; q += kk + 8; Wk.g = q; q += kk; Wk.dp = q; q += kk; Wk.LDbuf = q; q += kk + 8;
-        Wk.fidx = (int *)q; Wk.nfree = Wk.fidx + D.n_wb + 2;
-        const int Tk = c->ms.T; c->ms.T = kk; const MsBuf M = c->ms;
-        LAUNCHK(k_wb_init, dim3(1), dim3(64), 0, c->stream, Wk.fidx, Wk.nfree, D.n_wb);
-        LAUNCHK(k_wb_units, dim3(1024), dim3(256), 0, c->stream, W, M, Bw);
-        launch_ms_solve(c, svok);
-        LAUNCHK(k_wb_gather, dim3(std::min(1024, (kk*kk + 255)/256)), dim3(256), 0, c->stream, W, M, Bw);
-        LAUNCHK(k_wb_EG, dim3(D.n_wb), dim3(256), 0, c->stream, W, D, Bw);
-        LAUNCHK(k_wb_K2, dim3(std::min(2048, (kk*kk + 255)/256)), dim3(256), 0, c->stream, W, Bw, K2);
-        c->ms.T = Tk;
-    }
-    bool wb_factored = false;
-    auto correct = [&](const double *yp, double ys) {              // z = M_W^-1 r from y = M^-1 r = ys * yp[]
-        WbBuf &Bw = c->wb; Work &Wk = c->Wk; MsBuf M = c->ms; M.T = kk;
-        LAUNCHK(k_wb_rhs, dim3(1), dim3(512), 0, c->stream, W, Bw, yp, ys, Wk.g);
-        if (!wb_factored) {                                        // once per LM trial: the k x k factor (in place, over a copy), with this right-hand side riding along
-            hipMemcpyAsync(Wk.S, K2, sizeof(double)*(size_t)kk*kk, hipMemcpyDeviceToDevice, c->stream);
-            launch_dense_chol(c, Wk, kk); wb_factored = true;
-        } else {                                                   // later applications: the two substitutions on that factor (0.28 ms of factorisation each before)
-            const int lds_bs = (CH_NB*(CH_NB + 1) + 2*CH_NB + 8*CH_NB)*(int)sizeof(double);
-            LAUNCHK(k_chol_rhs, dim3((kk + 255)/256), dim3(256), 0, c->stream, Wk);
-            LAUNCHK(k_chol_fwd, dim3(1), dim3(1024), lds_bs, c->stream, Wk, kk);
-            LAUNCHK(k_chol_backsub, dim3(1), dim3(1024), lds_bs, c->stream, Wk, kk);
-        }
-        LAUNCHK(k_wb_Gw, dim3(1), dim3(512), 0, c->stream, W, Bw, (const double *)Wk.dp);
-        LAUNCHK(k_wb_Ex, dim3(D.n_wb), dim3(64), 0, c->stream, W, D, Bw, (const double *)Bw.xu);
-        LAUNCHK(k_wb_apply, dim3(512), dim3(256), 0, c->stream, W, M, Bw, yp, ys);
-    };
-    if (wb) { correct(W.Sy, -1.0); LAUNCHK(k_pcg_begin, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, (const double *)c->wb.z, 1.0); }
-    else LAUNCHK(k_pcg_begin, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, (const double *)W.Sy, -1.0);
-    if (wb) LAUNCHK(k_pcg_rcheck, dim3(1), dim3(64), 0, c->stream, W, -1, nbp, 0.0);
-    // M^-1 on the residual: the solve phase of the partitioned band solver on the factor this trial's first solve left (tsba_bandms.h); where
-    // that is not available (a single interior, the sequential separator solve) the factorisation is run again with the residual as right-hand side
-    // (measured at 5000 keyframes, one column: 1.3 ms per application against 0.57 ms for the factorisation re-run -- the solve phase pays for 64
-    // columns whether it has them or not; it is the default only for the block variants.  pcg_refactor = 2 selects it for the single-vector iteration)
-    const bool ms = !wb && ms_available(c) && c->dbg.pcg_refactor == 2 && ms_reserve(c, std::max(1, c->ms_cap)) == TSBA_OK;
-    const bool sv = !ms && svok && (c->dbg.pcg_refactor == 0 || c->dbg.pcg_refactor == 3);      // (the single-vector solve phase, tsba_bandsv.h: the default)
-    const bool fused_dot = sv && !wb && c->band_parts <= 144 && c->dbg.pcg_refactor == 0; const int rz2_off = 5*nbp + 16;
-    const double *zp = wb ? c->wb.z : W.Sy; double zs = wb ? 1.0 : -1.0;
-    int it = 0;
-    for (; it < cap; it++) {
-        if (pcg_finished(c, seq, it)) break;
-        LAUNCHK(k_pcg_matvec, dim3(nmv), dim3(64*PCG_MW), 0, c->stream, W, D, it, seq, B, tol2, (it > 0 && fused_dot) ? rz2_off : 0, (it > 0 && fused_dot) ? c->band_parts : nbp, pq_off, zp, zs);
-        if (ms) { LAUNCHK(k_pcg_update, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, it, nbp, pq_off, nmv, c->ms.R, 1.0);
-            const int Tk = c->ms.T; c->ms.T = 1; launch_ms_solve(c, svok); c->ms.T = Tk; zp = c->ms.X; zs = 1.0; }
-        else if (sv && fused_dot && !(c->dbg.sv_per_level & 4)) {      // the iteration's update step (alpha; x, r) inside the first kernel of the preconditioner application
-            launch_sv_solve(c, W.pc_r, 1.0, W.pc_r, W.pc_part + rz2_off, SvUpd{1, it, nmv, pq_off});
-            zp = c->sv.X; zs = 1.0; }
-        else if (sv) { LAUNCHK(k_pcg_update, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, it, nbp, pq_off, nmv, c->sv.R, 1.0);
-            if (wb) LAUNCHK(k_pcg_rcheck, dim3(1), dim3(64), 0, c->stream, W, it, nbp, 1e-20);      // |r| <= 1e-10 |b|
-            if (fused_dot) launch_sv_solve(c, c->sv.R, 1.0, c->sv.R, W.pc_part + rz2_off);      // (r.z comes along: no k_pcg_dot)
-            else launch_sv_solve(c, c->sv.R, 1.0);
-            zp = c->sv.X; zs = 1.0;
-            if (wb) { correct(c->sv.X, 1.0); zp = c->wb.z; } }
-        else { LAUNCHK(k_pcg_update, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, it, nbp, pq_off, nmv, W.g, -1.0);
-            if (wb) LAUNCHK(k_pcg_rcheck, dim3(1), dim3(64), 0, c->stream, W, it, nbp, 1e-20);      // |r| <= 1e-10 |b|
-            launch_solve(c);
-            if (wb) { correct(W.Sy, -1.0); zp = c->wb.z; zs = 1.0; } }
-        if (!fused_dot) LAUNCHK(k_pcg_dot, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, zp, zs);
-    }
-    LAUNCHK(k_pcg_finish, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, it);
-}
+#include "tsba_solve_launch.h"      // what a trial's reduced-system solve enqueues: launch_solve, the solve phases, launch_solve_full
 
 // a trial's decision is taken by the NEXT trial's k_schur_t (the last trial's by k_decide after the loop, or -- window_pass, decision_in_mid -- by a workgroup of k_pass_end): windows on one GPU without blocks outside the band
 static bool fused_decisions(const Ctx *c, const LevelDev &D) { return c->W.st_next != nullptr && D.far_B <= 0; }

@@ -85,6 +85,16 @@ __device__ __noinline__ int4 bandp_part_call(const int *nfree, int ring, int rin
 }
 // separator labels run below this bound (pool, slots and solution are indexed by label)
 __device__ __host__ __forceinline__ int cr_mmax(int ring, int Pmax, int Gmax) { return ring ? (Pmax > Gmax ? RING_OFF : 0) + Gmax + 1 : Pmax - 1; }
+// Host: the pivots of cyclic-reduction level h >= 1 among the labels lab0 .. mmax - 1 are the odd multiples (2 k + 1) h, k = *kb .. *kb + n - 1; returns n.
+// lab0: the lowest separator label (0 on a chain and on a ring without a tail; a ring's tail counts down from RING_OFF).
+// The guard is for h > mmax - 1, where the truncating division would give k = 0 a pivot: the solve phases walk h < mmax of a chain that may have
+// no separator at all (mmax <= 1).  The factorisation's levels never get there -- a chain has h < mmax, a ring h < G = mmax - 1, a ring with a
+// tail h < max(G, RING_OFF) < RING_OFF + G = mmax - 1 -- so guarded and unguarded forms agree for it.
+static inline int cr_level_pivots(int mmax, int h, int lab0, int *kb) {
+    *kb = lab0/(2*h);
+    const int n = mmax - 1 - h < 0 ? 0 : (mmax - 1 - h)/(2*h) - *kb + 1;
+    return n > 0 ? n : 0;
+}
 static size_t bandp_lds_doubles(int bw, int cb) {               // window + border rows + rhs row, LD table, scratch
     const int rows = 6*cb + 2*bw;
     return (size_t)rowoff(rows + 2) + 16 + (size_t)SOLVE_LD*((6*cb + bw)/6) + 36*BANDP_PW + 8 + 64;
