@@ -8,6 +8,8 @@
  *   tool::GetBoxAllPixs                 /root/reference/src/tool.cc:1264-1337     -> tsframe_box_pixels
  *   tracking::TextJudgeSingle (xn)      /root/reference/src/tracking.cc:1991-2131 -> tsframe_text_judge
  *   tracking::TrackNewTextFeat          /root/reference/src/tracking.cc:1752-1785 -> tsframe_klt_track
+ *   mapText::GetObjectInfo              src/mapText.cc:64-107 (tool::CalTextinfo src/tool.cc:1178-1262, CalNormvec :1342-1355,
+ *                                       GetBoxAllPixs :1264-1337; callers src/tracking.cc:932-957 and InitialLandmarker) -> tsframe_text_object_info
  * The pyramid stays resident in HBM: tsframe_level_ptr hands the device pointers to the BA library, so the four levels of a
  * keyframe need no host round trip between GetPyrMat and the photometric residuals.
  * All functions return 0 on success, a negative TSFRAME_ERR_* otherwise; tsframe_last_error gives the text. */
@@ -119,6 +121,38 @@ int tsframe_klt_track(void *prev_ctx, void *cur_ctx, int n, const float *prev_xy
  * or outside [3, 31], max_level outside [0, 7], max_iter outside [1, 100], eps < 0, too few resident levels.  TSFRAME_ERR_STATE: a context
  * without an image.  n == 0 launches nothing.  The points and the results travel through cur_ctx's pinned staging block and stream: the
  * previous frame's context must stay alive (and keep its image) until the call returns. */
+
+/* mapText::GetObjectInfo (src/mapText.cc:64-107) for the n_obj new text objects of a keyframe on the resident pyramid of this context
+ * (the reference keyframe), ONE launch, one workgroup per (object, level).  L = the context's n_levels.
+ * In: quad = vTextDete (level-0 corners); the corners of level l are quad[k]*inv_scale[l] (one fp64 product, mapText.cc:78-81).  The features
+ * (vRefFeature) are laid out as tsframe_pyramid_pts_batch writes them: object i owns the elements [feat_off[i]*L, feat_off[i+1]*L) of u, v, inten,
+ * ninten, in (and eight times that of inten8 / ninten8), level l of it is [level_off[i][l], level_off[i][l+1]) behind that base; what lies past
+ * level_off[i][L] in a slice is neither read nor written.
+ * Per (object, level): tool::CalTextinfo (src/tool.cc:1178-1262) -- corner truncation (cv::Point), the clamped bounding box and cv::fillPoly as in
+ * tsframe_box_pixels; musigma[i][l] = {mu, sigma} from the integer histogram of the masked pixels (mu is exact; sigma is the sample deviation, n - 1).
+ * ok[i][l] = 1 with at least 2 pixels and sigma != 0; fewer than 2 pixels give mu = sigma = 0, a constant region keeps its mu with sigma = 0.
+ * tool::CalNormvec (src/tool.cc:1342-1355) on the level's features: inten8 / ninten8 / in are what tsframe_neighbours gives with that mu, sigma, bit for
+ * bit, and ninten = (inten - mu) / sigma (featureNInten).  With ok = 0 (CalNormvec returns false) the raw inten8 and in are still written, ninten and
+ * ninten8 are 0.0.
+ * Level 0 additionally, tool::GetBoxAllPixs (src/tool.cc:1264-1337) on the same mask: object i's pixels are [pix_off[i], pix_off[i+1]) of pix_u, pix_v,
+ * pix_inten, pix_ninten, exactly what tsframe_box_pixels(level 0) writes for that quad with mu, sigma of level 0 (pix_ninten = 0.0 with ok = 0).
+ * pix_off is always complete.  pix_cap = capacity of the four pixel arrays; pix_cap == 0 only counts (they may be NULL); a total above pix_cap:
+ * TSFRAME_ERR_ARG with pix_off complete, the pixel arrays untouched and every other output written.  The sum of the clamped level-0 box areas bounds
+ * the total, so one call suffices.
+ * n_obj == 0 returns TSFRAME_OK without reading any pointer.  TSFRAME_ERR_ARG (tsframe_last_error names this function and, where it applies, the
+ * object), checked before anything is launched or any output touched: a NULL pointer where data is needed, n_obj < 0, pix_cap < 0, feat_off[0] != 0
+ * or a decreasing feat_off, a level_off row that does not start at 0, decreases or ends above (feat_off[i+1] - feat_off[i])*L, a corner, inv_scale
+ * or scaled corner that is not finite or >= 1e9 in magnitude, a non-finite u / v, an image wider than 307200 pixels.  TSFRAME_ERR_STATE: no image
+ * set.  The inputs go up as one block through the pinned staging, the results come back through it; the resident planes are left unchanged. */
+int tsframe_text_object_info(void *ctx, int n_obj,
+    const double *quad        /*[n_obj][4][2] vTextDete: level-0 corners*/,
+    const double *inv_scale   /*[L], L = the context's n_levels*/,
+    const int32_t *feat_off   /*[n_obj + 1]*/, const int32_t *level_off /*[n_obj][L + 1]*/,
+    const double *u, const double *v, const double *inten,   /* vRefFeature, laid out as tsframe_pyramid_pts_batch writes it */
+    int pix_cap,
+    double *musigma /*[n_obj][L][2]*/, uint8_t *ok /*[n_obj][L]*/,
+    double *ninten  /* featureNInten, layout of inten */, double *inten8, double *ninten8 /* [..][8], same feature index */, uint8_t *in,
+    int32_t *pix_off /*[n_obj + 1]*/, int32_t *pix_u, int32_t *pix_v, double *pix_inten, double *pix_ninten);
 
 #ifdef __cplusplus
 }

@@ -339,6 +339,7 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
 
 #include "tsklt.h"
 #include "tspts.h"
+#include "tsobj.h"
 
 static int ensure_host(FCtx *c, size_t bytes) {
     if (bytes <= c->h_cap) return 0;
@@ -746,6 +747,133 @@ int tsframe_klt_track(void *prev_ctx, void *cur_ctx, int n, const float *prev_xy
     CKF(hipMemcpyAsync(h + o_out, d + o_out, tot - o_out, hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream));
     memcpy(next_xy, h + o_out, 8*(size_t)n); memcpy(status, h + o_st, (size_t)n);
+    return TSFRAME_OK;
+}
+
+int tsframe_text_object_info(void *ctx, int n_obj, const double *quad, const double *inv_scale, const int32_t *feat_off, const int32_t *level_off,
+                             const double *u, const double *v, const double *inten, int pix_cap,
+                             double *musigma, uint8_t *ok, double *ninten, double *inten8, double *ninten8, uint8_t *in,
+                             int32_t *pix_off, int32_t *pix_u, int32_t *pix_v, double *pix_inten, double *pix_ninten) {
+    FCtx *c = (FCtx *)ctx;
+    if (!c) return TSFRAME_ERR_ARG;
+    auto bad = [&](const std::string &what) { c->err = "tsframe_text_object_info: " + what; return TSFRAME_ERR_ARG; };
+    auto at_obj = [](const char *what, int i) { return std::string(what) + " (object " + std::to_string(i) + ")"; };
+    if (n_obj < 0) return bad("n_obj < 0");
+    if (n_obj == 0) return TSFRAME_OK;
+    if (!quad || !inv_scale || !feat_off || !level_off || !musigma || !ok || !pix_off) return bad("NULL quad / inv_scale / feat_off / level_off / musigma / ok / pix_off");
+    if (pix_cap < 0) return bad("pix_cap < 0");
+    if (pix_cap > 0 && (!pix_u || !pix_v || !pix_inten || !pix_ninten)) return bad("NULL pixel array with pix_cap > 0");
+    if (c->n_levels == 0) { c->err = "tsframe_text_object_info: no image set"; return TSFRAME_ERR_STATE; }
+    const int L = c->n_levels;
+    if ((size_t)c->w[0] > (size_t)MS_MASK_WORDS*32) return bad("the image is wider than one band of the quad mask");
+    auto wild = [](double x) { return !(fabs(x) < 1e9); };       // (NaN and infinities included)
+    for (int l = 0; l < L; l++) if (wild(inv_scale[l])) return bad("inv_scale not finite or >= 1e9 in magnitude");
+    if (feat_off[0] != 0) return bad("feat_off[0] != 0");
+    size_t nfeat = 0;                                            // the packed features: object i's [0, level_off[i][L]) only
+    for (int i = 0; i < n_obj; i++) {
+        if (feat_off[i + 1] < feat_off[i]) return bad(at_obj("feat_off decreasing", i));
+        const int32_t *lo = level_off + (size_t)i*(L + 1);
+        if (lo[0] != 0) return bad(at_obj("level_off row does not start at 0", i));
+        for (int l = 0; l < L; l++) if (lo[l + 1] < lo[l]) return bad(at_obj("level_off decreasing", i));
+        if ((long long)lo[L] > (long long)(feat_off[i + 1] - feat_off[i])*L) return bad(at_obj("level_off ends above the object's slice", i));
+        for (int k = 0; k < 8; k++) {
+            if (wild(quad[8*(size_t)i + k])) return bad(at_obj("corner not finite or >= 1e9 in magnitude", i));
+            for (int l = 0; l < L; l++) if (wild(quad[8*(size_t)i + k]*inv_scale[l])) return bad(at_obj("scaled corner >= 1e9 in magnitude", i));
+        }
+        nfeat += (size_t)lo[L];
+    }
+    if ((size_t)feat_off[n_obj] > (size_t)(INT32_MAX / L) || nfeat > (size_t)(INT32_MAX / 8)) return bad("too many features");
+    if (nfeat > 0 && (!u || !v || !inten || !ninten || !inten8 || !ninten8 || !in)) return bad("NULL feature array with features");
+    for (int i = 0; i < n_obj; i++) {
+        const size_t b = (size_t)feat_off[i]*L, m = (size_t)level_off[(size_t)i*(L + 1) + L];
+        for (size_t k = b; k < b + m; k++) if (!std::isfinite(u[k]) || !std::isfinite(v[k])) return bad(at_obj("u / v not finite", i));
+    }
+    // jobs: one per (object, level); the corners are quad * inv_scale[l] (mapText.cc:78-81), truncated and boxed statement by statement as tool.cc:1269-1298
+    std::vector<ObjJob> jobs((size_t)n_obj*L);
+    std::vector<size_t> fbase((size_t)n_obj + 1, 0), pbase((size_t)n_obj + 1, 0);
+    const bool want_pix = pix_cap > 0;
+    for (int i = 0; i < n_obj; i++) {
+        const int32_t *lo = level_off + (size_t)i*(L + 1);
+        for (int l = 0; l < L; l++) {
+            ObjJob &J = jobs[(size_t)i*L + l];
+            const int w = c->w[l], h = c->h[l];
+            int xMin = w + 1, xMax = -1, yMin = h + 1, yMax = -1;
+            for (int k = 0; k < 4; k++) {
+                const double x = quad[8*(size_t)i + 2*k]*inv_scale[l], y = quad[8*(size_t)i + 2*k + 1]*inv_scale[l];
+                J.xy[2*k] = (int)x; J.xy[2*k + 1] = (int)y;
+                if (x > xMax) xMax = (int)ceil(x);
+                if (x < xMin) xMin = (int)floor(x);
+                if (y > yMax) yMax = (int)ceil(y);
+                if (y < yMin) yMin = (int)floor(y);
+            }
+            if (xMin < 0) xMin = 0;
+            if (xMin >= w) xMin = w - 1;
+            if (yMin < 0) yMin = 0;
+            if (yMin >= h) yMin = h - 1;
+            if (xMax >= w) xMax = w - 1;
+            if (xMax < 0) xMax = 0;
+            if (yMax >= h) yMax = h - 1;
+            if (yMax < 0) yMax = 0;
+            J.img = c->plane[TSFRAME_IMG][l]; J.w = w; J.h = h;
+            J.x0 = xMin; J.x1 = xMax; J.y0 = yMin; J.y1 = yMax;
+            J.f0 = (int)(fbase[i] + (size_t)lo[l]); J.nf = lo[l + 1] - lo[l];
+            J.pix0 = -1;
+            if (l == 0) {
+                const size_t area = (xMax >= xMin && yMax >= yMin) ? (size_t)(xMax - xMin + 1)*(size_t)(yMax - yMin + 1) : 0;
+                if (want_pix) J.pix0 = (long long)pbase[i];
+                pbase[i + 1] = pbase[i] + area;
+            }
+        }
+        fbase[i + 1] = fbase[i] + (size_t)lo[L];
+    }
+    const size_t nreg = want_pix ? pbase[n_obj] : 0;             // slots of the pixel regions (the sum of the clamped level-0 boxes)
+    hipSetDevice(c->device);
+    // one block, inputs then outputs: jobs | u | v | inten || out | ninten | inten8 | ninten8 | in | pix_u | pix_v | pix_inten | pix_ninten
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nj = jobs.size();
+    const size_t o_u = al(sizeof(ObjJob)*nj), o_v = o_u + al(8*nfeat), o_I = o_v + al(8*nfeat), o_out = o_I + al(8*nfeat), o_n = o_out + al(sizeof(ObjOut)*nj),
+                 o_i8 = o_n + al(8*nfeat), o_n8 = o_i8 + al(64*nfeat), o_in = o_n8 + al(64*nfeat), o_pu = o_in + al(nfeat), o_pv = o_pu + al(4*nreg),
+                 o_pI = o_pv + al(4*nreg), o_pN = o_pI + al(8*nreg), tot = o_pN + al(8*nreg);
+    int rc = ensure_work(c, tot); if (rc) return rc;
+    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    uint8_t *h = c->h_stage, *d = c->d_work;
+    memcpy(h, jobs.data(), sizeof(ObjJob)*nj);
+    for (int i = 0; i < n_obj; i++) {
+        const size_t b = (size_t)feat_off[i]*L, m = fbase[i + 1] - fbase[i];
+        if (!m) continue;
+        memcpy(h + o_u + 8*fbase[i], u + b, 8*m); memcpy(h + o_v + 8*fbase[i], v + b, 8*m); memcpy(h + o_I + 8*fbase[i], inten + b, 8*m);
+    }
+    CKF(hipMemcpyAsync(d, h, o_out, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_object_info, dim3((unsigned)nj), dim3(OBJ_NT), 0, c->stream, (const ObjJob *)d, (const double *)(d + o_u), (const double *)(d + o_v),
+                       (const double *)(d + o_I), (ObjOut *)(d + o_out), (double *)(d + o_n), (double *)(d + o_i8), (double *)(d + o_n8), d + o_in,
+                       (int *)(d + o_pu), (int *)(d + o_pv), (double *)(d + o_pI), (double *)(d + o_pN));
+    CKF(hipGetLastError());
+    CKF(hipMemcpyAsync(h + o_out, d + o_out, (want_pix ? tot : o_pu) - o_out, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipStreamSynchronize(c->stream));
+    const ObjOut *ho = (const ObjOut *)(h + o_out);
+    long long total = 0;
+    pix_off[0] = 0;
+    for (int i = 0; i < n_obj; i++) {
+        for (int l = 0; l < L; l++) {
+            const ObjOut &o = ho[(size_t)i*L + l];
+            musigma[2*((size_t)i*L + l)] = o.mu; musigma[2*((size_t)i*L + l) + 1] = o.sigma; ok[(size_t)i*L + l] = (uint8_t)o.ok;
+        }
+        const size_t b = (size_t)feat_off[i]*L, m = fbase[i + 1] - fbase[i];
+        if (m) {
+            memcpy(ninten + b, h + o_n + 8*fbase[i], 8*m); memcpy(inten8 + 8*b, h + o_i8 + 64*fbase[i], 64*m);
+            memcpy(ninten8 + 8*b, h + o_n8 + 64*fbase[i], 64*m); memcpy(in + b, h + o_in + fbase[i], m);
+        }
+        total += std::min((long long)ho[(size_t)i*L].npix, (long long)(pbase[i + 1] - pbase[i]));
+        pix_off[i + 1] = (int32_t)std::min(total, (long long)INT32_MAX);
+    }
+    if (pix_cap == 0) return TSFRAME_OK;                         // count only
+    if (total > (long long)pix_cap) return bad("pix_cap too small (pix_off holds the counts)");
+    for (int i = 0; i < n_obj; i++) {                            // close the gaps between the regions
+        const size_t src = pbase[i], dst = (size_t)pix_off[i], m = (size_t)(pix_off[i + 1] - pix_off[i]);
+        if (!m) continue;
+        memcpy(pix_u + dst, h + o_pu + 4*src, 4*m); memcpy(pix_v + dst, h + o_pv + 4*src, 4*m);
+        memcpy(pix_inten + dst, h + o_pI + 8*src, 8*m); memcpy(pix_ninten + dst, h + o_pN + 8*src, 8*m);
+    }
     return TSFRAME_OK;
 }
 

@@ -7,6 +7,7 @@
   Frame.GetBoxAllPixs(level, vTextDete, mu, std, K)   tool::GetBoxAllPixs       /root/reference/src/tool.cc:1264-1337
   Frame.TextJudgeBatch(...)                           tracking::TextJudgeSingle /root/reference/src/tracking.cc:1991-2131 (n planes, one launch)
   Frame.TrackKLT(prev_frame, pts, ...)                tracking::TrackNewTextFeat /root/reference/src/tracking.cc:1752-1785 (all points, one launch)
+  Frame.GetObjectInfoBatch(quads, inv_scale, feats)   mapText::GetObjectInfo    src/mapText.cc:64-107 (all new objects, one launch)
 
 No CPU fallback: without the HIP library / a GPU every call raises.
 """
@@ -18,7 +19,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libtsframe.so")
 EXPORTED_SYMBOLS = ["tsframe_create", "tsframe_destroy", "tsframe_last_error", "tsframe_set_image", "tsframe_level_size", "tsframe_level_ptr",
-                    "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_pyramid_pts_batch", "tsframe_neighbours", "tsframe_box_pixels", "tsframe_text_judge", "tsframe_klt_track"]
+                    "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_pyramid_pts_batch", "tsframe_neighbours", "tsframe_box_pixels", "tsframe_text_judge", "tsframe_klt_track",
+                    "tsframe_text_object_info"]
 IMG, GRAD, GRADX, GRADY = 0, 1, 2, 3
 JUDGE_PASS, JUDGE_ORIENT, JUDGE_DEPTH, JUDGE_BOX, JUDGE_ZNCC = 0, 1, 2, 3, 4
 
@@ -58,6 +60,8 @@ def _load():
     L.tsframe_text_judge.restype = C.c_int
     L.tsframe_klt_track.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_float), up]
     L.tsframe_klt_track.restype = C.c_int
+    L.tsframe_text_object_info.argtypes = [vp, C.c_int, dp, dp, ip, ip, dp, dp, dp, C.c_int, dp, up, dp, dp, dp, up, ip, ip, ip, dp, dp]
+    L.tsframe_text_object_info.restype = C.c_int
     return L
 
 
@@ -214,3 +218,46 @@ class Frame:
         self._check(self.lib.tsframe_klt_track(prev_frame.ctx, self.ctx, n, xy.ctypes.data_as(fp), int(win), int(max_level), int(max_iter), float(eps),
                                                float(min_eig), nxt.ctypes.data_as(fp), _up(st)), "tsframe_klt_track")
         return nxt[:n], st[:n]
+
+    def GetObjectInfoBatch(self, quads, vInvScalefactor, feats, K=None):
+        """mapText::GetObjectInfo for every new text object of the keyframe in one launch (include/tsframe.h: tsframe_text_object_info).
+        quads [n, 4, 2] = vTextDete (level-0 corners); feats = one dict per object as GetPyramidPtsBatch returns it (level_off, u, v, inten are read).
+        Returns one dict per object: statistics [L, 2] (mu, sigma), ok [L], and per feature (the order of feats[i]) featureNInten, neighbourInten [m, 8],
+        neighbourNInten [m, 8], IN; vRefPixs = the level-0 box pixels as GetBoxAllPixs returns them (with ray when K = (fx, fy, cx, cy) is given).
+        The pixel capacity is the sum of the clamped level-0 boxes, so one call does it."""
+        nl = self.n_levels
+        q = np.ascontiguousarray(quads, np.float64).reshape(-1, 4, 2); n = len(q); assert len(feats) == n
+        inv = np.ascontiguousarray(vInvScalefactor, np.float64); assert len(inv) == nl
+        if n == 0:
+            return []
+        lo = np.ascontiguousarray([f["level_off"] for f in feats], np.int32).reshape(n, nl + 1)
+        cnt = [int(r[nl]) for r in lo]
+        foff = np.zeros(n + 1, np.int32); foff[1:] = np.cumsum([(c + nl - 1)//nl for c in cnt])      # the smallest slices that hold the features
+        cap = max(1, int(foff[n])*nl)
+        u = np.zeros(cap); v = np.zeros(cap); I = np.zeros(cap)
+        for i, f in enumerate(feats):
+            b = int(foff[i])*nl
+            u[b:b + cnt[i]] = f["u"][:cnt[i]]; v[b:b + cnt[i]] = f["v"][:cnt[i]]; I[b:b + cnt[i]] = f["inten"][:cnt[i]]
+        h0, w0 = self.level_shape(0)
+        c0 = q*inv[0]
+        x0 = np.clip(np.floor(c0[:, :, 0].min(1)), 0, w0 - 1); x1 = np.clip(np.ceil(c0[:, :, 0].max(1)), 0, w0 - 1)
+        y0 = np.clip(np.floor(c0[:, :, 1].min(1)), 0, h0 - 1); y1 = np.clip(np.ceil(c0[:, :, 1].max(1)), 0, h0 - 1)
+        pcap = max(1, int(np.sum((x1 - x0 + 1)*(y1 - y0 + 1))))
+        ms = np.zeros((n, nl, 2)); ok = np.zeros((n, nl), np.uint8)
+        N = np.zeros(cap); I8 = np.zeros((cap, 8)); N8 = np.zeros((cap, 8)); inn = np.zeros(cap, np.uint8)
+        poff = np.zeros(n + 1, np.int32); pu = np.zeros(pcap, np.int32); pv = np.zeros(pcap, np.int32); pI = np.zeros(pcap); pN = np.zeros(pcap)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.tsframe_text_object_info(self.ctx, n, _dp(q), _dp(inv), foff.ctypes.data_as(ip), lo.ctypes.data_as(ip), _dp(u), _dp(v), _dp(I), pcap,
+                                                      _dp(ms), _up(ok), _dp(N), _dp(I8), _dp(N8), _up(inn),
+                                                      poff.ctypes.data_as(ip), pu.ctypes.data_as(ip), pv.ctypes.data_as(ip), _dp(pI), _dp(pN)),
+                    "tsframe_text_object_info")
+        out = []
+        for i in range(n):
+            b = int(foff[i])*nl; e = b + cnt[i]; a, z = int(poff[i]), int(poff[i + 1])
+            pix = {"u": pu[a:z], "v": pv[a:z], "featureInten": pI[a:z], "featureNInten": pN[a:z]}
+            if K is not None:
+                fx, fy, cx, cy = K
+                pix["ray"] = np.stack([(pix["u"] - cx)/fx, (pix["v"] - cy)/fy, np.ones(z - a)], 1)
+            out.append({"statistics": ms[i].copy(), "ok": ok[i].astype(bool), "level_off": lo[i].copy(), "featureNInten": N[b:e],
+                        "neighbourInten": I8[b:e], "neighbourNInten": N8[b:e], "IN": inn[b:e], "vRefPixs": pix})
+        return out
