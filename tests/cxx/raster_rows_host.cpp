@@ -1,7 +1,12 @@
-// raster_quad_rows (csrc/tsraster.h) as host code behind tests/cxx/host_shim: the union of the row bands of a quad's fill against the oracle's cv::fillPoly
-// restatement (tsba_oracle_fillpoly4) at every pixel, at image sizes above the LDS mask.  Bands as the kernels take them: MS_MASK_WORDS*32 / w rows each, from the
-// clamped yMin of the corners' bounding box to its yMax; the mask is a heap block of exactly MS_MASK_WORDS words, so a sanitizer build sees any bit outside it.
-// Also, at sampled pixels, quad_covers against the same fill.  Prints one line per size and "raster rows host: ok"; exit status 1 on the first difference.
+// The quad fill (csrc/tsraster.h) as host code behind tests/cxx/host_shim, against the oracle's cv::fillPoly restatement (tsba_oracle_fillpoly4).
+// Above the LDS mask (648 x 480 and larger): the union of the row bands of raster_quad_rows at every pixel.  Bands as the kernels take them: MS_MASK_WORDS*32 / w
+// rows each, from the clamped yMin of the corners' bounding box to its yMax; the mask is a heap block of exactly MS_MASK_WORDS words, so a sanitizer build sees any
+// bit outside it.  Also, at sampled pixels, quad_covers against the same fill.
+// At and below the mask (2 x 2 ... 640 x 480, B == hh there): raster_quad itself at every pixel, raster_quad_rows on windows [y0, y1) against the same rows of the
+// fill (one row, first row, last row, sweeps), each mask block sized to exactly the window's words; quad_covers at every pixel up to 97 x 61; 4 and 256 "threads"
+// (with 4, one thread owns a whole edge and the interior stride equals the edge count); the QUADS table and quads from a fixed-seed generator with corners up
+// to one image size outside on every side, some corners repeated.
+// Prints one line per size and "raster rows host: ok"; exit status 1 on the first difference.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,7 +42,84 @@ static const Quad QUADS[] = {
     {"sliver",                 {0.05, 0.05, 0.95, 0.93, 0.95, 0.94, 0.05, 0.06}, {0}},
 };
 
+static uint32_t lcg_state = 20260118u;
+static uint32_t lcg() { lcg_state = lcg_state*1664525u + 1013904223u; return lcg_state >> 8; }
+
+// rows [y0, y1) of the fill with nt threads, in a block of exactly the window's words, against the same rows of ref
+static bool window_equal(const int *xy, int w, int h, int y0, int y1, int nt, const std::vector<uint8_t> &ref, const char *name) {
+    const size_t words = (size_t)(((y1 - y0)*w + 31) >> 5);
+    unsigned *m = (unsigned *)calloc(words, sizeof(unsigned));
+    for (int tid = 0; tid < nt; tid++) raster_quad_rows(m, xy, w, h, y0, y1, tid, nt);
+    bool same = true;
+    for (int y = y0; y < y1 && same; y++) for (int x = 0; x < w; x++) {
+        const int bit = (y - y0)*w + x; const int g = (m[bit >> 5] >> (bit & 31)) & 1u, r = ref[(size_t)y*w + x] ? 1 : 0;
+        if (g != r) { printf("%d x %d, quad '%s', rows [%d, %d), %d threads: pixel (%d, %d) is %d, %d in the oracle\n", w, h, name, y0, y1, nt, x, y, g, r); same = false; break; }
+    }
+    for (size_t b = (size_t)(y1 - y0)*w; b < 32*words && same; b++)      // the last word's bits past the window stay clear
+        if ((m[b >> 5] >> (b & 31)) & 1u) { printf("%d x %d, quad '%s', rows [%d, %d), %d threads: bit %zu past the window is set\n", w, h, name, y0, y1, nt, b); same = false; }
+    free(m);
+    return same;
+}
+
+// one quad at a size at or below the mask; sweep: every one-row window and tiled windows of several heights, else first row, last row and three drawn windows
+static bool small_quad_equal(const int *xy, int w, int h, const char *name, bool sweep, bool every_pixel, long long &n_set, long long &n_win, long long &n_cov) {
+    std::vector<uint8_t> ref((size_t)w*h, 0);
+    tsba_oracle_fillpoly4(w, h, xy, ref.data());
+    for (uint8_t r : ref) n_set += r ? 1 : 0;
+    for (int nt : {4, 256}) {
+        const size_t words = (size_t)((w*h + 31) >> 5);
+        unsigned *m = (unsigned *)calloc(words, sizeof(unsigned));
+        for (int tid = 0; tid < nt; tid++) raster_quad(m, xy, w, h, tid, nt);
+        for (int p = 0; p < w*h; p++)
+            if ((int)((m[p >> 5] >> (p & 31)) & 1u) != (ref[p] ? 1 : 0)) { printf("%d x %d, quad '%s', %d threads: raster_quad differs at (%d, %d)\n", w, h, name, nt, p % w, p / w); free(m); return false; }
+        free(m);
+        if (!window_equal(xy, w, h, 0, 1, nt, ref, name) || !window_equal(xy, w, h, h - 1, h, nt, ref, name)) return false;
+        n_win += 2;
+        if (sweep) {
+            for (int hgt : {1, 2, 3, h/2 + 1, h})
+                for (int y0 = 0; y0 < h; y0 += hgt) { if (!window_equal(xy, w, h, y0, std::min(y0 + hgt, h), nt, ref, name)) return false; n_win++; }
+        } else {
+            for (int k = 0; k < 3; k++) {
+                const int y0 = (int)(lcg() % (uint32_t)h), y1 = y0 + 1 + (int)(lcg() % (uint32_t)(h - y0));
+                if (!window_equal(xy, w, h, y0, k == 0 ? y0 + 1 : y1, nt, ref, name)) return false;
+                n_win++;
+            }
+        }
+    }
+    for (size_t p = 0; p < (size_t)w*h; p += every_pixel ? 1 : 97) {
+        const int x = (int)(p % w), y = (int)(p / w);
+        if (quad_covers(xy, w, h, x, y) != (ref[p] != 0)) { printf("%d x %d, quad '%s': quad_covers differs at (%d, %d)\n", w, h, name, x, y); return false; }
+        n_cov++;
+    }
+    if (!every_pixel)
+        for (int x = 0; x < w; x++) for (int y : {0, h - 1})
+            if (quad_covers(xy, w, h, x, y) != (ref[(size_t)y*w + x] != 0)) { printf("%d x %d, quad '%s': quad_covers differs at (%d, %d)\n", w, h, name, x, y); return false; }
+    return true;
+}
+
 int main() {
+    const int small[][2] = {{2, 2}, {5, 3}, {33, 17}, {97, 61}, {640, 480}};
+    for (const auto &sz : small) {
+        const int w = sz[0], h = sz[1];
+        const bool upto = w*h <= 97*61;                                    // every pixel and every window up to 97 x 61, the present sampling above
+        const int n_rand = upto ? 1000 : 60;
+        long long n_set = 0, n_win = 0, n_cov = 0;
+        for (const Quad &q : QUADS) {
+            int xy[8];
+            for (int k = 0; k < 8; k++) xy[k] = (int)(q.f[k]*((k & 1) ? h : w)) + q.d[k];
+            if (!small_quad_equal(xy, w, h, q.name, true, upto, n_set, n_win, n_cov)) return 1;
+        }
+        for (int i = 0; i < n_rand; i++) {
+            int xy[8]; char name[32];
+            for (int k = 0; k < 8; k++) { const int s = (k & 1) ? h : w; xy[k] = (int)(lcg() % (uint32_t)(3*s)) - s; }      // [-s, 2 s)
+            if (i % 7 == 3) { xy[2] = xy[0]; xy[3] = xy[1]; }
+            if (i % 11 == 5) { xy[6] = xy[2]; xy[7] = xy[3]; }
+            if (i % 13 == 6) { xy[5] = xy[3]; }                            // (a horizontal edge)
+            snprintf(name, sizeof(name), "generated %d", i);
+            if (!small_quad_equal(xy, w, h, name, false, upto, n_set, n_win, n_cov)) return 1;
+        }
+        printf("%d x %d: %d + %d quads, 4 and 256 threads, %lld windows, %lld pixels set, %lld point tests: equal\n", w, h, (int)(sizeof(QUADS)/sizeof(QUADS[0])), n_rand, n_win, n_set, n_cov);
+    }
     const int sizes[][2] = {{648, 480}, {1280, 720}, {1920, 1080}};
     const int NT = 256;
     unsigned *mask = (unsigned *)malloc(sizeof(unsigned)*MS_MASK_WORDS);

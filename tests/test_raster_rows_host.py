@@ -1,6 +1,8 @@
-"""raster_quad_rows (csrc/tsraster.h) on the host: tests/cxx/raster_rows_host.cpp compiles the header as plain C++ behind tests/cxx/host_shim and compares the
-union of a quad's row bands with the oracle's cv::fillPoly restatement at every pixel (648 x 480, 1280 x 720, 1920 x 1080; quads inside, with corners outside
-on each side and on all sides, degenerate).  Built with -fsanitize=address,undefined and run as a program of its own."""
+"""The quad fill (csrc/tsraster.h) on the host: tests/cxx/raster_rows_host.cpp compiles the header as plain C++ behind tests/cxx/host_shim and compares it with
+the oracle's cv::fillPoly restatement.  Above the mask (648 x 480, 1280 x 720, 1920 x 1080) the union of a quad's row bands at every pixel; at and below it
+(2 x 2, 5 x 3, 33 x 17, 97 x 61, 640 x 480) raster_quad itself, raster_quad_rows on windows sized to exactly their words, quad_covers, with 4 and 256 threads;
+quads inside, with corners outside on each side and on all sides, degenerate, and from a fixed-seed generator.  Built with -fsanitize=address,undefined and
+run as a program of its own."""
 import os
 import subprocess
 
@@ -17,4 +19,4 @@ def test_bands_equal_the_oracle_fill_under_sanitizers(tmp_path):
     print(res.stdout)
     assert res.returncode == 0, res.stdout + res.stderr
     assert "raster rows host: ok" in res.stdout and res.stderr == "", res.stdout + res.stderr
-    assert sum("equal" in line for line in res.stdout.splitlines()) == 3
+    assert sum("equal" in line for line in res.stdout.splitlines()) == 8

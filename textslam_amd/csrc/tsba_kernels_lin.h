@@ -246,7 +246,7 @@ __global__ __launch_bounds__(1024) void k_gauge_par(Work W, const uint8_t *kf_in
 // pose (h_in) or its T_wr (3x4), th: the plane, (mx, my): box corner tid & 3.  Returns n < 2 (no moments: mu = sigma = 0) as false; *mu / *sigma in
 // every thread otherwise.  LDS: mask [MS_MASK_WORDS], hist [256], s_xy [8], s_bb [4], s_c [16], s_red [NT].
 // BIG = false: w hh <= MS_MASK_WORDS*32, the whole level's mask in LDS.  BIG = true: any size -- the mask is built and read in bands of B = MS_MASK_WORDS*32 / w rows
-// that start at the box's clamped yMin (raster_quad_rows: the full image's fill, a window of its rows), so a box no taller than B rows costs one band.  The moments
+// that start at the box's clamped yMin (raster_quad_rows, the one fill: a window of the full image's rows; BIG = false takes raster_quad, the window of all rows), so a box no taller than B rows costs one band.  The moments
 // come from the integer histogram: the same bits whatever the order of the pixels and however they are banded.
 template <int NT, bool BIG>
 __device__ __forceinline__ bool musigma_core(const double pc[7], const double ph[12], bool h_in, const double th[3], double mx, double my,
@@ -444,7 +444,7 @@ __device__ __noinline__ LabelQuad label_quad(const double *pose, const double *t
     return q;
 }
 
-// BIG (a level above MS_MASK_WORDS*32 pixels): every quad in bands of MS_MASK_WORDS*32 / w rows from its clamped yMin (raster_quad_rows); out[] keeps the full
+// BIG (a level above MS_MASK_WORDS*32 pixels): every quad in bands of MS_MASK_WORDS*32 / w rows from its clamped yMin (raster_quad_rows, the one fill; raster_quad below is its window of all rows); out[] keeps the full
 // image's index, only the mask's bit is relative to the band.
 #define LBL_THREADS 1024
 template <bool BIG>

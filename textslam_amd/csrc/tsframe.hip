@@ -144,14 +144,30 @@ __global__ __launch_bounds__(256) void k_neighbours(const uint8_t *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+// Ordered compaction of one tile by a workgroup of NWAVES waves (k_box_pixels, k_pts_batch, k_object_info): the slot of a hit = base + the hits of the lower
+// waves (s_w [NWAVES]) + the hits of the lower lanes (ballot); base advances by the tile's total.  Every thread of the workgroup calls it: the two
+// barriers are those around s_w.  The slot of a miss means nothing.
+template <int NWAVES>
+__device__ __forceinline__ int wg_ordered_slot(bool hit, int *s_w, int &base) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(hit);
+    if (lane == 0) s_w[wave] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+#pragma unroll
+    for (int q = 0; q < NWAVES; q++) { const int c = s_w[q]; if (q < wave) off += c; tot += c; }
+    base += tot;
+    __syncthreads();
+    return off + __popcll(bal & ((1ull << lane) - 1ull));
+}
 // ---- tool::GetBoxAllPixs (tool.cc:1264-1337): every pixel of the level image inside the filled detection quad, in row-major order
 // of the clamped bounding box.  One workgroup: scan conversion of the quad into a bit mask (cv::fillPoly semantics, tsraster.h), then an
-// ordered compaction of the box in tiles of 1024 pixels (ballot + wave counts).
+// ordered compaction of the box in tiles of 1024 pixels (wg_ordered_slot).
 struct BoxDev { int xy[8]; int x0, x1, y0, y1; };
 __global__ __launch_bounds__(1024) void k_box_pixels(const uint8_t *__restrict__ img, int w, int h, BoxDev B, double mu, double sigma, unsigned *mask,
                                                      int *cnt, int *__restrict__ u, int *__restrict__ v, double *__restrict__ inten, double *__restrict__ ninten) {
     __shared__ int s_xy[8], s_w[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid < 8) s_xy[tid] = B.xy[tid];
     for (int k = tid; k < (w*h + 31) >> 5; k += 1024) mask[k] = 0;
     __syncthreads();
@@ -163,18 +179,11 @@ __global__ __launch_bounds__(1024) void k_box_pixels(const uint8_t *__restrict__
         const int k = k0 + tid;
         int x = 0, y = 0; bool in = false;
         if (k < npx) { x = B.x0 + k % bw; y = B.y0 + k / bw; const int bit = y*w + x; in = (mask[bit >> 5] >> (bit & 31)) & 1u; }
-        const unsigned long long bal = __ballot(in);
-        if (lane == 0) s_w[wave] = __popcll(bal);
-        __syncthreads();
-        int off = base, tot = 0;
-        for (int q = 0; q < 16; q++) { const int c = s_w[q]; if (q < wave) off += c; tot += c; }
+        const int at = wg_ordered_slot<16>(in, s_w, base);
         if (in) {
-            const int at = off + __popcll(bal & ((1ull << lane) - 1ull));
             const double I = (double)img[y*w + x];
             u[at] = x; v[at] = y; inten[at] = I; ninten[at] = (I - mu)/sigma;
         }
-        base += tot;
-        __syncthreads();
     }
     if (tid == 0) *cnt = base;
 }
@@ -304,33 +313,23 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
     // 4. detection association (tracking.cc:2116-2128): label image = the quad filled by cv::fillPoly; centre (round(u), round(v)), half away from zero
     if (dete_bits && A.dete_words > 0) {
         unsigned *bits = dete_bits + (size_t)p*A.dete_words;
-        if constexpr (BIG) {
-            for (int k = tid; k < A.dete_words; k += JUDGE_NT) {
-                unsigned word = 0;
-                if (reason == TSFRAME_JUDGE_PASS)
-                    for (int j = 32*k; j < min(32*k + 32, A.n_dete); j++) {
-                        const double ru = round(dete_xy[2*j]), rv = round(dete_xy[2*j + 1]);
-                        if (!(ru >= 0.0 && ru <= (double)(A.w0 - 1) && rv >= 0.0 && rv <= (double)(A.h0 - 1))) continue;
-                        if (quad_covers(s_xy, A.w0, A.h0, (int)ru, (int)rv)) word |= 1u << (j & 31);
-                    }
-                bits[k] = word;
+        if constexpr (!BIG)
+            if (reason == TSFRAME_JUDGE_PASS) {
+                for (int k = tid; k < (A.w0*A.h0 + 31) >> 5; k += JUDGE_NT) s_u.mask[k] = 0;
+                __syncthreads();
+                raster_quad(s_u.mask, s_xy, A.w0, A.h0, tid, JUDGE_NT);
+                __syncthreads();
             }
-            return;
-        }
-        if (reason == TSFRAME_JUDGE_PASS) {
-            for (int k = tid; k < (A.w0*A.h0 + 31) >> 5; k += JUDGE_NT) s_u.mask[k] = 0;
-            __syncthreads();
-            raster_quad(s_u.mask, s_xy, A.w0, A.h0, tid, JUDGE_NT);
-            __syncthreads();
-        }
         for (int k = tid; k < A.dete_words; k += JUDGE_NT) {
             unsigned word = 0;
             if (reason == TSFRAME_JUDGE_PASS)
                 for (int j = 32*k; j < min(32*k + 32, A.n_dete); j++) {
                     const double ru = round(dete_xy[2*j]), rv = round(dete_xy[2*j + 1]);
                     if (!(ru >= 0.0 && ru <= (double)(A.w0 - 1) && rv >= 0.0 && rv <= (double)(A.h0 - 1))) continue;
-                    const int bit = (int)rv*A.w0 + (int)ru;
-                    if ((s_u.mask[bit >> 5] >> (bit & 31)) & 1u) word |= 1u << (j & 31);
+                    bool in;
+                    if constexpr (BIG) in = quad_covers(s_xy, A.w0, A.h0, (int)ru, (int)rv);
+                    else { const int bit = (int)rv*A.w0 + (int)ru; in = (s_u.mask[bit >> 5] >> (bit & 31)) & 1u; }
+                    if (in) word |= 1u << (j & 31);
                 }
             bits[k] = word;
         }
@@ -348,12 +347,39 @@ static int ensure_host(FCtx *c, size_t bytes) {
     CKF(hipHostMalloc((void **)&c->h_stage, bytes, hipHostMallocDefault));
     c->h_cap = bytes; return 0;
 }
-static int ensure_work(FCtx *c, size_t bytes) {
-    if (bytes <= c->d_cap) return 0;
-    if (c->d_work) hipFree(c->d_work);
-    c->d_work = nullptr; c->d_cap = 0;
-    CKF(hipMalloc((void **)&c->d_work, bytes));
-    c->d_cap = bytes; return 0;
+// the feature calls' staging: device scratch of dev_bytes, pinned block of host_bytes (never below the level-0 image, which tsframe_set_image stages there)
+static int ensure_stage(FCtx *c, size_t dev_bytes, size_t host_bytes) {
+    if (dev_bytes > c->d_cap) {
+        if (c->d_work) hipFree(c->d_work);
+        c->d_work = nullptr; c->d_cap = 0;
+        CKF(hipMalloc((void **)&c->d_work, dev_bytes));
+        c->d_cap = dev_bytes;
+    }
+    return ensure_host(c, std::max(host_bytes, (size_t)c->w[0]*c->h[0]));
+}
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The corners of quad * scale as cv::Point(double, double) (truncation) and their clamped bounding box, statement by statement as tool.cc:1269-1298: min / max
+// on strict improvement from w + 1 / -1, then the eight clamps in the reference's order.  An empty box has x1 < x0 or y1 < y0.
+static void quad_box(const double *quad, double scale, int w, int h, int xy[8], int &x0, int &x1, int &y0, int &y1) {
+    int xMin = w + 1, xMax = -1, yMin = h + 1, yMax = -1;
+    for (int i = 0; i < 4; i++) {
+        const double x = quad[2*i]*scale, y = quad[2*i + 1]*scale;
+        xy[2*i] = (int)x; xy[2*i + 1] = (int)y;
+        if (x > xMax) xMax = (int)ceil(x);
+        if (x < xMin) xMin = (int)floor(x);
+        if (y > yMax) yMax = (int)ceil(y);
+        if (y < yMin) yMin = (int)floor(y);
+    }
+    if (xMin < 0) xMin = 0;
+    if (xMin >= w) xMin = w - 1;
+    if (yMin < 0) yMin = 0;
+    if (yMin >= h) yMin = h - 1;
+    if (xMax >= w) xMax = w - 1;
+    if (xMax < 0) xMax = 0;
+    if (yMax >= h) yMax = h - 1;
+    if (yMax < 0) yMax = 0;
+    x0 = xMin; x1 = xMax; y0 = yMin; y1 = yMax;
 }
 
 // the cell grid of level l >= 1 for a set of n raw features (host doubles, the reference's expressions: tool.cc:599-616 / :898-907), shared by
@@ -453,11 +479,9 @@ int tsframe_pyramid_pts(void *ctx, int mode, const float *xy, int n, const doubl
         max_cell = std::max(max_cell, (size_t)G[l].cw*G[l].ch);
     }
     // device scratch: xy | sel | cnt, level_off | u | v | inten | idx | in
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_xy = 0, o_sel = o_xy + al(sizeof(float)*2*(size_t)std::max(n, 1)), o_cnt = o_sel + al(sizeof(int)*max_cell), o_u = o_cnt + al(sizeof(int)*(L + 4)),
-                 o_v = o_u + al(8*cap), o_I = o_v + al(8*cap), o_idx = o_I + al(8*cap), o_in = o_idx + al(4*cap), tot = o_in + al(cap);
-    int rc = ensure_work(c, tot + 256); if (rc) return rc;
-    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    const size_t o_xy = 0, o_sel = o_xy + al256(sizeof(float)*2*(size_t)std::max(n, 1)), o_cnt = o_sel + al256(sizeof(int)*max_cell), o_u = o_cnt + al256(sizeof(int)*(L + 4)),
+                 o_v = o_u + al256(8*cap), o_I = o_v + al256(8*cap), o_idx = o_I + al256(8*cap), o_in = o_idx + al256(4*cap), tot = o_in + al256(cap);
+    int rc = ensure_stage(c, tot + 256, tot); if (rc) return rc;
     uint8_t *d = c->d_work;
     if (n > 0) { memcpy(c->h_stage, xy, sizeof(float)*2*(size_t)n); CKF(hipMemcpyAsync(d + o_xy, c->h_stage, sizeof(float)*2*(size_t)n, hipMemcpyHostToDevice, c->stream)); }
     int *cnt = (int *)(d + o_cnt), *loff = cnt + 2;
@@ -533,12 +557,10 @@ int tsframe_pyramid_pts_batch(void *ctx, int n_set, const int32_t *mode, const i
     if (total == 0) { memset(level_off, 0, sizeof(int32_t)*(size_t)n_set*(L + 1)); return TSFRAME_OK; }
     hipSetDevice(c->device);
     // one block, inputs then outputs: jobs | xy || cnt | u | v | inten | idx | in; then the large grids' scratch (device only)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t cap = total*L, nj = jobs.size();
-    const size_t o_xy = al(sizeof(PtsJob)*nj), o_cnt = o_xy + al(8*total), o_u = o_cnt + al(4*nj), o_v = o_u + al(8*cap), o_I = o_v + al(8*cap),
-                 o_idx = o_I + al(8*cap), o_in = o_idx + al(4*cap), tot = o_in + al(cap);
-    int rc = ensure_work(c, tot + 4*sel_ints); if (rc) return rc;
-    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    const size_t o_xy = al256(sizeof(PtsJob)*nj), o_cnt = o_xy + al256(8*total), o_u = o_cnt + al256(4*nj), o_v = o_u + al256(8*cap), o_I = o_v + al256(8*cap),
+                 o_idx = o_I + al256(8*cap), o_in = o_idx + al256(4*cap), tot = o_in + al256(cap);
+    int rc = ensure_stage(c, tot + 4*sel_ints, tot); if (rc) return rc;
     uint8_t *h = c->h_stage, *d = c->d_work;
     memcpy(h, jobs.data(), sizeof(PtsJob)*nj); memcpy(h + o_xy, xy, 8*total);
     CKF(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, c->stream));
@@ -570,10 +592,8 @@ int tsframe_neighbours(void *ctx, int level, const double *uv, int n, double mu,
     if (sigma == 0.0) { c->err = "sigma == 0 (tool::CalNormvec returns false)"; return TSFRAME_ERR_ARG; }
     if (n == 0) return TSFRAME_OK;
     hipSetDevice(c->device);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_uv = 0, o_I = al(16*(size_t)n), o_N = o_I + al(64*(size_t)n), o_in = o_N + al(64*(size_t)n), tot = o_in + al(n);
-    int rc = ensure_work(c, tot); if (rc) return rc;
-    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    const size_t o_uv = 0, o_I = al256(16*(size_t)n), o_N = o_I + al256(64*(size_t)n), o_in = o_N + al256(64*(size_t)n), tot = o_in + al256(n);
+    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
     uint8_t *d = c->d_work;
     memcpy(c->h_stage, uv, 16*(size_t)n);
     CKF(hipMemcpyAsync(d + o_uv, c->h_stage, 16*(size_t)n, hipMemcpyHostToDevice, c->stream));
@@ -593,33 +613,14 @@ int tsframe_box_pixels(void *ctx, int level, const double *quad, double mu, doub
     for (int i = 0; i < 8; i++) if (!(fabs(quad[i]) < 1e9)) { c->err = "quad corner not finite"; return TSFRAME_ERR_ARG; }
     hipSetDevice(c->device);
     const int w = c->w[level], h = c->h[level];
-    // corners (cv::Point(double, double): truncation) and the clamped bounding box, statement by statement as tool.cc:1269-1298
     BoxDev B;
-    int xMin = w + 1, xMax = -1, yMin = h + 1, yMax = -1;
-    for (int i = 0; i < 4; i++) {
-        const double x = quad[2*i], y = quad[2*i + 1];
-        B.xy[2*i] = (int)x; B.xy[2*i + 1] = (int)y;
-        if (x > xMax) xMax = (int)ceil(x);
-        if (x < xMin) xMin = (int)floor(x);
-        if (y > yMax) yMax = (int)ceil(y);
-        if (y < yMin) yMin = (int)floor(y);
-    }
-    if (xMin < 0) xMin = 0;
-    if (xMin >= w) xMin = w - 1;
-    if (yMin < 0) yMin = 0;
-    if (yMin >= h) yMin = h - 1;
-    if (xMax >= w) xMax = w - 1;
-    if (xMax < 0) xMax = 0;
-    if (yMax >= h) yMax = h - 1;
-    if (yMax < 0) yMax = 0;
-    B.x0 = xMin; B.x1 = xMax; B.y0 = yMin; B.y1 = yMax;
+    quad_box(quad, 1.0, w, h, B.xy, B.x0, B.x1, B.y0, B.y1);
+    const int xMin = B.x0, xMax = B.x1, yMin = B.y0, yMax = B.y1;
     *n_out = 0;
     if (xMax < xMin || yMax < yMin) return TSFRAME_OK;
     const size_t npx = (size_t)(xMax - xMin + 1)*(size_t)(yMax - yMin + 1);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_cnt = 0, o_mask = 256, o_u = o_mask + al(4*(((size_t)w*h + 31) >> 5)), o_v = o_u + al(4*npx), o_I = o_v + al(4*npx), o_N = o_I + al(8*npx), tot = o_N + al(8*npx);
-    int rc = ensure_work(c, tot); if (rc) return rc;
-    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    const size_t o_cnt = 0, o_mask = 256, o_u = o_mask + al256(4*(((size_t)w*h + 31) >> 5)), o_v = o_u + al256(4*npx), o_I = o_v + al256(4*npx), o_N = o_I + al256(8*npx), tot = o_N + al256(8*npx);
+    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
     uint8_t *d = c->d_work;
     hipLaunchKernelGGL(k_box_pixels, dim3(1), dim3(1024), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], w, h, B, mu, sigma, (unsigned *)(d + o_mask),
                        (int *)(d + o_cnt), (int *)(d + o_u), (int *)(d + o_v), (double *)(d + o_I), (double *)(d + o_N));
@@ -668,12 +669,10 @@ int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const d
     for (int k = 0; k < 4; k++) { A.Kr[k] = K_ref[k]; A.K[k] = K[k]; }
     A.cos_min = cos_min; A.zncc_min = zncc_min;
     // one pinned block, inputs then outputs: planes | dete_xy | pix_off | pix_uv | pix_inten || out | bits
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t nd = words > 0 ? (size_t)n_dete : 0;
-    const size_t o_pl = 0, o_dx = o_pl + al(sizeof(JudgePlane)*(size_t)n), o_off = o_dx + al(16*nd), o_uv = o_off + al(4*((size_t)n + 1)),
-                 o_in = o_uv + al(4*npix), o_out = o_in + al(npix), o_bits = o_out + al(sizeof(JudgeOut)*(size_t)n), tot = o_bits + al(4*(size_t)n*words);
-    int rc = ensure_work(c, tot); if (rc) return rc;
-    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    const size_t o_pl = 0, o_dx = o_pl + al256(sizeof(JudgePlane)*(size_t)n), o_off = o_dx + al256(16*nd), o_uv = o_off + al256(4*((size_t)n + 1)),
+                 o_in = o_uv + al256(4*npix), o_out = o_in + al256(npix), o_bits = o_out + al256(sizeof(JudgeOut)*(size_t)n), tot = o_bits + al256(4*(size_t)n*words);
+    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
     uint8_t *h = c->h_stage, *d = c->d_work;
     JudgePlane *hp = (JudgePlane *)(h + o_pl);
     for (int i = 0; i < n; i++) {
@@ -733,10 +732,8 @@ int tsframe_klt_track(void *prev_ctx, void *cur_ctx, int n, const float *prev_xy
     A.n = n; A.n_levels = need; A.win = win; A.max_iter = max_iter;
     A.eps2 = (float)eps*(float)eps; A.min_eig = (float)min_eig;
     // one pinned block: prev_xy || next_xy | status
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_out = al(8*(size_t)n), o_st = o_out + al(8*(size_t)n), tot = o_st + al((size_t)n);
-    int rc = ensure_work(c, tot); if (rc) return rc;
-    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    const size_t o_out = al256(8*(size_t)n), o_st = o_out + al256(8*(size_t)n), tot = o_st + al256((size_t)n);
+    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
     uint8_t *h = c->h_stage, *d = c->d_work;
     memcpy(h, prev_xy, 8*(size_t)n);
     CKF(hipMemcpyAsync(d, h, 8*(size_t)n, hipMemcpyHostToDevice, c->stream));
@@ -788,7 +785,7 @@ int tsframe_text_object_info(void *ctx, int n_obj, const double *quad, const dou
         const size_t b = (size_t)feat_off[i]*L, m = (size_t)level_off[(size_t)i*(L + 1) + L];
         for (size_t k = b; k < b + m; k++) if (!std::isfinite(u[k]) || !std::isfinite(v[k])) return bad(at_obj("u / v not finite", i));
     }
-    // jobs: one per (object, level); the corners are quad * inv_scale[l] (mapText.cc:78-81), truncated and boxed statement by statement as tool.cc:1269-1298
+    // jobs: one per (object, level); the corners are quad * inv_scale[l] (mapText.cc:78-81), truncated and boxed by quad_box
     std::vector<ObjJob> jobs((size_t)n_obj*L);
     std::vector<size_t> fbase((size_t)n_obj + 1, 0), pbase((size_t)n_obj + 1, 0);
     const bool want_pix = pix_cap > 0;
@@ -797,25 +794,9 @@ int tsframe_text_object_info(void *ctx, int n_obj, const double *quad, const dou
         for (int l = 0; l < L; l++) {
             ObjJob &J = jobs[(size_t)i*L + l];
             const int w = c->w[l], h = c->h[l];
-            int xMin = w + 1, xMax = -1, yMin = h + 1, yMax = -1;
-            for (int k = 0; k < 4; k++) {
-                const double x = quad[8*(size_t)i + 2*k]*inv_scale[l], y = quad[8*(size_t)i + 2*k + 1]*inv_scale[l];
-                J.xy[2*k] = (int)x; J.xy[2*k + 1] = (int)y;
-                if (x > xMax) xMax = (int)ceil(x);
-                if (x < xMin) xMin = (int)floor(x);
-                if (y > yMax) yMax = (int)ceil(y);
-                if (y < yMin) yMin = (int)floor(y);
-            }
-            if (xMin < 0) xMin = 0;
-            if (xMin >= w) xMin = w - 1;
-            if (yMin < 0) yMin = 0;
-            if (yMin >= h) yMin = h - 1;
-            if (xMax >= w) xMax = w - 1;
-            if (xMax < 0) xMax = 0;
-            if (yMax >= h) yMax = h - 1;
-            if (yMax < 0) yMax = 0;
+            quad_box(quad + 8*(size_t)i, inv_scale[l], w, h, J.xy, J.x0, J.x1, J.y0, J.y1);
+            const int xMin = J.x0, xMax = J.x1, yMin = J.y0, yMax = J.y1;
             J.img = c->plane[TSFRAME_IMG][l]; J.w = w; J.h = h;
-            J.x0 = xMin; J.x1 = xMax; J.y0 = yMin; J.y1 = yMax;
             J.f0 = (int)(fbase[i] + (size_t)lo[l]); J.nf = lo[l + 1] - lo[l];
             J.pix0 = -1;
             if (l == 0) {
@@ -829,13 +810,11 @@ int tsframe_text_object_info(void *ctx, int n_obj, const double *quad, const dou
     const size_t nreg = want_pix ? pbase[n_obj] : 0;             // slots of the pixel regions (the sum of the clamped level-0 boxes)
     hipSetDevice(c->device);
     // one block, inputs then outputs: jobs | u | v | inten || out | ninten | inten8 | ninten8 | in | pix_u | pix_v | pix_inten | pix_ninten
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t nj = jobs.size();
-    const size_t o_u = al(sizeof(ObjJob)*nj), o_v = o_u + al(8*nfeat), o_I = o_v + al(8*nfeat), o_out = o_I + al(8*nfeat), o_n = o_out + al(sizeof(ObjOut)*nj),
-                 o_i8 = o_n + al(8*nfeat), o_n8 = o_i8 + al(64*nfeat), o_in = o_n8 + al(64*nfeat), o_pu = o_in + al(nfeat), o_pv = o_pu + al(4*nreg),
-                 o_pI = o_pv + al(4*nreg), o_pN = o_pI + al(8*nreg), tot = o_pN + al(8*nreg);
-    int rc = ensure_work(c, tot); if (rc) return rc;
-    rc = ensure_host(c, std::max(tot, (size_t)c->w[0]*c->h[0])); if (rc) return rc;
+    const size_t o_u = al256(sizeof(ObjJob)*nj), o_v = o_u + al256(8*nfeat), o_I = o_v + al256(8*nfeat), o_out = o_I + al256(8*nfeat), o_n = o_out + al256(sizeof(ObjOut)*nj),
+                 o_i8 = o_n + al256(8*nfeat), o_n8 = o_i8 + al256(64*nfeat), o_in = o_n8 + al256(64*nfeat), o_pu = o_in + al256(nfeat), o_pv = o_pu + al256(4*nreg),
+                 o_pI = o_pv + al256(4*nreg), o_pN = o_pI + al256(8*nreg), tot = o_pN + al256(8*nreg);
+    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
     uint8_t *h = c->h_stage, *d = c->d_work;
     memcpy(h, jobs.data(), sizeof(ObjJob)*nj);
     for (int i = 0; i < n_obj; i++) {

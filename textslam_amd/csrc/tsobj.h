@@ -4,12 +4,12 @@
 //                       (the moments of musigma_core, csrc/tsba_kernels_lin.h: mu exact, sigma from the 256 bins in a fixed order);
 //   tool::CalNormvec    (src/tool.cc:1342-1355): the level's features, thread = (feature, tap) with k_neighbours' expressions;
 //   tool::GetBoxAllPixs (src/tool.cc:1264-1337): at level 0 the pixels of the SAME mask, ordered compaction as k_box_pixels (ballot + wave counts with
-//                       a running base) into the object's own region of the pixel arrays.
-// The host truncates the corners and clamps the bounding box (the statements of tsframe_box_pixels); the region of object i is sized by its clamped
+//                       a running base: wg_ordered_slot) into the object's own region of the pixel arrays.
+// The host truncates the corners and clamps the bounding box (quad_box, as tsframe_box_pixels); the region of object i is sized by its clamped
 // level-0 box, so its place is known before the launch and no workgroup waits for another: the host's copy-out closes the gaps.
 // The quad mask lives in LDS (MS_MASK_WORDS).  Every level is rastered with raster_quad_rows in bands of B = MS_MASK_WORDS*32 / w rows from the box's first
-// row: a level of at most 640 x 480 pixels is one band whatever the box (B >= h), a larger one takes ceil(box rows / B).  raster_quad_rows gives the
-// bits of raster_quad's full mask, the histogram does not depend on the banding, and the pixels leave band after band: row-major order.  With one
+// row: a level of at most 640 x 480 pixels is one band whatever the box (B >= h), a larger one takes ceil(box rows / B).  raster_quad_rows is the one
+// fill (raster_quad is its window of all rows), the histogram does not depend on the banding, and the pixels leave band after band: row-major order.  With one
 // band the mask of the moments is still there for the pixels; with more, the bands are rastered a second time (mu and sigma are needed first).
 // Every loop bound is a size of the job: box rows and columns, bands, features.
 #ifndef TSOBJ_H
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(OBJ_NT) void k_object_info(const ObjJob *__restrict
     __shared__ unsigned s_hist[256];
     __shared__ double s_red[257];
     __shared__ int s_xy[8], s_w[OBJ_NT/64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const ObjJob J = jobs[blockIdx.x];
     const uint8_t *__restrict__ img = J.img;
     const int w = J.w, h = J.h;
@@ -112,19 +112,12 @@ __global__ __launch_bounds__(OBJ_NT) void k_object_info(const ObjJob *__restrict
             const int k = k0 + tid;
             int x = 0, y = 0; bool hit = false;
             if (k < npx) { const int r = k/bw; x = J.x0 + (k - r*bw); y = yb + r; const int bit = r*w + x; hit = (s_mask[bit >> 5] >> (bit & 31)) & 1u; }
-            const unsigned long long bal = __ballot(hit);
-            if (lane == 0) s_w[wave] = __popcll(bal);
-            __syncthreads();
-            int off = base, tot = 0;
-#pragma unroll
-            for (int q = 0; q < OBJ_NT/64; q++) { const int c = s_w[q]; if (q < wave) off += c; tot += c; }
+            const int slot = wg_ordered_slot<OBJ_NT/64>(hit, s_w, base);
             if (hit) {                                           // at most the masked pixels of the box: inside the region of bw*bh slots
-                const size_t at = (size_t)J.pix0 + (size_t)(off + __popcll(bal & ((1ull << lane) - 1ull)));
+                const size_t at = (size_t)J.pix0 + (size_t)slot;
                 const double I = (double)img[(size_t)y*w + x];
                 pu[at] = x; pv[at] = y; pI[at] = I; pN[at] = ok ? (I - mu)/sigma : 0.0;
             }
-            base += tot;
-            __syncthreads();
         }
     }
 }

@@ -26,7 +26,7 @@ __device__ __forceinline__ void pts_emit_one(const uint8_t *__restrict__ img, in
 // sel: LDS or global (the address space is resolved after inlining); returns the number of entries written from J.out0
 __device__ __forceinline__ int pts_level(int *sel, int *s_w, const PtsJob &J, const float *__restrict__ xy,
                                          double *u, double *v, int *idx, double *inten, uint8_t *in) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, w = J.w, h = J.h;
+    const int tid = threadIdx.x, w = J.w, h = J.h;
     const uint8_t *__restrict__ img = J.img, *__restrict__ grad = J.grad;
     const GridDev &G = J.G;
     const int ncell = G.cw*G.ch;
@@ -47,15 +47,9 @@ __device__ __forceinline__ int pts_level(int *sel, int *s_w, const PtsJob &J, co
         const int o = c0 + tid;                                // visiting order: o = i3 * ch + i4
         int j = -1;
         if (o < ncell) { const int i3 = o / G.ch, i4 = o - i3*G.ch; j = sel[i4*G.cw + i3]; }
-        const unsigned long long bal = __ballot(j >= 0);
-        if (lane == 0) s_w[wave] = __popcll(bal);
-        __syncthreads();
-        int off = base, tot = 0;
-        for (int k = 0; k < PTS_NT/64; k++) { const int c = s_w[k]; if (k < wave) off += c; tot += c; }
+        const int slot = wg_ordered_slot<PTS_NT/64>(j >= 0, s_w, base);
         if (j >= 0)                                            // a feature sits in one cell only: at most J.n entries in all
-            pts_emit_one(img, w, h, (double)xy[2*j]*G.s, (double)xy[2*j + 1]*G.s, j, J.out0 + off + __popcll(bal & ((1ull << lane) - 1ull)), u, v, idx, inten, in);
-        base += tot;
-        __syncthreads();
+            pts_emit_one(img, w, h, (double)xy[2*j]*G.s, (double)xy[2*j + 1]*G.s, j, J.out0 + slot, u, v, idx, inten, in);
     }
     return base;
 }
