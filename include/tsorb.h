@@ -80,6 +80,41 @@ int tsorb_match_set_features(void *ctx, const float *kp6, const uint8_t *desc, i
 int tsorb_match_search(void *ctx, int nq, const float *qxy, const float *qr, const int32_t *qlev, const uint8_t *qdesc, int max_cand,
                        int32_t *cand_idx, int32_t *cand_dist, int32_t *cand_cnt, int32_t *best_idx, int32_t *best_dist, int32_t *best_dist2);
 
+/* ---- All-pairs matching of loop closing: loopClosing::SearchMatch for every loop candidate of ComputeSim3 (src/loopClosing.cc:306-377, :738-925).
+ * Both calls need only a context: no resident batch, and the resident batch and the match grid are left as they were.  Host pointers in, host pointers out.
+ * Offset arrays start at 0 and never decrease; a set (a pair's queries or train rows, the current keyframe's features, a candidate's features) has at most
+ * TSORB_BRUTE_MAX_FEAT rows: a feature index then fits the 16 low bits of the (distance << 16 | index) key the device reduces, whose distance field (0 .. 256, and
+ * 0x7fff for "none") stays below 2^15, so the key never leaves a positive int32.
+ *
+ *   tsorb_match_brute_text   <- loopClosing::FeatureMatch_brute(Descrip1, Descrip2, USETHRESH = true) (:1491-1519) for n_pair (query set, train set) pairs: per
+ *     query row the nearest train row of ITS pair by 256-bit Hamming distance (cv::BFMatcher("BruteForce-Hamming")::match as docs/bfmatcher_recalled.md states it:
+ *     one match per query, the first index on a tie), train_idx relative to the pair, dist its distance, good = dist < max(2 min_dist, 30.0) in doubles with
+ *     min_dist the minimum over the pair's queries.  The reference's good_matches are the good rows in query order.  A pair without queries writes nothing; a pair
+ *     with an empty train set gives train_idx -1, dist INT32_MAX, good 0 (the reference skips such pairs: loopClosing.cc:799).
+ *   tsorb_match_brute_scene  <- loopClosing::SearchMatch_Other (:823-925) for n_cand candidates against the current keyframe's n1 features, the candidates independent
+ *     of each other.  has3d = the reference's Cond1 evaluated by the caller (scene feature: vMatches2D3D >= 0; text feature: vTextDeteCorMap[vTextObjInfo] >= 0).
+ *     Cond2: candidate k's boxes are rows [qoff[k], qoff[k+1]) of quad_cur (painted into the current keyframe's label image by SearchMatch_Text for this candidate)
+ *     and of quad_can (into the candidate's); a feature is out when one of its image's boxes covers the pixel ((int)roundf(x), (int)roundf(y)) in the sense of
+ *     cv::fillPoly on a w x h image (corners truncated like cv::Point(double, double), boundary included); a rounded pixel outside the image is not covered (the
+ *     reference reads out of bounds there).  Then the reference's scan, exactly: i1 in index order, the first minimum and the runner-up distance over the eligible i2
+ *     with !(vMatchDist[i2] <= dist), accepted when best <= th_low && best < (double)second*ratio (second = INT_MAX when there is none), a later i1 taking an i2 from
+ *     an earlier one.  match12 [n_cand][n1] = vMatchIdx12 (-1 = none), n_match [n_cand] = nMatches = the entries >= 0 of the row.  th_low 50 and ratio 0.9 are the
+ *     reference's values.
+ * n_pair == 0 / n_cand == 0: TSORB_OK, no pointer is read.  n1 == 0: n_match = 0, nothing is launched.  TSORB_ERR_ARG (tsorb_last_error names the function, nothing is
+ * launched, no output is touched) for: a NULL context or a NULL pointer where data is needed, a negative count, an offset array that does not start at 0 or
+ * decreases, w or h outside [1, 8192], a coordinate that is not finite, a quad corner that is not finite or beyond 2^30, th_low outside [0, 256], a ratio that is
+ * not finite or negative, a set above TSORB_BRUTE_MAX_FEAT. */
+#define TSORB_BRUTE_MAX_FEAT 65536
+int tsorb_match_brute_text(void *ctx, int n_pair,
+                           const int32_t *off1 /*[n_pair+1]*/, const uint8_t *desc1 /*[off1[n_pair]][32]*/,
+                           const int32_t *off2 /*[n_pair+1]*/, const uint8_t *desc2 /*[off2[n_pair]][32]*/,
+                           int32_t *train_idx /*[off1[n_pair]]*/, int32_t *dist /*[off1[n_pair]]*/, uint8_t *good /*[off1[n_pair]]*/);
+int tsorb_match_brute_scene(void *ctx, int w, int h,
+                            int n1, const float *xy1 /*[n1][2]*/, const uint8_t *desc1 /*[n1][32]*/, const uint8_t *has3d1 /*[n1]*/,
+                            int n_cand, const int32_t *off2 /*[n_cand+1]*/, const float *xy2, const uint8_t *desc2, const uint8_t *has3d2,
+                            const int32_t *qoff /*[n_cand+1]*/, const double *quad_cur /*[qoff[n_cand]][4][2]*/, const double *quad_can /*same*/,
+                            int th_low, double ratio, int32_t *match12 /*[n_cand][n1]*/, int32_t *n_match /*[n_cand]*/);
+
 /* ---- Text features of a frame.
  * frame::FeatExtracText (src/frame.cc:334-355): for each of n_dete detection quads (level-0 pixels, double x, y; truncated like cv::Point)
  * cv::ORB::create()->detect on the frame masked to the quad (tool::GetMask) and ->compute on the frame itself, OpenCV 3.3 defaults;

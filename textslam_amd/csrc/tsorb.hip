@@ -1449,6 +1449,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
 }
 
 #include "tscvorb.h"
+#include "tsbrute.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -1465,6 +1466,7 @@ struct OCtx {
     void *mq_dev = nullptr, *mq_host = nullptr; size_t mq_cap = 0;
     bool ran = false;                                                           // the resident batch has been through tsorb_run (its level 0 is in place)
     CvoDev CV; int cv_w = 0, cv_h = 0, cv_nd = 0; void *cv_geo = nullptr, *cv_det = nullptr, *cv_sel = nullptr, *cv_pin = nullptr; size_t cv_sel_cap = 0, cv_pin_cap = 0;   // tsorb_text_extract's scratch, kept between calls
+    void *br_dev = nullptr, *br_pin = nullptr; size_t br_dev_cap = 0, br_pin_cap = 0;                       // tsorb_match_brute_*: device block and pinned staging, kept between calls
     int key[5] = {0, 0, 0, 0, 0}; uint8_t *h_img = nullptr; void *h_out = nullptr; size_t h_img_sz = 0, h_out_sz = 0;
 };
 static int cv_round_f(float v) { return (int)lrintf(v); }
@@ -1508,6 +1510,7 @@ int tsorb_destroy(void *ctx) { OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_A
     if (c->h_fb) hipHostFree(c->h_fb);
     if (c->cv_geo) hipFree(c->cv_geo); if (c->cv_det) hipFree(c->cv_det); if (c->cv_sel) hipFree(c->cv_sel); if (c->cv_pin) hipHostFree(c->cv_pin);
     if (c->m_buf) hipFree(c->m_buf); if (c->m_feat) hipFree(c->m_feat); if (c->mq_dev) hipFree(c->mq_dev); if (c->mq_host) hipHostFree(c->mq_host);
+    if (c->br_dev) hipFree(c->br_dev); if (c->br_pin) hipHostFree(c->br_pin);
     hipStreamDestroy(c->stream); delete c; return TSORB_OK; }
 const char *tsorb_last_error(void *ctx) { return ctx ? ((OCtx *)ctx)->err.c_str() : "null ctx"; }
 int tsorb_get_levels(void *ctx) { return ctx ? ((OCtx *)ctx)->nlevels : TSORB_ERR_ARG; }
@@ -1859,6 +1862,115 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
         if (n > cap) { rc = bad("a detection has more keypoints than cap (count[] is complete, nothing written for it)"); continue; }
         memcpy(kp + 6*(size_t)d*cap, o_kp + 24*(size_t)d*cap, 24*(size_t)n); memcpy(desc + 32*(size_t)d*cap, o_desc + 32*(size_t)d*cap, 32*(size_t)n); }
     return rc;
+}
+
+// ---- loopClosing::SearchMatch: every loop candidate's all-pairs matching (tsbrute.h).  Both calls need only a context: the resident batch and the match
+// grid are not touched.  One pinned block up ([in]), one device block ([in | scratch | out]), one pinned block down ([out]).
+static size_t br_al(size_t n) { return (n + 15) & ~(size_t)15; }
+static int br_room(OCtx *c, size_t dev, size_t pin) {
+    if (c->br_dev_cap < dev) { if (c->br_dev) hipFree(c->br_dev); c->br_dev = nullptr; c->br_dev_cap = 0; OCK(hipMalloc(&c->br_dev, dev)); c->br_dev_cap = dev; }
+    if (c->br_pin_cap < pin) { if (c->br_pin) hipHostFree(c->br_pin); c->br_pin = nullptr; c->br_pin_cap = 0; OCK(hipHostMalloc(&c->br_pin, pin, hipHostMallocDefault)); c->br_pin_cap = pin; }
+    return TSORB_OK;
+}
+// an offset array: starts at 0, never decreases, no set above TSORB_BRUTE_MAX_FEAT (limit < 0: no limit)
+static const char *br_offsets(const int32_t *off, int n, int limit) {
+    if (off[0] != 0) return "an offset array does not start at 0";
+    for (int i = 0; i < n; i++) { if (off[i + 1] < off[i]) return "an offset array decreases";
+        if (limit >= 0 && off[i + 1] - off[i] > limit) return "a set has more than TSORB_BRUTE_MAX_FEAT features"; }
+    return nullptr;
+}
+int tsorb_match_brute_text(void *ctx, int n_pair, const int32_t *off1, const uint8_t *desc1, const int32_t *off2, const uint8_t *desc2,
+                           int32_t *train_idx, int32_t *dist, uint8_t *good) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_match_brute_text: ") + m; return TSORB_ERR_ARG; };
+    if (n_pair < 0) return bad("n_pair < 0");
+    if (n_pair == 0) return TSORB_OK;
+    if (!off1 || !off2) return bad("NULL pointer");
+    if (const char *m = br_offsets(off1, n_pair, TSORB_BRUTE_MAX_FEAT)) return bad(m);
+    if (const char *m = br_offsets(off2, n_pair, TSORB_BRUTE_MAX_FEAT)) return bad(m);
+    const size_t nq = (size_t)off1[n_pair], nt = (size_t)off2[n_pair];
+    if (nq == 0) return TSORB_OK;                                               // no query anywhere: nothing to write
+    if (!desc1 || !train_idx || !dist || !good || (nt > 0 && !desc2)) return bad("NULL pointer");
+    hipSetDevice(c->device);
+    size_t ntile = 0;
+    for (int p = 0; p < n_pair; p++) ntile += ((size_t)(off1[p + 1] - off1[p]) + BR_T - 1)/BR_T;
+    // in: [off1 | off2 | tiles | pmin | desc1 | desc2]   out: [train | dist | good]
+    const size_t b_off = br_al(4*((size_t)n_pair + 1)), b_tile = br_al(8*ntile), b_pmin = br_al(4*(size_t)n_pair), b_d1 = br_al(32*nq), b_d2 = br_al(32*nt);
+    const size_t in_sz = 2*b_off + b_tile + b_pmin + b_d1 + b_d2, b_i = br_al(4*nq), out_sz = 2*b_i + br_al(nq);
+    if (int rc = br_room(c, in_sz + out_sz, in_sz + out_sz)) return rc;
+    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
+    memcpy(h, off1, 4*((size_t)n_pair + 1)); memcpy(h + b_off, off2, 4*((size_t)n_pair + 1));
+    { int32_t *t = (int32_t *)(h + 2*b_off); size_t k = 0;
+      for (int p = 0; p < n_pair; p++) for (int q0 = off1[p]; q0 < off1[p + 1]; q0 += BR_T) { t[2*k] = p; t[2*k + 1] = q0; k++; }
+      int32_t *pm = (int32_t *)(h + 2*b_off + b_tile); for (int p = 0; p < n_pair; p++) pm[p] = INT32_MAX; }
+    memcpy(h + 2*b_off + b_tile + b_pmin, desc1, 32*nq);
+    if (nt) memcpy(h + 2*b_off + b_tile + b_pmin + b_d1, desc2, 32*nt);
+    OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
+    BruteText B;
+    B.off1 = (const int *)d; B.off2 = (const int *)(d + b_off); B.tile = (const int2 *)(d + 2*b_off); B.pmin = (int *)(d + 2*b_off + b_tile);
+    B.desc1 = (const uint8_t *)(d + 2*b_off + b_tile + b_pmin); B.desc2 = B.desc1 + b_d1;
+    B.train = (int *)(d + in_sz); B.dist = (int *)(d + in_sz + b_i); B.good = (uint8_t *)(d + in_sz + 2*b_i);
+    hipLaunchKernelGGL(k_brute_text, dim3((unsigned)ntile), dim3(BR_T), 0, c->stream, B);
+    hipLaunchKernelGGL(k_brute_good, dim3((unsigned)ntile), dim3(BR_T), 0, c->stream, B);
+    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    memcpy(train_idx, h + in_sz, 4*nq); memcpy(dist, h + in_sz + b_i, 4*nq); memcpy(good, h + in_sz + 2*b_i, nq);
+    return TSORB_OK;
+}
+
+int tsorb_match_brute_scene(void *ctx, int w, int h, int n1, const float *xy1, const uint8_t *desc1, const uint8_t *has3d1,
+                            int n_cand, const int32_t *off2, const float *xy2, const uint8_t *desc2, const uint8_t *has3d2,
+                            const int32_t *qoff, const double *quad_cur, const double *quad_can, int th_low, double ratio,
+                            int32_t *match12, int32_t *n_match) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_match_brute_scene: ") + m; return TSORB_ERR_ARG; };
+    if (n_cand < 0 || n1 < 0) return bad("a negative count");
+    if (n_cand == 0) return TSORB_OK;
+    if (w < 1 || h < 1 || w > 8192 || h > 8192) return bad("w or h outside [1, 8192]");
+    if (th_low < 0 || th_low > 256) return bad("th_low outside [0, 256]");
+    if (!std::isfinite(ratio) || ratio < 0.0) return bad("ratio not finite or negative");
+    if (n1 > TSORB_BRUTE_MAX_FEAT) return bad("a set has more than TSORB_BRUTE_MAX_FEAT features");
+    if (!off2 || !qoff || !n_match) return bad("NULL pointer");
+    if (const char *m = br_offsets(off2, n_cand, TSORB_BRUTE_MAX_FEAT)) return bad(m);
+    if (const char *m = br_offsets(qoff, n_cand, -1)) return bad(m);
+    const size_t N2 = (size_t)off2[n_cand], NQ = (size_t)qoff[n_cand], N1 = (size_t)n1;
+    if ((N1 > 0 && (!xy1 || !desc1 || !has3d1 || !match12)) || (N2 > 0 && (!xy2 || !desc2 || !has3d2)) || (NQ > 0 && (!quad_cur || !quad_can))) return bad("NULL pointer");
+    for (size_t i = 0; i < 2*N1; i++) if (!std::isfinite(xy1[i])) return bad("a coordinate is not finite");
+    for (size_t i = 0; i < 2*N2; i++) if (!std::isfinite(xy2[i])) return bad("a coordinate is not finite");
+    for (size_t i = 0; i < 8*NQ; i++) if (!std::isfinite(quad_cur[i]) || fabs(quad_cur[i]) > 1073741824.0 || !std::isfinite(quad_can[i]) || fabs(quad_can[i]) > 1073741824.0)
+        return bad("quad coordinate not finite (or beyond 2^30)");
+    if (n1 == 0) { for (int k = 0; k < n_cand; k++) n_match[k] = 0; return TSORB_OK; }
+    hipSetDevice(c->device);
+    // in: [off2 | qoff | quad_cur | quad_can | xy1 | xy2 | desc1 | desc2 | has3d1 | has3d2]   scratch: [md | own]   out: [match12 | n_match]
+    const size_t b_off = br_al(4*((size_t)n_cand + 1)), b_q = br_al(32*NQ), b_xy1 = br_al(8*N1), b_xy2 = br_al(8*N2), b_d1 = br_al(32*N1), b_d2 = br_al(32*N2),
+                 b_h1 = br_al(N1), b_h2 = br_al(N2);
+    const size_t in_sz = 2*b_off + 2*b_q + b_xy1 + b_xy2 + b_d1 + b_d2 + b_h1 + b_h2, b_md = br_al(4*N2), b_m12 = br_al(4*N1*(size_t)n_cand), out_sz = b_m12 + br_al(4*(size_t)n_cand);
+    if (int rc = br_room(c, in_sz + 2*b_md + out_sz, in_sz + out_sz)) return rc;
+    char *hp = (char *)c->br_pin, *d = (char *)c->br_dev;
+    size_t o = 0;
+    const size_t o_off2 = o; memcpy(hp + o, off2, 4*((size_t)n_cand + 1)); o += b_off;
+    const size_t o_qoff = o; memcpy(hp + o, qoff, 4*((size_t)n_cand + 1)); o += b_off;
+    const size_t o_qcur = o; for (size_t i = 0; i < 8*NQ; i++) ((int32_t *)(hp + o))[i] = (int)quad_cur[i]; o += b_q;          // cv::Point(double, double): truncation
+    const size_t o_qcan = o; for (size_t i = 0; i < 8*NQ; i++) ((int32_t *)(hp + o))[i] = (int)quad_can[i]; o += b_q;
+    const size_t o_xy1 = o; memcpy(hp + o, xy1, 8*N1); o += b_xy1;
+    const size_t o_xy2 = o; if (N2) memcpy(hp + o, xy2, 8*N2); o += b_xy2;
+    const size_t o_d1 = o; memcpy(hp + o, desc1, 32*N1); o += b_d1;
+    const size_t o_d2 = o; if (N2) memcpy(hp + o, desc2, 32*N2); o += b_d2;
+    const size_t o_h1 = o; memcpy(hp + o, has3d1, N1); o += b_h1;
+    const size_t o_h2 = o; if (N2) memcpy(hp + o, has3d2, N2); o += b_h2;
+    OCK(hipMemcpyAsync(d, hp, in_sz, hipMemcpyHostToDevice, c->stream));
+    BruteScene S;
+    S.w = w; S.h = h; S.n1 = n1; S.th_low = th_low; S.ratio = ratio;
+    S.xy1 = (const float *)(d + o_xy1); S.desc1 = (const uint8_t *)(d + o_d1); S.has3d1 = (const uint8_t *)(d + o_h1);
+    S.off2 = (const int *)(d + o_off2); S.xy2 = (const float *)(d + o_xy2); S.desc2 = (const uint8_t *)(d + o_d2); S.has3d2 = (const uint8_t *)(d + o_h2);
+    S.qoff = (const int *)(d + o_qoff); S.quad_cur = (const int *)(d + o_qcur); S.quad_can = (const int *)(d + o_qcan);
+    S.md = (int *)(d + in_sz); S.own = (int *)(d + in_sz + b_md);
+    S.match12 = (int *)(d + in_sz + 2*b_md); S.n_match = (int *)(d + in_sz + 2*b_md + b_m12);
+    hipLaunchKernelGGL(k_brute_scene, dim3(n_cand), dim3(BR_T), 0, c->stream, S);
+    OCK(hipMemcpyAsync(hp + in_sz, d + in_sz + 2*b_md, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    memcpy(match12, hp + in_sz, 4*N1*(size_t)n_cand); memcpy(n_match, hp + in_sz + b_m12, 4*(size_t)n_cand);
+    return TSORB_OK;
 }
 
 } // extern "C"

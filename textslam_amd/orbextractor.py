@@ -13,7 +13,8 @@ _lib = None
 EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_get_levels", "tsorb_get_scale_factors",
                     "tsorb_get_features_per_level", "tsorb_extract_batch", "tsorb_upload", "tsorb_run", "tsorb_download",
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
-                    "tsorb_text_extract"]
+                    "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene"]
+BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
 
 
 class TsorbError(RuntimeError):
@@ -46,6 +47,11 @@ def load_library():
         L.tsorb_match_search.argtypes = [vp, C.c_int, fp, fp, ip, up, C.c_int, ip, ip, ip, ip, ip, ip]
         L.tsorb_text_extract.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, fp, up, ip]
         L.tsorb_text_extract.restype = C.c_int
+        dp = C.POINTER(C.c_double)
+        L.tsorb_match_brute_text.argtypes = [vp, C.c_int, ip, up, ip, up, ip, ip, up]
+        L.tsorb_match_brute_text.restype = C.c_int
+        L.tsorb_match_brute_scene.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, up, up, C.c_int, ip, fp, up, up, ip, dp, dp, C.c_int, C.c_double, ip, ip]
+        L.tsorb_match_brute_scene.restype = C.c_int
         _lib = L
     return _lib
 
@@ -157,6 +163,47 @@ class ORBextractor:
                                                 kp.ctypes.data_as(C.POINTER(C.c_float)), desc.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                 cnt.ctypes.data_as(C.POINTER(C.c_int32))), "tsorb_text_extract")
         return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy()) for i in range(n)]
+
+    # ---- loop closing's all-pairs matching (loopClosing::SearchMatch_Text / SearchMatch_Other), every loop candidate in one call
+    def match_brute_text(self, pairs):
+        """pairs: list of (desc1 [n1, 32], desc2 [n2, 32]), one per matched text pair of any candidate.  Returns per pair a dict train_idx [n1] int32
+        (the nearest row of desc2, first index on a tie; -1 for an empty desc2), dist [n1] int32, good [n1] uint8 (dist < max(2 min_dist, 30.0))."""
+        d1 = [np.ascontiguousarray(a, np.uint8).reshape(-1, 32) for a, _ in pairs]; d2 = [np.ascontiguousarray(b, np.uint8).reshape(-1, 32) for _, b in pairs]
+        n = len(pairs)
+        off1 = np.zeros(n + 1, np.int32); off2 = np.zeros(n + 1, np.int32)
+        off1[1:] = np.cumsum([len(a) for a in d1]); off2[1:] = np.cumsum([len(b) for b in d2])
+        a1 = np.concatenate(d1) if n else np.zeros((0, 32), np.uint8); a2 = np.concatenate(d2) if n else np.zeros((0, 32), np.uint8)
+        nq = int(off1[n])
+        ti = np.zeros(max(nq, 1), np.int32); di = np.zeros(max(nq, 1), np.int32); good = np.zeros(max(nq, 1), np.uint8)
+        ip_ = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)); up_ = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+        a1 = np.ascontiguousarray(a1); a2 = np.ascontiguousarray(a2)
+        self._check(self.lib.tsorb_match_brute_text(self.ctx, n, ip_(off1), up_(a1) if a1.size else None, ip_(off2), up_(a2) if a2.size else None,
+                                                    ip_(ti), ip_(di), up_(good)), "tsorb_match_brute_text")
+        return [dict(train_idx=ti[off1[p]:off1[p + 1]].copy(), dist=di[off1[p]:off1[p + 1]].copy(), good=good[off1[p]:off1[p + 1]].copy()) for p in range(n)]
+
+    def match_brute_scene(self, w, h, xy1, desc1, has3d1, cands, th_low=50, ratio=0.9):
+        """The current keyframe's features (xy1 [n1, 2], desc1 [n1, 32], has3d1 [n1]) against every loop candidate.  cands: list of dicts
+        xy [n2, 2], desc [n2, 32], has3d [n2], quad_cur [nq, 4, 2], quad_can [nq, 4, 2] (the text boxes SearchMatch_Text painted for this candidate into
+        the current keyframe's and the candidate's label image).  w, h: the label images' size.  Returns (match12 [n_cand, n1] int32, n_match [n_cand] int32)."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2); desc1 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32)
+        has3d1 = np.ascontiguousarray(has3d1, np.uint8).reshape(-1)
+        n1, nc = xy1.shape[0], len(cands)
+        off2 = np.zeros(nc + 1, np.int32); qoff = np.zeros(nc + 1, np.int32)
+        xy2 = [np.asarray(c["xy"], np.float32).reshape(-1, 2) for c in cands]
+        qc = [np.asarray(c["quad_cur"], np.float64).reshape(-1, 4, 2) for c in cands]; qn = [np.asarray(c["quad_can"], np.float64).reshape(-1, 4, 2) for c in cands]
+        off2[1:] = np.cumsum([len(a) for a in xy2]); qoff[1:] = np.cumsum([len(a) for a in qc])
+        cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(shape, dt), dt)
+        xy2 = cat(xy2, (0, 2), np.float32)
+        desc2 = cat([np.asarray(c["desc"], np.uint8).reshape(-1, 32) for c in cands], (0, 32), np.uint8)
+        has3d2 = cat([np.asarray(c["has3d"], np.uint8).reshape(-1) for c in cands], (0,), np.uint8)
+        qc = cat(qc, (0, 4, 2), np.float64); qn = cat(qn, (0, 4, 2), np.float64)
+        m12 = np.zeros((max(nc, 1), max(n1, 1)), np.int32); nm = np.zeros(max(nc, 1), np.int32)
+        ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a.size else None
+        self._check(self.lib.tsorb_match_brute_scene(self.ctx, int(w), int(h), n1, ptr(xy1, C.c_float), ptr(desc1, C.c_uint8), ptr(has3d1, C.c_uint8),
+                                                     nc, ptr(off2, C.c_int32), ptr(xy2, C.c_float), ptr(desc2, C.c_uint8), ptr(has3d2, C.c_uint8),
+                                                     ptr(qoff, C.c_int32), ptr(qc, C.c_double), ptr(qn, C.c_double), int(th_low), float(ratio),
+                                                     ptr(m12, C.c_int32), ptr(nm, C.c_int32)), "tsorb_match_brute_scene")
+        return m12[:nc, :n1].copy(), nm[:nc].copy()
 
     def debug_fast_shape(self, shape=-1):
         """Diagnostics: the shape of the FAST launches (include/tsorb.h); -1 = chosen by the batch size."""
