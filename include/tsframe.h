@@ -43,7 +43,11 @@ int tsframe_get_level(void *ctx, int level, int which, uint8_t *out);
 /* tool::GetPyramidPts.  mode 0: text features, grid over the detection box box = {PMin.x, PMin.y, PMax.x, PMax.y} (level-0 pixels);
  * mode 1: scene features, grid over the image (box ignored).  xy = n raw features (float x, y at level 0), inv_scale[n_levels].
  * Outputs are level-major, level l in [level_off[l], level_off[l+1]); capacity of every output array: n * n_levels.
- * u, v: level coordinates; idx: IdxToRaw; inten: bilinear intensity on the level image; in: the bilinear sample was inside. */
+ * u, v: level coordinates; idx: IdxToRaw; inten: bilinear intensity on the level image; in: the bilinear sample was inside.
+ * This is tsframe_pyramid_pts_batch for one set: the same kernel in one launch, with this call's own argument checks.  TSFRAME_ERR_ARG: a NULL
+ * pointer (xy only with n > 0; box only with mode 0), n < 0, a mode other than 0 or 1, a grid that is degenerate at some level (cw < 1 or
+ * ch < 1: an empty box) or exceeds 2^31 - 1 cells, n * n_levels above INT32_MAX.  Coordinates are not checked for finiteness or magnitude.
+ * TSFRAME_ERR_STATE: no image set.  On any error no output array is touched; n == 0 gives a zero level_off. */
 int tsframe_pyramid_pts(void *ctx, int mode, const float *xy, int n, const double *box, const double *inv_scale,
                         int32_t *level_off, double *u, double *v, int32_t *idx, double *inten, uint8_t *in);
 
@@ -51,13 +55,13 @@ int tsframe_pyramid_pts(void *ctx, int mode, const float *xy, int n, const doubl
  * launch.  Set i: mode[i] (0 text / 1 scene), its n_i = xy_off[i+1] - xy_off[i] raw features xy[xy_off[i] ..], box[i][4] (read for mode-0 sets only;
  * box may be NULL without one); inv_scale[n_levels].  With L = the context's n_levels, set i owns the elements [xy_off[i]*L, xy_off[i+1]*L) of u, v,
  * idx, inten and in, and row i of level_off[n_set][L + 1]; inside that range the contents and their order, the level_off row (relative to the set's
- * base) and idx (relative to the set's first feature) are exactly what tsframe_pyramid_pts writes for that set alone, so a loop over the single
- * call can be swapped for this one.  The sets are independent of each other.  The inputs go to the device as one block through the pinned
+ * base) and idx (relative to the set's first feature) are exactly what tsframe_pyramid_pts writes for that set alone (it is this call with one
+ * set), so a loop over the single call can be swapped for this one.  The sets are independent of each other.  The inputs go to the device as one block through the pinned
  * staging, one kernel runs (one workgroup per set and level, whatever n_set and n_levels are), the results come back in one copy.
  * n_set == 0 returns TSFRAME_OK without reading any pointer; with n_set > 0 and no feature at all nothing is launched and level_off is zeroed.
  * TSFRAME_ERR_ARG (tsframe_last_error names this function and, where it applies, the set): a NULL pointer where data is needed, n_set < 0, a mode
  * other than 0 or 1, xy_off[0] != 0 or a decreasing xy_off, more than INT32_MAX / n_levels features, a set whose grid is degenerate at some level
- * (cw < 1 or ch < 1: an empty box) as in the single call, and a coordinate of xy, of a mode-0 box or of inv_scale that is not finite or above
+ * (cw < 1 or ch < 1: an empty box) or exceeds 2^31 - 1 cells, as in the single call, and a coordinate of xy, of a mode-0 box or of inv_scale that is not finite or above
  * 2^20 in magnitude.  That last bound keeps the cell index inside an int on the device and in the CPU restatement alike; the single call does not
  * check it.  TSFRAME_ERR_STATE: no image set.  On any error nothing is launched and no output array is touched. */
 int tsframe_pyramid_pts_batch(void *ctx, int n_set, const int32_t *mode /*[n_set], 0 text / 1 scene*/,

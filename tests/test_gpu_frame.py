@@ -1,5 +1,7 @@
 """GPU parity of the BA-pyramid / reference-feature front-end (libtsframe.so through the C ABI) against the CPU oracle: bit-exact
 planes (integer arithmetic), bit-exact fp64 samples (no FMA contraction on either side), identical selections and orders."""
+import ctypes as C
+
 import numpy as np
 import pytest
 from scipy import ndimage
@@ -56,6 +58,38 @@ def test_pyramid_pts_bit_exact(fr, oracle_lib, mode):
             assert np.array_equal(got[k], ref[k]), (n, k)
         if n >= 300:
             assert ref["level_off"][2] - ref["level_off"][1] > 20        # the coarse levels keep a real subset
+
+
+def test_pyramid_pts_refusals_leave_the_outputs_untouched(fr):
+    """tsframe_pyramid_pts through raw ctypes with sentinel-filled outputs: its own argument checks, and the degenerate grid, whose text names no
+    other entry point."""
+    from textslam_amd.frame import Frame
+    fr.GetPyrMat(_img(3), 4)
+    n, L = 50, 4
+    rng = np.random.default_rng(6)
+    box = np.array([200.0, 150.0, 460.0, 260.0])
+    xy = np.stack([rng.uniform(box[0], box[2], n), rng.uniform(box[1], box[3], n)], 1).astype(np.float32)
+    inv = np.array([1.0, 0.5, 0.25, 0.125])
+    ip, dp, fp, up = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+
+    def refused(code, mode=0, box=box, inv=inv, ctx=None):
+        lo = np.full(L + 1, -77, np.int32); u = np.full(n*L, -7.5); v = np.full(n*L, -7.5); I = np.full(n*L, -7.5)
+        idx = np.full(n*L, -77, np.int32); inn = np.full(n*L, 99, np.uint8)
+        ctx = fr.ctx if ctx is None else ctx
+        rc = fr.lib.tsframe_pyramid_pts(ctx, mode, xy.ctypes.data_as(fp), n, None if box is None else box.ctypes.data_as(dp),
+                                        None if inv is None else inv.ctypes.data_as(dp), lo.ctypes.data_as(ip), u.ctypes.data_as(dp), v.ctypes.data_as(dp),
+                                        idx.ctypes.data_as(ip), I.ctypes.data_as(dp), inn.ctypes.data_as(up))
+        assert rc == code, (rc, fr.lib.tsframe_last_error(ctx))
+        assert np.all(lo == -77) and np.all(u == -7.5) and np.all(v == -7.5) and np.all(I == -7.5) and np.all(idx == -77) and np.all(inn == 99)
+        return fr.lib.tsframe_last_error(ctx).decode()
+
+    refused(-1, mode=2)
+    refused(-1, mode=0, box=None)
+    refused(-1, inv=None)
+    fresh = Frame(0)
+    refused(-3, ctx=fresh.ctx)                                              # no image set
+    msg = refused(-1, box=np.array([300.0, 150.0, 300.0, 260.0]))           # an empty box: x0 == x1
+    assert "degenerate feature grid" in msg and "batch" not in msg, msg
 
 
 def test_neighbours_bit_exact_and_edges(fr, oracle_lib):

@@ -1,6 +1,6 @@
 """tsframe_pyramid_pts_batch (include/tsframe.h): tool::GetPyramidPts for all feature sets of a frame in one launch.  Every set's slice is
 compared with np.array_equal / tobytes against the CPU oracle (oracle/tsframe_oracle.c) and against the single call tsframe_pyramid_pts: no
-tolerance anywhere.  The shapes are the smallest that reach every path of the kernel: empty and one-feature sets, grids on both sides of the LDS
+tolerance anywhere.  The single call is the batch of one set, so the same sets go through it too.  The shapes are the smallest that reach every path of the kernel: empty and one-feature sets, grids on both sides of the LDS
 capacity (and two grids in the device scratch at once), one level, eight levels, levels of a few pixels."""
 import ctypes as C
 import math
@@ -56,6 +56,12 @@ def _bytes(d):
     return b"".join(np.ascontiguousarray(d[k]).tobytes() for k in KEYS)
 
 
+def _single(fr, s, inv):
+    """One set through the single call tsframe_pyramid_pts."""
+    m, xy, box = s
+    return fr.GetPyramidPts(xy, box[:2], box[2:], inv) if m == 0 else fr.GetPyramidPtsScene(xy, inv)
+
+
 def _oracle(oracle_lib, sets, pyr, inv):
     return [oracle_lib.frame_pyramid_pts(m, xy, box, pyr, inv) for m, xy, box in sets]
 
@@ -105,8 +111,7 @@ def test_equal_to_the_single_call_byte_for_byte(fr, mixed):
     fr.GetPyrMat(mixed["img"], 4)
     got = fr.GetPyramidPtsBatch(mixed["sets"], INV4)
     for i, (m, xy, box) in enumerate(mixed["sets"]):
-        one = fr.GetPyramidPts(xy, box[:2], box[2:], INV4) if m == 0 else fr.GetPyramidPtsScene(xy, INV4)
-        assert _bytes(got[i]) == _bytes(one), i
+        assert _bytes(got[i]) == _bytes(_single(fr, (m, xy, box), INV4)), i
 
 
 def test_sets_are_independent_and_scratch_is_reused(fr, mixed, oracle_lib):
@@ -142,11 +147,13 @@ def _scene_grid(n, s, w, h):
     return ncell, int(math.sqrt(ncell*wh)), int(math.sqrt(ncell/wh))
 
 
-def test_both_sides_of_the_lds_capacity(fr, oracle_lib):
+@pytest.fixture(scope="module")
+def big(oracle_lib):
+    """A 640 x 480 frame, 4 levels, with six sets whose level-1 grids lie on both sides of the LDS capacity, and the oracle's result per set; shared,
+    read-only."""
     from textslam_amd.frame import PTS_LDS_CELLS
     w, h = 640, 480
     img = _img(24, h, w)
-    fr.GetPyrMat(img, 4)
     pyr = oracle_lib.frame_pyramid(img, 4)
     # the largest n whose level-1 ncell is <= the capacity and the smallest above it; the kernel decides on cw * ch <= ncell, so also the two n
     # on either side of that, and a larger set whose level-1 grid is a second one in the device scratch
@@ -161,11 +168,35 @@ def test_both_sides_of_the_lds_capacity(fr, oracle_lib):
     box = (200.0, 150.0, 460.0, 260.0)
     sets = [(1, _scene(rng, n_lo, w, h), None), (1, _scene(rng, n_lo + 1, w, h), None), (0, _text(rng, 60, box, w, h), box),
             (1, _scene(rng, n - 1, w, h), None), (1, _scene(rng, n, w, h), None), (1, _scene(rng, 40000, w, h), None)]
+    return {"img": img, "sets": sets, "ref": _oracle(oracle_lib, sets, pyr, INV4)}
+
+
+def test_both_sides_of_the_lds_capacity(fr, big):
+    fr.GetPyrMat(big["img"], 4)
+    sets = big["sets"]
     got = fr.GetPyramidPtsBatch(sets, INV4)
-    for i, (g, r) in enumerate(zip(got, _oracle(oracle_lib, sets, pyr, INV4))):
+    for i, (g, r) in enumerate(zip(got, big["ref"])):
         _same(g, r, i)
         cnt = np.diff(r["level_off"])
         assert all(0 < c < len(sets[i][1]) for c in cnt[1:]), (i, cnt)
+    # the single call is the batch of one set: the same choice between LDS and scratch per level, on every one of the six
+    for i, s in enumerate(sets):
+        _same(_single(fr, s, INV4), big["ref"][i], ("single", i))
+
+
+def test_nothing_left_over_in_the_scratch(fr, big):
+    """A grid in the device scratch is initialised by its own workgroup, not by a memset: a large scene set, a small text set whose block lies where that
+    grid lay, a batch of the two and the large set again, on one context."""
+    fr.GetPyrMat(big["img"], 4)
+    scene, text = big["sets"][5], big["sets"][2]
+    assert len(scene[1]) == 40000 and len(text[1]) == 60
+    first = _single(fr, scene, INV4)
+    small = _single(fr, text, INV4)
+    both = fr.GetPyramidPtsBatch([scene, text], INV4)
+    last = _single(fr, scene, INV4)
+    _same(first, big["ref"][5], "first"); _same(small, big["ref"][2], "text"); _same(last, big["ref"][5], "last")
+    _same(both[0], big["ref"][5], "batch scene"); _same(both[1], big["ref"][2], "batch text")
+    assert _bytes(first) == _bytes(last)
 
 
 @pytest.mark.parametrize("shape,levels", [((18, 33), 4), ((18, 33), 1), ((480, 640), 8)])
@@ -178,14 +209,27 @@ def test_level_counts_and_small_levels(fr, oracle_lib, shape, levels):
     rng = np.random.default_rng(27)
     box = (float(np.float32(0.25*w)), float(np.float32(0.2*h)), float(np.float32(0.8*w)), float(np.float32(0.75*h)))
     sets = [(0, _text(rng, 120, box, w, h), box), (1, _scene(rng, 400, w, h), None), (0, _text(rng, 9, box, w, h, extras=False), box)]
+    one = _text(rng, 1, box, w, h, extras=False)
+    extra = [(0, np.zeros((0, 2), np.float32), box), (1, np.zeros((0, 2), np.float32), None), (0, one, box), (1, one, None)]
+    ref = _oracle(oracle_lib, sets + extra, pyr, inv)
     got = fr.GetPyramidPtsBatch(sets, inv)
-    for i, (g, r) in enumerate(zip(got, _oracle(oracle_lib, sets, pyr, inv))):
+    for i, (g, r) in enumerate(zip(got, ref)):
         _same(g, r, i)
         assert len(g["level_off"]) == levels + 1
         if levels == 1:
             assert list(g["level_off"]) == [0, len(sets[i][1])]
     if levels > 1:
         assert 0 < np.diff(got[1]["level_off"])[-1] < 400
+    # the same sets, and sets of no and of one feature in both modes, through the single call
+    for i, (s, r) in enumerate(zip(sets + extra, ref)):
+        g = _single(fr, s, inv)
+        _same(g, r, ("single", i))
+        n = len(s[1])
+        assert len(g["level_off"]) == levels + 1 and g["level_off"][0] == 0 and g["level_off"][1] == n
+        if levels == 1:
+            assert list(g["level_off"]) == [0, n]
+        if n == 0:
+            assert not g["level_off"].any()
 
 
 class _Raw:

@@ -72,65 +72,6 @@ __device__ __forceinline__ bool bilinear(const uint8_t *__restrict__ img, int w,
 
 struct GridDev { int mode, cw, ch; double s, x0, y0, fx, fy; };
 
-// per raw feature: gradient sample, cell, "last qualifying feature of the cell" = max index (tool.cc:678-685: MAX is never updated)
-__global__ __launch_bounds__(256) void k_pts_cells(const float *__restrict__ xy, int n, const uint8_t *__restrict__ grad, int w, int h, GridDev G, int *sel) {
-    const int j = blockIdx.x*256 + threadIdx.x;
-    if (j >= n) return;
-    const double pu = (double)xy[2*j]*G.s, pv = (double)xy[2*j + 1]*G.s;
-    double g; bilinear(grad, w, h, pu, pv, g);
-    int m = (int)round(G.mode == 0 ? (pu - G.x0)/G.fx : pu/G.fx), q = (int)round(G.mode == 0 ? (pv - G.y0)/G.fy : pv/G.fy);
-    if (m == G.cw) m = G.cw - 1;
-    if (q == G.ch) q = G.ch - 1;
-    if (m < 0 || q < 0 || m >= G.cw || q >= G.ch) return;
-    if (G.mode == 0 ? (g > 0.0) : (g >= 0.0)) atomicMax(&sel[q*G.cw + m], j);
-}
-
-// level 0: every raw feature; level l: the cells in the reference's visiting order (x outer, y inner), ordered compaction by one
-// workgroup (a few thousand cells), appended after the previous levels (running offset in cnt[0])
-__global__ __launch_bounds__(1024) void k_pts_emit(const float *__restrict__ xy, int n, int level, const uint8_t *__restrict__ img, int w, int h, GridDev G,
-                                                   const int *__restrict__ sel, int *cnt, int *level_off,
-                                                   double *u, double *v, int *idx, double *inten, uint8_t *in) {
-    __shared__ int s_scan[1024]; __shared__ int s_base;
-    const int tid = threadIdx.x;
-    const int base0 = level == 0 ? 0 : cnt[0];
-    if (level == 0) {
-        for (int j = tid; j < n; j += 1024) {
-            const double pu = xy[2*j], pv = xy[2*j + 1];
-            u[j] = pu; v[j] = pv; idx[j] = j;
-            double I; in[j] = bilinear(img, w, h, pu, pv, I) ? 1 : 0; inten[j] = I;
-        }
-        if (tid == 0) { level_off[0] = 0; level_off[1] = n; cnt[0] = n; }
-        return;
-    }
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    const int ncell = G.cw*G.ch;
-    for (int c0 = 0; c0 < ncell; c0 += 1024) {
-        const int o = c0 + tid;                                // visiting order: o = i3 * ch + i4
-        int j = -1;
-        if (o < ncell) { const int i3 = o / G.ch, i4 = o - i3*G.ch; j = sel[i4*G.cw + i3]; }
-        s_scan[tid] = j >= 0 ? 1 : 0;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {                   // inclusive scan
-            const int t = tid >= d ? s_scan[tid - d] : 0;
-            __syncthreads();
-            s_scan[tid] += t;
-            __syncthreads();
-        }
-        const int rank = s_base + s_scan[tid] - 1, total = s_scan[1023];
-        if (j >= 0) {
-            const int o2 = base0 + rank;
-            const double pu = (double)xy[2*j]*G.s, pv = (double)xy[2*j + 1]*G.s;
-            u[o2] = pu; v[o2] = pv; idx[o2] = j;
-            double I; in[o2] = bilinear(img, w, h, pu, pv, I) ? 1 : 0; inten[o2] = I;
-        }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
-    }
-    if (tid == 0) { cnt[0] = base0 + s_base; level_off[level + 1] = base0 + s_base; }
-}
-
 __device__ __constant__ double NB_DX[8] = { 0, 2, 1, 0, -1, -2, -1, 0 };
 __device__ __constant__ double NB_DY[8] = { 0, 0, -1, -2, -1, 0, 1, 2 };
 // tool::GetNeighbour(INTERVAL8): thread = (feature, tap)
@@ -382,8 +323,8 @@ static void quad_box(const double *quad, double scale, int w, int h, int xy[8], 
     x0 = xMin; x1 = xMax; y0 = yMin; y1 = yMax;
 }
 
-// the cell grid of level l >= 1 for a set of n raw features (host doubles, the reference's expressions: tool.cc:599-616 / :898-907), shared by
-// tsframe_pyramid_pts and tsframe_pyramid_pts_batch; false: degenerate (cw < 1 or ch < 1)
+// the cell grid of level l >= 1 for a set of n raw features (host doubles, the reference's expressions: tool.cc:599-616 / :898-907);
+// false: degenerate (cw < 1 or ch < 1)
 static bool pts_grid(const FCtx *c, int mode, int n, const double *box, int l, double s, GridDev &g) {
     const size_t ncell = (size_t)((double)n*s*s + (mode == 0 ? 100 : 500));
     g.mode = mode; g.s = s; g.x0 = 0.0; g.y0 = 0.0;
@@ -399,6 +340,61 @@ static bool pts_grid(const FCtx *c, int mode, int n, const double *box, int l, d
         g.fx = (double)c->w[l]/(double)g.cw; g.fy = (double)c->h[l]/(double)g.ch;
     }
     return g.cw >= 1 && g.ch >= 1;
+}
+
+// GetPyramidPts on the device, for tsframe_pyramid_pts (one set) and tsframe_pyramid_pts_batch.  pts_set_jobs: the L jobs of one set of n features that
+// starts at feature xy0, level-major, with the LDS / scratch choice per level (sel_ints: the scratch handed out so far); returns the reason of a refusal,
+// which the caller words for its entry point, or NULL.  Both refusals protect memory: the kernel's int indices rest on them, and on the caller's bound
+// of INT32_MAX / L features in all, which out0 needs.
+static const char *pts_set_jobs(const FCtx *c, int mode, int xy0, int n, const double *box, const double *inv_scale, PtsJob *jobs, size_t &sel_ints) {
+    const int L = c->n_levels;
+    for (int l = 0; l < L; l++) {
+        PtsJob &J = jobs[l];
+        J.G = GridDev{mode, 1, 1, 1.0, 0, 0, 1, 1};
+        if (l > 0 && !pts_grid(c, mode, n, box, l, inv_scale[l], J.G)) return "degenerate feature grid (empty box?)";
+        const size_t ncell = (size_t)J.G.cw*(size_t)J.G.ch;
+        if (ncell > (size_t)INT32_MAX) return "feature grid above 2^31 cells";
+        J.img = c->plane[TSFRAME_IMG][l]; J.grad = c->plane[TSFRAME_GRAD][l]; J.w = c->w[l]; J.h = c->h[l];
+        J.level = l; J.xy0 = xy0; J.n = n; J.out0 = xy0*L + l*n;
+        J.sel_off = -1;
+        if (l > 0 && n > 0 && ncell > PTS_LDS_CELLS) { J.sel_off = (long long)sel_ints; sel_ints += ncell; }
+    }
+    return nullptr;
+}
+// pts_run: the jobs of n_set sets (pts_set_jobs) as one block up, one launch of k_pts_batch, one copy back, and the packing copy-out
+static int pts_run(FCtx *c, int n_set, const int32_t *xy_off, const float *xy, const std::vector<PtsJob> &jobs, size_t sel_ints,
+                   int32_t *level_off, double *u, double *v, int32_t *idx, double *inten, uint8_t *in) {
+    const int L = c->n_levels;
+    const size_t total = (size_t)xy_off[n_set];
+    if (total == 0) { memset(level_off, 0, sizeof(int32_t)*(size_t)n_set*(L + 1)); return TSFRAME_OK; }
+    hipSetDevice(c->device);
+    // one block, inputs then outputs: jobs | xy || cnt | u | v | inten | idx | in; then the large grids' scratch (device only)
+    const size_t cap = total*L, nj = jobs.size();
+    const size_t o_xy = al256(sizeof(PtsJob)*nj), o_cnt = o_xy + al256(8*total), o_u = o_cnt + al256(4*nj), o_v = o_u + al256(8*cap), o_I = o_v + al256(8*cap),
+                 o_idx = o_I + al256(8*cap), o_in = o_idx + al256(4*cap), tot = o_in + al256(cap);
+    int rc = ensure_stage(c, tot + 4*sel_ints, tot); if (rc) return rc;
+    uint8_t *h = c->h_stage, *d = c->d_work;
+    memcpy(h, jobs.data(), sizeof(PtsJob)*nj); memcpy(h + o_xy, xy, 8*total);
+    CKF(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_pts_batch, dim3((unsigned)nj), dim3(PTS_NT), 0, c->stream, (const PtsJob *)d, (const float *)(d + o_xy), (int *)(d + tot), (int *)(d + o_cnt),
+                       (double *)(d + o_u), (double *)(d + o_v), (int *)(d + o_idx), (double *)(d + o_I), d + o_in);
+    CKF(hipGetLastError());
+    CKF(hipMemcpyAsync(h + o_cnt, d + o_cnt, tot - o_cnt, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipStreamSynchronize(c->stream));
+    // copy-out: level l of set i lies at out0 = xy_off[i]*L + l*n_i with cnt entries; packed behind the set's base
+    const int *cnt = (const int *)(h + o_cnt);
+    for (int i = 0; i < n_set; i++) {
+        int32_t *lo = level_off + (size_t)i*(L + 1);
+        const size_t base = (size_t)xy_off[i]*L;
+        lo[0] = 0;
+        for (int l = 0; l < L; l++) {
+            const size_t src = (size_t)jobs[(size_t)i*L + l].out0, dst = base + (size_t)lo[l], m = std::min((size_t)cnt[(size_t)i*L + l], (size_t)(xy_off[i + 1] - xy_off[i]));
+            memcpy(u + dst, h + o_u + 8*src, 8*m); memcpy(v + dst, h + o_v + 8*src, 8*m); memcpy(inten + dst, h + o_I + 8*src, 8*m);
+            memcpy(idx + dst, h + o_idx + 4*src, 4*m); memcpy(in + dst, h + o_in + src, m);
+            lo[l + 1] = lo[l] + (int32_t)m;
+        }
+    }
+    return TSFRAME_OK;
 }
 
 extern "C" {
@@ -470,39 +466,13 @@ int tsframe_pyramid_pts(void *ctx, int mode, const float *xy, int n, const doubl
     FCtx *c = (FCtx *)ctx;
     if (!c || n < 0 || (n > 0 && !xy) || !inv_scale || !level_off || !u || !v || !idx || !inten || !in || (mode != 0 && mode != 1) || (mode == 0 && !box)) return TSFRAME_ERR_ARG;
     if (c->n_levels == 0) { c->err = "no image set"; return TSFRAME_ERR_STATE; }
-    hipSetDevice(c->device);
-    const int L = c->n_levels; const size_t cap = (size_t)n*L;
-    // grids (pts_grid)
-    std::vector<GridDev> G(L); size_t max_cell = 1;
-    for (int l = 1; l < L; l++) {
-        if (!pts_grid(c, mode, n, box, l, inv_scale[l], G[l])) { c->err = "degenerate feature grid (empty box?)"; return TSFRAME_ERR_ARG; }
-        max_cell = std::max(max_cell, (size_t)G[l].cw*G[l].ch);
-    }
-    // device scratch: xy | sel | cnt, level_off | u | v | inten | idx | in
-    const size_t o_xy = 0, o_sel = o_xy + al256(sizeof(float)*2*(size_t)std::max(n, 1)), o_cnt = o_sel + al256(sizeof(int)*max_cell), o_u = o_cnt + al256(sizeof(int)*(L + 4)),
-                 o_v = o_u + al256(8*cap), o_I = o_v + al256(8*cap), o_idx = o_I + al256(8*cap), o_in = o_idx + al256(4*cap), tot = o_in + al256(cap);
-    int rc = ensure_stage(c, tot + 256, tot); if (rc) return rc;
-    uint8_t *d = c->d_work;
-    if (n > 0) { memcpy(c->h_stage, xy, sizeof(float)*2*(size_t)n); CKF(hipMemcpyAsync(d + o_xy, c->h_stage, sizeof(float)*2*(size_t)n, hipMemcpyHostToDevice, c->stream)); }
-    int *cnt = (int *)(d + o_cnt), *loff = cnt + 2;
-    for (int l = 0; l < L; l++) {
-        if (l > 0) {
-            CKF(hipMemsetAsync(d + o_sel, 0xff, sizeof(int)*(size_t)G[l].cw*G[l].ch, c->stream));
-            if (n > 0) hipLaunchKernelGGL(k_pts_cells, dim3((n + 255)/256), dim3(256), 0, c->stream, (const float *)(d + o_xy), n,
-                                          (const uint8_t *)c->plane[TSFRAME_GRAD][l], c->w[l], c->h[l], G[l], (int *)(d + o_sel));
-        }
-        hipLaunchKernelGGL(k_pts_emit, dim3(1), dim3(1024), 0, c->stream, (const float *)(d + o_xy), n, l, (const uint8_t *)c->plane[TSFRAME_IMG][l], c->w[l], c->h[l],
-                           l > 0 ? G[l] : GridDev{mode, 1, 1, 1.0, 0, 0, 1, 1}, (const int *)(d + o_sel), cnt, loff,
-                           (double *)(d + o_u), (double *)(d + o_v), (int *)(d + o_idx), (double *)(d + o_I), d + o_in);
-    }
-    CKF(hipMemcpyAsync(c->h_stage + o_cnt, d + o_cnt, tot - o_cnt, hipMemcpyDeviceToHost, c->stream));      // one copy for all outputs
-    CKF(hipStreamSynchronize(c->stream)); CKF(hipGetLastError());
-    const int *hl = (const int *)(c->h_stage + o_cnt) + 2;
-    for (int l = 0; l <= L; l++) level_off[l] = hl[l];
-    const size_t m = (size_t)level_off[L];
-    memcpy(u, c->h_stage + o_u, 8*m); memcpy(v, c->h_stage + o_v, 8*m); memcpy(inten, c->h_stage + o_I, 8*m);
-    memcpy(idx, c->h_stage + o_idx, 4*m); memcpy(in, c->h_stage + o_in, m);
-    return TSFRAME_OK;
+    if (n > INT32_MAX / c->n_levels) { c->err = "more than INT32_MAX / n_levels features"; return TSFRAME_ERR_ARG; }
+    // the batch of one set
+    const int32_t xy_off[2] = { 0, n };
+    std::vector<PtsJob> jobs((size_t)c->n_levels);
+    size_t sel_ints = 0;
+    if (const char *why = pts_set_jobs(c, mode, 0, n, box, inv_scale, jobs.data(), sel_ints)) { c->err = why; return TSFRAME_ERR_ARG; }
+    return pts_run(c, 1, xy_off, xy, jobs, sel_ints, level_off, u, v, idx, inten, in);
 }
 
 int tsframe_pyramid_pts_batch(void *ctx, int n_set, const int32_t *mode, const int32_t *xy_off, const float *xy, const double *box, const double *inv_scale,
@@ -535,54 +505,15 @@ int tsframe_pyramid_pts_batch(void *ctx, int n_set, const int32_t *mode, const i
             int i = 0; while (xy_off[i + 1] <= (int32_t)(k/2)) i++;
             return bad(at_set("coordinate not finite or above 2^20 in magnitude", i));
         }
-    // jobs: one per (set, level), level-major inside a set; the grids are the single call's (pts_grid)
+    // a set's box, then its jobs: a refusal names the first set that has either fault
     std::vector<PtsJob> jobs((size_t)n_set*L);
     size_t sel_ints = 0;
     for (int i = 0; i < n_set; i++) {
-        const int n = xy_off[i + 1] - xy_off[i];
         const double *bx = mode[i] == 0 ? box + 4*(size_t)i : nullptr;
         if (bx) for (int k = 0; k < 4; k++) if (wild(bx[k])) return bad(at_set("box not finite or above 2^20 in magnitude", i));
-        for (int l = 0; l < L; l++) {
-            PtsJob &J = jobs[(size_t)i*L + l];
-            J.G = GridDev{mode[i], 1, 1, 1.0, 0, 0, 1, 1};
-            if (l > 0 && !pts_grid(c, mode[i], n, bx, l, inv_scale[l], J.G)) return bad(at_set("degenerate feature grid (empty box?)", i));
-            const size_t ncell = (size_t)J.G.cw*(size_t)J.G.ch;
-            if (ncell > (size_t)INT32_MAX) return bad(at_set("feature grid above 2^31 cells", i));
-            J.img = c->plane[TSFRAME_IMG][l]; J.grad = c->plane[TSFRAME_GRAD][l]; J.w = c->w[l]; J.h = c->h[l];
-            J.level = l; J.xy0 = xy_off[i]; J.n = n; J.out0 = xy_off[i]*L + l*n;
-            J.sel_off = -1;
-            if (l > 0 && n > 0 && ncell > PTS_LDS_CELLS) { J.sel_off = (long long)sel_ints; sel_ints += ncell; }
-        }
+        if (const char *why = pts_set_jobs(c, mode[i], xy_off[i], xy_off[i + 1] - xy_off[i], bx, inv_scale, &jobs[(size_t)i*L], sel_ints)) return bad(at_set(why, i));
     }
-    if (total == 0) { memset(level_off, 0, sizeof(int32_t)*(size_t)n_set*(L + 1)); return TSFRAME_OK; }
-    hipSetDevice(c->device);
-    // one block, inputs then outputs: jobs | xy || cnt | u | v | inten | idx | in; then the large grids' scratch (device only)
-    const size_t cap = total*L, nj = jobs.size();
-    const size_t o_xy = al256(sizeof(PtsJob)*nj), o_cnt = o_xy + al256(8*total), o_u = o_cnt + al256(4*nj), o_v = o_u + al256(8*cap), o_I = o_v + al256(8*cap),
-                 o_idx = o_I + al256(8*cap), o_in = o_idx + al256(4*cap), tot = o_in + al256(cap);
-    int rc = ensure_stage(c, tot + 4*sel_ints, tot); if (rc) return rc;
-    uint8_t *h = c->h_stage, *d = c->d_work;
-    memcpy(h, jobs.data(), sizeof(PtsJob)*nj); memcpy(h + o_xy, xy, 8*total);
-    CKF(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_pts_batch, dim3((unsigned)nj), dim3(PTS_NT), 0, c->stream, (const PtsJob *)d, (const float *)(d + o_xy), (int *)(d + tot), (int *)(d + o_cnt),
-                       (double *)(d + o_u), (double *)(d + o_v), (int *)(d + o_idx), (double *)(d + o_I), d + o_in);
-    CKF(hipGetLastError());
-    CKF(hipMemcpyAsync(h + o_cnt, d + o_cnt, tot - o_cnt, hipMemcpyDeviceToHost, c->stream));
-    CKF(hipStreamSynchronize(c->stream));
-    // copy-out: level l of set i lies at out0 = xy_off[i]*L + l*n_i with cnt entries; packed behind the set's base, as the single call leaves it
-    const int *cnt = (const int *)(h + o_cnt);
-    for (int i = 0; i < n_set; i++) {
-        int32_t *lo = level_off + (size_t)i*(L + 1);
-        const size_t base = (size_t)xy_off[i]*L;
-        lo[0] = 0;
-        for (int l = 0; l < L; l++) {
-            const size_t src = (size_t)jobs[(size_t)i*L + l].out0, dst = base + (size_t)lo[l], m = std::min((size_t)cnt[(size_t)i*L + l], (size_t)(xy_off[i + 1] - xy_off[i]));
-            memcpy(u + dst, h + o_u + 8*src, 8*m); memcpy(v + dst, h + o_v + 8*src, 8*m); memcpy(inten + dst, h + o_I + 8*src, 8*m);
-            memcpy(idx + dst, h + o_idx + 4*src, 4*m); memcpy(in + dst, h + o_in + src, m);
-            lo[l + 1] = lo[l] + (int32_t)m;
-        }
-    }
-    return TSFRAME_OK;
+    return pts_run(c, n_set, xy_off, xy, jobs, sel_ints, level_off, u, v, idx, inten, in);
 }
 
 int tsframe_neighbours(void *ctx, int level, const double *uv, int n, double mu, double sigma, double *inten8, double *ninten8, uint8_t *in) {

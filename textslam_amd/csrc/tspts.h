@@ -1,11 +1,14 @@
-// tspts.h -- tsframe_pyramid_pts_batch's kernel (included by tsframe.hip after bilinear and GridDev): tool::GetPyramidPts for all feature sets of
-// a frame in ONE launch, one workgroup per (set, level) job.  A job is independent of every other: level l of set i writes at most n_i entries
-// from out0 = xy_off[i]*L + l*n_i and leaves its count in cnt[job]; the host's copy-out closes the gaps, so no workgroup waits for another.
-// Level 0 copies the raw features.  Level l >= 1: the cell grid ("last qualifying feature of the cell" = max index, as k_pts_cells) lives in LDS
-// up to PTS_LDS_CELLS cells, above that in the job's own region of the device scratch; either way this workgroup initialises it, so nothing
-// is left over from an earlier call.  The cells are then emitted in the reference's visiting order (x outer, y inner) by an ordered compaction:
-// wave ballot + popcount, and a sum over the PTS_NT/64 wave totals per chunk of PTS_NT cells.  The per-feature expressions are those of
-// k_pts_cells / k_pts_emit, so a set's results are the single call's to the bit.  Every loop bound (n, cw*ch) comes from the host's job.
+// tspts.h -- tool::GetPyramidPts on the device (included by tsframe.hip after bilinear and GridDev): k_pts_batch serves the feature sets of a frame
+// in ONE launch, one workgroup per (set, level) job, for tsframe_pyramid_pts (one set) and tsframe_pyramid_pts_batch alike; this is the only device
+// code of the function.  A job is independent of every other: level l of set i writes at most n_i entries from out0 = xy_off[i]*L + l*n_i and
+// leaves its count in cnt[job]; the host's copy-out closes the gaps, so no workgroup waits for another.
+// Level 0 copies the raw features.  Level l >= 1 lays the reference's cell grid over the box (text, tool.cc:599-616) or the level image (scene,
+// tool.cc:898-907); the host computes it (pts_grid).  A cell keeps one feature: the reference's search (tool.cc:678-685) compares each gradient
+// with MAX, but MAX is never updated, so the last feature of the cell whose gradient passes (> 0 text, >= 0 scene) wins: the max index.  The grid
+// lives in LDS up to PTS_LDS_CELLS cells, above that in the job's own region of the device scratch; either way this workgroup initialises it,
+// so nothing is left over from an earlier call.  The cells are then emitted in the reference's visiting order (x outer, y inner) by an ordered
+// compaction: wave ballot + popcount, and a sum over the PTS_NT/64 wave totals per chunk of PTS_NT cells.  Every loop bound (n, cw*ch) comes
+// from the host's job.
 #ifndef TSPTS_H
 #define TSPTS_H
 
@@ -32,6 +35,8 @@ __device__ __forceinline__ int pts_level(int *sel, int *s_w, const PtsJob &J, co
     const int ncell = G.cw*G.ch;
     for (int k = tid; k < ncell; k += PTS_NT) sel[k] = -1;
     __syncthreads();
+    // per raw feature (tool.cc:620-637): the gradient sample at the level position, the cell by round() with the max edge folded into the last cell
+    // (m == cw), and the cell's max qualifying index.  A feature outside the grid, where the reference would index past CellIdx, takes no cell.
     for (int j = tid; j < J.n; j += PTS_NT) {
         const double pu = (double)xy[2*j]*G.s, pv = (double)xy[2*j + 1]*G.s;
         double g; bilinear(grad, w, h, pu, pv, g);
