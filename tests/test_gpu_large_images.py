@@ -1,8 +1,10 @@
-"""Text paths on images above 640 x 480: the quad's bit mask in row bands (tsraster.h raster_quad_rows; the BIG instantiations of the mu / sigma and label
-kernels) and the judge's association by point tests.  Every test fails with TSBA_ERR_ARG / TSFRAME_ERR_ARG on a build that caps the text paths at 640 x 480.
+"""Text paths on images above 640 x 480: the quad's bit mask in row bands (tsraster.h raster_quad_rows; csrc/tsquadstat.h quad_moments and k_label band every
+level, and a level of at most 640 x 480 is one band: there is one path) and the judge's association by point tests.  Every test fails with TSBA_ERR_ARG /
+TSFRAME_ERR_ARG on a build that caps the text paths at 640 x 480.
 
-Sizes: 648 x 480 (just past the mask: 474-row bands, only level 0 banded), 1280 x 720 (240-row bands; levels 1 and 2 on the whole-level mask: both kinds in one
-solve), 1920 x 1080 (levels 0 and 1 banded: 160- and 320-row bands).  Tolerances: those of the 640 x 480 tests (test_gpu_parity, test_gpu_theta_batch,
+Sizes: 648 x 480 (just past the mask: 474-row bands, only level 0 takes more than one), 1280 x 720 (240-row bands; levels 1 and 2 fit one band: both in one
+solve), 1920 x 1080 (levels 0 and 1 in several bands: 160- and 320-row bands); box by box also 640 x 480 itself, where plane c's single band is all 480 rows
+and so every word of the mask.  Tolerances: those of the 640 x 480 tests (test_gpu_parity, test_gpu_theta_batch,
 test_gpu_label_at, test_gpu_text_judge) unchanged -- the arithmetic is the same, only the mask's addressing differs; label images and the judge's bits are exact.
 The synthetic problems are synth.camera's; the oracle's results are computed once per size and shared."""
 import functools
@@ -124,9 +126,11 @@ def check_box_conditions(w, h):
     return out
 
 
-@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("w,h", [(640, 480)] + SIZES)
 def test_musigma_and_label_image_box_by_box(gpu, oracle_lib, w, h):
     P, (a, b, c) = boxes_at(w, h)
+    if (w, h) == (640, 480):                                 # the one band of plane c is the whole level: every word of the mask
+        assert w*h == MASK_BITS and clamped_rows(P, 0, P.n_kf - 1, c) == (0, h - 1)
     for fig in check_box_conditions(w, h):
         print("%d x %d level %d (%d x %d): %d of 14 observations with moments, rows of (a, b, c) %s" % ((w, h) + fig[:4] + (fig[4],)))
     ms, lab = boxes_oracle(w, h)

@@ -36,6 +36,7 @@
 #include "../../include/tsba_debug.h"
 #include "tsba_device.h"
 #include "tsraster.h"
+#include "tsquadstat.h"
 #include "tsba_plan.h"
 
 #include "tsba_types.h"
@@ -79,10 +80,6 @@ static void lds_poison_hook(hipStream_t st) {
 }
 #define LAUNCHK(kern, grid, block, lds, st, ...) do { lds_poison_hook(st); hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__); } while (0)
 // ------------------------------------------------------------------------------------------------ host side
-// a kernel with a mu / sigma part, in the instantiation for the level's geometry: BIG where the level's bit mask does not fit MS_MASK_WORDS (musigma_core)
-static inline bool ms_big(int w, int h) { return (size_t)w*(size_t)h > (size_t)MS_MASK_WORDS*32; }
-static inline bool ms_big(const LevelDev &D) { return ms_big(D.img_w, D.img_h); }
-#define LAUNCHK_MS(big, kern, ...) do { if (big) LAUNCHK(kern<true>, __VA_ARGS__); else LAUNCHK(kern<false>, __VA_ARGS__); } while (0)
 static inline bool image_dims_ok(int w, int h) { return w > 0 && h > 0 && w <= TSBA_MAX_IMAGE_DIM && h <= TSBA_MAX_IMAGE_DIM; }
 static int pose_grid(const LevelDev &D) { return std::max(1, (D.n_sc + 255)/256 + (D.n_pf + 31)/32); }    // workgroups of k_pose_iter
 struct Ctx {
@@ -921,7 +918,7 @@ static void launch_pass_init(Ctx *c, const LevelDev &D, int pass) {
     else LAUNCHK(k_gauge, dim3(1), dim3(64), 0, c->stream, W, (const uint8_t *)c->kf_initial, o.state, ncp, D.kf_order);
     if (D.far_B > 0 && D.far_rec) { const int ne = D.n_far_ent;      // the blocks outside the band by keyframe, with the other keyframe's row (the gauge is fixed now)
         if (ne > 0) LAUNCHK(k_far_rows, dim3((ne + 255)/256), dim3(256), 0, c->stream, W, D, ne); }
-    if (D.n_tg > 0) LAUNCHK_MS(ms_big(D), k_musigma, dim3(D.n_tg), dim3(MS_THREADS), 0, c->stream, W, D);
+    if (D.n_tg > 0) LAUNCHK(k_musigma, dim3(D.n_tg), dim3(MS_THREADS), 0, c->stream, W, D);
 }
 // k_mid's blocks: 256 landmarks / pairs each.  tsba_debug_options.trial_launches = 1 / 2 (the k_lin_mid experiment and its comparison partner): 128 (MID_TW: what a
 // workgroup of the linearisation can take over)
@@ -1142,7 +1139,7 @@ static int pose_pass(Ctx *c, int ps, PassCarry &carry) {
     const tsba_options &o = c->opt; const LevelDev &D = c->lev[o.levels[ps]]; const int G = pose_grid(D);
     const bool one_launch = !carry.per_step && grid_resident(c, (const void *)k_pose_pass, POSE_WG, 0, G);
     c->W.hprog = c->hprog; c->W.pass_seq = ++c->pass_seq;                 // (k_pose_begin: k_pass_reset + k_participation + k_gauge + k_musigma in one launch)
-    LAUNCHK_MS(ms_big(D), k_pose_begin, dim3(D.n_tg + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial,
+    LAUNCHK(k_pose_begin, dim3(D.n_tg + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial,
             one_launch ? c->W.ppart : (double *)nullptr, 3*28*G, carry.log_pending ? c->st_log + ps - 1 : (LmState *)nullptr);
     int k_last = -1;                                     // (k_pose_pass leaves the final state in pst[0])
     if (one_launch) LAUNCHK(k_pose_pass, dim3(G), dim3(POSE_WG), 0, c->stream, c->W, D, o, G, o.its[ps]);
@@ -1183,7 +1180,7 @@ static int window_pass(Ctx *c, int ps, PassCarry &carry) {
     c->W.hprog = c->hprog; c->W.pass_seq = ++c->pass_seq; c->W.trace_pass = ps;
     // (at most PB_WG workgroups walk k_participation's npb blocks: every arrival at the ticket is a device-wide fence and an atomic on one word -- 30 - 40 ns each, one after the other: tools/ticket_bench.hip)
     const int npb = (D.n_sc + 255)/256 + (D.n_tg + 3)/4, nwg = std::min(npb, PB_WG), n_ms = carry.ms_ahead == ps ? 0 : D.n_tg;
-    LAUNCHK_MS(ms_big(D), k_pass_begin, dim3(nwg + n_ms), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial, o.state,
+    LAUNCHK(k_pass_begin, dim3(nwg + n_ms), dim3(MS_THREADS), 0, c->stream, c->W, D, o.initial_radius, o.its[ps], (const uint8_t *)c->kf_initial, o.state,
                        npb, nwg, n_ms, carry.log_pending ? c->st_log + ps - 1 : (LmState *)nullptr, c->ticket);
     // k_postlin (the first linearisation's scaling, cost, gradient test: 8.6 us of one workgroup) inside the first trial's assembly
     bool end_decides = false;
@@ -1196,7 +1193,7 @@ static int window_pass(Ctx *c, int ps, PassCarry &carry) {
     PassDec pd{0, 0, 0, tsba_options{}};                 // (+ the workgroup of the last trial's decision, in front: k_decide's arguments)
     if (end_decides) { int nb_pt, nb_tx, nb_pr; mid_blocks(c, D, nb_pt, nb_tx, nb_pr);
         pd = PassDec{1, back_blocks_pt(c->n_pt) + back_blocks_tx(c->n_text) + (c->n_kf + 255)/256, nb_pt + nb_tx + nb_pr, c->opt}; }
-    LAUNCHK_MS(Dn && ms_big(*Dn), k_pass_end, dim3(pd.on + (nb_out + 3)/4 + n_msn + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, Dn ? *Dn : D, nb_out, n_msn, c->musig2[c->musig_sel ^ 1],
+    LAUNCHK(k_pass_end, dim3(pd.on + (nb_out + 3)/4 + n_msn + 1), dim3(MS_THREADS), 0, c->stream, c->W, D, Dn ? *Dn : D, nb_out, n_msn, c->musig2[c->musig_sel ^ 1],
                        o.chi2_mono[ps], o.chi2_text[ps], o.text_bad_ratio, o.outlier_scene, o.outlier_text, pd);
     if (Dn) { c->musig_sel ^= 1; c->W.musig = c->musig2[c->musig_sel]; carry.ms_ahead = ps + 1; }
     record_cov(c, ps);
@@ -1524,9 +1521,7 @@ int tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const t
     auto t1 = std::chrono::steady_clock::now();
     ThArgs A; A.hdr = (const ThHdr *)(db + o_hdr); A.obs = (const ThObs *)(db + o_obs); A.fuv = (const double *)(db + o_uv); A.fref = (const double *)(db + o_ref);
     A.scr = (double *)(db + o_scr); A.out = (ThOut *)(db + o_out);
-    bool big = false;                                              // (one launch walks every pass's level: BIG if any of them needs it)
-    for (int i = 0; i < n; i++) for (int ps = 0; ps < o->n_passes; ps++) big = big || ms_big(probs[i]->img_w[o->levels[ps]], probs[i]->img_h[o->levels[ps]]);
-    void (*const kern)(ThArgs, tsba_options) = big ? k_theta_batch<THETA_WG, true> : k_theta_batch<THETA_WG, false>;
+    void (*const kern)(ThArgs, tsba_options) = k_theta_batch<THETA_WG>;
     LAUNCHK(kern, dim3(n), dim3(THETA_WG), 0, c->stream, A, *o);
     CK(hipGetLastError());
     CK(hipMemcpyAsync(c->tb_out, db + o_out, sizeof(ThOut)*n, hipMemcpyDeviceToHost, c->stream));

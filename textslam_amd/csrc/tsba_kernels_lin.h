@@ -1,43 +1,6 @@
-// Kernels of a linearisation: reductions, start / pass set-up, mu-sigma and label rasters, k_linearize, k_mid, pose sums, k_postlin.  (part of the single translation unit tsba.hip: included there, in this order)
+// Kernels of a linearisation: start / pass set-up, mu-sigma and label rasters, k_linearize, k_mid, pose sums, k_postlin.  (part of the single translation unit tsba.hip: included there, in this order)
 #pragma once
 // ------------------------------------------------------------------------------------------------ kernels
-__device__ __forceinline__ double wave_sum1(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <int NT>
-__device__ __forceinline__ double block_sum(double v, double *lds) {     // deterministic (fixed order), NT threads, all get the result
-    const int t = threadIdx.x;
-    lds[t] = v; __syncthreads();
-    if (t < 64) {
-        double s = lds[t];
-#pragma unroll
-        for (int k = 64; k < NT; k += 64) s += lds[t + k];
-        s = wave_sum1(s);
-        if (t == 0) lds[0] = s;
-    }
-    __syncthreads();
-    const double r = lds[0]; __syncthreads();
-    return r;
-}
-template <int NT>
-__device__ __forceinline__ double block_max(double v, double *lds) {
-    const int t = threadIdx.x;
-    lds[t] = v; __syncthreads();
-    if (t < 64) {
-        double s = lds[t];
-#pragma unroll
-        for (int k = 64; k < NT; k += 64) s = fmax(s, lds[t + k]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s = fmax(s, __shfl_xor(s, o, 64));
-        if (t == 0) lds[0] = s;
-    }
-    __syncthreads();
-    const double r = lds[0]; __syncthreads();
-    return r;
-}
-
 // Sum over a variable-length gather list with U entries (index, then value) in flight per round trip instead of one:
 // val(idx) is evaluated for clamped indices and masked, the summation order is the list order.
 template <int U, class F>
@@ -236,22 +199,14 @@ __global__ __launch_bounds__(1024) void k_gauge_par(Work W, const uint8_t *kf_in
 // with cv::fillPoly's scan conversion (boundary Bresenham lines + 16.16 fixed-point scanline spans).  One workgroup per
 // (KF, text) observation; the polygon mask of the clamped bounding box lives in LDS as a bit field.
 #define MS_THREADS 256
-#ifdef MID_STAMPS                           // (tools/mid_stamps.sh: cycles of a mu / sigma workgroup by phase into W.dbg[56..63] -- the slots of k_schur_t's gradient rows in that build)
-#define MS_STAMP(slot) do { if (threadIdx.x == 0 && dbg) atomicAdd((unsigned long long *)&dbg[56 + (slot)], (unsigned long long)(clock64() - us_t0)); } while (0)
-#else
-#define MS_STAMP(slot) do { } while (0)
-#endif
-// The rasteriser / histogram core shared by musigma_wg and the batched theta solve (tsba_theta.h): one box, one image, NT >= 256 threads (the moments
-// sum the 256 bins through block_sum<NT>: the slots past 255 add +0.0, so every NT gives the bits of NT = 256).  pc: the observing pose, ph: the host
-// pose (h_in) or its T_wr (3x4), th: the plane, (mx, my): box corner tid & 3.  Returns n < 2 (no moments: mu = sigma = 0) as false; *mu / *sigma in
-// every thread otherwise.  LDS: mask [MS_MASK_WORDS], hist [256], s_xy [8], s_bb [4], s_c [16], s_red [NT].
-// BIG = false: w hh <= MS_MASK_WORDS*32, the whole level's mask in LDS.  BIG = true: any size -- the mask is built and read in bands of B = MS_MASK_WORDS*32 / w rows
-// that start at the box's clamped yMin (raster_quad_rows, the one fill: a window of the full image's rows; BIG = false takes raster_quad, the window of all rows), so a box no taller than B rows costs one band.  The moments
-// come from the integer histogram: the same bits whatever the order of the pixels and however they are banded.
-template <int NT, bool BIG>
+// The rasteriser / histogram core shared by musigma_wg and the batched theta solve (tsba_theta.h): one box, one image, NT >= 256 threads.  pc: the observing
+// pose, ph: the host pose (h_in) or its T_wr (3x4), th: the plane, (mx, my): box corner tid & 3.  The four corners are projected and the box is clamped here;
+// the histogram and the moments are quad_moments (tsquadstat.h: the mask in row bands, one band on a level of at most 640 x 480).  Returns n < 2 (no
+// moments: mu = sigma = 0) as false; *mu / *sigma in every thread.  LDS: mask [MS_MASK_WORDS], hist [256], s_xy [8], s_c [16], s_red [NT].
+template <int NT>
 __device__ __forceinline__ bool musigma_core(const double pc[7], const double ph[12], bool h_in, const double th[3], double mx, double my,
                                              const double K[4], int w, int hh, const uint8_t *img,
-                                             unsigned *mask, unsigned *hist, int *s_xy, int *s_bb, int *s_c, double *s_red, double *mu_out, double *sig_out
+                                             unsigned *mask, unsigned *hist, int *s_xy, int *s_c, double *s_red, double *mu_out, double *sig_out
 #ifdef MID_STAMPS
                                              , long long *dbg, long long us_t0
 #endif
@@ -276,103 +231,34 @@ __device__ __forceinline__ bool musigma_core(const double pc[7], const double ph
         s_c[4*b + 3] = cv < (double)(hh + 1) ? (int)floor(cv) : hh + 1;
     }
     __syncthreads();
-    if (tid == 0) {
-        int xMax = max(max(s_c[0], s_c[4]), max(s_c[8], s_c[12])), xMin = min(min(s_c[1], s_c[5]), min(s_c[9], s_c[13]));
-        int yMax = max(max(s_c[2], s_c[6]), max(s_c[10], s_c[14])), yMin = min(min(s_c[3], s_c[7]), min(s_c[11], s_c[15]));
-        if (xMin < 0) xMin = 0;
-        if (xMin >= w) xMin = w - 1;
-        if (yMin < 0) yMin = 0;
-        if (yMin >= hh) yMin = hh - 1;
-        if (xMax >= w) xMax = w - 1;
-        if (xMax < 0) xMax = 0;
-        if (yMax >= hh) yMax = hh - 1;
-        if (yMax < 0) yMax = 0;
-        s_bb[0] = xMin; s_bb[1] = xMax; s_bb[2] = yMin; s_bb[3] = yMax;
-    }
+    // the clamped box, in every thread (the candidates are LDS broadcasts; readfirstlane: the band and pixel loops' bounds are uniform, and the compiler is told so)
+    int xMax = max(max(s_c[0], s_c[4]), max(s_c[8], s_c[12])), xMin = min(min(s_c[1], s_c[5]), min(s_c[9], s_c[13]));
+    int yMax = max(max(s_c[2], s_c[6]), max(s_c[10], s_c[14])), yMin = min(min(s_c[3], s_c[7]), min(s_c[11], s_c[15]));
+    if (xMin < 0) xMin = 0;
+    if (xMin >= w) xMin = w - 1;
+    if (yMin < 0) yMin = 0;
+    if (yMin >= hh) yMin = hh - 1;
+    if (xMax >= w) xMax = w - 1;
+    if (xMax < 0) xMax = 0;
+    if (yMax >= hh) yMax = hh - 1;
+    if (yMax < 0) yMax = 0;
+    xMin = __builtin_amdgcn_readfirstlane(xMin); xMax = __builtin_amdgcn_readfirstlane(xMax);
+    yMin = __builtin_amdgcn_readfirstlane(yMin); yMax = __builtin_amdgcn_readfirstlane(yMax);
     MS_STAMP(1);                                              // (corners projected)
-    if constexpr (BIG) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        const int xMin = s_bb[0], xMax = s_bb[1], yMin = s_bb[2], yMax = s_bb[3];
-        const int bw = xMax - xMin + 1, B = (MS_MASK_WORDS*32)/w;
-        if (bw > 0)
-            for (int yb = yMin; yb <= yMax; yb += B) {
-                const int ye = min(yb + B, yMax + 1), bh = ye - yb;
-                for (int k = tid; k < (bh*w + 31) >> 5; k += NT) mask[k] = 0;
-                __syncthreads();
-                raster_quad_rows(mask, s_xy, w, hh, yb, ye, tid, NT);
-                __syncthreads();
-                const int npx = bw*bh, dx = NT % bw, dy = NT / bw;
-                int x = tid % bw, y = tid / bw;
-                for (int k0 = tid; k0 < npx; k0 += 4*NT) {
-                    int bit[4]; bool in[4]; unsigned px[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        bit[u] = y*w + xMin + x;                      // (band-relative: the image's pixel is yb w further)
-                        in[u] = k0 + u*NT < npx && (mask[bit[u] >> 5] & (1u << (bit[u] & 31)));
-                        x += dx; y += dy; if (x >= bw) { x -= bw; y++; }
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) px[u] = in[u] ? img[yb*w + bit[u]] : 0u;
-#pragma unroll
-                    for (int u = 0; u < 4; u++) if (in[u]) atomicAdd(&hist[px[u]], 1u);
-                }
-                __syncthreads();
-            }
-    } else {
-    for (int k = tid; k < min((w*hh + 31) >> 5, MS_MASK_WORDS); k += NT) mask[k] = 0;
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    const int xMin = s_bb[0], xMax = s_bb[1], yMin = s_bb[2], yMax = s_bb[3];
-    MS_STAMP(2);                                              // (mask cleared)
+    const QuadMoments M = quad_moments<NT>(img, w, hh, s_xy, xMin, xMax, yMin, yMax, mask, hist, s_red
 #ifdef MID_STAMPS
-    raster_quad(mask, s_xy, w, hh, tid, NT, dbg ? dbg + 48 : nullptr);
-#else
-    raster_quad(mask, s_xy, w, hh, tid, NT);
+                                           , dbg, us_t0
 #endif
-    __syncthreads();
-    MS_STAMP(3);                                              // (quad rasterised)
-    // histogram of masked pixels inside the clamped bounding box (tool.cc:1217-1232)
-    int bw = xMax - xMin + 1, bh = yMax - yMin + 1;
-    {   // four pixels per thread and round with their loads in flight together; (x, y) advance without a division per pixel
-        const int npx = bw*bh, dx = NT % bw, dy = NT / bw;
-        int x = tid % bw, y = tid / bw;
-        for (int k0 = tid; k0 < npx; k0 += 4*NT) {
-            int bit[4]; bool in[4]; unsigned px[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                bit[u] = (yMin + y)*w + xMin + x;
-                in[u] = k0 + u*NT < npx && (mask[bit[u] >> 5] & (1u << (bit[u] & 31)));
-                x += dx; y += dy; if (x >= bw) { x -= bw; y++; }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) px[u] = in[u] ? img[bit[u]] : 0u;
-#pragma unroll
-            for (int u = 0; u < 4; u++) if (in[u]) atomicAdd(&hist[px[u]], 1u);
-        }
-    }
-    __syncthreads();
-    MS_STAMP(4);                                              // (histogram)
-    }
-    const double hv = tid < 256 ? (double)hist[tid] : 0.0;
-    double cnt = hv, sum = hv*(double)tid;
-    double n = block_sum<NT>(cnt, s_red), sm = block_sum<NT>(sum, s_red);
-    if (n < 2.0) { *mu_out = 0.0; *sig_out = 0.0; return false; }
-    double mu = sm/n;
-    double d = (double)tid - mu;
-    double ss = block_sum<NT>(hv*d*d, s_red);
-    *mu_out = mu; *sig_out = sqrt(ss/(n - 1.0));
-    return true;
+                                           );
+    *mu_out = M.mu; *sig_out = M.sigma;
+    return M.n >= 2.0;
 }
 
-// ---- mu / sigma of a projected text box: tool::GetProjText x4 + tool::CalTextinfo (src/tool.cc:1178-1262,1655-1728)
-// with cv::fillPoly's scan conversion (boundary Bresenham lines + 16.16 fixed-point scanline spans).  One workgroup per
-// (KF, text) observation; the polygon mask of the clamped bounding box lives in LDS as a bit field.
-template <bool BIG>
+// One workgroup per (KF, text) observation.
 __device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, const int g, const double *pose, const double *theta) {
     __shared__ unsigned mask[MS_MASK_WORDS];
     __shared__ unsigned hist[256];
-    __shared__ int s_xy[8], s_bb[4];
+    __shared__ int s_xy[8];
     __shared__ double s_red[MS_THREADS];
     const int tid = threadIdx.x;
     // (round 6) the group's static record (tobs, keyframe, text, host: one 16-byte load) instead of three lists and then the host; what hangs off it -- the good
@@ -399,7 +285,7 @@ __device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, con
     MS_STAMP(0);                                              // (operands there)
     __shared__ int s_c[16];
     double mu, sigma;
-    const bool ok = musigma_core<MS_THREADS, BIG>(pc, ph, h >= 0, th, mx, my, L.K, L.img_w, L.img_h, img, mask, hist, s_xy, s_bb, s_c, s_red, &mu, &sigma
+    const bool ok = musigma_core<MS_THREADS>(pc, ph, h >= 0, th, mx, my, L.K, L.img_w, L.img_h, img, mask, hist, s_xy, s_c, s_red, &mu, &sigma
 #ifdef MID_STAMPS
                                              , dbg, us_t0
 #endif
@@ -412,9 +298,8 @@ __device__ __forceinline__ void musigma_wg(const Work &W, const LevelDev &L, con
 #endif
 }
 
-template <bool BIG>
 __global__ __launch_bounds__(MS_THREADS) void k_musigma(Work W, LevelDev L) {
-    musigma_wg<BIG>(W, L, blockIdx.x, W.pose[W.st->cur], W.theta[W.st->cur]);
+    musigma_wg(W, L, blockIdx.x, W.pose[W.st->cur], W.theta[W.st->cur]);
 }
 
 // ---- text label image of one keyframe (optimizer::ShowBAReproj_TextBox -> tool::TextBoxWithFill, optimizer.cc:2508-2582,
@@ -444,10 +329,9 @@ __device__ __noinline__ LabelQuad label_quad(const double *pose, const double *t
     return q;
 }
 
-// BIG (a level above MS_MASK_WORDS*32 pixels): every quad in bands of MS_MASK_WORDS*32 / w rows from its clamped yMin (raster_quad_rows, the one fill; raster_quad below is its window of all rows); out[] keeps the full
-// image's index, only the mask's bit is relative to the band.
+// Every quad in bands of MS_MASK_WORDS*32 / w rows from its clamped yMin (raster_quad_rows, the one fill): one band on a level of at most 640 x 480, whatever
+// the quad.  out[] keeps the full image's index, only the mask's bit is relative to the band.
 #define LBL_THREADS 1024
-template <bool BIG>
 __global__ __launch_bounds__(LBL_THREADS) void k_label(Work W, int kf, int w, int hh, double fx, double fy, double cx, double cy, float *out) {
     __shared__ unsigned mask[MS_MASK_WORDS];
     __shared__ int s_xy[8], s_bb[4];
@@ -468,38 +352,22 @@ __global__ __launch_bounds__(LBL_THREADS) void k_label(Work W, int kf, int w, in
             }
             s_bb[0] = max(xMin, 0); s_bb[1] = min(xMax, w - 1); s_bb[2] = max(yMin, 0); s_bb[3] = min(yMax, hh - 1);
         }
-        if constexpr (BIG) {
-            __syncthreads();
-            const int x0 = s_bb[0], x1 = s_bb[1], y0 = s_bb[2], y1 = s_bb[3];
-            const int bw = x1 - x0 + 1, B = (MS_MASK_WORDS*32)/w;
-            for (int yb = y0; yb <= y1; yb += B) {
-                const int ye = min(yb + B, y1 + 1), bh = ye - yb;
-                for (int k = tid; k < (bh*w + 31) >> 5; k += LBL_THREADS) mask[k] = 0;
-                __syncthreads();
-                raster_quad_rows(mask, s_xy, w, hh, yb, ye, tid, LBL_THREADS);
-                __syncthreads();
-                if (bw > 0)
-                    for (int k = tid; k < bw*bh; k += LBL_THREADS) {
-                        const int x = x0 + k % bw, y = k / bw, bit = y*w + x;
-                        if (mask[bit >> 5] & (1u << (bit & 31))) out[(yb + y)*w + x] = (float)rank;
-                    }
-                __syncthreads();
-            }
-            rank++;
-            __syncthreads();
-            continue;
-        }
-        for (int k = tid; k < MS_MASK_WORDS; k += LBL_THREADS) mask[k] = 0;
-        __syncthreads();
-        raster_quad(mask, s_xy, w, hh, tid, LBL_THREADS);
         __syncthreads();
         const int x0 = s_bb[0], x1 = s_bb[1], y0 = s_bb[2], y1 = s_bb[3];     // the filled set lies inside the corners' bounding box
-        const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
-        if (bw > 0 && bh > 0)
-            for (int k = tid; k < bw*bh; k += LBL_THREADS) {
-                const int x = x0 + k % bw, y = y0 + k / bw, bit = y*w + x;
-                if (mask[bit >> 5] & (1u << (bit & 31))) out[bit] = (float)rank;
-            }
+        const int bw = x1 - x0 + 1, B = (MS_MASK_WORDS*32)/w;
+        for (int yb = y0; yb <= y1; yb += B) {
+            const int ye = min(yb + B, y1 + 1), bh = ye - yb;
+            for (int k = tid; k < (bh*w + 31) >> 5; k += LBL_THREADS) mask[k] = 0;
+            __syncthreads();
+            raster_quad_rows(mask, s_xy, w, hh, yb, ye, tid, LBL_THREADS);
+            __syncthreads();
+            if (bw > 0)
+                for (int k = tid; k < bw*bh; k += LBL_THREADS) {
+                    const int x = x0 + k % bw, y = k / bw, bit = y*w + x;
+                    if (mask[bit >> 5] & (1u << (bit & 31))) out[(yb + y)*w + x] = (float)rank;
+                }
+            __syncthreads();
+        }
         rank++;
         __syncthreads();
     }

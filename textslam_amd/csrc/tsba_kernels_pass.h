@@ -37,11 +37,10 @@ __device__ __forceinline__ void gauge_wave_body(const Work &W, const uint8_t *kf
 #define PB_WG 128                           // workgroups that walk k_participation's blocks in k_pass_begin.  Round 6: 24 -> 128 (C4 level 0: 215 blocks, nine in turn per workgroup at ~2 us
                                             // each were the kernel once mu / sigma stopped being it: 20.7 us at 24, 15.9 at 48, 14.4 at 72, 13.6 at 128; the ticket's 128 arrivals cost ~4 us of that)
 #endif
-template <bool BIG>
 __global__ __launch_bounds__(MS_THREADS) void k_pass_begin(Work W, LevelDev L, double radius0, int max_it, const uint8_t *kf_initial, int state,
                                                            int npb, int nwg, int n_ms, LmState *log_prev, int *ticket) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (b >= nwg) { if (b - nwg < n_ms) musigma_wg<BIG>(W, L, b - nwg, W.pose[W.st->cur], W.theta[W.st->cur]); return; }
+    if (b >= nwg) { if (b - nwg < n_ms) musigma_wg(W, L, b - nwg, W.pose[W.st->cur], W.theta[W.st->cur]); return; }
     for (int vb = b; vb < npb; vb += nwg) { participation_wg(W, L, vb, 1); __syncthreads(); }       // (k_participation's block vb: its partial counts go to cntpart[vb])
     __shared__ int s_last; __shared__ int s_cnt2[2];
     if (tid == 0) { __threadfence(); s_last = atomicAdd(ticket, 1) == nwg - 1; s_cnt2[0] = 0; s_cnt2[1] = 0; }
@@ -66,21 +65,20 @@ __global__ __launch_bounds__(MS_THREADS) void k_pass_begin(Work W, LevelDev L, d
 }
 
 // nb_out: k_outlier's blocks of this pass ((n_sc + 63)/64 + n_tg; 0: no outlier pass).  n_ms: text observations of the NEXT pass's level Ln whose mu / sigma
-// go to ms_next (0: there is no next pass, or its level is not on the device yet -- k_pass_begin computes them then).  BIG: the geometry of Ln, not of L
+// go to ms_next (0: there is no next pass, or its level is not on the device yet -- k_pass_begin computes them then).
 // pd.on (windows whose k_mid launches carry the decision block): workgroup 0 takes the FULL decision on the pass's last trial -- k_decide's body, on the state in
 // place -- and the other roles follow from workgroup 1.  They need the decision's outcome only as far as `cur` goes (the final parameters), and that is in the
 // record the last trial's decision block left (W.dec: the same sums in the same order as the full decision, so the same accept / reject); they read no field of
 // the state that the decision writes -- nt_active and the outlier counters (atomics) are not among them.  A pass that ended before its last queued trial: the
 // decision workgroup returns on `done` as k_decide does, and the record's `cur` is the final state's (no decision block has written it since).
 struct PassDec { int on, nb_back, nb_lm; tsba_options o; };
-template <bool BIG>
 __global__ __launch_bounds__(MS_THREADS) void k_pass_end(Work W, LevelDev L, LevelDev Ln, int nb_out, int n_ms, double *ms_next,
                                                          double chi2_mono, double chi2_text, double bad_ratio, int do_scene, int do_text, PassDec pd) {
     static_assert(MS_THREADS == 256, "the decision workgroup is k_decide's: 256 threads");
     if (pd.on && blockIdx.x == 0) { decide_body(W, L, pd.nb_back, pd.nb_lm, pd.o, 0, 0); return; }
     const int b = (int)blockIdx.x - (pd.on ? 1 : 0), tid = threadIdx.x, nbo = (nb_out + 3) >> 2;
     if (b < nbo) { const int ob = 4*b + (tid >> 6); if (ob < nb_out) outlier_wave(W, L, ob, tid & 63, chi2_mono, chi2_text, bad_ratio, do_scene, do_text, nullptr, pd.on ? W.dec->cur : -1); return; }
-    if (b < nbo + n_ms) { Work Wn = W; Wn.musig = ms_next; const int cur = pd.on ? W.dec->cur : W.st->cur; musigma_wg<BIG>(Wn, Ln, b - nbo, W.pose[cur], W.theta[cur]); return; }
+    if (b < nbo + n_ms) { Work Wn = W; Wn.musig = ms_next; const int cur = pd.on ? W.dec->cur : W.st->cur; musigma_wg(Wn, Ln, b - nbo, W.pose[cur], W.theta[cur]); return; }
     for (int k = tid; k < W.n_kf; k += MS_THREADS) W.kf_in[k] = 0;
     for (int k = tid; k < W.n_pt; k += MS_THREADS) W.act_pt[k] = 0;
     for (int k = tid; k < W.n_text; k += MS_THREADS) W.act_tx[k] = 0;

@@ -380,9 +380,8 @@ __global__ __launch_bounds__(POSE_WG) void k_pose_pass(Work W, LevelDev L, tsba_
 
 // pass start of the pose-only path in one launch: workgroups 0 .. n_tg-1 = k_musigma (the pose is the same in both parameter
 // buffers here); workgroup n_tg = k_pass_reset + k_participation + k_gauge for one keyframe
-template <bool BIG>
 __global__ __launch_bounds__(MS_THREADS) void k_pose_begin(Work W, LevelDev L, double radius0, int max_it, const uint8_t *kf_initial, double *sums_nan, int n_nan, LmState *log_prev) {
-    if ((int)blockIdx.x < L.n_tg) { musigma_wg<BIG>(W, L, blockIdx.x, W.pose[0], W.theta[0]); return; }
+    if ((int)blockIdx.x < L.n_tg) { musigma_wg(W, L, blockIdx.x, W.pose[0], W.theta[0]); return; }
     __shared__ int cnt_s, cnt_t;
     const int tid = threadIdx.x;
     if (sums_nan) for (int e = tid; e < n_nan; e += MS_THREADS) sums_nan[e] = __builtin_nan("");      // k_pose_pass: "not there yet"

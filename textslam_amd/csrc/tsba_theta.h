@@ -199,12 +199,11 @@ __device__ __forceinline__ void theta_step(ThState &S, const double tot[10], boo
     S.mcc = mcc; S.step2 = step2; S.fail = fail ? 1 : 0;
 }
 
-// BIG: some level of some plane of the batch is above MS_MASK_WORDS*32 pixels -- every mu / sigma of the launch through the banded mask (the same bits at any size)
-template <int NT, bool BIG>
+template <int NT>
 __global__ __launch_bounds__(NT) void k_theta_batch(ThArgs A, tsba_options o) {
     __shared__ unsigned mask[MS_MASK_WORDS];                 // mu / sigma: the box's polygon mask
     __shared__ unsigned hist[256];
-    __shared__ int s_xy[8], s_bb[4], s_c[16];
+    __shared__ int s_xy[8], s_c[16];
     __shared__ double s_red[NT];                             // mu / sigma moments; the sweep's per-wave sums (NT/64 x 10)
     __shared__ double s_x[3];                                // the point the next sweep is taken at
     __shared__ int s_ctl[2];                                 // done, sweep
@@ -243,7 +242,7 @@ __global__ __launch_bounds__(NT) void k_theta_batch(ThArgs A, tsba_options o) {
                 double pc[7], mu, sigma;
 #pragma unroll
                 for (int k = 0; k < 7; k++) pc[k] = obs[t].pose[k];
-                musigma_core<NT, BIG>(pc, ph, true, x, mx, my, Kl, w, hh, obs[t].img[l], mask, hist, s_xy, s_bb, s_c, s_red, &mu, &sigma
+                musigma_core<NT>(pc, ph, true, x, mx, my, Kl, w, hh, obs[t].img[l], mask, hist, s_xy, s_c, s_red, &mu, &sigma
 #ifdef MID_STAMPS
                                  , nullptr, 0
 #endif

@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/tsframe.h"
 #include "tsraster.h"
+#include "tsquadstat.h"
 
 struct FCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -146,22 +147,6 @@ struct JudgeArgs {
     int w, h, w0, h0, margin, n_dete, dete_words; double Kr[4], K[4], cos_min, zncc_min;
 };
 
-__device__ __forceinline__ double judge_block_sum(double v, double *lds) {      // fixed order: lane-strided column sums, then a wave butterfly
-    const int t = threadIdx.x;
-    lds[t] = v; __syncthreads();
-    if (t < 64) {
-        double s = lds[t];
-#pragma unroll
-        for (int k = 64; k < JUDGE_NT; k += 64) s += lds[t + k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (t == 0) lds[0] = s;
-    }
-    __syncthreads();
-    const double r = lds[0]; __syncthreads();
-    return r;
-}
-
 // tool::GetProjText (Mat31 overload, tool.cc:1593) of the reference pixel (u, v) and tool::GetIntenBilinterPtr on the current level image: the
 // depth's sign is ignored, a sample outside the image (or at a NaN position, which the reference's int conversion sends below 0) gives 0.
 __device__ __forceinline__ double judge_sample(const uint8_t *__restrict__ img, const JudgeArgs &A, const double *th, const double *T, int u, int v) {
@@ -227,14 +212,14 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
                 if (i < JUDGE_CACHE) s_u.cache[i] = c;
                 sr += (double)pix_inten[i0 + i]; sc += c;
             }
-            const double mr = judge_block_sum(sr, s_red)/(double)n, mc = judge_block_sum(sc, s_red)/(double)n;
+            const double mr = block_sum<JUDGE_NT>(sr, s_red)/(double)n, mc = block_sum<JUDGE_NT>(sc, s_red)/(double)n;
             double vr = 0.0, vc = 0.0;
             for (int i = tid; i < n; i += JUDGE_NT) {
                 const double c = i < JUDGE_CACHE ? s_u.cache[i] : judge_sample(img, A, s_th, s_T, pix_uv[2*(i0 + i)], pix_uv[2*(i0 + i) + 1]);
                 const double r = (double)pix_inten[i0 + i];
                 vr += (r - mr)*(r - mr); vc += (c - mc)*(c - mc);
             }
-            const double sdr = sqrt(judge_block_sum(vr, s_red)/(double)(n - 1)), sdc = sqrt(judge_block_sum(vc, s_red)/(double)(n - 1));
+            const double sdr = sqrt(block_sum<JUDGE_NT>(vr, s_red)/(double)(n - 1)), sdc = sqrt(block_sum<JUDGE_NT>(vc, s_red)/(double)(n - 1));
             if (sdr != 0.0 && sdc != 0.0) {
                 double sp = 0.0;
                 for (int i = tid; i < n; i += JUDGE_NT) {
@@ -242,7 +227,7 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
                     const double r = (double)pix_inten[i0 + i];
                     sp += ((r - mr)/sdr)*((c - mc)/sdc);
                 }
-                zncc = judge_block_sum(sp, s_red)/(double)n;
+                zncc = block_sum<JUDGE_NT>(sp, s_red)/(double)n;
             } else {
                 zncc = -100.0;
             }

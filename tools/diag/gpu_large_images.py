@@ -1,5 +1,5 @@
-"""GPU diagnostic (not a pytest): what the text paths cost on images above 640 x 480, where a projected text box's fill mask is built in row bands
-(csrc/tsraster.h raster_quad_rows) instead of whole in LDS, and the judge's association tests points instead of building a mask.
+"""GPU diagnostic (not a pytest): what the text paths cost on images above 640 x 480, where a projected text box's fill mask takes more than one row band
+(csrc/tsraster.h raster_quad_rows, csrc/tsquadstat.h quad_moments), and the judge's association tests points instead of building a mask.
 
 One mid-sized window (8 keyframes x 600 points x 12 text planes, synth.camera) at 640 x 480, 1280 x 720 and 1920 x 1080.  At each size, host clock around the
 call (every call ends in a stream synchronisation), median of --calls calls after a warm-up:
@@ -96,8 +96,8 @@ for w, h in ((640, 480), (1280, 720), (1920, 1080)):
     c_ms = "%.3f vs %.3f ms: %+.1f us per box (%d evaluations)" % (m_all, m_own, (m_all - m_own)*1e3/max(n_eval, 1), n_eval)
     say("%-12s %-10.1f | %-28s | %-28s | %-28s | %-28s | %s" % ("%d x %d" % (w, h), mb, c_local, c_pose, c_label, c_judge, c_ms))
 say()
-say("(Python call overhead -- ctypes, copies of the problem, the label image's allocation -- is inside every column.  640 x 480 runs the whole-level mask and the")
-say(" judge's mask; the larger sizes run the banded mask at level 0 (1920 x 1080: levels 0 and 1) and the judge's point tests.  The whole-frame column compares two")
+say("(Python call overhead -- ctypes, copies of the problem, the label image's allocation -- is inside every column.  Every size runs the same banded mask: one band per box at")
+say(" 640 x 480 (and the judge's mask), several at level 0 of the larger sizes (1920 x 1080: levels 0 and 1), where the judge tests points.  The whole-frame column compares two")
 say(" different solves -- the boxes change mu / sigma and with them the residuals -- so it bounds the cost of a box from above only loosely.)")
 if args.out != "/dev/null":
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
