@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE -- NOT PRODUCT CODE.
 
 ctypes loader for the CPU oracle (oracle/tsba_oracle.c, a plain-C restatement of the reference's
-BA / pose-optimisation algorithm; PARITY UNPINNED, see tsba_oracle.h).  Importable only from
+BA / pose-optimisation algorithm; its cost functors are pinned against the reference's own, the rest is not: see tsba_oracle.h).  Importable only from
 tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.
 """
 import ctypes as C
@@ -660,3 +660,281 @@ def pg_eval(x1, x2, m):
     a = [np.ascontiguousarray(v, np.float64) for v in (x1, x2, m)]
     L.tsloop_oracle_pg_eval(_dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(r), _dp(J1), _dp(J2))
     return r, J1, J2
+
+
+# ---- TextSLAM's own cost functors, compiled from the reference tree against oracle/ref_shims (oracle/ref_driver.cpp; RECALLED.md)
+_REF = False
+
+
+def ref_lib():
+    """oracle/_ref/libtsref.so, or None where it was not built (no reference tree at build time: oracle/Makefile, target `ref`)."""
+    global _REF
+    if _REF is False:
+        so = os.path.join(_HERE, "_ref", "libtsref.so")
+        _REF = C.CDLL(so) if os.path.exists(so) else None
+        if _REF is not None:
+            for name in ("tsref_ba_scene", "tsref_pose_scene", "tsref_ini_scene", "tsref_rho_scene", "tsref_ba_text", "tsref_pose_text", "tsref_ini_text",
+                         "tsref_theta_text", "tsref_sim", "tsref_loop", "tsref_logsim3", "tsref_textproj"):
+                getattr(_REF, name).restype = None
+    return _REF
+
+
+def _f64(a, shape):
+    a = np.ascontiguousarray(a, np.float64).reshape(shape)
+    return a
+
+
+def K33(K4):
+    """(fx, fy, cx, cy) -> the 3x3 matrix the reference hands its functors (K(2,2) = 1)."""
+    return np.array([[K4[0], 0.0, K4[2]], [0.0, K4[1], K4[3]], [0.0, 0.0, 1.0]])
+
+
+def T44(T12):
+    """[n][12] row-major 3x4 -> [n][16] row-major 4x4."""
+    T12 = np.asarray(T12, np.float64).reshape(-1, 12); out = np.zeros((len(T12), 16)); out[:, :12] = T12; out[:, 15] = 1.0
+    return out
+
+
+def quat_plus_jacobian(q):
+    """The oracle's ceres::QuaternionParameterization::ComputeJacobian (4 x 3), RECALLED row C11."""
+    J = np.zeros(12); L = lib(); L.tsba_oracle_quat_plus_jacobian.restype = None
+    L.tsba_oracle_quat_plus_jacobian(_dp(np.ascontiguousarray(q, np.float64)), _dp(J))
+    return J.reshape(4, 3)
+
+
+def ref_ba_scene(obv, ray, K, wx, wy, qcw, tcw, qrw, trw, rho, nw=False):
+    """auto_BAScene (auto_BASceneNW with nw) on n blocks -> (res [n,2], jac [n,2,15] over qcw|tcw|qrw|trw|rho)."""
+    n = len(np.asarray(rho).reshape(-1)); a = [_f64(obv, (n, 2)), _f64(ray, (n, 3)), _f64(K, (3, 3))]
+    b = [_f64(qcw, (n, 4)), _f64(tcw, (n, 3)), _f64(qrw, (n, 4)), _f64(trw, (n, 3)), _f64(rho, (n,))]
+    res = np.zeros((n, 2)); jac = np.zeros((n, 2, 15))
+    ref_lib().tsref_ba_scene(C.c_int(n), C.c_int(int(nw)), _dp(a[0]), _dp(a[1]), _dp(a[2]), C.c_double(wx), C.c_double(wy), *[_dp(v) for v in b], _dp(res), _dp(jac))
+    return res, jac
+
+
+def ref_pose_scene(obv, rayrho, Trw, K, wx, wy, q, t):
+    """auto_PoseOptimScene -> (res [n,2], jac [n,2,7] over q|t).  Trw [n,16]."""
+    n = len(np.asarray(q).reshape(-1, 4)); a = [_f64(obv, (n, 2)), _f64(rayrho, (n, 3)), _f64(Trw, (n, 16)), _f64(K, (3, 3))]
+    b = [_f64(q, (n, 4)), _f64(t, (n, 3))]; res = np.zeros((n, 2)); jac = np.zeros((n, 2, 7))
+    ref_lib().tsref_pose_scene(C.c_int(n), *[_dp(v) for v in a], C.c_double(wx), C.c_double(wy), _dp(b[0]), _dp(b[1]), _dp(res), _dp(jac))
+    return res, jac
+
+
+def ref_ini_scene(obv, ray, K, q, t, rho):
+    """auto_IniBAScene -> (res [n,2], jac [n,2,8] over q|t|rho)."""
+    n = len(np.asarray(rho).reshape(-1)); a = [_f64(obv, (n, 2)), _f64(ray, (n, 3)), _f64(K, (3, 3)), _f64(q, (n, 4)), _f64(t, (n, 3)), _f64(rho, (n,))]
+    res = np.zeros((n, 2)); jac = np.zeros((n, 2, 8))
+    ref_lib().tsref_ini_scene(C.c_int(n), *[_dp(v) for v in a], _dp(res), _dp(jac))
+    return res, jac
+
+
+def ref_rho_scene(obv, ray, Tcr, K, rho):
+    """auto_RhoScene -> (res [n,2], jac [n,2,1])."""
+    n = len(np.asarray(rho).reshape(-1)); a = [_f64(obv, (n, 2)), _f64(ray, (n, 3)), _f64(Tcr, (n, 16)), _f64(K, (3, 3)), _f64(rho, (n,))]
+    res = np.zeros((n, 2)); jac = np.zeros((n, 2, 1))
+    ref_lib().tsref_rho_scene(C.c_int(n), *[_dp(v) for v in a], _dp(res), _dp(jac))
+    return res, jac
+
+
+def _img_ptrs(imgs):
+    """n image pointers for the text functors.  They read img_ptr[1], img_ptr[stride] and img_ptr[stride + 1] before weighting them (a tap
+    on the last row or column reads past the image with weight 0), so every distinct image is handed over as a copy with two spare rows."""
+    h, w = np.asarray(imgs[0]).shape if len(imgs) else (0, 0)
+    pad, order = {}, []
+    for i in imgs:
+        assert i.shape == (h, w) and i.dtype == np.uint8
+        key = (i.__array_interface__["data"][0], i.strides)
+        if key not in pad:
+            b = np.zeros((h + 2, w), np.uint8); b[:h] = i; pad[key] = b
+        order.append(pad[key])
+    return pad, (C.POINTER(C.c_uint8)*max(len(order), 1))(*[_u8p(b) for b in order]), C.c_int(w), C.c_int(h)
+
+
+def ref_ba_text(imgs, rays, ref, mu, sigma, K, wT, qcw, tcw, qrw, trw, theta):
+    """nume_BAText on n blocks: imgs = n images (one shape), rays [n,8,3], ref [n,8] -> res [n,8]."""
+    keep, ptrs, w, h = _img_ptrs(imgs); n = len(imgs)
+    a = [_f64(rays, (n, 8, 3)), _f64(ref, (n, 8)), _f64(mu, (n,)), _f64(sigma, (n,)), _f64(K, (3, 3))]
+    b = [_f64(qcw, (n, 4)), _f64(tcw, (n, 3)), _f64(qrw, (n, 4)), _f64(trw, (n, 3)), _f64(theta, (n, 3))]; res = np.zeros((n, 8))
+    ref_lib().tsref_ba_text(C.c_int(n), ptrs, w, h, *[_dp(v) for v in a], C.c_double(wT), *[_dp(v) for v in b], _dp(res))
+    return res
+
+
+def ref_pose_text(imgs, Twr, theta, rays, ref, mu, sigma, K, wT, q, t):
+    """nume_PoseOptimText -> res [n,8].  Twr [n,16]."""
+    keep, ptrs, w, h = _img_ptrs(imgs); n = len(imgs)
+    a = [_f64(Twr, (n, 16)), _f64(theta, (n, 3)), _f64(rays, (n, 8, 3)), _f64(ref, (n, 8)), _f64(mu, (n,)), _f64(sigma, (n,)), _f64(K, (3, 3))]
+    b = [_f64(q, (n, 4)), _f64(t, (n, 3))]; res = np.zeros((n, 8))
+    ref_lib().tsref_pose_text(C.c_int(n), ptrs, w, h, *[_dp(v) for v in a], C.c_double(wT), _dp(b[0]), _dp(b[1]), _dp(res))
+    return res
+
+
+def ref_ini_text(imgs, rays, ref, mu, sigma, K, q, t, theta):
+    """nume_IniBAText -> res [n,8]."""
+    keep, ptrs, w, h = _img_ptrs(imgs); n = len(imgs)
+    a = [_f64(rays, (n, 8, 3)), _f64(ref, (n, 8)), _f64(mu, (n,)), _f64(sigma, (n,)), _f64(K, (3, 3)), _f64(q, (n, 4)), _f64(t, (n, 3)), _f64(theta, (n, 3))]
+    res = np.zeros((n, 8))
+    ref_lib().tsref_ini_text(C.c_int(n), ptrs, w, h, *[_dp(v) for v in a], _dp(res))
+    return res
+
+
+def ref_theta_text(imgs, rays, ref, mu, sigma, Tcr, K, theta):
+    """nume_thetaText -> res [n,8].  Tcr [n,16] (the functor calls it _Trw)."""
+    keep, ptrs, w, h = _img_ptrs(imgs); n = len(imgs)
+    a = [_f64(rays, (n, 8, 3)), _f64(ref, (n, 8)), _f64(mu, (n,)), _f64(sigma, (n,)), _f64(Tcr, (n, 16)), _f64(K, (3, 3)), _f64(theta, (n, 3))]
+    res = np.zeros((n, 8))
+    ref_lib().tsref_theta_text(C.c_int(n), ptrs, w, h, *[_dp(v) for v in a], _dp(res))
+    return res
+
+
+def ref_sim(P, obv, K, x, inv=False):
+    """auto_sim (auto_siminv with inv) of n matches at one Sim3 x = (q|t|s) -> (res [n,2], jac [n,2,8])."""
+    P = _f64(P, (-1, 3)); n = len(P); obv = _f64(obv, (n, 2)); K = _f64(K, (3, 3)); x = _f64(x, (8,))
+    res = np.zeros((n, 2)); jac = np.zeros((n, 2, 8))
+    ref_lib().tsref_sim(C.c_int(n), C.c_int(int(inv)), _dp(P), _dp(obv), _dp(K), _dp(x), _dp(res), _dp(jac))
+    return res, jac
+
+
+def ref_loop(meas, x1, x2):
+    """numer_loop_ver2 of n connections: meas = S21, x1 / x2 the keyframes' Sim3 (q|t|s) -> res [n,7]."""
+    meas = _f64(meas, (-1, 8)); n = len(meas); x1 = _f64(x1, (n, 8)); x2 = _f64(x2, (n, 8)); res = np.zeros((n, 7))
+    ref_lib().tsref_loop(C.c_int(n), _dp(meas), _dp(x1), _dp(x2), _dp(res))
+    return res
+
+
+def ref_logsim3(q, t, s):
+    q = _f64(q, (-1, 4)); n = len(q); t = _f64(t, (n, 3)); s = _f64(s, (n,)); res = np.zeros((n, 7))
+    ref_lib().tsref_logsim3(C.c_int(n), _dp(q), _dp(t), _dp(s), _dp(res))
+    return res
+
+
+def ref_textproj(ray, Tcr, theta, K):
+    """TextProj, both overloads -> (p [n,3] in the target camera, uv [n,2])."""
+    ray = _f64(ray, (-1, 3)); n = len(ray); Tcr = _f64(Tcr, (n, 16)); theta = _f64(theta, (n, 3)); K = _f64(K, (3, 3)); p = np.zeros((n, 3)); uv = np.zeros((n, 2))
+    ref_lib().tsref_textproj(C.c_int(n), _dp(ray), _dp(Tcr), _dp(theta), _dp(K), _dp(p), _dp(uv))
+    return p, uv
+
+
+TAP_DX = np.array([0, 2, 1, 0, -1, -2, -1, 0], np.float64)          # INTERVAL8, tool.cc:1550-1557
+TAP_DY = np.array([0, 0, -1, -2, -1, 0, 1, 2], np.float64)
+
+
+def _pose_T44(pose7):
+    """T_cw [n,16] of poses (q|t) the way the text functors build it: q.normalized() -> rotation matrix (E2)."""
+    p = np.asarray(pose7, np.float64).reshape(-1, 7); q = p[:, :4]/np.linalg.norm(p[:, :4], axis=1)[:, None]
+    w, x, y, z = q.T; T = np.zeros((len(p), 4, 4)); T[:, 3, 3] = 1.0
+    T[:, 0, 0] = 1 - 2*(y*y + z*z); T[:, 0, 1] = 2*(x*y - w*z); T[:, 0, 2] = 2*(x*z + w*y)
+    T[:, 1, 0] = 2*(x*y + w*z); T[:, 1, 1] = 1 - 2*(x*x + z*z); T[:, 1, 2] = 2*(y*z - w*x)
+    T[:, 2, 0] = 2*(x*z - w*y); T[:, 2, 1] = 2*(y*z + w*x); T[:, 2, 2] = 1 - 2*(x*x + y*y)
+    T[:, :3, 3] = p[:, 4:]
+    return T
+
+
+def _relative_T44(pose_c, pose_r):
+    """T_cr = T_cw T_rw^-1 [n,16] = [R_c R_r^T | t_c - R_c R_r^T t_r], element by element (no BLAS: the same bits on every host)."""
+    Tc, Tr = _pose_T44(pose_c), _pose_T44(pose_r); n = len(Tc); T = np.zeros((n, 4, 4)); T[:, 3, 3] = 1.0
+    for i in range(3):
+        for j in range(3):
+            T[:, i, j] = Tc[:, i, 0]*Tr[:, j, 0] + Tc[:, i, 1]*Tr[:, j, 1] + Tc[:, i, 2]*Tr[:, j, 2]
+    for i in range(3):
+        T[:, i, 3] = Tc[:, i, 3] - (T[:, i, 0]*Tr[:, 0, 3] + T[:, i, 1]*Tr[:, 1, 3] + T[:, i, 2]*Tr[:, 2, 3])
+    return T.reshape(n, 16)
+
+
+def ba_blocks(prob: BAProblem, opt: TsbaOptions, level: int):
+    """The residual blocks of a level in tsba_eval's order (pass_build of tsba_oracle.c, restated on the numpy arrays):
+    -> (scene [ns,3] = (target kf, point, observation index), text [nt,4] = (target kf, text, feature index, observation index))."""
+    sc = []
+    for s in range(len(prob.sobs_kf[level])):
+        if opt.filter_good and not prob.sgood[prob.sobs_flag[level][s]]: continue
+        kf, pt = int(prob.sobs_kf[level][s]), int(prob.sobs_pt[level][s])
+        if prob.pt_host[pt] == kf: continue
+        sc.append((kf, pt, s))
+    tx = []
+    if opt.use_text:
+        for t in range(prob.n_tobs):
+            if opt.filter_good and not prob.tobs_good[t]: continue
+            kf, j = int(prob.tobs_kf[t]), int(prob.tobs_text[t])
+            if prob.text_host[j] == kf: continue
+            for f in range(int(prob.tfeat_off[level][j]), int(prob.tfeat_off[level][j + 1])):
+                if opt.filter_good and not prob.tfgood[prob.tobs_fgood_off[t] + prob.tfeat_raw[level][f]]: continue
+                tx.append((kf, j, f, t))
+    return np.array(sc, np.int64).reshape(-1, 3), np.array(tx, np.int64).reshape(-1, 4)
+
+
+def ref_ba_eval(prob: BAProblem, opt: TsbaOptions, level: int, musigma):
+    """Every residual block of a level through the reference functor optimizer.cc gives it, in tsba_eval's order.  mu / sigma of
+    the text observations are inputs of the functors (musigma [n_tobs,2], e.g. evaluate(...)["musigma"]).
+    -> dict(resid [2 ns + 8 nt]; jac_scene [ns,2,15]: the Jet Jacobian over (qcw|tcw|qrw|trw|rho), frozen-host blocks fill (q|t) only;
+    scene blocks with a host in the window go through auto_BAScene, or with unit weights through auto_BASceneNW;
+    and, where the block also has the form of another functor family (same arguments), that family's values: resid_ini / jac_ini [.,2,8] + idx_ini auto_IniBAScene (unit weights, host at the
+    identity), resid_rho / jac_rho [.,2,1] auto_RhoScene (unit weights), resid_ini_text + idx_ini_text nume_IniBAText, resid_theta_text
+    + idx_theta_text nume_thetaText)."""
+    sc, tx = ba_blocks(prob, opt, level); ns, nt = len(sc), len(tx)
+    pose = np.asarray(prob.pose, np.float64).reshape(-1, 7); rho = np.asarray(prob.rho, np.float64).reshape(-1); theta = np.asarray(prob.theta, np.float64).reshape(-1, 3)
+    K0 = K33(prob.K); Kl4 = np.array(prob.K, np.float64)
+    for _ in range(level): Kl4 = Kl4*0.5                                    # optimizer.cc:43-52
+    Kl = K33(Kl4)
+    out = {"ns": ns, "nt": nt}
+    resid_s = np.zeros((ns, 2)); jac_s = np.zeros((ns, 2, 15))
+    unit = opt.w_sx == 1.0 and opt.w_sy == 1.0
+    ident = np.array([1.0, 0, 0, 0, 0, 0, 0])
+    if ns:
+        kf, pt, so = sc.T; host = np.asarray(prob.pt_host)[pt]
+        obv = np.asarray(prob.sobs_uv0[level], np.float64).reshape(-1, 2)[so]
+        ray = np.concatenate([np.asarray(prob.pt_ray, np.float64).reshape(-1, 2)[pt], np.ones((ns, 1))], axis=1)
+        ba = np.nonzero(host >= 0)[0]; po = np.nonzero(host < 0)[0]
+        if len(ba):
+            a = (obv[ba], ray[ba], K0, opt.w_sx, opt.w_sy, pose[kf[ba], :4], pose[kf[ba], 4:], pose[host[ba], :4], pose[host[ba], 4:], rho[pt[ba]])
+            resid_s[ba], jac_s[ba] = ref_ba_scene(*a, nw=unit)              # unit weights: the unweighted functor (auto_BASceneNW), as GlobalBA adds it
+            if unit:
+                ini = ba[np.all(pose[host[ba]] == ident, axis=1)]
+                if len(ini):
+                    out["resid_ini"], out["jac_ini"] = ref_ini_scene(obv[ini], ray[ini], K0, pose[kf[ini], :4], pose[kf[ini], 4:], rho[pt[ini]])
+                    out["idx_ini"] = ini
+            if unit and np.all(np.asarray(prob.kf_initial) == 1):          # every pose constant: OptimizeLandmarker's form, T_cr a constant of the block
+                Tcr = _relative_T44(pose[kf[ba]], pose[host[ba]])
+                out["resid_rho"], out["jac_rho"] = ref_rho_scene(obv[ba], ray[ba], Tcr, K0, rho[pt[ba]])
+                out["idx_rho"] = ba
+        if len(po):
+            rayrho = np.concatenate([ray[po, :2], rho[pt[po], None]], axis=1)
+            Trw = T44(np.asarray(prob.pt_host_Trw, np.float64).reshape(-1, 12)[pt[po]])
+            r, j = ref_pose_scene(obv[po], rayrho, Trw, K0, opt.w_sx, opt.w_sy, pose[kf[po], :4], pose[kf[po], 4:])
+            resid_s[po] = r; jac_s[po, :, :7] = j
+    resid_t = np.zeros((nt, 8))
+    if nt:
+        kf, j, f, t = tx.T; host = np.asarray(prob.text_host)[j]
+        fuv = np.asarray(prob.tfeat_uv[level], np.float64).reshape(-1, 2)[f]; ref = np.asarray(prob.tfeat_ref[level], np.float64).reshape(-1, 8)[f]
+        rays = np.stack([(fuv[:, None, 0] + TAP_DX[None, :] - Kl4[2])/Kl4[0], (fuv[:, None, 1] + TAP_DY[None, :] - Kl4[3])/Kl4[1], np.ones((nt, 8))], axis=2)   # tool.cc:1561
+        ms = np.asarray(musigma, np.float64).reshape(-1, 2)[t]
+        imgs = prob.img[level]
+        ba = np.nonzero(host >= 0)[0]; po = np.nonzero(host < 0)[0]
+        if len(ba):
+            im = [imgs[k] for k in kf[ba]]
+            resid_t[ba] = ref_ba_text(im, rays[ba], ref[ba], ms[ba, 0], ms[ba, 1], Kl, opt.w_t, pose[kf[ba], :4], pose[kf[ba], 4:], pose[host[ba], :4], pose[host[ba], 4:], theta[j[ba]])
+            if opt.w_t == 1.0:
+                ini = ba[np.all(pose[host[ba]] == ident, axis=1)]
+                if len(ini):
+                    out["resid_ini_text"] = ref_ini_text([imgs[k] for k in kf[ini]], rays[ini], ref[ini], ms[ini, 0], ms[ini, 1], Kl, pose[kf[ini], :4], pose[kf[ini], 4:], theta[j[ini]])
+                    out["idx_ini_text"] = ini
+            if opt.w_t == 1.0 and np.all(np.asarray(prob.kf_initial) == 1):
+                Tcr = _relative_T44(pose[kf[ba]], pose[host[ba]])
+                out["resid_theta_text"] = ref_theta_text(im, rays[ba], ref[ba], ms[ba, 0], ms[ba, 1], Tcr, Kl, theta[j[ba]])
+                out["idx_theta_text"] = ba
+        if len(po):
+            Twr = T44(np.asarray(prob.text_host_Twr, np.float64).reshape(-1, 12)[j[po]])
+            resid_t[po] = ref_pose_text([imgs[k] for k in kf[po]], Twr, theta[j[po]], rays[po], ref[po], ms[po, 0], ms[po, 1], Kl, opt.w_t, pose[kf[po], :4], pose[kf[po], 4:])
+    out["resid"] = np.concatenate([resid_s.reshape(-1), resid_t.reshape(-1)])
+    out["jac_scene"] = jac_s
+    out["scene_blocks"], out["text_blocks"] = sc, tx
+    return out
+
+
+def scene_tangent(jac15, prob: BAProblem, scene_blocks):
+    """Jet Jacobians [ns,2,15] of ref_ba_eval -> the 2 x 13 tangent-space layout of tsba_eval (target 6 | host 6 | rho), through the
+    oracle's plus-Jacobian (RECALLED row C11: still recalled, not pinned).  A frozen-host block keeps its host columns 0."""
+    pose = np.asarray(prob.pose, np.float64).reshape(-1, 7); host = np.asarray(prob.pt_host)[scene_blocks[:, 1]]
+    out = np.zeros((len(jac15), 2, 13))
+    for i, (kf, pt, _) in enumerate(scene_blocks):
+        out[i, :, 0:3] = jac15[i, :, 0:4] @ quat_plus_jacobian(pose[kf, :4]); out[i, :, 3:6] = jac15[i, :, 4:7]
+        if host[i] >= 0:
+            out[i, :, 6:9] = jac15[i, :, 7:11] @ quat_plus_jacobian(pose[host[i], :4]); out[i, :, 9:12] = jac15[i, :, 11:14]; out[i, :, 12] = jac15[i, :, 14]
+    return out

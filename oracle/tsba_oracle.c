@@ -1419,3 +1419,6 @@ void tsba_oracle_default_options(tsba_options *o, int kind) {       /* 0 local, 
         o->outlier_scene = 1; o->outlier_text = 1;
     }
 }
+
+/* test hook: the plus-Jacobian (4 x 3, row-major) the tangent-space Jacobians above are chained through -- RECALLED row C11 */
+void tsba_oracle_quat_plus_jacobian(const double x[4], double J[12]) { quat_plus_jacobian(x, J); }

@@ -1,5 +1,7 @@
-/* TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  PARITY UNPINNED (Ceres / Eigen are not in this image; the LM constants and the
- * trust-region loop are the Ceres 1.x behaviour recalled in SURVEY.md 8c, as in oracle/tsba_oracle.c).
+/* TEST INFRASTRUCTURE -- NOT PRODUCT CODE.  PARITY PINNED for the residuals of auto_sim, auto_siminv and numer_loop_ver2 / logSim3 and
+ * for the Sim3 Jacobians (tests/test_ref_functors.py, against the reference's functors: see oracle/tsba_oracle.h), UNPINNED for the
+ * rest (Ceres / Eigen are not in this image; the LM constants and the trust-region loop are the Ceres 1.x behaviour recalled in
+ * SURVEY.md 8c, as in oracle/tsba_oracle.c).
  *
  * Plain-C restatement of optimizer::OptimizeSim3 (src/optimizer.cc:626-731): the cost functors auto_sim (include/auto_sim.h:28-58)
  * and auto_siminv (include/auto_siminv.h:28-66) over the parameter blocks q (4, ceres::QuaternionParameterization), t (3), s (1),
