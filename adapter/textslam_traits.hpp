@@ -11,6 +11,7 @@
 #include <mapPts.h>
 #include <mapText.h>
 #include <map.h>
+#include <Random.h>
 
 namespace tsba_adapter {
 
@@ -50,6 +51,8 @@ struct TextSlamTraits {
         const double p7[7] = { pose[0], pose[1], pose[2], pose[3], pose[4]/pose[7], pose[5]/pose[7], pose[6]/pose[7] };
         set_pose(kf, p7);
     }
+    // Sim3Solver's index draws (adapter/tsloop_sim3_ransac.hpp): the reference's own generator, Sim3Solver.cc:81
+    static int random_int(int lo, int hi) { return DUtils::Random::RandomInt(lo, hi); }
     // nume_BAText.h:25: the cost functors index cv::Mat::data directly, i.e. continuous CV_8UC1 with step == cols
     static const uint8_t *img(const cv::Mat &im) { CV_Assert(im.type() == CV_8UC1 && im.isContinuous()); return im.data; }
     static int img_w(const cv::Mat &im) { return im.cols; }

@@ -6,6 +6,7 @@
 // iteration: sweep (residuals, closed-form tangent-space Jacobians, Huber weights; 36 sums = 28 J^T W J + 7 J^T W r + cost through LDS
 // transposes), Jacobi-scaled damped 7x7 LDL^T in registers (every thread, redundantly), candidate on the manifold, cost sweep,
 // Ceres' accept / reject / radius logic -- then the 4-pixel inlier test of the reference.
+// tsloop_sim3_batch (tsloop_ransac.h) runs that solve for every loop candidate in one launch, behind the candidate's Sim3Solver RANSAC.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -25,6 +26,7 @@
 struct LCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
     uint8_t *h_stage = nullptr; size_t h_cap = 0; uint8_t *d_buf = nullptr; size_t d_cap = 0;
+    uint8_t *h_out = nullptr; size_t h_out_cap = 0;                     // tsloop_sim3_batch's pinned block out
 };
 #define CKL(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); return TSLOOP_ERR_DEVICE; } } while (0)
 
@@ -98,9 +100,10 @@ __device__ __forceinline__ double wg_sum_to_lane(const double *acc, double *lds 
 
 __device__ __forceinline__ constexpr int sym7(int r, int c) { return r <= c ? r*7 - r*(r - 1)/2 + (c - r) : c*7 - c*(c - 1)/2 + (r - c); }
 
-__global__ __launch_bounds__(SIM_T) void k_sim3_lm(Sim3Dev P, tsloop_options o) {
-    __shared__ double lds[SIM_NW*18*65 + SIM_NW*32];
-    __shared__ double s_tot[40];
+#define SIM_LDS_DOUBLES (SIM_NW*18*65 + SIM_NW*32)
+// The whole LM solve of one Sim3 problem by the calling workgroup (SIM_T threads; lds: SIM_LDS_DOUBLES, s_tot: 40 doubles of LDS).  k_sim3_lm runs it on
+// the one problem of tsloop_optimize_sim3, k_sim3_batch (tsloop_ransac.h) on each candidate's slice after its RANSAC: one statement of the arithmetic.
+__device__ __forceinline__ void sim3_lm_body(const Sim3Dev P, const tsloop_options o, double *lds, double *s_tot) {
     const int tid = threadIdx.x;
     double x[8];
     {   const double n = sqrt(P.sim[0]*P.sim[0] + P.sim[1]*P.sim[1] + P.sim[2]*P.sim[2] + P.sim[3]*P.sim[3]);      // q = q.normalized(), optimizer.cc:639
@@ -265,6 +268,14 @@ __global__ __launch_bounds__(SIM_T) void k_sim3_lm(Sim3Dev P, tsloop_options o) 
     }
 }
 
+__global__ __launch_bounds__(SIM_T) void k_sim3_lm(Sim3Dev P, tsloop_options o) {
+    __shared__ double lds[SIM_LDS_DOUBLES];
+    __shared__ double s_tot[40];
+    sim3_lm_body(P, o, lds, s_tot);
+}
+
+#include "tsloop_ransac.h"
+
 // ------------------------------------------------------------------------------------------------ host side
 extern "C" {
 
@@ -287,6 +298,7 @@ void tsloop_destroy(void *ctx) {
     hipSetDevice(c->device);
     if (c->d_buf) hipFree(c->d_buf);
     if (c->h_stage) hipHostFree(c->h_stage);
+    if (c->h_out) hipHostFree(c->h_out);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -316,6 +328,100 @@ int tsloop_optimize_sim3(void *ctx, tsloop_sim3_problem *p, const tsloop_options
     memcpy(p->sim, h + o_sim, 64); memcpy(r, h + o_rep, sizeof(tsloop_report)); memcpy(p->inlier, h + o_inl, n);
     r->t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return r->termination == 5 ? TSLOOP_ERR_NUMERIC : TSLOOP_OK;
+}
+
+void tsloop_default_options_sim3_ransac(tsloop_sim3_batch_problem *p) { p->min_inliers = 20; p->max_err2 = 45.0; p->optimise = 1; }
+
+int tsloop_sim3_batch(void *ctx, tsloop_sim3_batch_problem *p, const tsloop_options *o) {
+    LCtx *c = (LCtx *)ctx;
+    if (!c) return TSLOOP_ERR_ARG;
+    auto bad = [&](const char *what) { c->err = std::string("tsloop_sim3_batch: ") + what; return TSLOOP_ERR_ARG; };
+    if (!p || !o) return bad("NULL problem or options");
+    if (p->n_cand < 0) return bad("negative n_cand");
+    if (p->n_cand == 0) return TSLOOP_OK;
+    const int nc = p->n_cand;
+    if (!p->off || !p->hyp_off || !p->K2 || !p->ok || !p->sel || !p->n_inlier_ransac || !p->sim_ransac) return bad("NULL pointer");
+    if (p->optimise && (!p->sim || !p->rep)) return bad("NULL sim or rep with optimise");
+    if (p->off[0] != 0 || p->hyp_off[0] != 0) return bad("offsets do not start at 0");
+    for (int k = 0; k < nc; k++) {
+        if (p->off[k + 1] < p->off[k] || p->hyp_off[k + 1] < p->hyp_off[k]) return bad("offsets decrease");
+        if (p->hyp_off[k + 1] - p->hyp_off[k] > TSLOOP_RANSAC_MAX_HYP) return bad("more than TSLOOP_RANSAC_MAX_HYP hypotheses of a candidate");
+    }
+    const size_t n = (size_t)p->off[nc], nh = (size_t)p->hyp_off[nc];
+    if (n > (size_t)INT32_MAX/3) return bad("more matches than the kernels index (3 n must fit an int32)");
+    if (n > 0 && (!p->P1 || !p->P2 || !p->pred1 || !p->pred2 || !p->uv1 || !p->uv2 || !p->inlier)) return bad("NULL match array");
+    if (nh > 0 && !p->triple) return bad("NULL triple");
+    if (p->min_inliers < 0) return bad("min_inliers < 0");
+    if (!std::isfinite(p->max_err2) || p->max_err2 < 0.0) return bad("max_err2 not finite or negative");
+    std::vector<int32_t> act;
+    for (int k = 0; k < nc; k++) {
+        const int nk = p->off[k + 1] - p->off[k];
+        for (int h = p->hyp_off[k]; h < p->hyp_off[k + 1]; h++) {
+            const int32_t *t = p->triple + 3*(size_t)h;
+            if (t[0] < 0 || t[0] >= nk || t[1] < 0 || t[1] >= nk || t[2] < 0 || t[2] >= nk) return bad("triple index outside the candidate");
+            if (t[0] == t[1] || t[0] == t[2] || t[1] == t[2]) return bad("equal indices in a triple");
+        }
+        if (p->hyp_off[k + 1] > p->hyp_off[k]) act.push_back(k);
+    }
+    {   bool fin = true;
+        for (int j = 0; j < 4; j++) fin = fin && std::isfinite(p->K1[j]) && std::isfinite(p->K[j]);
+        for (size_t j = 0; j < 4*(size_t)nc; j++) fin = fin && std::isfinite(p->K2[j]);
+        for (size_t j = 0; j < 3*n; j++) fin = fin && std::isfinite(p->P1[j]) && std::isfinite(p->P2[j]);
+        for (size_t j = 0; j < 2*n; j++) fin = fin && std::isfinite(p->pred1[j]) && std::isfinite(p->pred2[j]) && std::isfinite(p->uv1[j]) && std::isfinite(p->uv2[j]);
+        if (!fin) return bad("non-finite P, pred, uv or K"); }
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t na = act.size();
+    // a candidate without hypotheses (N < mRansacMinInliers, Sim3Solver.cc:65-69) is answered here: not ok, nothing selected, no work of its own
+    auto fill_idle = [&]() {
+        for (int k = 0; k < nc; k++) if (p->hyp_off[k + 1] == p->hyp_off[k]) {
+            p->ok[k] = 0; p->sel[k] = -1; p->n_inlier_ransac[k] = 0; memset(p->sim_ransac + 8*(size_t)k, 0, 64);
+            if (p->off[k + 1] > p->off[k]) memset(p->inlier + p->off[k], 0, (size_t)(p->off[k + 1] - p->off[k]));
+        } };
+    if (na == 0) { fill_idle(); return TSLOOP_OK; }
+    hipSetDevice(c->device);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t off = 0; auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
+    const size_t o_cand = take(4*na), o_off = take(4*((size_t)nc + 1)), o_hoff = take(4*((size_t)nc + 1)), o_tri = take(12*nh), o_K2 = take(32*(size_t)nc),
+                 o_P1 = take(24*n), o_P2 = take(24*n), o_q1 = take(16*n), o_q2 = take(16*n), o_u1 = take(8*n), o_u2 = take(8*n), in_end = off,      // uploaded
+                 o_ok = take(4*(size_t)nc), o_sel = take(4*(size_t)nc), o_ni = take(4*(size_t)nc), o_hc = take(4*nh), o_sr = take(64*(size_t)nc), o_sim = take(64*(size_t)nc),
+                 o_hs = take(64*nh), o_rep = take(sizeof(tsloop_report)*(size_t)nc), o_inl = take(n), tot = off, out_sz = tot - in_end;             // downloaded
+    if (in_end > c->h_cap) { if (c->h_stage) hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_cap = 0; CKL(hipHostMalloc((void **)&c->h_stage, in_end, hipHostMallocDefault)); c->h_cap = in_end; }
+    if (out_sz > c->h_out_cap) { if (c->h_out) hipHostFree(c->h_out); c->h_out = nullptr; c->h_out_cap = 0; CKL(hipHostMalloc((void **)&c->h_out, out_sz, hipHostMallocDefault)); c->h_out_cap = out_sz; }
+    if (tot > c->d_cap) { if (c->d_buf) hipFree(c->d_buf); c->d_buf = nullptr; c->d_cap = 0; CKL(hipMalloc((void **)&c->d_buf, tot)); c->d_cap = tot; }
+    uint8_t *h = c->h_stage, *d = c->d_buf; auto out_at = [&](size_t o_x) { return (const uint8_t *)c->h_out + (o_x - in_end); };   // output x in the pinned block out
+    memcpy(h + o_cand, act.data(), 4*na); memcpy(h + o_off, p->off, 4*((size_t)nc + 1)); memcpy(h + o_hoff, p->hyp_off, 4*((size_t)nc + 1));
+    memcpy(h + o_tri, p->triple, 12*nh); memcpy(h + o_K2, p->K2, 32*(size_t)nc);
+    memcpy(h + o_P1, p->P1, 24*n); memcpy(h + o_P2, p->P2, 24*n); memcpy(h + o_q1, p->pred1, 16*n); memcpy(h + o_q2, p->pred2, 16*n);
+    memcpy(h + o_u1, p->uv1, 8*n); memcpy(h + o_u2, p->uv2, 8*n);
+    CKL(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));                            // one copy in, one launch, one copy out
+    Sim3BatchDev B;
+    B.cand = (const int32_t *)(d + o_cand); B.off = (const int32_t *)(d + o_off); B.hyp_off = (const int32_t *)(d + o_hoff); B.triple = (const int32_t *)(d + o_tri);
+    B.P1 = (const double *)(d + o_P1); B.P2 = (const double *)(d + o_P2); B.pred1 = (const double *)(d + o_q1); B.pred2 = (const double *)(d + o_q2);
+    B.uv1 = (const float *)(d + o_u1); B.uv2 = (const float *)(d + o_u2); B.K2 = (const double *)(d + o_K2);
+    memcpy(B.K1, p->K1, sizeof(B.K1)); memcpy(B.K, p->K, sizeof(B.K)); B.max_err2 = p->max_err2; B.min_inliers = p->min_inliers; B.optimise = p->optimise ? 1 : 0;
+    B.ok = (int32_t *)(d + o_ok); B.sel = (int32_t *)(d + o_sel); B.ninl = (int32_t *)(d + o_ni); B.hyp_count = (int32_t *)(d + o_hc);
+    B.sim_ransac = (double *)(d + o_sr); B.sim = (double *)(d + o_sim); B.hyp_sim = (double *)(d + o_hs); B.rep = (tsloop_report *)(d + o_rep); B.inlier = d + o_inl;
+    hipLaunchKernelGGL(k_sim3_batch, dim3((unsigned)na), dim3(SIM_T), 0, c->stream, B, *o);
+    CKL(hipMemcpyAsync(c->h_out, d + in_end, out_sz, hipMemcpyDeviceToHost, c->stream));
+    CKL(hipStreamSynchronize(c->stream)); CKL(hipGetLastError());
+    const double t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    fill_idle();
+    int rc = TSLOOP_OK;
+    for (size_t a = 0; a < na; a++) {
+        const size_t k = (size_t)act[a];
+        const int ok = ((const int32_t *)out_at(o_ok))[k];
+        p->ok[k] = ok ? 1 : 0; p->sel[k] = ((const int32_t *)out_at(o_sel))[k]; p->n_inlier_ransac[k] = ((const int32_t *)out_at(o_ni))[k];
+        memcpy(p->sim_ransac + 8*k, out_at(o_sr) + 64*k, 64);
+        memcpy(p->inlier + p->off[k], out_at(o_inl) + p->off[k], (size_t)(p->off[k + 1] - p->off[k]));
+        if (ok && p->optimise) {
+            memcpy(p->sim + 8*k, out_at(o_sim) + 64*k, 64); memcpy(p->rep + k, out_at(o_rep) + sizeof(tsloop_report)*k, sizeof(tsloop_report));
+            p->rep[k].t_ms = t_ms;
+            if (p->rep[k].termination == 5) rc = TSLOOP_ERR_NUMERIC;
+        }
+    }
+    if (p->hyp_count) memcpy(p->hyp_count, out_at(o_hc), 4*nh);
+    if (p->hyp_sim) memcpy(p->hyp_sim, out_at(o_hs), 64*nh);
+    return rc;
 }
 
 void tsloop_default_options_loop(tsloop_options *o) {

@@ -2,6 +2,7 @@
 
   LoopOptimizer.OptimizeSim3(...)     optimizer::OptimizeSim3     /root/reference/src/optimizer.cc:626-731
   LoopOptimizer.OptimizeLoop(...)     optimizer::OptimizeLoop     /root/reference/src/optimizer.cc:733-957 (the solve; the map update stays with the caller)
+  LoopOptimizer.Sim3Batch(...)        Sim3Solver::iterate + optimizer::OptimizeSim3 of every loop candidate, one launch (src/Sim3Solver.cc:59-253)
 
 No CPU fallback: without the HIP library / a GPU every call raises.
 """
@@ -12,7 +13,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libtsloop.so")
 EXPORTED_SYMBOLS = ["tsloop_default_options_sim3", "tsloop_default_options_loop", "tsloop_create", "tsloop_destroy", "tsloop_last_error",
-                    "tsloop_optimize_sim3", "tsloop_optimize_loop"]
+                    "tsloop_optimize_sim3", "tsloop_optimize_loop", "tsloop_default_options_sim3_ransac", "tsloop_sim3_batch"]
+RANSAC_MAX_HYP = 64                    # TSLOOP_RANSAC_MAX_HYP
 
 
 class TsloopOptions(C.Structure):
@@ -36,6 +38,49 @@ class TsloopSim3Problem(C.Structure):
 class TsloopGraphProblem(C.Structure):
     _fields_ = [("n_kf", C.c_int32), ("n_edge", C.c_int32), ("pose", C.POINTER(C.c_double)), ("fixed", C.POINTER(C.c_uint8)),
                 ("edge_i", C.POINTER(C.c_int32)), ("edge_j", C.POINTER(C.c_int32)), ("meas", C.POINTER(C.c_double))]
+
+
+class TsloopSim3BatchProblem(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("optimise", C.c_int32),
+                ("off", C.POINTER(C.c_int32)), ("hyp_off", C.POINTER(C.c_int32)), ("triple", C.POINTER(C.c_int32)),
+                ("P1", C.POINTER(C.c_double)), ("P2", C.POINTER(C.c_double)), ("pred1", C.POINTER(C.c_double)), ("pred2", C.POINTER(C.c_double)),
+                ("uv1", C.POINTER(C.c_float)), ("uv2", C.POINTER(C.c_float)), ("K2", C.POINTER(C.c_double)),
+                ("K1", C.c_double*4), ("K", C.c_double*4), ("min_inliers", C.c_int32), ("pad", C.c_int32), ("max_err2", C.c_double),
+                ("ok", C.POINTER(C.c_uint8)), ("sel", C.POINTER(C.c_int32)), ("n_inlier_ransac", C.POINTER(C.c_int32)),
+                ("sim_ransac", C.POINTER(C.c_double)), ("sim", C.POINTER(C.c_double)), ("rep", C.POINTER(TsloopReport)),
+                ("inlier", C.POINTER(C.c_uint8)), ("hyp_count", C.POINTER(C.c_int32)), ("hyp_sim", C.POINTER(C.c_double))]
+
+
+def make_sim3_batch_problem(cands, K1, K, optimise=True, min_inliers=20, max_err2=45.0, fill=None):
+    """cands: per candidate a dict(P1 [n,3], P2, pred1 [n,2], pred2, uv1, uv2, triples [H,3], K2 [4]).  Returns (struct, arrays): arrays holds the flat inputs
+    and the outputs the struct points at.  fill = (byte, int32, float64): what the outputs hold before the call (tests look for what is left untouched)."""
+    nc = len(cands)
+    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(c[key], dt).reshape(-1, w) for c in cands]) if nc else np.zeros((0, w), dt))
+    A = {"P1": cat("P1", np.float64, 3), "P2": cat("P2", np.float64, 3), "pred1": cat("pred1", np.float64, 2), "pred2": cat("pred2", np.float64, 2),
+         "uv1": cat("uv1", np.float32, 2), "uv2": cat("uv2", np.float32, 2), "triple": cat("triples", np.int32, 3), "K2": cat("K2", np.float64, 4)}
+    ns = [len(np.asarray(c["P1"]).reshape(-1, 3)) for c in cands]; hs = [len(np.asarray(c["triples"]).reshape(-1, 3)) for c in cands]
+    for c, n in zip(cands, ns):
+        assert all(np.asarray(c[key]).size == n*w for key, w in (("P2", 3), ("pred1", 2), ("pred2", 2), ("uv1", 2), ("uv2", 2)))
+    A["off"] = np.concatenate([[0], np.cumsum(ns)]).astype(np.int32); A["hyp_off"] = np.concatenate([[0], np.cumsum(hs)]).astype(np.int32)
+    n, nh = int(A["off"][-1]), int(A["hyp_off"][-1])
+    fb, fi, fd = fill if fill is not None else (0, 0, 0.0)
+    A["ok"] = np.full(nc, fb, np.uint8); A["sel"] = np.full(nc, fi, np.int32); A["n_inlier_ransac"] = np.full(nc, fi, np.int32)
+    A["sim_ransac"] = np.full((nc, 8), fd); A["sim"] = np.full((nc, 8), fd); A["inlier"] = np.full(n, fb, np.uint8)
+    A["hyp_count"] = np.full(nh, fi, np.int32); A["hyp_sim"] = np.full((nh, 8), fd)
+    A["rep"] = (TsloopReport*max(nc, 1))()
+    if fill is not None:
+        C.memset(A["rep"], fb, C.sizeof(A["rep"]))
+    p = TsloopSim3BatchProblem()
+    p.n_cand = nc; p.optimise = 1 if optimise else 0; p.min_inliers = int(min_inliers); p.max_err2 = float(max_err2)
+    for k in range(4):
+        p.K1[k] = float(K1[k]); p.K[k] = float(K[k])
+    for name, ct in (("off", C.c_int32), ("hyp_off", C.c_int32), ("triple", C.c_int32), ("P1", C.c_double), ("P2", C.c_double), ("pred1", C.c_double),
+                     ("pred2", C.c_double), ("uv1", C.c_float), ("uv2", C.c_float), ("K2", C.c_double), ("ok", C.c_uint8), ("sel", C.c_int32),
+                     ("n_inlier_ransac", C.c_int32), ("sim_ransac", C.c_double), ("sim", C.c_double), ("inlier", C.c_uint8), ("hyp_count", C.c_int32),
+                     ("hyp_sim", C.c_double)):
+        setattr(p, name, A[name].ctypes.data_as(C.POINTER(ct)))
+    p.rep = C.cast(A["rep"], C.POINTER(TsloopReport))
+    return p, A
 
 
 def make_graph_problem(pose, fixed, edge_i, edge_j, meas):
@@ -85,6 +130,8 @@ class LoopOptimizer:
         L.tsloop_optimize_sim3.argtypes = [C.c_void_p, C.POINTER(TsloopSim3Problem), C.POINTER(TsloopOptions), C.POINTER(TsloopReport)]
         L.tsloop_default_options_loop.argtypes = [C.POINTER(TsloopOptions)]; L.tsloop_default_options_loop.restype = None
         L.tsloop_optimize_loop.argtypes = [C.c_void_p, C.POINTER(TsloopGraphProblem), C.POINTER(TsloopOptions), C.POINTER(TsloopReport)]
+        L.tsloop_default_options_sim3_ransac.argtypes = [C.POINTER(TsloopSim3BatchProblem)]; L.tsloop_default_options_sim3_ransac.restype = None
+        L.tsloop_sim3_batch.argtypes = [C.c_void_p, C.POINTER(TsloopSim3BatchProblem), C.POINTER(TsloopOptions)]; L.tsloop_sim3_batch.restype = C.c_int
         self.ctx = C.c_void_p()
         rc = L.tsloop_create(device, C.byref(self.ctx))
         if rc != 0:
@@ -108,6 +155,28 @@ class LoopOptimizer:
             raise LoopError("tsloop_optimize_sim3 failed (%d): %s" % (rc, self.lib.tsloop_last_error(self.ctx).decode()))
         rep = report_dict(r); rep["status"] = rc
         return r.n_inlier, np.array(list(p.sim)), inl.astype(bool), rep
+
+    def Sim3Batch(self, cands, K1, K, optimise=True, min_inliers=None, max_err2=None, options=None):
+        """loopClosing::ComputeSim3's Sim3Solver + OptimizeSim3 for every candidate in one launch.  cands: per candidate a dict(P1, P2 (posObv), pred1, pred2
+        (obv2dPred), uv1, uv2 (obv2d.pt), triples [H, 3] (the caller's draws), K2 [4]).  Returns one dict per candidate: ok, sel, n_inlier_ransac, sim_ransac [8],
+        inlier [n] bool, hyp_count [H], hyp_sim [H, 8], and for an ok candidate with optimise sim [8] and report (else None)."""
+        o = options or self.default_options_sim3()
+        d = TsloopSim3BatchProblem(); self.lib.tsloop_default_options_sim3_ransac(C.byref(d))
+        p, A = make_sim3_batch_problem(cands, K1, K, optimise, d.min_inliers if min_inliers is None else min_inliers, d.max_err2 if max_err2 is None else max_err2)
+        rc = self.lib.tsloop_sim3_batch(self.ctx, C.byref(p), C.byref(o))
+        if rc not in (0, -3):
+            raise LoopError("tsloop_sim3_batch failed (%d): %s" % (rc, self.lib.tsloop_last_error(self.ctx).decode()))
+        out = []
+        for k in range(len(cands)):
+            a, b, ha, hb = int(A["off"][k]), int(A["off"][k + 1]), int(A["hyp_off"][k]), int(A["hyp_off"][k + 1])
+            done = bool(A["ok"][k]) and bool(optimise)
+            rep = None
+            if done:
+                rep = report_dict(A["rep"][k]); rep["status"] = -3 if rep["termination"] == 5 else 0
+            out.append({"ok": bool(A["ok"][k]), "sel": int(A["sel"][k]), "n_inlier_ransac": int(A["n_inlier_ransac"][k]), "sim_ransac": A["sim_ransac"][k].copy(),
+                        "inlier": A["inlier"][a:b].astype(bool), "hyp_count": A["hyp_count"][ha:hb].copy(), "hyp_sim": A["hyp_sim"][ha:hb].copy(),
+                        "sim": A["sim"][k].copy() if done else None, "report": rep})
+        return out
 
     def default_options_loop(self):
         o = TsloopOptions(); self.lib.tsloop_default_options_loop(C.byref(o)); return o
