@@ -51,6 +51,33 @@ struct TextSlamTraits {
         const double p7[7] = { pose[0], pose[1], pose[2], pose[3], pose[4]/pose[7], pose[5]/pose[7], pose[6]/pose[7] };
         set_pose(kf, p7);
     }
+    // ---- loop fusion's window searches (adapter/tsorb_loop_fuse.hpp; `using tsorb_adapter::FUSE_*` values 0 / 1 / 2 = searched / negative depth / outside the image)
+    static int rows(const cv::Mat &m) { return m.rows; }
+    static const uint8_t *row(const cv::Mat &m, int i) { return m.ptr<uint8_t>(i); }
+    // loopClosing.cc:1172-1181 and :1196-1211, SearchAndFuse_Scene's own expressions: Tcw = [R | t / s], Tcr, Pc, the depth test, mK * Pc, IsInImage -- all in doubles
+    static int fuse_project(KeyFrame *kf, const Sim3 &S, MapPt *pt, double &u, double &v) {
+        using namespace TextSLAM;
+        Mat44 T_cw = Mat44::Identity();                                        // [R | t / s]
+        T_cw.block<3, 3>(0, 0) = Mat33(S.r);
+        Mat31 t = S.t; t /= S.s; T_cw.block<3, 1>(0, 3) = t;
+        const Mat44 T_cr = T_cw * pt->RefKF->mTcw.inverse();
+        const Mat31 p_r = pt->GetRaydir()/pt->GetInverD();
+        const Mat31 p_c = T_cr.block<3, 3>(0, 0) * p_r + T_cr.block<3, 1>(0, 3);
+        if (p_c(2, 0) < 0.0) return 1;
+        const Mat31 h = kf->mK * p_c;
+        u = h(0)/h(2); v = h(1)/h(2);
+        return kf->IsInImage(u, v) ? 0 : 2;
+    }
+    // loopClosing.cc:1422-1432, MatchMore's own expressions (products in its order: (R * invrho) * ray, K * (R p + t))
+    static void more_project(KeyFrame *kf1, KeyFrame *kf2, const Sim3 &g, MapPt *pt, double &u, double &v) {
+        using namespace TextSLAM;
+        const Mat31 ray = pt->GetRaydir(); const double inv_rho = 1.0/pt->GetInverD();
+        const Mat44 T = kf2->mTcw * pt->RefKF->mTwc;
+        const Eigen::Quaterniond q = g.r; const Mat33 R(q);
+        const Mat31 p2 = T.block<3, 3>(0, 0) * inv_rho * ray + T.block<3, 1>(0, 3);
+        const Mat31 h = kf1->mK * (R * p2 + g.t);
+        u = h(0)/h(2); v = h(1)/h(2);
+    }
     // Sim3Solver's index draws (adapter/tsloop_sim3_ransac.hpp): the reference's own generator, Sim3Solver.cc:81
     static int random_int(int lo, int hi) { return DUtils::Random::RandomInt(lo, hi); }
     // nume_BAText.h:25: the cost functors index cv::Mat::data directly, i.e. continuous CV_8UC1 with step == cols

@@ -115,6 +115,30 @@ int tsorb_match_brute_scene(void *ctx, int w, int h,
                             const int32_t *qoff /*[n_cand+1]*/, const double *quad_cur /*[qoff[n_cand]][4][2]*/, const double *quad_can /*same*/,
                             int th_low, double ratio, int32_t *match12 /*[n_cand][n1]*/, int32_t *n_match /*[n_cand]*/);
 
+/* ---- Window searches in many feature sets: loop fusion.  loopClosing::SearchAndFuse_Scene (src/loopClosing.cc:1168-1288) projects every loop map point into the current
+ * keyframe and into each of its connected keyframes and scans keyframe::GetFeaturesInArea(u, v, 15) (src/keyframe.cc:217-256) with DescriptorDistance, a host loop of
+ * K keyframes x P points; loopClosing::MatchMore (:1398-1489) does the same per loop candidate.  Here every (set, query) pair of such a step goes to ONE call: a grid launch
+ * (a workgroup per set) and a search launch (a wave per query).
+ *   Set s = rows [foff[s], foff[s+1]) of kp6 / desc with bounds[s] = min_x, max_x, min_y, max_y (the keyframe's mnMinX ..).  Query q searches set qset[q] at qxy[q] with
+ *   radius qr[q], octave range qlev[q] (NULL = no level check, keyframe::GetFeaturesInArea) and descriptor row qdi[q] of qdesc (NULL = row q; then n_qdesc == nq): K
+ *   keyframes searched with the same P descriptors send them once.
+ * Query q gets exactly what tsorb_match_set_features(kp6 + 6 foff[s], desc + 32 foff[s], foff[s+1] - foff[s], bounds[s]) followed by a one-query tsorb_match_search returns:
+ * the candidates in the reference's order (window cells column by column, features in index order inside a cell), the Hamming distances, the first minimum under strict <,
+ * the runner-up distance, -1 / INT32_MAX when there is none; indices relative to the set.  Output pointers may be NULL; max_cand = 0: no candidate lists.
+ * Needs only a context: the resident batch and the single-set grid of tsorb_match_set_* are left as they were.  n_set == 0 or nq == 0: TSORB_OK, no pointer is read.  A set
+ * without features is legal (cand_cnt 0, -1, INT32_MAX, INT32_MAX).  TSORB_ERR_ARG (tsorb_last_error names the function, nothing is launched, no output is touched) for: a
+ * NULL context or a NULL pointer where data is needed, a negative count, n_set > TSORB_SETS_MAX, a foff that does not start at 0 or decreases, a set above
+ * TSORB_BRUTE_MAX_FEAT rows, bounds with max <= min or not finite, a qset outside [0, n_set), a qdi outside [0, n_qdesc), qdi == NULL with n_qdesc != nq, a query
+ * coordinate or radius that is not finite, max_cand < 0. */
+#define TSORB_SETS_MAX 1024
+int tsorb_match_search_sets(void *ctx,
+        int n_set, const int32_t *foff /*[n_set+1]*/, const float *kp6 /*[foff[n_set]][6]*/, const uint8_t *desc /*[foff[n_set]][32]*/,
+        const double *bounds /*[n_set][4] = min_x, max_x, min_y, max_y*/,
+        int n_qdesc, const uint8_t *qdesc /*[n_qdesc][32]*/,
+        int nq, const int32_t *qset /*[nq]*/, const int32_t *qdi /*[nq] row of qdesc, NULL = the query's own index (then n_qdesc == nq)*/,
+        const float *qxy /*[nq][2]*/, const float *qr /*[nq]*/, const int32_t *qlev /*[nq][2], NULL = no level check*/,
+        int max_cand, int32_t *cand_idx, int32_t *cand_dist, int32_t *cand_cnt, int32_t *best_idx, int32_t *best_dist, int32_t *best_dist2);
+
 /* ---- Text features of a frame.
  * frame::FeatExtracText (src/frame.cc:334-355): for each of n_dete detection quads (level-0 pixels, double x, y; truncated like cv::Point)
  * cv::ORB::create()->detect on the frame masked to the quad (tool::GetMask) and ->compute on the frame itself, OpenCV 3.3 defaults;

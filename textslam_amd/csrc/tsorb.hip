@@ -18,6 +18,7 @@
 // (orientation inside the descriptor's launch, results also stored in the pinned block the download hands out).  Levels the LDS quadtree cannot hold are
 // flagged in pinned memory and redone by k_octree_serial behind the run's synchronisation.
 // Window search (tracking::SearchFrom3D*): k_mg_cell / k_mg_scan / k_mg_place build a frame's 64 x 48 grid, k_match searches it, a wave per query.
+// Loop fusion's window searches in many feature sets at once (tswindow.h): k_ws_grid builds every set's grid, k_ws_match runs k_match's walk (match_walk) per query.
 // Integer / fp32 arithmetic is written so that every rounding matches the CPU oracle: no FMA contraction where the
 // reference has separate multiplies and adds (__fmul_rn / __fadd_rn / __dmul_rn ...), rintf = cvRound (half to even).
 #include <hip/hip_runtime.h>
@@ -1331,11 +1332,15 @@ struct MatchDev {
     double min_x, min_y, iw, ih;
     int *cell, *off, *list;                           // [n], [MG_CELLS + 1], [n]
 };
+// frame::PosInGrid (frame.cc:395-407) in the reference's doubles: the feature's cell (column-major, as the window walk counts them), -1 outside the grid
+__device__ __forceinline__ int mg_cell_of(const float fx, const float fy, const double min_x, const double min_y, const double iw, const double ih) {
+    const int px = (int)round(((double)fx - min_x)*iw), py = (int)round(((double)fy - min_y)*ih);
+    return (px < 0 || px >= MG_COLS || py < 0 || py >= MG_ROWS) ? -1 : px*MG_ROWS + py;
+}
 __global__ __launch_bounds__(256) void k_mg_cell(MatchDev M) {
     const int i = blockIdx.x*256 + threadIdx.x;
     if (i >= M.n) return;
-    const int px = (int)round(((double)M.kp[6*i] - M.min_x)*M.iw), py = (int)round(((double)M.kp[6*i+1] - M.min_y)*M.ih);   // PosInGrid
-    const int c = (px < 0 || px >= MG_COLS || py < 0 || py >= MG_ROWS) ? -1 : px*MG_ROWS + py;
+    const int c = mg_cell_of(M.kp[6*i], M.kp[6*i+1], M.min_x, M.min_y, M.iw, M.ih);
     M.cell[i] = c;
     if (c >= 0) atomicAdd(&M.off[c + 1], 1);
 }
@@ -1376,17 +1381,11 @@ __global__ __launch_bounds__(256) void k_mg_place(MatchDev M) {           // ran
 // frame.cc:415-468), their feature counts as a wave scan; then the window's features on the lanes, again in that order (a lane finds its feature's cell in the scan), the
 // reference's filters and the Hamming distance per lane; the survivors keep their order through a ballot, best / second best as the two smallest of the multiset with the
 // first minimum's index (what the reference's sequential scan ends with).
-__global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *qxy, const float *qr, const int *qlev, const uint8_t *qdesc, int max_cand,
-                                               int *cand_idx, int *cand_dist, int *cand_cnt, int *best_idx, int *best_dist, int *best_dist2) {
-    __shared__ int s_inc[4][64], s_o0[4][64];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, q = blockIdx.x*4 + wv;
-    if (q >= nq) return;                                     // (a whole wave)
-    int *inc = s_inc[wv], *o0s = s_o0[wv];
-    const float x = qxy[2*q], y = qxy[2*q+1], r = qr[q];
-    const int minLevel = qlev ? qlev[2*q] : -1, maxLevel = qlev ? qlev[2*q+1] : -1;
-    uint32_t qd[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) qd[k] = ((const uint32_t *)qdesc)[8*(size_t)q + k];
+// The walk of one query by one wave, stated once: k_match (the context's single grid) and k_ws_match (tswindow.h: a grid per set) both call it.  G is the searched
+// grid by value; inc / o0s are the wave's 64-entry LDS scratch; cand_idx / cand_dist are the query's own rows (max_cand entries, unused slots included).
+struct MatchGrid { const float *kp; const uint8_t *desc; const int *off, *list; double min_x, min_y, iw, ih; };
+__device__ __forceinline__ void match_walk(const MatchGrid M, const int lane, int *inc, int *o0s, const float x, const float y, const float r, const int minLevel, const int maxLevel,
+                                           const uint32_t (&qd)[8], const int max_cand, int *cand_idx, int *cand_dist, int *cand_cnt, int *best_idx, int *best_dist, int *best_dist2) {
     int nc = 0, bi = -1, bd = 2147483647, bd2 = 2147483647;
     const int c0x = max(0, (int)floor(((double)x - M.min_x - (double)r)*M.iw)), c1x = min(MG_COLS - 1, (int)ceil(((double)x - M.min_x + (double)r)*M.iw));
     const int c0y = max(0, (int)floor(((double)y - M.min_y - (double)r)*M.ih)), c1y = min(MG_ROWS - 1, (int)ceil(((double)y - M.min_y + (double)r)*M.ih));
@@ -1425,7 +1424,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
                 const unsigned long long pm = __ballot(pass);
                 if (pm) {
                     const int rank = nc + __popcll(pm & lt);
-                    if (pass && rank < max_cand) { cand_idx[(size_t)q*max_cand + rank] = i; cand_dist[(size_t)q*max_cand + rank] = d; }
+                    if (pass && rank < max_cand) { cand_idx[rank] = i; cand_dist[rank] = d; }
                     nc += __popcll(pm);
                     // the chunk's two smallest distances and the first lane of the smallest
                     int m1 = pass ? d : 2147483647;
@@ -1444,12 +1443,25 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // (the next 64 cells overwrite the scan)
         }
     }
-    for (int k = nc + lane; k < max_cand; k += 64) { cand_idx[(size_t)q*max_cand + k] = -1; cand_dist[(size_t)q*max_cand + k] = -1; }     // unused slots
-    if (lane == 0) { cand_cnt[q] = nc; best_idx[q] = bi; best_dist[q] = bd; best_dist2[q] = bd2; }
+    for (int k = nc + lane; k < max_cand; k += 64) { cand_idx[k] = -1; cand_dist[k] = -1; }     // unused slots
+    if (lane == 0) { *cand_cnt = nc; *best_idx = bi; *best_dist = bd; *best_dist2 = bd2; }
+}
+__global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *qxy, const float *qr, const int *qlev, const uint8_t *qdesc, int max_cand,
+                                               int *cand_idx, int *cand_dist, int *cand_cnt, int *best_idx, int *best_dist, int *best_dist2) {
+    __shared__ int s_inc[4][64], s_o0[4][64];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, q = blockIdx.x*4 + wv;
+    if (q >= nq) return;                                     // (a whole wave)
+    uint32_t qd[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) qd[k] = ((const uint32_t *)qdesc)[8*(size_t)q + k];
+    MatchGrid G; G.kp = M.kp; G.desc = M.desc; G.off = M.off; G.list = M.list; G.min_x = M.min_x; G.min_y = M.min_y; G.iw = M.iw; G.ih = M.ih;
+    match_walk(G, lane, s_inc[wv], s_o0[wv], qxy[2*q], qxy[2*q+1], qr[q], qlev ? qlev[2*q] : -1, qlev ? qlev[2*q+1] : -1, qd, max_cand,
+               cand_idx + (size_t)q*max_cand, cand_dist + (size_t)q*max_cand, cand_cnt + q, best_idx + q, best_dist + q, best_dist2 + q);
 }
 
 #include "tscvorb.h"
 #include "tsbrute.h"
+#include "tswindow.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -1970,6 +1982,70 @@ int tsorb_match_brute_scene(void *ctx, int w, int h, int n1, const float *xy1, c
     OCK(hipMemcpyAsync(hp + in_sz, d + in_sz + 2*b_md, out_sz, hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
     memcpy(match12, hp + in_sz, 4*N1*(size_t)n_cand); memcpy(n_match, hp + in_sz + b_m12, 4*(size_t)n_cand);
+    return TSORB_OK;
+}
+
+// ---- loopClosing::SearchAndFuse_Scene / MatchMore: window searches in many feature sets (tswindow.h).  Needs only a context, like the calls above, and shares their blocks:
+// one pinned block [up | queries | results], one device block [up | off | list]; `up` = [foff | grid | kp | desc | qdesc] crosses in ONE copy, the queries are read from and
+// the results stored into the pinned block by the search kernel itself (as tsorb_match_search does).
+int tsorb_match_search_sets(void *ctx, int n_set, const int32_t *foff, const float *kp6, const uint8_t *desc, const double *bounds,
+                            int n_qdesc, const uint8_t *qdesc, int nq, const int32_t *qset, const int32_t *qdi, const float *qxy, const float *qr, const int32_t *qlev,
+                            int max_cand, int32_t *cand_idx, int32_t *cand_dist, int32_t *cand_cnt, int32_t *best_idx, int32_t *best_dist, int32_t *best_dist2) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_match_search_sets: ") + m; return TSORB_ERR_ARG; };
+    if (n_set < 0 || nq < 0 || n_qdesc < 0) return bad("a negative count");
+    if (max_cand < 0) return bad("max_cand < 0");
+    if (n_set > TSORB_SETS_MAX) return bad("n_set above TSORB_SETS_MAX");
+    if (n_set == 0 || nq == 0) return TSORB_OK;
+    if (!foff || !bounds || !qset || !qxy || !qr || !qdesc) return bad("NULL pointer");
+    if (const char *m = br_offsets(foff, n_set, TSORB_BRUTE_MAX_FEAT)) return bad(m);
+    const size_t F = (size_t)foff[n_set], NQ = (size_t)nq, ND = (size_t)n_qdesc;
+    if (F > 0 && (!kp6 || !desc)) return bad("NULL pointer");
+    for (int s = 0; s < n_set; s++) { const double *b = bounds + 4*(size_t)s;
+        if (!std::isfinite(b[0]) || !std::isfinite(b[1]) || !std::isfinite(b[2]) || !std::isfinite(b[3])) return bad("bounds not finite");
+        if (!(b[1] > b[0]) || !(b[3] > b[2])) return bad("bounds with max <= min"); }
+    if (!qdi && n_qdesc != nq) return bad("qdi NULL with n_qdesc != nq");
+    for (size_t q = 0; q < NQ; q++) {
+        if (qset[q] < 0 || qset[q] >= n_set) return bad("a qset outside [0, n_set)");
+        if (qdi && (qdi[q] < 0 || qdi[q] >= n_qdesc)) return bad("a qdi outside [0, n_qdesc)");
+        if (!std::isfinite(qxy[2*q]) || !std::isfinite(qxy[2*q + 1]) || !std::isfinite(qr[q])) return bad("a query coordinate or radius is not finite");
+    }
+    hipSetDevice(c->device);
+    const size_t b_off = br_al(4*((size_t)n_set + 1)), b_grid = br_al(32*(size_t)n_set), b_kp = br_al(24*F), b_desc = br_al(32*F), b_qd = br_al(32*ND), up_sz = b_off + b_grid + b_kp + b_desc + b_qd;
+    const size_t b_cell = br_al(4*(size_t)n_set*(MG_CELLS + 1)), b_list = br_al(4*F);
+    const size_t b_xy = br_al(8*NQ), b_i = br_al(4*NQ), q_sz = b_xy + b_i + 2*b_i + b_i + b_i, b_c = br_al(4*NQ*(size_t)max_cand), out_sz = 2*b_c + 4*b_i;
+    if (int rc = br_room(c, up_sz + b_cell + b_list, up_sz + q_sz + out_sz)) return rc;
+    char *h = (char *)c->br_pin, *d = (char *)c->br_dev, *hq = h + up_sz, *ho = hq + q_sz;
+    memcpy(h, foff, 4*((size_t)n_set + 1));
+    { double *g = (double *)(h + b_off);
+      for (int s = 0; s < n_set; s++) { const double *b = bounds + 4*(size_t)s; g[4*s] = b[0]; g[4*s + 1] = b[2];
+          g[4*s + 2] = (double)MG_COLS/(b[1] - b[0]); g[4*s + 3] = (double)MG_ROWS/(b[3] - b[2]); } }                 // frame.cc:124-125, as match_build
+    if (F) { memcpy(h + b_off + b_grid, kp6, 24*F); memcpy(h + b_off + b_grid + b_kp, desc, 32*F); }
+    memcpy(h + b_off + b_grid + b_kp + b_desc, qdesc, 32*ND);
+    memcpy(hq, qxy, 8*NQ); memcpy(hq + b_xy, qr, 4*NQ);
+    { int32_t *lev = (int32_t *)(hq + b_xy + b_i), *st = lev + b_i/2, *di = st + b_i/4;
+      if (qlev) memcpy(lev, qlev, 8*NQ); else for (size_t k = 0; k < 2*NQ; k++) lev[k] = -1;
+      memcpy(st, qset, 4*NQ);
+      if (qdi) memcpy(di, qdi, 4*NQ); else for (size_t k = 0; k < NQ; k++) di[k] = (int32_t)k; }
+    OCK(hipMemcpyAsync(d, h, up_sz, hipMemcpyHostToDevice, c->stream));
+    char *pq = nullptr; { void *hd = nullptr; OCK(hipHostGetDevicePointer(&hd, c->br_pin, 0)); pq = (char *)hd + up_sz; }
+    char *po = pq + q_sz;
+    WindowSets W;
+    W.n_set = n_set; W.nq = nq; W.max_cand = max_cand;
+    W.foff = (const int *)d; W.grid = (const double *)(d + b_off); W.kp = (const float *)(d + b_off + b_grid); W.desc = (const uint8_t *)(d + b_off + b_grid + b_kp);
+    W.qdesc = (const uint8_t *)(d + b_off + b_grid + b_kp + b_desc); W.off = (int *)(d + up_sz); W.list = (int *)(d + up_sz + b_cell);
+    W.qxy = (const float *)pq; W.qr = (const float *)(pq + b_xy); W.qlev = (const int *)(pq + b_xy + b_i); W.qset = (const int *)(pq + b_xy + 3*b_i); W.qdi = (const int *)(pq + b_xy + 4*b_i);
+    W.cand_idx = (int *)po; W.cand_dist = (int *)(po + b_c); W.cand_cnt = (int *)(po + 2*b_c); W.best_idx = (int *)(po + 2*b_c + b_i); W.best_dist = (int *)(po + 2*b_c + 2*b_i);
+    W.best_dist2 = (int *)(po + 2*b_c + 3*b_i);
+    hipLaunchKernelGGL(k_ws_grid, dim3(n_set), dim3(WS_T), 0, c->stream, W);
+    hipLaunchKernelGGL(k_ws_match, dim3((nq + WS_T/64 - 1)/(WS_T/64)), dim3(WS_T), 0, c->stream, W);
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    if (cand_idx) memcpy(cand_idx, ho, 4*NQ*(size_t)max_cand);
+    if (cand_dist) memcpy(cand_dist, ho + b_c, 4*NQ*(size_t)max_cand);
+    if (cand_cnt) memcpy(cand_cnt, ho + 2*b_c, 4*NQ);
+    if (best_idx) memcpy(best_idx, ho + 2*b_c + b_i, 4*NQ);
+    if (best_dist) memcpy(best_dist, ho + 2*b_c + 2*b_i, 4*NQ);
+    if (best_dist2) memcpy(best_dist2, ho + 2*b_c + 3*b_i, 4*NQ);
     return TSORB_OK;
 }
 

@@ -13,8 +13,9 @@ _lib = None
 EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_get_levels", "tsorb_get_scale_factors",
                     "tsorb_get_features_per_level", "tsorb_extract_batch", "tsorb_upload", "tsorb_run", "tsorb_download",
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
-                    "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene"]
+                    "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets"]
 BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
+SETS_MAX = 1024                                                         # TSORB_SETS_MAX of include/tsorb.h
 
 
 class TsorbError(RuntimeError):
@@ -52,6 +53,8 @@ def load_library():
         L.tsorb_match_brute_text.restype = C.c_int
         L.tsorb_match_brute_scene.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, up, up, C.c_int, ip, fp, up, up, ip, dp, dp, C.c_int, C.c_double, ip, ip]
         L.tsorb_match_brute_scene.restype = C.c_int
+        L.tsorb_match_search_sets.argtypes = [vp, C.c_int, ip, fp, up, dp, C.c_int, up, C.c_int, ip, ip, fp, fp, ip, C.c_int, ip, ip, ip, ip, ip, ip]
+        L.tsorb_match_search_sets.restype = C.c_int
         _lib = L
     return _lib
 
@@ -204,6 +207,29 @@ class ORBextractor:
                                                      ptr(qoff, C.c_int32), ptr(qc, C.c_double), ptr(qn, C.c_double), int(th_low), float(ratio),
                                                      ptr(m12, C.c_int32), ptr(nm, C.c_int32)), "tsorb_match_brute_scene")
         return m12[:nc, :n1].copy(), nm[:nc].copy()
+
+    # ---- loop fusion's window searches (loopClosing::SearchAndFuse_Scene / MatchMore), every searched keyframe in one call
+    def match_search_sets(self, sets, qset, qxy, qr, qdesc, qdi=None, qlev=None, max_cand=0):
+        """sets: list of (kp6 [n, 6], desc [n, 32], bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY)), one per searched keyframe.  Query q searches sets[qset[q]] at qxy[q] with
+        radius qr[q] and descriptor qdesc[qdi[q]] (qdi None: qdesc[q]); qlev [nq, 2] or None = no level check.  Returns match_search's dictionary, indices relative to
+        the query's set: what match_set_features(*sets[qset[q]]) + match_search of that one query returns."""
+        kps = [np.ascontiguousarray(k, np.float32).reshape(-1, 6) for k, _, _ in sets]; ds = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for _, d, _ in sets]
+        ns = len(sets)
+        foff = np.zeros(ns + 1, np.int32); foff[1:] = np.cumsum([len(k) for k in kps])
+        kp = np.ascontiguousarray(np.concatenate(kps) if ns else np.zeros((0, 6), np.float32)); desc = np.ascontiguousarray(np.concatenate(ds) if ns else np.zeros((0, 32), np.uint8))
+        bounds = np.ascontiguousarray([[float(v) for v in b] for _, _, b in sets], np.float64).reshape(-1, 4)
+        qset = np.ascontiguousarray(qset, np.int32).reshape(-1); qxy = np.ascontiguousarray(qxy, np.float32).reshape(-1, 2); qr = np.ascontiguousarray(qr, np.float32).reshape(-1)
+        qdesc = np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
+        qdi_p = None if qdi is None else np.ascontiguousarray(qdi, np.int32).reshape(-1); qlev_p = None if qlev is None else np.ascontiguousarray(qlev, np.int32).reshape(-1, 2)
+        nq = qxy.shape[0]
+        ci = np.full((nq, max_cand), -1, np.int32); cd = np.full((nq, max_cand), -1, np.int32)
+        cc = np.zeros(nq, np.int32); bi = np.zeros(nq, np.int32); bd = np.zeros(nq, np.int32); bd2 = np.zeros(nq, np.int32)
+        ptr = lambda a, t: None if a is None or a.size == 0 else a.ctypes.data_as(C.POINTER(t))
+        self._check(self.lib.tsorb_match_search_sets(self.ctx, ns, ptr(foff, C.c_int32), ptr(kp, C.c_float), ptr(desc, C.c_uint8), ptr(bounds, C.c_double),
+                                                     qdesc.shape[0], ptr(qdesc, C.c_uint8), nq, ptr(qset, C.c_int32), ptr(qdi_p, C.c_int32), ptr(qxy, C.c_float), ptr(qr, C.c_float),
+                                                     ptr(qlev_p, C.c_int32), int(max_cand), ptr(ci, C.c_int32), ptr(cd, C.c_int32), ptr(cc, C.c_int32), ptr(bi, C.c_int32),
+                                                     ptr(bd, C.c_int32), ptr(bd2, C.c_int32)), "tsorb_match_search_sets")
+        return dict(cand_idx=ci, cand_dist=cd, cand_cnt=cc, best_idx=bi, best_dist=bd, best_dist2=bd2)
 
     def debug_fast_shape(self, shape=-1):
         """Diagnostics: the shape of the FAST launches (include/tsorb.h); -1 = chosen by the batch size."""
