@@ -2,6 +2,8 @@
  *
  *   optimizer::OptimizeSim3   /root/reference/src/optimizer.cc:626-731  (auto_sim.h, auto_siminv.h)   -> tsloop_optimize_sim3
  *   optimizer::OptimizeLoop   /root/reference/src/optimizer.cc:733-957  (numer_loop_ver2.h, ModelTool.hpp:354-432 logSim3) -> tsloop_optimize_loop
+ *   Sim3Solver::iterate + optimizer::OptimizeSim3 per loop candidate  src/Sim3Solver.cc:59-253             -> tsloop_sim3_batch
+ *   loopClosing::DetectLoop   src/loopClosing.cc:119-304  (tool::LevenshteinDist, src/tool.cc:264-299)       -> tsloop_detect_loop
  *
  * Same Levenberg-Marquardt semantics as the BA library (Ceres 1.x TrustRegionMinimizer + LevenbergMarquardtStrategy with Jacobi
  * scaling), fp64.  All functions return 0 on success, a negative TSLOOP_ERR_* otherwise. */
@@ -95,6 +97,40 @@ typedef struct tsloop_sim3_batch_problem {
     double *hyp_sim;
 } tsloop_sim3_batch_problem;
 
+/* loopClosing::DetectLoop (src/loopClosing.cc:119-304): the Levenshtein scan of every text the current keyframe observes against every text object of the map,
+ * the match lists, the vote through the matched objects' observing keyframes and the candidate walk, in one call (three launches, integers and one fp64 quotient).
+ * Strings are bytes, flat behind offsets: query q is q_str[q_off[q] .. q_off[q+1]), map text m is m_str[m_off[m] .. m_off[m+1]), at most TSLOOP_TEXT_MAX_LEN each.
+ *   pair (q, m): dist = the DP of tool::LevenshteinDist (src/tool.cc:281-296) over bytes, maxlen = max(len_q, len_m), score = (double)(maxlen - dist) / (double)maxlen.
+ *     Not scored (the reference's -1): m_skip[m] (STATE == TEXTBAD, :180), m == q_self[q] (:184), and maxlen == 0 -- a stated difference: the reference divides 0 / 0.
+ *   query q: ScoreMax = its largest score; no match if nothing is scored or ScoreMax < min_str_score (:203).  Scoreth = ScoreMax if ScoreMax == 1.0, else
+ *     max(ScoreMax*2.0/3.0, score_thresh_min) in fp64 in that order (:207-210).  Its matches are the scored m with !(score < Scoreth) (:216), in descending score,
+ *     equal scores by ascending m -- the order of a stable sort; the second stated difference: std::sort (:199) leaves equal scores in an unspecified order.
+ *   votes: kf_score[k] = the (q, matched m) pairs with k in m's row of obs_kf (:255), kf_nobj[k] = the distinct matched m with k in their row (:258-261).  The rows
+ *     hold only ELIGIBLE keyframes -- those the tests of :230-245 let through -- as indices into the caller's vKFs.
+ *   candidates: the keyframes with kf_score > min_matched_words && kf_nobj > min_matched_words by descending kf_score, equal scores by ascending index, the first
+ *     min(top_n, n_kf) of them: the walk of :277-300 (break on the score, continue on the object count, break at TopN).  The CovisibleNum test of :294-296 cannot
+ *     fire for an eligible keyframe: eligibility (:232) already requires that entry of vM[0] to be 0.
+ * Outputs: match_cnt [n_query]; of query q entries [0, match_cnt[q]) of row q of match_idx / match_dist / match_score ([n_query][max_match]; the rest of the row
+ * is not written); kf_score / kf_nobj [n_kf]; n_cand and cand[0 .. n_cand) (cand holds top_n; the rest is not written). */
+#define TSLOOP_TEXT_MAX_LEN 64          /* bytes of one recognition string */
+typedef struct tsloop_detect_problem {
+    int32_t n_query, n_map, n_kf, top_n;          /* top_n: TopN = 10, loopClosing.cc:273 */
+    const int32_t *q_off;  const uint8_t *q_str;  /* [n_query + 1] byte offsets, the bytes of textCur.mean */
+    const int32_t *q_self;                        /* [n_query] map index of the query's own object (:184), or -1 */
+    const int32_t *m_off;  const uint8_t *m_str;  /* [n_map + 1], the bytes of every map text's TextMean.mean */
+    const uint8_t *m_skip;                        /* [n_map] 1 = STATE == TEXTBAD (:180) */
+    const int32_t *obs_off, *obs_kf;              /* [n_map + 1], [obs_off[n_map]]: the ELIGIBLE keyframes observing map text m,
+                                                     as indices in [0, n_kf), strictly increasing inside a row */
+    double  min_str_score, score_thresh_min;      /* 0.3 (:122);  ScoreThresh_min 0.51 / 0.35 (:30,36) */
+    int32_t min_matched_words, max_match;         /* MinMatchedWords;  capacity of a query's match list */
+    /* out */
+    int32_t *match_cnt;                           /* [n_query] */
+    int32_t *match_idx, *match_dist;              /* [n_query][max_match] */
+    double  *match_score;                         /* [n_query][max_match] */
+    int32_t *kf_score, *kf_nobj;                  /* [n_kf]: vMapKFScore[k].second, vKFsMathedObjs[k].size() */
+    int32_t *n_cand, *cand;                       /* [1], [top_n]: vMatchKFs as keyframe indices, in the reference's order */
+} tsloop_detect_problem;
+
 void tsloop_default_options_sim3(tsloop_options *o);
 void tsloop_default_options_loop(tsloop_options *o);    /* 20 iterations, no loss (huber_delta / thresh_outlier unused) */
 int  tsloop_create(int device, void **ctx);          /* TSLOOP_ERR_DEVICE without a usable GPU: there is no CPU path */
@@ -110,6 +146,14 @@ void tsloop_default_options_sim3_ransac(tsloop_sim3_batch_problem *p);    /* min
  * pred, uv or K, min_inliers < 0, a non-finite or negative max_err2, more than INT32_MAX / 3 matches in all.  n_cand == 0 returns
  * TSLOOP_OK and reads no pointer. */
 int  tsloop_sim3_batch(void *ctx, tsloop_sim3_batch_problem *p, const tsloop_options *o);
+void tsloop_default_options_detect(tsloop_detect_problem *p);   /* min_str_score = 0.3, score_thresh_min = 0.51, top_n = 10, max_match = 64; nothing else is touched */
+/* TSLOOP_OK with n_query == 0 (no pointer is read; kf_score, kf_nobj and n_cand are zeroed where they are not NULL) and with n_map == 0 (match_cnt, kf_score,
+ * kf_nobj and n_cand are zeroed): nothing is launched.  TSLOOP_ERR_ARG -- nothing launched, no output touched, tsloop_last_error names the function -- for a NULL
+ * pointer where data is needed, a negative count, top_n < 1, max_match < 1, min_matched_words < 0, a non-finite threshold, offsets that do not start at 0 or
+ * decrease, a string longer than TSLOOP_TEXT_MAX_LEN, q_self outside [-1, n_map), an obs_kf outside [0, n_kf) or not strictly increasing in its row.
+ * A query with more matches than max_match: match_cnt, kf_score, kf_nobj, n_cand and cand are complete (the votes do not depend on the lists), that query's list
+ * is not written, and the call returns TSLOOP_ERR_ARG with a message that says so (tsorb_text_extract's convention for cap): call again with the largest match_cnt. */
+int  tsloop_detect_loop(void *ctx, tsloop_detect_problem *p);
 
 #ifdef __cplusplus
 }

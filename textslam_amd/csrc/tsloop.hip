@@ -7,6 +7,7 @@
 // transposes), Jacobi-scaled damped 7x7 LDL^T in registers (every thread, redundantly), candidate on the manifold, cost sweep,
 // Ceres' accept / reject / radius logic -- then the 4-pixel inlier test of the reference.
 // tsloop_sim3_batch (tsloop_ransac.h) runs that solve for every loop candidate in one launch, behind the candidate's Sim3Solver RANSAC.
+// tsloop_detect_loop (tsloop_detect.h) is loopClosing::DetectLoop's string scan and keyframe vote: integers and one fp64 quotient per pair.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -275,6 +276,7 @@ __global__ __launch_bounds__(SIM_T) void k_sim3_lm(Sim3Dev P, tsloop_options o) 
 }
 
 #include "tsloop_ransac.h"
+#include "tsloop_detect.h"
 
 // ------------------------------------------------------------------------------------------------ host side
 extern "C" {
@@ -422,6 +424,101 @@ int tsloop_sim3_batch(void *ctx, tsloop_sim3_batch_problem *p, const tsloop_opti
     if (p->hyp_count) memcpy(p->hyp_count, out_at(o_hc), 4*nh);
     if (p->hyp_sim) memcpy(p->hyp_sim, out_at(o_hs), 64*nh);
     return rc;
+}
+
+void tsloop_default_options_detect(tsloop_detect_problem *p) { p->min_str_score = 0.3; p->score_thresh_min = 0.51; p->top_n = 10; p->max_match = 64; }
+
+int tsloop_detect_loop(void *ctx, tsloop_detect_problem *p) {
+    LCtx *c = (LCtx *)ctx;
+    if (!c) return TSLOOP_ERR_ARG;
+    auto bad = [&](const char *what) { c->err = std::string("tsloop_detect_loop: ") + what; return TSLOOP_ERR_ARG; };
+    if (!p) return bad("NULL problem");
+    if (p->n_query < 0 || p->n_map < 0 || p->n_kf < 0) return bad("negative count");
+    if (p->top_n < 1) return bad("top_n < 1");
+    if (p->max_match < 1) return bad("max_match < 1");
+    if (p->min_matched_words < 0) return bad("min_matched_words < 0");
+    if (!std::isfinite(p->min_str_score) || !std::isfinite(p->score_thresh_min)) return bad("non-finite threshold");
+    const size_t nq = (size_t)p->n_query, nm = (size_t)p->n_map, nk = (size_t)p->n_kf, mm = (size_t)p->max_match;
+    auto no_votes = [&]() { if (p->kf_score) memset(p->kf_score, 0, 4*nk); if (p->kf_nobj) memset(p->kf_nobj, 0, 4*nk); if (p->n_cand) *p->n_cand = 0; };
+    if (nq == 0) { no_votes(); return TSLOOP_OK; }                      // no query: no input is read, the vote is empty
+    if (!p->match_cnt || !p->match_idx || !p->match_dist || !p->match_score || !p->n_cand || !p->cand || (nk > 0 && (!p->kf_score || !p->kf_nobj))) return bad("NULL output pointer");
+    if (nm == 0) { memset(p->match_cnt, 0, 4*nq); no_votes(); return TSLOOP_OK; }
+    if (!p->q_off || !p->q_self || !p->m_off || !p->m_skip || !p->obs_off) return bad("NULL input pointer");
+    if (p->q_off[0] != 0 || p->m_off[0] != 0 || p->obs_off[0] != 0) return bad("offsets do not start at 0");
+    for (size_t q = 0; q < nq; q++) {
+        if (p->q_off[q + 1] < p->q_off[q]) return bad("q_off decreases");
+        if (p->q_off[q + 1] - p->q_off[q] > TSLOOP_TEXT_MAX_LEN) return bad("a query string longer than TSLOOP_TEXT_MAX_LEN");
+        if (p->q_self[q] < -1 || p->q_self[q] >= p->n_map) return bad("q_self outside [-1, n_map)");
+    }
+    for (size_t m = 0; m < nm; m++) {
+        if (p->m_off[m + 1] < p->m_off[m] || p->obs_off[m + 1] < p->obs_off[m]) return bad("m_off or obs_off decreases");
+        if (p->m_off[m + 1] - p->m_off[m] > TSLOOP_TEXT_MAX_LEN) return bad("a map string longer than TSLOOP_TEXT_MAX_LEN");
+    }
+    const size_t qb = (size_t)p->q_off[nq], mb = (size_t)p->m_off[nm], no = (size_t)p->obs_off[nm];
+    if ((qb > 0 && !p->q_str) || (mb > 0 && !p->m_str) || (no > 0 && !p->obs_kf)) return bad("NULL q_str, m_str or obs_kf");
+    for (size_t m = 0; m < nm; m++)
+        for (int e = p->obs_off[m]; e < p->obs_off[m + 1]; e++) {
+            if (p->obs_kf[e] < 0 || p->obs_kf[e] >= p->n_kf) return bad("obs_kf outside [0, n_kf)");
+            if (e > p->obs_off[m] && p->obs_kf[e] <= p->obs_kf[e - 1]) return bad("obs_kf not strictly increasing in its row");
+        }
+    const size_t n_tile = (nm + TD_T - 1)/TD_T;
+    if (n_tile*nq > (size_t)INT32_MAX) return bad("more (query, tile of map texts) pairs than a grid holds");
+    hipSetDevice(c->device);
+    const size_t nsel = std::min((size_t)p->top_n, nk);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t off = 0; auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
+    const size_t o_qoff = take(4*(nq + 1)), o_qstr = take(qb), o_qself = take(4*nq), o_moff = take(4*(nm + 1)), o_mstr = take(mb), o_mskip = take(nm),
+                 o_ooff = take(4*(nm + 1)), o_okf = take(4*no), in_end = off,                                                                        // uploaded
+                 o_dist = take(nq*nm), o_hit = take(4*nm), o_tidx = take(4*nq*mm), o_tsc = take(8*nq*mm), o_rrec = take(sizeof(TdRec)*nq*mm), out_begin = off,     // scratch
+                 o_cnt = take(4*nq), o_roff = take(4*(nq + 1)), o_ks = take(4*nk), o_ko = take(4*nk), o_nc = take(4), o_cand = take(4*nsel),
+                 o_rec = take(sizeof(TdRec)*nq*mm), tot = off;                                                                                        // downloaded
+    // the packed lists come last: the one copy out takes as many records as the default capacity holds, a second one only what lies beyond them
+    const size_t n_first = nq*std::min(mm, (size_t)64), out_sz = (o_rec - out_begin) + sizeof(TdRec)*n_first;
+    if (in_end > c->h_cap) { if (c->h_stage) hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_cap = 0; CKL(hipHostMalloc((void **)&c->h_stage, in_end, hipHostMallocDefault)); c->h_cap = in_end; }
+    if (out_sz > c->h_out_cap) { if (c->h_out) hipHostFree(c->h_out); c->h_out = nullptr; c->h_out_cap = 0; CKL(hipHostMalloc((void **)&c->h_out, out_sz, hipHostMallocDefault)); c->h_out_cap = out_sz; }
+    if (tot > c->d_cap) { if (c->d_buf) hipFree(c->d_buf); c->d_buf = nullptr; c->d_cap = 0; CKL(hipMalloc((void **)&c->d_buf, tot)); c->d_cap = tot; }
+    uint8_t *h = c->h_stage, *d = c->d_buf; auto out_at = [&](size_t o_x) { return (const uint8_t *)c->h_out + (o_x - out_begin); };
+    memcpy(h + o_qoff, p->q_off, 4*(nq + 1)); if (qb) memcpy(h + o_qstr, p->q_str, qb); memcpy(h + o_qself, p->q_self, 4*nq);
+    memcpy(h + o_moff, p->m_off, 4*(nm + 1)); if (mb) memcpy(h + o_mstr, p->m_str, mb); memcpy(h + o_mskip, p->m_skip, nm);
+    memcpy(h + o_ooff, p->obs_off, 4*(nm + 1)); if (no) memcpy(h + o_okf, p->obs_kf, 4*no);
+    CKL(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));                            // one copy in, three launches, one copy out (two after a max_match above the default)
+    TdDev D;
+    D.n_query = p->n_query; D.n_map = p->n_map; D.n_kf = p->n_kf; D.top_n = p->top_n; D.n_tile = (int32_t)n_tile; D.max_match = p->max_match; D.min_matched_words = p->min_matched_words;
+    D.q_off = (const int32_t *)(d + o_qoff); D.q_str = d + o_qstr; D.q_self = (const int32_t *)(d + o_qself);
+    D.m_off = (const int32_t *)(d + o_moff); D.m_str = d + o_mstr; D.m_skip = d + o_mskip; D.obs_off = (const int32_t *)(d + o_ooff); D.obs_kf = (const int32_t *)(d + o_okf);
+    D.min_str_score = p->min_str_score; D.score_thresh_min = p->score_thresh_min;
+    D.dist = d + o_dist; D.hit = (int32_t *)(d + o_hit); D.tmp_idx = (int32_t *)(d + o_tidx); D.tmp_score = (double *)(d + o_tsc);
+    D.rank_rec = (TdRec *)(d + o_rrec); D.match_cnt = (int32_t *)(d + o_cnt); D.rec_off = (int32_t *)(d + o_roff); D.out_rec = (TdRec *)(d + o_rec);
+    D.kf_score = (int32_t *)(d + o_ks); D.kf_nobj = (int32_t *)(d + o_ko); D.n_cand = (int32_t *)(d + o_nc); D.cand = (int32_t *)(d + o_cand);
+    hipLaunchKernelGGL(k_td_scan, dim3((unsigned)(n_tile*nq)), dim3(TD_T), 0, c->stream, D);
+    hipLaunchKernelGGL(k_td_pick, dim3((unsigned)nq), dim3(TD_T), 0, c->stream, D);
+    hipLaunchKernelGGL(k_td_vote, dim3(1), dim3(TD_T), 0, c->stream, D);
+    CKL(hipMemcpyAsync(c->h_out, d + out_begin, out_sz, hipMemcpyDeviceToHost, c->stream));
+    CKL(hipStreamSynchronize(c->stream)); CKL(hipGetLastError());
+    const int32_t *cnt = (const int32_t *)out_at(o_cnt), *roff = (const int32_t *)out_at(o_roff);
+    const TdRec *first = (const TdRec *)out_at(o_rec);
+    const size_t n_rec = (size_t)roff[nq];
+    std::vector<TdRec> rest;                                           // (only after a call with a max_match above the default)
+    if (n_rec > n_first) { rest.resize(n_rec - n_first); CKL(hipMemcpy(rest.data(), d + o_rec + sizeof(TdRec)*n_first, sizeof(TdRec)*rest.size(), hipMemcpyDeviceToHost)); }
+    memcpy(p->match_cnt, cnt, 4*nq);
+    int over = -1;
+    for (size_t q = 0; q < nq; q++) {
+        const size_t n = (size_t)cnt[q];
+        if (n > mm) { if (over < 0) over = (int)q; continue; }         // that query's list stays as it was
+        for (size_t j = 0; j < n; j++) {
+            const size_t at = (size_t)roff[q] + j; const TdRec &r = at < n_first ? first[at] : rest[at - n_first];
+            p->match_idx[q*mm + j] = r.idx; p->match_dist[q*mm + j] = r.dist; p->match_score[q*mm + j] = r.score;
+        }
+    }
+    if (nk > 0) { memcpy(p->kf_score, out_at(o_ks), 4*nk); memcpy(p->kf_nobj, out_at(o_ko), 4*nk); }
+    const int32_t nc = *(const int32_t *)out_at(o_nc);
+    *p->n_cand = nc; memcpy(p->cand, out_at(o_cand), 4*(size_t)nc);
+    if (over >= 0) {
+        c->err = "tsloop_detect_loop: query " + std::to_string(over) + " has " + std::to_string(cnt[over]) + " matches, more than max_match = " + std::to_string(p->max_match) +
+                 " (match_cnt, kf_score, kf_nobj, n_cand and cand are complete; the lists of such queries are not written)";
+        return TSLOOP_ERR_ARG;
+    }
+    return TSLOOP_OK;
 }
 
 void tsloop_default_options_loop(tsloop_options *o) {

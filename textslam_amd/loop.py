@@ -3,6 +3,7 @@
   LoopOptimizer.OptimizeSim3(...)     optimizer::OptimizeSim3     /root/reference/src/optimizer.cc:626-731
   LoopOptimizer.OptimizeLoop(...)     optimizer::OptimizeLoop     /root/reference/src/optimizer.cc:733-957 (the solve; the map update stays with the caller)
   LoopOptimizer.Sim3Batch(...)        Sim3Solver::iterate + optimizer::OptimizeSim3 of every loop candidate, one launch (src/Sim3Solver.cc:59-253)
+  LoopOptimizer.DetectLoop(...)       loopClosing::DetectLoop: the string scan, the match lists, the vote and the candidates (src/loopClosing.cc:119-304)
 
 No CPU fallback: without the HIP library / a GPU every call raises.
 """
@@ -13,8 +14,10 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libtsloop.so")
 EXPORTED_SYMBOLS = ["tsloop_default_options_sim3", "tsloop_default_options_loop", "tsloop_create", "tsloop_destroy", "tsloop_last_error",
-                    "tsloop_optimize_sim3", "tsloop_optimize_loop", "tsloop_default_options_sim3_ransac", "tsloop_sim3_batch"]
+                    "tsloop_optimize_sim3", "tsloop_optimize_loop", "tsloop_default_options_sim3_ransac", "tsloop_sim3_batch",
+                    "tsloop_default_options_detect", "tsloop_detect_loop"]
 RANSAC_MAX_HYP = 64                    # TSLOOP_RANSAC_MAX_HYP
+TEXT_MAX_LEN = 64                      # TSLOOP_TEXT_MAX_LEN
 
 
 class TsloopOptions(C.Structure):
@@ -83,6 +86,64 @@ def make_sim3_batch_problem(cands, K1, K, optimise=True, min_inliers=20, max_err
     return p, A
 
 
+class TsloopDetectProblem(C.Structure):
+    _fields_ = [("n_query", C.c_int32), ("n_map", C.c_int32), ("n_kf", C.c_int32), ("top_n", C.c_int32),
+                ("q_off", C.POINTER(C.c_int32)), ("q_str", C.POINTER(C.c_uint8)), ("q_self", C.POINTER(C.c_int32)),
+                ("m_off", C.POINTER(C.c_int32)), ("m_str", C.POINTER(C.c_uint8)), ("m_skip", C.POINTER(C.c_uint8)),
+                ("obs_off", C.POINTER(C.c_int32)), ("obs_kf", C.POINTER(C.c_int32)),
+                ("min_str_score", C.c_double), ("score_thresh_min", C.c_double), ("min_matched_words", C.c_int32), ("max_match", C.c_int32),
+                ("match_cnt", C.POINTER(C.c_int32)), ("match_idx", C.POINTER(C.c_int32)), ("match_dist", C.POINTER(C.c_int32)),
+                ("match_score", C.POINTER(C.c_double)), ("kf_score", C.POINTER(C.c_int32)), ("kf_nobj", C.POINTER(C.c_int32)),
+                ("n_cand", C.POINTER(C.c_int32)), ("cand", C.POINTER(C.c_int32))]
+
+
+def _flat_bytes(strings):
+    """bytes-like strings -> ([n + 1] int32 offsets, uint8 bytes; one spare byte so that the array is never empty)."""
+    bs = [bytes(x) for x in strings]
+    off = np.concatenate([[0], np.cumsum([len(b) for b in bs], dtype=np.int64)]).astype(np.int32)
+    return off, np.frombuffer(b"".join(bs) + b"\0", np.uint8).copy()
+
+
+def make_detect_problem(queries, q_self, map_texts, m_skip, obs_rows, n_kf, min_matched_words=1, score_thresh_min=0.51, min_str_score=0.3, top_n=10,
+                        max_match=64, fill=None):
+    """queries / map_texts: bytes per text (textCur.mean / TextMean.mean);  q_self [n_query]: the map index of a query's own object or -1;  m_skip [n_map]:
+    1 = TEXTBAD;  obs_rows: per map text the eligible keyframes that observe it, as increasing indices in [0, n_kf).  Returns (struct, arrays): arrays holds the
+    flat inputs and the outputs the struct points at.  fill = (int32, float64): what the outputs hold before the call."""
+    nq, nm = len(queries), len(map_texts)
+    assert len(q_self) == nq and len(m_skip) == nm and len(obs_rows) == nm
+    A = {}
+    A["q_off"], A["q_str"] = _flat_bytes(queries); A["m_off"], A["m_str"] = _flat_bytes(map_texts)
+    A["q_self"] = np.ascontiguousarray(q_self, np.int32).reshape(nq).copy(); A["m_skip"] = np.ascontiguousarray(m_skip, np.uint8).reshape(nm).copy()
+    A["m_skip"] = np.concatenate([A["m_skip"], np.zeros(1, np.uint8)]); A["q_self"] = np.concatenate([A["q_self"], np.zeros(1, np.int32)])      # (never empty)
+    A["obs_off"] = np.concatenate([[0], np.cumsum([len(r) for r in obs_rows], dtype=np.int64)]).astype(np.int32)
+    A["obs_kf"] = np.concatenate([np.asarray(r, np.int32).reshape(-1) for r in obs_rows] + [np.zeros(1, np.int32)]).astype(np.int32)
+    fi, fd = fill if fill is not None else (0, 0.0)
+    mm = max(int(max_match), 1)
+    A["match_cnt"] = np.full(max(nq, 1), fi, np.int32); A["match_idx"] = np.full((max(nq, 1), mm), fi, np.int32); A["match_dist"] = np.full((max(nq, 1), mm), fi, np.int32)
+    A["match_score"] = np.full((max(nq, 1), mm), fd, np.float64); A["kf_score"] = np.full(max(int(n_kf), 1), fi, np.int32); A["kf_nobj"] = np.full(max(int(n_kf), 1), fi, np.int32)
+    A["n_cand"] = np.full(1, fi, np.int32); A["cand"] = np.full(max(int(top_n), 1), fi, np.int32)
+    p = TsloopDetectProblem()
+    p.n_query = nq; p.n_map = nm; p.n_kf = int(n_kf); p.top_n = int(top_n); p.max_match = int(max_match); p.min_matched_words = int(min_matched_words)
+    p.min_str_score = float(min_str_score); p.score_thresh_min = float(score_thresh_min)
+    for name, ct in TsloopDetectProblem._fields_:
+        if name in A:
+            setattr(p, name, A[name].ctypes.data_as(ct))
+    return p, A
+
+
+def detect_result(p, A):
+    """The outputs of a tsloop_detect_loop call as a dict: per query the match list (idx, dist, score arrays; None for a list that did not fit max_match)."""
+    nq, nk = p.n_query, p.n_kf
+    cnt = A["match_cnt"][:nq].copy()
+    fits = [int(n) <= p.max_match for n in cnt]
+    nc = int(A["n_cand"][0])
+    return {"match_cnt": cnt,
+            "match_idx": [A["match_idx"][q, :cnt[q]].copy() if fits[q] else None for q in range(nq)],
+            "match_dist": [A["match_dist"][q, :cnt[q]].copy() if fits[q] else None for q in range(nq)],
+            "match_score": [A["match_score"][q, :cnt[q]].copy() if fits[q] else None for q in range(nq)],
+            "kf_score": A["kf_score"][:nk].copy(), "kf_nobj": A["kf_nobj"][:nk].copy(), "n_cand": nc, "cand": A["cand"][:nc].copy()}
+
+
 def make_graph_problem(pose, fixed, edge_i, edge_j, meas):
     pose = np.ascontiguousarray(pose, np.float64).reshape(-1, 8).copy(); fixed = np.ascontiguousarray(fixed, np.uint8)
     ei = np.ascontiguousarray(edge_i, np.int32); ej = np.ascontiguousarray(edge_j, np.int32); meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 8)
@@ -132,6 +193,8 @@ class LoopOptimizer:
         L.tsloop_optimize_loop.argtypes = [C.c_void_p, C.POINTER(TsloopGraphProblem), C.POINTER(TsloopOptions), C.POINTER(TsloopReport)]
         L.tsloop_default_options_sim3_ransac.argtypes = [C.POINTER(TsloopSim3BatchProblem)]; L.tsloop_default_options_sim3_ransac.restype = None
         L.tsloop_sim3_batch.argtypes = [C.c_void_p, C.POINTER(TsloopSim3BatchProblem), C.POINTER(TsloopOptions)]; L.tsloop_sim3_batch.restype = C.c_int
+        L.tsloop_default_options_detect.argtypes = [C.POINTER(TsloopDetectProblem)]; L.tsloop_default_options_detect.restype = None
+        L.tsloop_detect_loop.argtypes = [C.c_void_p, C.POINTER(TsloopDetectProblem)]; L.tsloop_detect_loop.restype = C.c_int
         self.ctx = C.c_void_p()
         rc = L.tsloop_create(device, C.byref(self.ctx))
         if rc != 0:
@@ -176,6 +239,22 @@ class LoopOptimizer:
             out.append({"ok": bool(A["ok"][k]), "sel": int(A["sel"][k]), "n_inlier_ransac": int(A["n_inlier_ransac"][k]), "sim_ransac": A["sim_ransac"][k].copy(),
                         "inlier": A["inlier"][a:b].astype(bool), "hyp_count": A["hyp_count"][ha:hb].copy(), "hyp_sim": A["hyp_sim"][ha:hb].copy(),
                         "sim": A["sim"][k].copy() if done else None, "report": rep})
+        return out
+
+    def DetectLoop(self, queries, q_self, map_texts, m_skip, obs_rows, n_kf, min_matched_words=1, score_thresh_min=None, min_str_score=None, top_n=None,
+                   max_match=None):
+        """loopClosing::DetectLoop's scan, lists, vote and candidates in one call (make_detect_problem names the arguments; None = the library's default).
+        Returns detect_result's dict plus "status": 0, or -1 when a query has more matches than max_match -- then match_cnt, kf_score, kf_nobj, n_cand and cand
+        are complete and that query's lists are None (call again with max_match = match_cnt.max())."""
+        d = TsloopDetectProblem(); self.lib.tsloop_default_options_detect(C.byref(d))
+        p, A = make_detect_problem(queries, q_self, map_texts, m_skip, obs_rows, n_kf, min_matched_words,
+                                   d.score_thresh_min if score_thresh_min is None else score_thresh_min, d.min_str_score if min_str_score is None else min_str_score,
+                                   d.top_n if top_n is None else top_n, d.max_match if max_match is None else max_match)
+        A["match_cnt"][:] = 0
+        rc = self.lib.tsloop_detect_loop(self.ctx, C.byref(p))
+        if rc != 0 and not (rc == -1 and p.n_query > 0 and int(A["match_cnt"][:p.n_query].max()) > p.max_match):
+            raise LoopError("tsloop_detect_loop failed (%d): %s" % (rc, self.lib.tsloop_last_error(self.ctx).decode()))
+        out = detect_result(p, A); out["status"] = rc
         return out
 
     def default_options_loop(self):
