@@ -71,7 +71,7 @@ typedef struct tsba_debug_options {
     int32_t pcg_tol_exp;       // > 0: relative tolerance 10^-pcg_tol_exp of the conjugate gradients in the M^-1 norm (default 10)
     int32_t pcg_refactor;      // preconditioner of the single-vector iteration: 0 the single-vector solve phase (tsba_bandsv.h) where it exists, else the factorisation re-run with the residual as right-hand side; 1: always the re-run; 2: the many-column solve phase with one column; 3: as 0 with r.z by its own kernel instead of inside the solve phase (A/B runs)
     int32_t pcg_block;         // 0 / 1: the single-vector iteration, 2: enlarged conjugate gradients (32 columns per preconditioner application, tsba_pcg.h) where the many-column solve phase of the band solver exists
-    int32_t solve_variant;     // reduced system of a small window (one workgroup, S in LDS): 0 the two-panel-wave schedule (tsba_solve.h), 1 the look-ahead schedule with a separate diagonal wave (tsba_solve_la.h: built in round 4 and measured SLOWER, 39.3 against 33.2 us on C4; kept for A/B runs), 2 as 1 with the update tiles handed out in wave order, 3 the production solver with the back-substitution and the step decision as launches of their own (k_solve_t + k_back + k_decide per trial, production until round 4) instead of in the solver's launch (k_solve_back) and in the next trial's k_schur_t, 4 as 3 with every 6x6 diagonal block factored from a scratch copy in LDS by every lane of the panel waves (production until round 5) instead of in place across six lanes with v_readlane broadcasts (bit-identical), 5 as 0 (production) with that scratch-copy factorisation
+    int32_t solve_variant;     // reduced system of a small window (one workgroup, S in LDS): 0 the two-panel-wave schedule (tsba_solve.h), 1 the look-ahead schedule with a separate diagonal wave (tsba_solve_la.h: built in round 4 and measured SLOWER, 39.3 against 33.2 us on C4; kept for A/B runs), 2 as 1 with the update tiles handed out in wave order, 3 the production solver with the back-substitution and the step decision as launches of their own (k_solve_t + k_back + k_decide per trial, production until round 4) instead of in the solver's launch (k_solve_back) and in the next trial's k_schur_t, 4 as 3 with every 6x6 diagonal block factored from a scratch copy in LDS by every lane of the panel waves (production until round 5) instead of in place across six lanes with v_readlane broadcasts (bit-identical), 5 as 0 (production) with that scratch-copy factorisation, 6 as 0 with the solver workgroup of k_solve_back loading and publishing as it did before block step 0 ran beside the load (S element by element by all twelve waves behind a barrier, the pose step stored by one thread per keyframe that looks its free block up behind the back-substitution's barrier; bit-identical, kept for A/B runs)
     int32_t sv_per_level;      // bit 0: the separator tree of the single-vector solve phase as one launch per level (k_sv_cre_fwd / _top / _back, production until round 4) instead of one launch for the whole tree (k_sv_cre_tree); bit 1: the back substitution of the factorisation's own solve on maps with long-range blocks as a launch per level (k_cre_back) instead of one launch through the solve phase's products (k_cre_back_tree); bit 2: the update step of a conjugate-gradient iteration (alpha; x, r) as a launch of its own (k_pcg_update) instead of inside the first kernel of the preconditioner application; bit 3: the interiors' back substitution of the solve phase as a launch of its own (k_sv_back_int) instead of in the tree's launch (k_sv_tree_back): A/B runs, bit-identity / parity tests
     int32_t host_pair_lists;   // 0: on the device for problems of at least 4096 scene observations, on the host below; 2: on the device at any size; 1: the slot pairs of the S blocks are built on the host (as every map did until round 4 and every window until round 6) instead of on the device (tsba_devplan.h): A/B runs, list comparison; and single-frame problems (tsba_pose_optim) get their plan from the generic builder on plan threads, the later passes' levels staged during the solve (until round 6), instead of build_plan_single_frame on the calling thread
     int32_t pass_launches;     // 1: a window's pass begins and ends with the launches of rounds 1-4 (k_pass_reset, k_participation, k_gauge_wave, k_musigma | k_outlier, state copy) instead of k_pass_begin | k_pass_end (tsba_kernels_pass.h); PoseOptim: a launch per LM step (k_pose_iter) instead of one per pass (k_pose_pass): A/B runs, agreement tests; 2: PoseOptim (one GPU): the first attempt runs as in production and the host then treats it as abandoned, as if it had reported one give-up (tsba_report.poll_timeouts) -- nothing on the device waits, times out or fails -- so that the retry with a launch per LM step runs under test; every other context: as 1

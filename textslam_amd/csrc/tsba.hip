@@ -640,9 +640,9 @@ static SolverLayout upload_layout(const Ctx *c) {
 static int alloc_reduced_system(Ctx *c, const tsba_problem *p, const SolverLayout &L) {
     Work &W = c->W; const int bw = L.bw_rows;
     c->lay = L;
-    W.dp_poll = L.use_lds && !is_multi(c) && !c->pose_only && (c->dbg.solve_variant == 0 || c->dbg.solve_variant == 5);        // solver and back-substitution in one launch (k_solve_back)
+    W.dp_poll = L.use_lds && !is_multi(c) && !c->pose_only && (c->dbg.solve_variant == 0 || c->dbg.solve_variant == 5 || c->dbg.solve_variant == 6);        // solver and back-substitution in one launch (k_solve_back)
     if (W.dp_poll) {                           // ... whose workgroups poll the solver's: only where the whole grid is resident at once (else k_solve_t + k_back + k_decide)
-        const int ldsb = std::max((int)(solve_lds_doubles(W.N)*sizeof(double)), (int)((768 + W.N + 2)*sizeof(double)));
+        const int ldsb = solve_back_lds_bytes((int)(solve_lds_doubles(W.N)*sizeof(double)), W.N);
         ATTR(k_solve_back<true>, ldsb);
         if (!grid_resident(c, (const void *)k_solve_back<true>, SOLVE_THREADS, (size_t)ldsb, 1 + (c->nb_back_max + 2)/3)) W.dp_poll = 0;
     }
@@ -1013,8 +1013,9 @@ static int set_solver_attrs(Ctx *c) {
     int use_lds; int lds = solve_lds_bytes(c, &use_lds);
     if (use_lds) { ATTR(k_solve_t<false>, lds);
         ATTR((k_solve_t<false, false>), lds);
-        ATTR(k_solve_back<true>, std::max(lds, (int)((768 + c->W.N + 2)*sizeof(double))));
-        ATTR(k_solve_back<false>, std::max(lds, (int)((768 + c->W.N + 2)*sizeof(double))));
+        ATTR(k_solve_back<true>, solve_back_lds_bytes(lds, c->W.N));
+        ATTR(k_solve_back<false>, solve_back_lds_bytes(lds, c->W.N));
+        ATTR((k_solve_back<true, true>), solve_back_lds_bytes(lds, c->W.N));
         ATTR(k_solve_la, (int)std::min<size_t>(solve_la_lds_doubles(c->W.N)*sizeof(double), 160*1024 - 64)); }
     else {
         ATTR(k_band_solve, 156*1024);
@@ -1090,8 +1091,9 @@ static void launch_step(Ctx *c, const LevelDev &D, bool decide_prev = false, boo
     }
     if (W.dp_poll && D.far_B <= 0) {               // small window: solver (workgroup 0) and back-substitution (three blocks per workgroup, polling the step) in one launch
         int use_lds; const int lds = solve_lds_bytes(c, &use_lds);
-        const int ldsb = std::max(lds, (int)((768 + W.N + 2)*sizeof(double)));
-        if (c->dbg.solve_variant == 5) LAUNCHK(k_solve_back<false>, dim3(1 + (nb_all + 2)/3), dim3(SOLVE_THREADS), ldsb, c->stream, W, D, bb_pt, bb_tx, nb_all);      // (A/B: the diagonal blocks through the LDS scratch)
+        const int ldsb = solve_back_lds_bytes(lds, W.N);
+        if (c->dbg.solve_variant == 6) LAUNCHK((k_solve_back<true, true>), dim3(1 + (nb_all + 2)/3), dim3(SOLVE_THREADS), ldsb, c->stream, W, D, bb_pt, bb_tx, nb_all);      // (A/B: the solver workgroup's load and publication as they were before the load by rows)
+        else if (c->dbg.solve_variant == 5) LAUNCHK(k_solve_back<false>, dim3(1 + (nb_all + 2)/3), dim3(SOLVE_THREADS), ldsb, c->stream, W, D, bb_pt, bb_tx, nb_all);      // (A/B: the diagonal blocks through the LDS scratch)
         else LAUNCHK(k_solve_back<true>, dim3(1 + (nb_all + 2)/3), dim3(SOLVE_THREADS), ldsb, c->stream, W, D, bb_pt, bb_tx, nb_all);
     } else {
         launch_solve_full(c, D);

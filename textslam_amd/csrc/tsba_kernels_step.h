@@ -189,29 +189,35 @@ __device__ __forceinline__ void back_body(const Work &W, const LevelDev &L, int 
             } else for (int k = 0; k < 7; k++) c[k] = x[k];
         }
     }
-    // the block's two partial sums: 256 values each, in block_sum<256>'s order (a block is four waves of its workgroup)
-    red[tid] = step2; __syncthreads();
-    if (tid < 64) { double sv = ((red[tid] + red[tid + 64]) + red[tid + 128]) + red[tid + 192]; sv = wave_sum1(sv); if (tid == 0 && live) W.partial[2*b] = sv; }
-    __syncthreads();
-    red[tid] = mcc; __syncthreads();
-    if (tid < 64) { double sv = ((red[tid] + red[tid + 64]) + red[tid + 128]) + red[tid + 192]; sv = wave_sum1(sv); if (tid == 0 && live) W.partial[2*b + 1] = sv; }
+    // the block's two partial sums: 256 values each, in block_sum<256>'s order (a block is four waves of its workgroup), both in one pass over red[2][256]
+    red[tid] = step2; red[256 + tid] = mcc; __syncthreads();
+    if (tid < 64) {
+        double sv = ((red[tid] + red[tid + 64]) + red[tid + 128]) + red[tid + 192], sm = ((red[256 + tid] + red[256 + tid + 64]) + red[256 + tid + 128]) + red[256 + tid + 192];
+        sv = wave_sum1(sv); sm = wave_sum1(sm);
+        if (tid == 0 && live) { W.partial[2*b] = sv; W.partial[2*b + 1] = sm; }
+    }
 }
 __global__ __launch_bounds__(256) void k_back(Work W, LevelDev L, int nb_pt, int nb_tx) {
-    __shared__ double red[256];
+    __shared__ double red[512];
     back_body<false>(W, L, nb_pt, nb_tx, blockIdx.x, threadIdx.x, true, red, nullptr);
 }
 // ---- the reduced system of a small window and the back-substitution in ONE launch: workgroup 0 is k_solve_t, every other workgroup three blocks of k_back
 // that wait for the pose step where k_back would wait for its launch (6.97 us per trial on C4, most of it the launch, the state round trip and the
 // records' round trip behind it).  The step reaches the waiting blocks ~0.65 us after the solver stores it (tools/handover_bench.hip).
-template <bool RL = true>
+// The solver workgroup runs block step 0 beside its load and stores the step with one thread per slot (solve_body); the other workgroups wait for exactly
+// those stores.  OLD (tsba_debug_options.solve_variant = 6, A/B runs and the bit-identity tests): the solver workgroup as it was before -- S element by element
+// behind a barrier before step 0, and a store loop of one thread per keyframe that looks its free block up behind the back-substitution's barrier.
+#define BACK_RED 512                        // a back block's reduction scratch: red[2][256]
+template <bool RL = true, bool OLD = false>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_back(Work W, LevelDev L, int nb_pt, int nb_tx, int nb_all) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if (blockIdx.x != 0) {
         const int sub = threadIdx.x >> 8, b = 3*((int)blockIdx.x - 1) + sub;
-        back_body<true>(W, L, nb_pt, nb_tx, b, threadIdx.x & 255, b < nb_all, smem + 256*sub, smem + 768);
+        back_body<true>(W, L, nb_pt, nb_tx, b, threadIdx.x & 255, b < nb_all, smem + BACK_RED*sub, smem + 3*BACK_RED);
         return; }
-    solve_body<false, true, RL>(W, 0, smem);
+    solve_body<false, true, RL, OLD>(W, 0, smem);
 }
+static inline int solve_back_lds_bytes(int solver_bytes, int N) { return std::max(solver_bytes, (int)((3*BACK_RED + N + 2)*sizeof(double))); }      // the solver workgroup's LDS | three back blocks' scratch + the polled step and its flag
 
 // ---- the decision on one LM trial (Ceres 1.x TrustRegionMinimizer / LevenbergMarquardtStrategy semantics) on the state s -- the state in device memory
 // (k_decide) or a workgroup's private copy of it (k_schur_t with the decision of the previous trial inside, tsba_kernels_schur.h).

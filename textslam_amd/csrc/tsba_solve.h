@@ -17,6 +17,10 @@
 // two-barrier MFMA look-ahead were measured within 10 % of this one; this is the simplest of the three.
 // The back-substitution L^T x = z runs in wave 0 with z in registers (60 rows per register: the register a block lives in is a
 // compile-time constant), x_block = L_jj^-T z_block from the stored inverse factors, next block's operands prefetched.
+// Around the chain (a window's system, solve_body<false, ..>): the panel waves load block column 0 themselves and run block step 0 while
+// the update waves, which have no work in it, load the rest of S by rows; and where the step is published to the launch's other
+// workgroups (k_solve_back) every slot has a thread that knows its free block before the back-substitution ends.  docs/kernel_notes.md,
+// "k_solve_back: what surrounds the block-step chain", has the measurements, and what was tried there and taken out.
 #define SOLVE_THREADS 768
 #define SOLVE_PW 2                          // panel waves
 #define SOLVE_PROWS (64 - 6)                // panel rows per wave and chunk
@@ -202,29 +206,97 @@ static size_t solve_diag_lds_doubles() { return solve_lds_doubles(SOLVE_DIAG_NB)
 //               (strict upper triangle) and the inverse's diagonal (W.LDbuf).
 // PUB: the result is published for workgroups of the SAME launch that poll it (k_solve_back, tsba_kernels_step.h): dp and, behind it, the failure flag
 // go out as device-coherent stores of values that are never NaN (the slots hold NaN until then)
+// OLD (k_solve_back only, tsba_debug_options.solve_variant = 6): the load and the publication as they were before block step 0 ran beside the load -- S
+// element by element (tri_row) by all twelve waves behind a barrier, g in a second round trip, the step stored by one thread per keyframe that looks its
+// free block up behind the back-substitution's barrier.  Same bits; kept for A/B runs.
 __device__ __forceinline__ double co_load(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void co_store(double *p, double v) { __hip_atomic_store(p, v == v ? v : __builtin_inf(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // RL: the 6x6 diagonal block is factored where it already lives -- row r in lane r of the panel wave -- with the pivot and the column below it
 // broadcast by v_readlane (uniform operands), instead of going through a wave-private LDS scratch to every lane and being factored there from a
 // private copy: same operations on the same operands in the same order (bit-identical: RL = false is kept for that comparison,
 // tsba_debug_options.solve_variant = 4), ~120 instructions on the chain of a block step instead of ~9 LDS reads + ~110 + the scratch hand-over
-template <bool DIAG, bool PUB, bool RL = true>
+template <bool DIAG, bool PUB, bool RL = true, bool OLD = false>
 __device__ __forceinline__ void solve_body(const Work &W, int B0, double *smem) {
     LmState *st = W.st;
     __shared__ int fail;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int NW = SOLVE_THREADS/64, NT = NW - SOLVE_PW;
+    constexpr bool ROWS = !DIAG && !OLD;                        // S by rows, block step 0 beside the load (DIAG: a block of a large system, element by element as before)
 #ifdef TSBA_SOLVE_STAMPS
     const long long Tl = clock64();
 #endif
     const int Nmax = W.N;
     double *A = smem;                                           // padded packed lower triangle, rows 0..n (row n = g)
-    // the element addresses do not depend on the number of free poses: the first round of loads is issued together with the
-    // loads of the solver state (one global round trip instead of two)
-    const int neMax = DIAG ? tri(SOLVE_DIAG_NB) : tri(Nmax);
     const size_t ldS = (size_t)W.ldS;
     const double *Sb = DIAG ? W.S + (size_t)B0*ldS + B0 : W.S;
     const int rmax = DIAG ? Nmax - 1 - B0 : Nmax - 1;           // (the last block of a large system may be short)
+    int done, nfree_all, sfail, nfree, n;
+    double *LD, *scr;
+    if constexpr (ROWS) {
+        // ---- Block step 0 beside the load.  Step 0 needs block column 0 only and no update wave has work in it: each lane of the panel waves brings in the
+        // six entries of the row(s) it owns at jb = 0 (lanes 0..5 of both waves the six diagonal rows: the same values to the same words) and the panel waves
+        // go into step 0 behind a wave-local fence; the other ten waves bring in columns >= 6 of every row, the rhs row included, and arrive at step 0's
+        // barrier.  They take S by rows, 64 columns of a row per request: the row offset is a scalar, the column is the lane, no tri_row.
+        // No address depends on the number of free poses (rows and columns are clamped to the system's last), only the destinations do: every load of the
+        // first batch -- S, g, the state -- is requested before the first answer is needed (one global round trip).
+        constexpr int P0 = 10, P1 = 4;                          // a loader wave's first batch: rows of column chunk 0, rows of column chunk 1 (ten loaders: rows 6..105 | 70..109)
+        constexpr int C0 = 6, LW0 = SOLVE_PW, LNW = NW - LW0;   // the loaders' first column, their first wave, how many they are
+        const bool loader = wave >= LW0;
+        const int wl = wave - LW0;
+        const int i0p = lane < 6 ? lane : 6 + wave*SOLVE_PROWS + lane - 6;                 // the row a panel lane owns at jb = 0
+        const int gk = C0 + tid - 64*LW0;                       // a loader thread's entry of g  (n < 64 LNW: lds_solver_fits)
+        double v0[P0], v1[P1], gv = 0.0, pv[6], pg[6];
+        if (loader) {
+#pragma unroll
+            for (int u = 0; u < P0; u++) { const int r = min(C0 + wl + LNW*u, rmax); v0[u] = Sb[(size_t)r*ldS + min(C0 + lane, r)]; }
+#pragma unroll
+            for (int u = 0; u < P1; u++) { const int r = min(C0 + 64 + wl + LNW*u, rmax); v1[u] = Sb[(size_t)r*ldS + min(C0 + 64 + lane, r)]; }
+            gv = W.g[min(gk, Nmax - 1)];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 6; c++) { const int r = min(i0p, rmax); pv[c] = Sb[(size_t)r*ldS + min(c, r)]; pg[c] = W.g[min(c, Nmax - 1)]; }
+        }
+        done = st->done; nfree_all = *W.nfree; sfail = st->step_fail;
+        if (done) return;
+        nfree = nfree_all; n = 6*nfree;
+        LD = A + rowoff(n + 1) + 16; scr = LD + SOLVE_LD*nfree;
+        if (loader) {
+#pragma unroll
+            for (int u = 0; u < P0; u++) { const int r = C0 + wl + LNW*u, c = C0 + lane; if (r < n && c <= r) A[rowoff(r) + c] = v0[u]; }
+#pragma unroll
+            for (int u = 0; u < P1; u++) { const int r = C0 + 64 + wl + LNW*u, c = C0 + 64 + lane; if (r < n && c <= r) A[rowoff(r) + c] = v1[u]; }
+            for (int ch = 0; C0 + 64*ch < n; ch++) {                                      // systems beyond the first batch, four rows of a column chunk in flight
+                const int c = C0 + 64*ch + lane;
+                for (int r0 = C0 + 64*ch + wl + LNW*(ch == 0 ? P0 : ch == 1 ? P1 : 0); r0 < n; r0 += 4*LNW) {
+                    double w[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const int r = min(r0 + LNW*u, n - 1); w[u] = Sb[(size_t)r*ldS + min(c, r)]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const int r = r0 + LNW*u; if (r < n && c <= r) A[rowoff(r) + c] = w[u]; }
+                }
+            }
+            if (gk < n) A[rowoff(n) + gk] = gv;
+        } else {
+            if (i0p < n) {
+                if (lane >= 6) st6(A + rowoff(i0p), pv);
+                else {
+#pragma unroll
+                    for (int c = 0; c < 6; c++) if (c <= lane) A[rowoff(i0p) + c] = pv[c];   // (the words behind a diagonal row's last entry are the next row's)
+                }
+            } else if (i0p == n) st6(A + rowoff(n), pg);
+            if (lane >= 6)
+                for (int i = i0p + SOLVE_PW*SOLVE_PROWS; i <= n; i += SOLVE_PW*SOLVE_PROWS) {  // more rows than one round of the panel lanes
+#pragma unroll
+                    for (int c = 0; c < 6; c++) pv[c] = i < n ? Sb[(size_t)i*ldS + c] : W.g[c];
+                    st6(A + rowoff(i), pv);
+                }
+            wave_lds_fence();
+        }
+        if (tid == 0) fail = sfail;
+    } else {
+    // the element addresses do not depend on the number of free poses: the first round of loads is issued together with the
+    // loads of the solver state (one global round trip instead of two)
+    const int neMax = DIAG ? tri(SOLVE_DIAG_NB) : tri(Nmax);
     double v[12]; int er[12], ec[12];
 #pragma unroll
     for (int u = 0; u < 12; u++) {
@@ -232,13 +304,14 @@ __device__ __forceinline__ void solve_body(const Work &W, int B0, double *smem) 
         er[u] = tri_row(e); ec[u] = e - tri(er[u]);
         v[u] = Sb[(size_t)min(er[u], rmax)*ldS + min(ec[u], rmax)];
     }
-    const int done = st->done, nfree_all = *W.nfree, sfail = st->step_fail;
+    done = st->done; nfree_all = *W.nfree; sfail = st->step_fail;
     if (done) return;
     if (DIAG && (sfail || 6*nfree_all <= B0)) return;
-    const int nfree = DIAG ? min(SOLVE_DIAG_NB, 6*nfree_all - B0)/6 : nfree_all;
-    const int n = 6*nfree, ne = tri(n);
-    double *LD = A + rowoff(n + 1) + 16;
-    double *scr = LD + SOLVE_LD*nfree;
+    nfree = DIAG ? min(SOLVE_DIAG_NB, 6*nfree_all - B0)/6 : nfree_all;
+    n = 6*nfree;
+    const int ne = tri(n);
+    LD = A + rowoff(n + 1) + 16;
+    scr = LD + SOLVE_LD*nfree;
 #pragma unroll
     for (int u = 0; u < 12; u++) if (u*SOLVE_THREADS + tid < ne) A[rowoff(er[u]) + ec[u]] = v[u];
     for (int base = 12*SOLVE_THREADS; base < ne; base += 12*SOLVE_THREADS) {
@@ -254,11 +327,14 @@ __device__ __forceinline__ void solve_body(const Work &W, int B0, double *smem) 
     for (int k = tid; k < n; k += SOLVE_THREADS) A[rowoff(n) + k] = DIAG ? 0.0 : W.g[k];
     if (tid == 0) fail = DIAG ? 0 : sfail;
     __syncthreads();
+    }
 #ifdef TSBA_SOLVE_STAMPS
     if (tid == 0) W.dbg[0] = clock64() - Tl;
+    if (tid == 64*SOLVE_PW) W.dbg[3] = clock64() - Tl;          // (the loader waves' arrival at step 0's barrier; dbg[0] is then the panel waves' own load)
     long long tx = clock64(), T0 = tx, ta = 0, tb = 0, tc = 0, td = 0;
 #endif
-    for (int jb = 0; jb < nfree && !fail; jb++) {
+    // (ROWS: no barrier lies between `fail = sfail` and the first test -- the assembly's flag is in every thread's registers)
+    for (int jb = 0; jb < nfree && !(jb == 0 ? (DIAG ? 0 : sfail) : fail); jb++) {
         const int j0 = 6*jb, R0 = j0 + 6, p0 = j0 - 6;
 #ifdef TSBA_SOLVE_STAMPS
         const long long tx0_ = clock64();
@@ -452,11 +528,29 @@ __device__ __forceinline__ void solve_body(const Work &W, int B0, double *smem) 
         }
         return;
     }
-    if (fail || nfree == 0) {
+    const bool failed = sfail || (nfree > 0 && fail);         // (nfree == 0 / sfail: the loop did not run and no barrier orders `fail`)
+    if (failed || nfree == 0) {
         for (int k = tid; k < Nmax; k += SOLVE_THREADS) { if (PUB) co_store(&W.dp[k], 0.0); else W.dp[k] = 0.0; }
-        if (PUB && tid == 0) co_store(&W.dp[Nmax], fail ? 1.0 : 0.0);
+        if (PUB && tid == 0) co_store(&W.dp[Nmax], failed ? 1.0 : 0.0);
         return; }
     double *rhs = A + rowoff(n);
+    if constexpr (PUB && !OLD) {
+        // One slot of the step per thread of waves 1..11 (6 n_kf = N < 704: lds_solver_fits).  The keyframe's free block is looked up while wave 0
+        // substitutes; a constant keyframe's zeros and the flag go out at once.  No order among the stores is needed: the consumers poll every slot for
+        // non-NaN on its own (back_body<true>).
+        const int k = tid - 64;
+        const bool mine = k >= 0 && k < Nmax;
+        int ia = -1;
+        if (mine) { ia = W.fidx[k/6]; if (ia < 0) co_store(&W.dp[k], 0.0); }
+        if (tid == SOLVE_THREADS - 1) co_store(&W.dp[Nmax], 0.0);
+        if (wave == 0) solve_backsub_wave(A, LD, n, nfree, lane);
+        __syncthreads();
+#ifdef TSBA_SOLVE_STAMPS
+        if (tid == 0) W.dbg[2] = clock64() - T1;
+#endif
+        if (mine && ia >= 0) co_store(&W.dp[k], -rhs[6*ia + k % 6]);
+        return;
+    }
     if (wave == 0) solve_backsub_wave(A, LD, n, nfree, lane);
     __syncthreads();
 #ifdef TSBA_SOLVE_STAMPS

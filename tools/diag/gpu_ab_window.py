@@ -12,7 +12,7 @@ from textslam_amd import synth, abi
 from textslam_amd.optimizer import Optimizer
 
 DEFAULT = ["production=", "ldl_scratch=solve_variant:5", "pass_launches=pass_launches:1", "lin_mid_fused=trial_launches:2", "round4=solve_variant:5,pass_launches:1",
-           "separate_launches=solve_variant:3"]
+           "separate_launches=solve_variant:3", "old_load_publish=solve_variant:6"]
 
 
 def main():

@@ -14,6 +14,7 @@ print("t_solve_ms", rep['t_solve_ms'])
 st = (ctypes.c_longlong * 64)()
 opt.lib.tsba_debug_stamps(opt.ctx, st)
 print("k_solve stamps (cycles): load %d factor %d backsub %d nfree %d" % (st[0], st[1], st[2], st[6]))
+print("   (load: wave 0 until it enters step 0 -- with step 0 beside the load, its own block column 0 only; the loader waves reach step 0's barrier at %d)" % st[3])
 for i, nm in enumerate(("P wave0 (look-ahead | scratch+ldl | solve | barrier)", "T wave2 (- | - | trailing | barrier)", "T last")):
     print("   %s: lookahead+scratch %d  ldl %d  solve/trailing %d  barrier-wait %d" % ((nm,) + tuple(st[8+4*i:12+4*i])))
 print("k_decide stamps (cycles): sums_local %d  pose_scale %d  partials %d  decision %d" % tuple(st[32:36]))
