@@ -139,6 +139,28 @@ int tsorb_match_search_sets(void *ctx,
         const float *qxy /*[nq][2]*/, const float *qr /*[nq]*/, const int32_t *qlev /*[nq][2], NULL = no level check*/,
         int max_cand, int32_t *cand_idx, int32_t *cand_dist, int32_t *cand_cnt, int32_t *best_idx, int32_t *best_dist, int32_t *best_dist2);
 
+/* ---- The outlier gate between the window search and PoseOptim: tracking::CheckMatch (src/tracking.cc:1499-1579), called by TrackWithMotMod / TrackWithOutMod as soon as
+ * more than 20 matches survive, = cv::solvePnPRansac(vP3d, vP2d, K, 0, rvec, tvec, false, 100, ReproError, 0.98, inliers, SOLVEPNP_EPNP) as docs/pnpransac_recalled.md states
+ * it: up to n_hyp five-point EPnP hypotheses, an inlier count of each over all n matches, the loop with RANSACUpdateNumIters' early stop.  The refit on the inliers that
+ * follows changes rvec / tvec only, which CheckMatch does not read: it is not built.
+ *   Pw [n][3]: the matches' world points as floats (OpenCV converts vP3d to CV_32F), uv [n][2]: their keypoints, K = fx, fy, cx, cy (EPnP runs on pixel coordinates).
+ *   subset [n_hyp][5]: the hypotheses' matches.  The library has no generator: the caller draws them (adapter/tsorb_pnp_check.hpp restates cv::RNG's draws).
+ *   ALL n_hyp hypotheses are evaluated and reported: hyp_count [n_hyp] = each one's inlier count (err <= (float)(reproj_err^2), no test on the depth's sign), hyp_pose
+ *   [n_hyp][12] = its R | t, 3 x 4 row-major.  result = { ok, n_inlier, sel, n_run }: the reference's loop over the counts keeps hypothesis sel (-1: none; a count must
+ *   exceed max(maxGood, 4), the first of equal counts stays) with n_inlier = maxGood inliers, would have run n_run hypotheses, and succeeds (ok) iff maxGood > 0.
+ *   inlier [n] = the kept hypothesis' mask, all 0 when not ok; pose [12] = its R | t (zeros when not ok).  pose, hyp_count, hyp_pose may be NULL.
+ * A degenerate subset (five points whose scatter has an eigenvalue ratio below 1e-12: coplanar, collinear, coincident) is a result, not an error: its pose is NaN and
+ * its count is what the comparisons give (a NaN compares false: 0).  Needs only a context: the resident batch and the match grid are left as they were.
+ * TSORB_ERR_ARG (tsorb_last_error names the function, nothing is launched, no output is touched) for: a NULL context or a NULL pointer where data is needed, n < 5,
+ * n > TSORB_PNP_MAX_POINTS, n_hyp outside [1, TSORB_PNP_MAX_HYP], a subset index outside [0, n) or twice in a subset, a point, pixel or K that is not finite,
+ * reproj_err not finite or <= 0, confidence outside [0, 1]. */
+#define TSORB_PNP_MAX_HYP 128
+#define TSORB_PNP_MAX_POINTS 65536
+int tsorb_match_pnp_ransac(void *ctx, int n, const float *Pw /*[n][3]*/, const float *uv /*[n][2]*/, const double K[4] /*fx fy cx cy*/,
+                           int n_hyp, const int32_t *subset /*[n_hyp][5], the caller draws them*/, double reproj_err, double confidence,
+                           uint8_t *inlier /*[n]*/, int32_t *result /*[4]: ok, n_inlier, sel, n_run*/, double *pose /*[12] R|t row-major, may be NULL*/,
+                           int32_t *hyp_count /*[n_hyp] or NULL*/, double *hyp_pose /*[n_hyp][12] or NULL*/);
+
 /* ---- Text features of a frame.
  * frame::FeatExtracText (src/frame.cc:334-355): for each of n_dete detection quads (level-0 pixels, double x, y; truncated like cv::Point)
  * cv::ORB::create()->detect on the frame masked to the quad (tool::GetMask) and ->compute on the frame itself, OpenCV 3.3 defaults;

@@ -1462,6 +1462,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
 #include "tscvorb.h"
 #include "tsbrute.h"
 #include "tswindow.h"
+#include "tspnp.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -2046,6 +2047,53 @@ int tsorb_match_search_sets(void *ctx, int n_set, const int32_t *foff, const flo
     if (best_idx) memcpy(best_idx, ho + 2*b_c + b_i, 4*NQ);
     if (best_dist) memcpy(best_dist, ho + 2*b_c + 2*b_i, 4*NQ);
     if (best_dist2) memcpy(best_dist2, ho + 2*b_c + 3*b_i, 4*NQ);
+    return TSORB_OK;
+}
+
+// ---- tracking::CheckMatch: cv::solvePnPRansac over caller-drawn subsets (tspnp.h, docs/pnpransac_recalled.md).  Needs only a context and shares the blocks of the calls
+// above: one pinned block [Pw | uv | subset | result | pose | count | hyp_pose | inlier], its image on the device, one copy up, three launches, one copy down, one synchronisation.
+int tsorb_match_pnp_ransac(void *ctx, int n, const float *Pw, const float *uv, const double K[4], int n_hyp, const int32_t *subset, double reproj_err, double confidence,
+                           uint8_t *inlier, int32_t *result, double *pose, int32_t *hyp_count, double *hyp_pose) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_match_pnp_ransac: ") + m; return TSORB_ERR_ARG; };
+    if (n < 5) return bad("n < 5");
+    if (n > TSORB_PNP_MAX_POINTS) return bad("n above TSORB_PNP_MAX_POINTS");
+    if (n_hyp < 1 || n_hyp > TSORB_PNP_MAX_HYP) return bad("n_hyp outside [1, TSORB_PNP_MAX_HYP]");
+    if (!Pw || !uv || !K || !subset || !inlier || !result) return bad("NULL pointer");
+    if (!std::isfinite(reproj_err) || !(reproj_err > 0.0)) return bad("reproj_err not finite or <= 0");
+    if (!(confidence >= 0.0 && confidence <= 1.0)) return bad("confidence outside [0, 1]");
+    for (int i = 0; i < 4; i++) if (!std::isfinite(K[i])) return bad("K is not finite");
+    const size_t N = (size_t)n, H = (size_t)n_hyp;
+    for (size_t i = 0; i < 3*N; i++) if (!std::isfinite(Pw[i])) return bad("a point is not finite");
+    for (size_t i = 0; i < 2*N; i++) if (!std::isfinite(uv[i])) return bad("a pixel is not finite");
+    for (size_t h = 0; h < H; h++) { const int32_t *s = subset + 5*h;
+        for (int i = 0; i < 5; i++) { if (s[i] < 0 || s[i] >= n) return bad("a subset index outside [0, n)");
+            for (int j = 0; j < i; j++) if (s[j] == s[i]) return bad("an index twice in a subset"); } }
+    hipSetDevice(c->device);
+    const size_t b_pw = br_al(12*N), b_uv = br_al(8*N), b_sub = br_al(20*H), in_sz = b_pw + b_uv + b_sub;
+    const size_t b_res = br_al(16), b_pose = br_al(96), b_cnt = br_al(4*H), b_hp = br_al(96*H), out_sz = b_res + b_pose + b_cnt + b_hp + br_al(N);
+    if (int rc = br_room(c, in_sz + out_sz, in_sz + out_sz)) return rc;
+    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
+    memcpy(h, Pw, 12*N); memcpy(h + b_pw, uv, 8*N); memcpy(h + b_pw + b_uv, subset, 20*H);
+    OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
+    PnpDev D;
+    D.n = n; D.n_hyp = n_hyp; D.Pw = (const float *)d; D.uv = (const float *)(d + b_pw); D.subset = (const int32_t *)(d + b_pw + b_uv);
+    for (int i = 0; i < 4; i++) D.K[i] = K[i];
+    D.thr = (float)(reproj_err*reproj_err); D.confidence = confidence;
+    D.result = (int32_t *)(d + in_sz); D.pose = (double *)(d + in_sz + b_res); D.count = (int32_t *)(d + in_sz + b_res + b_pose);
+    D.hyp_pose = (double *)(d + in_sz + b_res + b_pose + b_cnt); D.inlier = (uint8_t *)(d + in_sz + b_res + b_pose + b_cnt + b_hp);
+    const unsigned nb = (unsigned)((n + PNP_T - 1)/PNP_T);
+    hipLaunchKernelGGL(k_pnp_hyp, dim3((n_hyp + PNP_NW - 1)/PNP_NW), dim3(PNP_T), 0, c->stream, D);
+    hipLaunchKernelGGL(k_pnp_count, dim3(nb), dim3(PNP_T), 0, c->stream, D);
+    hipLaunchKernelGGL(k_pnp_select, dim3(nb), dim3(PNP_T), 0, c->stream, D);
+    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    const char *o = h + in_sz;
+    memcpy(result, o, 16);
+    if (pose) memcpy(pose, o + b_res, 96);
+    if (hyp_count) memcpy(hyp_count, o + b_res + b_pose, 4*H);
+    if (hyp_pose) memcpy(hyp_pose, o + b_res + b_pose + b_cnt, 96*H);
+    memcpy(inlier, o + b_res + b_pose + b_cnt + b_hp, N);
     return TSORB_OK;
 }
 

@@ -13,9 +13,11 @@ _lib = None
 EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_get_levels", "tsorb_get_scale_factors",
                     "tsorb_get_features_per_level", "tsorb_extract_batch", "tsorb_upload", "tsorb_run", "tsorb_download",
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
-                    "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets"]
+                    "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets", "tsorb_match_pnp_ransac"]
 BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
 SETS_MAX = 1024                                                         # TSORB_SETS_MAX of include/tsorb.h
+PNP_MAX_HYP = 128                                                       # TSORB_PNP_MAX_HYP of include/tsorb.h
+PNP_MAX_POINTS = 65536                                                  # TSORB_PNP_MAX_POINTS of include/tsorb.h
 
 
 class TsorbError(RuntimeError):
@@ -55,6 +57,8 @@ def load_library():
         L.tsorb_match_brute_scene.restype = C.c_int
         L.tsorb_match_search_sets.argtypes = [vp, C.c_int, ip, fp, up, dp, C.c_int, up, C.c_int, ip, ip, fp, fp, ip, C.c_int, ip, ip, ip, ip, ip, ip]
         L.tsorb_match_search_sets.restype = C.c_int
+        L.tsorb_match_pnp_ransac.argtypes = [vp, C.c_int, fp, fp, dp, C.c_int, ip, C.c_double, C.c_double, up, ip, dp, ip, dp]
+        L.tsorb_match_pnp_ransac.restype = C.c_int
         _lib = L
     return _lib
 
@@ -230,6 +234,23 @@ class ORBextractor:
                                                      ptr(qlev_p, C.c_int32), int(max_cand), ptr(ci, C.c_int32), ptr(cd, C.c_int32), ptr(cc, C.c_int32), ptr(bi, C.c_int32),
                                                      ptr(bd, C.c_int32), ptr(bd2, C.c_int32)), "tsorb_match_search_sets")
         return dict(cand_idx=ci, cand_dist=cd, cand_cnt=cc, best_idx=bi, best_dist=bd, best_dist2=bd2)
+
+    # ---- the outlier gate before PoseOptim (tracking::CheckMatch: cv::solvePnPRansac with EPnP, docs/pnpransac_recalled.md)
+    def match_pnp_ransac(self, Pw, uv, K, subsets, reproj_err=5.0, confidence=0.98):
+        """Pw [n, 3] world points and uv [n, 2] keypoints of the matches (floats), K = (fx, fy, cx, cy), subsets [H, 5]: the hypotheses' matches, drawn by the caller.
+        Returns a dict: ok, n_inlier, sel (-1: none), n_run of the reference's loop, inlier [n] bool (the kept hypothesis' mask), pose [3, 4] = R | t of the kept
+        hypothesis, and of EVERY hypothesis hyp_count [H] int32 and hyp_pose [H, 3, 4]."""
+        Pw = np.ascontiguousarray(Pw, np.float32).reshape(-1, 3); uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        K = np.ascontiguousarray(K, np.float64).reshape(4); subsets = np.ascontiguousarray(subsets, np.int32).reshape(-1, 5)
+        n, H = Pw.shape[0], subsets.shape[0]
+        inl = np.zeros(max(n, 1), np.uint8); res = np.zeros(4, np.int32); pose = np.zeros(12, np.float64)
+        hc = np.zeros(max(H, 1), np.int32); hp = np.zeros((max(H, 1), 12), np.float64)
+        ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a.size else None
+        self._check(self.lib.tsorb_match_pnp_ransac(self.ctx, n, ptr(Pw, C.c_float), ptr(uv, C.c_float), ptr(K, C.c_double), H, ptr(subsets, C.c_int32),
+                                                    float(reproj_err), float(confidence), ptr(inl, C.c_uint8), ptr(res, C.c_int32), ptr(pose, C.c_double),
+                                                    ptr(hc, C.c_int32), ptr(hp, C.c_double)), "tsorb_match_pnp_ransac")
+        return dict(ok=bool(res[0]), n_inlier=int(res[1]), sel=int(res[2]), n_run=int(res[3]), inlier=inl[:n].astype(bool), pose=pose.reshape(3, 4),
+                    hyp_count=hc[:H].copy(), hyp_pose=hp[:H].reshape(H, 3, 4).copy())
 
     def debug_fast_shape(self, shape=-1):
         """Diagnostics: the shape of the FAST launches (include/tsorb.h); -1 = chosen by the batch size."""
