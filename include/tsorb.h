@@ -161,6 +161,37 @@ int tsorb_match_pnp_ransac(void *ctx, int n, const float *Pw /*[n][3]*/, const f
                            uint8_t *inlier /*[n]*/, int32_t *result /*[4]: ok, n_inlier, sel, n_run*/, double *pose /*[12] R|t row-major, may be NULL*/,
                            int32_t *hyp_count /*[n_hyp] or NULL*/, double *hyp_pose /*[n_hyp][12] or NULL*/);
 
+/* ---- The two-view initializer's RANSAC: initializer::FindHomography + FindFundamental (src/initializer.cc:185-284, called at :95-96 on every frame until a pair
+ * initialises) with ComputeH21 / ComputeF21 (:287-364) and CheckHomography / CheckFundamental (:366-529), as docs/twoview_recalled.md states them: n_hyp eight-point
+ * homography fits and n_hyp eight-point fundamental-matrix fits on the SAME subsets, each model scored over all n matches, the two keep loops.
+ *   xy1, xy2 [n][2]: the matched keypoints mvKeys1[mvMatches12[i].first].pt and mvKeys2[mvMatches12[i].second].pt.
+ *   norm1, norm2 = meanX, meanY, sX, sY of initializer::Normalize (:819-865) over ALL keypoints of frame 1 / frame 2: an order-dependent float loop that the caller runs
+ *   (adapter/tsorb_two_view.hpp: two_view_normalize).  The library forms the normalised points (x - mean) * s with the reference's two float roundings and
+ *   T = [[sX, 0, -meanX sX], [0, sY, -meanY sY], [0, 0, 1]] in floats as the reference does.
+ *   subset [n_hyp][8]: the hypotheses' matches (mvSets).  The library has no generator: the caller draws them (libc rand() through DUtils::Random in the reference).
+ *   The fit: A from the reference's float products; from A on in fp64 -- the unit right singular vector of A's smallest singular value (one-sided Jacobi), its
+ *   largest-magnitude component positive (the first on ties); F: the 3 x 3's smallest singular value set to 0; H21i = T2^-1 Hn T1, F21i = T2^T Fn T1, each rounded to
+ *   float ONCE; H12i = the fp64 adjugate-over-determinant inverse of the float H21i, rounded to float (zeros when the determinant is 0).
+ *   The scoring is the reference's float arithmetic to the bit: every product and sum rounded to float as written, 1.0/(float expression) a double division rounded to
+ *   float, the score the SEQUENTIAL float sum over the matches in index order (first term then second).
+ *   ALL 2 n_hyp hypotheses are evaluated: hyp_score [2][n_hyp] (H first), hyp_model [2][n_hyp][9] (row-major 3 x 3) when not NULL.  The keep loops start from 0.0 and
+ *   keep on strictly greater (the first of equal scores stays, a NaN is never kept): sel = { kept H hypothesis, kept F hypothesis }, -1 = none; score = { SH, SF };
+ *   H21, F21 the kept models; inlier_h, inlier_f [n] their masks.  sel = -1 leaves that model's mask all 0, its matrix all 0 and its score 0.
+ * A degenerate subset (second smallest eigenvalue of AtA at most 1e-12 times the largest: coincident or collinear points) is a result, not an error: its model is NaN
+ * and its score is what the arithmetic then gives, NaN.  Needs only a context: the resident batch, its pyramid and the match grid are left as they were.
+ * TSORB_ERR_ARG (tsorb_last_error names the function, nothing is launched, no output is touched) for: a NULL context or a NULL required pointer (everything but
+ * hyp_score and hyp_model), n < 8, n > TSORB_TWOVIEW_MAX_POINTS, n_hyp outside [1, TSORB_TWOVIEW_MAX_HYP], a subset index outside [0, n) or twice in a subset, a
+ * coordinate or norm entry that is not finite, norm[2] or norm[3] <= 0, sigma not finite or <= 0. */
+#define TSORB_TWOVIEW_MAX_HYP 256
+#define TSORB_TWOVIEW_MAX_POINTS 65536
+int tsorb_match_two_view_ransac(void *ctx, int n,
+        const float *xy1 /*[n][2] matched keypoints of frame 1*/, const float *xy2 /*[n][2] of frame 2*/,
+        const float norm1[4] /*meanX, meanY, sX, sY of Normalize(mvKeys1)*/, const float norm2[4] /*of Normalize(mvKeys2)*/,
+        int n_hyp, const int32_t *subset /*[n_hyp][8], the caller draws them*/, float sigma,
+        uint8_t *inlier_h /*[n]*/, uint8_t *inlier_f /*[n]*/, float *H21 /*[9]*/, float *F21 /*[9]*/,
+        float *score /*[2]: SH, SF*/, int32_t *sel /*[2]: kept H hypothesis, kept F hypothesis, -1 = none*/,
+        float *hyp_score /*[2][n_hyp] or NULL*/, float *hyp_model /*[2][n_hyp][9] or NULL; H rows first*/);
+
 /* ---- Text features of a frame.
  * frame::FeatExtracText (src/frame.cc:334-355): for each of n_dete detection quads (level-0 pixels, double x, y; truncated like cv::Point)
  * cv::ORB::create()->detect on the frame masked to the quad (tool::GetMask) and ->compute on the frame itself, OpenCV 3.3 defaults;

@@ -1463,6 +1463,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
 #include "tsbrute.h"
 #include "tswindow.h"
 #include "tspnp.h"
+#include "tstwoview.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -2094,6 +2095,52 @@ int tsorb_match_pnp_ransac(void *ctx, int n, const float *Pw, const float *uv, c
     if (hyp_count) memcpy(hyp_count, o + b_res + b_pose, 4*H);
     if (hyp_pose) memcpy(hyp_pose, o + b_res + b_pose + b_cnt, 96*H);
     memcpy(inlier, o + b_res + b_pose + b_cnt + b_hp, N);
+    return TSORB_OK;
+}
+
+// ---- initializer::FindHomography + FindFundamental over caller-drawn subsets (tstwoview.h, docs/twoview_recalled.md).  Needs only a context and shares the blocks of the
+// calls above: one pinned block [xy1 | xy2 | subset | sel, score | H21, F21 | hyp_score | hyp_model | inlier_h | inlier_f], its image on the device, one copy up, three
+// launches, one copy down, one synchronisation.
+int tsorb_match_two_view_ransac(void *ctx, int n, const float *xy1, const float *xy2, const float norm1[4], const float norm2[4], int n_hyp, const int32_t *subset, float sigma,
+                                uint8_t *inlier_h, uint8_t *inlier_f, float *H21, float *F21, float *score, int32_t *sel, float *hyp_score, float *hyp_model) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_match_two_view_ransac: ") + m; return TSORB_ERR_ARG; };
+    if (n < 8) return bad("n < 8");
+    if (n > TSORB_TWOVIEW_MAX_POINTS) return bad("n above TSORB_TWOVIEW_MAX_POINTS");
+    if (n_hyp < 1 || n_hyp > TSORB_TWOVIEW_MAX_HYP) return bad("n_hyp outside [1, TSORB_TWOVIEW_MAX_HYP]");
+    if (!xy1 || !xy2 || !norm1 || !norm2 || !subset || !inlier_h || !inlier_f || !H21 || !F21 || !score || !sel) return bad("NULL pointer");
+    if (!std::isfinite(sigma) || !(sigma > 0.f)) return bad("sigma not finite or <= 0");
+    for (int i = 0; i < 4; i++) if (!std::isfinite(norm1[i]) || !std::isfinite(norm2[i])) return bad("a norm entry is not finite");
+    if (!(norm1[2] > 0.f) || !(norm1[3] > 0.f) || !(norm2[2] > 0.f) || !(norm2[3] > 0.f)) return bad("a norm scale <= 0");
+    const size_t N = (size_t)n, H = (size_t)n_hyp;
+    for (size_t i = 0; i < 2*N; i++) if (!std::isfinite(xy1[i]) || !std::isfinite(xy2[i])) return bad("a coordinate is not finite");
+    for (size_t h = 0; h < H; h++) { const int32_t *s = subset + 8*h;
+        for (int i = 0; i < 8; i++) { if (s[i] < 0 || s[i] >= n) return bad("a subset index outside [0, n)");
+            for (int j = 0; j < i; j++) if (s[j] == s[i]) return bad("an index twice in a subset"); } }
+    hipSetDevice(c->device);
+    const size_t b_xy = br_al(8*N), b_sub = br_al(32*H), in_sz = 2*b_xy + b_sub;
+    const size_t b_res = br_al(16), b_mdl = br_al(72), b_hs = br_al(8*H), b_hm = br_al(72*H), b_inl = br_al(N), out_sz = b_res + b_mdl + b_hs + b_hm + 2*b_inl;
+    if (int rc = br_room(c, in_sz + out_sz, in_sz + out_sz)) return rc;
+    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
+    memcpy(h, xy1, 8*N); memcpy(h + b_xy, xy2, 8*N); memcpy(h + 2*b_xy, subset, 32*H);
+    OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
+    TvDev D; char *o = d + in_sz;
+    D.n = n; D.n_hyp = n_hyp; D.xy1 = (const float *)d; D.xy2 = (const float *)(d + b_xy); D.subset = (const int32_t *)(d + 2*b_xy);
+    for (int i = 0; i < 4; i++) { D.norm1[i] = norm1[i]; D.norm2[i] = norm2[i]; }
+    D.sigma = sigma;
+    D.sel = (int32_t *)o; D.score = (float *)(o + 8); D.model = (float *)(o + b_res); D.hyp_score = (float *)(o + b_res + b_mdl); D.hyp_model = (float *)(o + b_res + b_mdl + b_hs);
+    D.inl_h = (uint8_t *)(o + b_res + b_mdl + b_hs + b_hm); D.inl_f = D.inl_h + b_inl;
+    const unsigned nb = (unsigned)((2*n_hyp + TV_NW - 1)/TV_NW);
+    hipLaunchKernelGGL(k_tv_fit, dim3(2*(unsigned)n_hyp), dim3(64), 0, c->stream, D);
+    hipLaunchKernelGGL(k_tv_score, dim3(nb), dim3(TV_T), 0, c->stream, D);
+    hipLaunchKernelGGL(k_tv_select, dim3(1), dim3(TV_T), 0, c->stream, D);
+    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    const char *r = h + in_sz;
+    memcpy(sel, r, 8); memcpy(score, r + 8, 8); memcpy(H21, r + b_res, 36); memcpy(F21, r + b_res + 36, 36);
+    if (hyp_score) memcpy(hyp_score, r + b_res + b_mdl, 8*H);
+    if (hyp_model) memcpy(hyp_model, r + b_res + b_mdl + b_hs, 72*H);
+    memcpy(inlier_h, r + b_res + b_mdl + b_hs + b_hm, N); memcpy(inlier_f, r + b_res + b_mdl + b_hs + b_hm + b_inl, N);
     return TSORB_OK;
 }
 

@@ -13,11 +13,14 @@ _lib = None
 EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_get_levels", "tsorb_get_scale_factors",
                     "tsorb_get_features_per_level", "tsorb_extract_batch", "tsorb_upload", "tsorb_run", "tsorb_download",
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
-                    "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets", "tsorb_match_pnp_ransac"]
+                    "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets", "tsorb_match_pnp_ransac",
+                    "tsorb_match_two_view_ransac"]
 BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
 SETS_MAX = 1024                                                         # TSORB_SETS_MAX of include/tsorb.h
 PNP_MAX_HYP = 128                                                       # TSORB_PNP_MAX_HYP of include/tsorb.h
 PNP_MAX_POINTS = 65536                                                  # TSORB_PNP_MAX_POINTS of include/tsorb.h
+TWOVIEW_MAX_HYP = 256                                                   # TSORB_TWOVIEW_MAX_HYP of include/tsorb.h
+TWOVIEW_MAX_POINTS = 65536                                              # TSORB_TWOVIEW_MAX_POINTS of include/tsorb.h
 
 
 class TsorbError(RuntimeError):
@@ -59,6 +62,8 @@ def load_library():
         L.tsorb_match_search_sets.restype = C.c_int
         L.tsorb_match_pnp_ransac.argtypes = [vp, C.c_int, fp, fp, dp, C.c_int, ip, C.c_double, C.c_double, up, ip, dp, ip, dp]
         L.tsorb_match_pnp_ransac.restype = C.c_int
+        L.tsorb_match_two_view_ransac.argtypes = [vp, C.c_int, fp, fp, fp, fp, C.c_int, ip, C.c_float, up, up, fp, fp, fp, ip, fp, fp]
+        L.tsorb_match_two_view_ransac.restype = C.c_int
         _lib = L
     return _lib
 
@@ -251,6 +256,26 @@ class ORBextractor:
                                                     ptr(hc, C.c_int32), ptr(hp, C.c_double)), "tsorb_match_pnp_ransac")
         return dict(ok=bool(res[0]), n_inlier=int(res[1]), sel=int(res[2]), n_run=int(res[3]), inlier=inl[:n].astype(bool), pose=pose.reshape(3, 4),
                     hyp_count=hc[:H].copy(), hyp_pose=hp[:H].reshape(H, 3, 4).copy())
+
+    # ---- the two-view initializer's RANSAC (initializer::FindHomography + FindFundamental, docs/twoview_recalled.md)
+    def match_two_view_ransac(self, xy1, xy2, norm1, norm2, subset, sigma=1.0):
+        """xy1, xy2 [n, 2] the matched keypoints of frame 1 / frame 2 (floats), norm1, norm2 = (meanX, meanY, sX, sY) of initializer::Normalize over ALL keypoints of
+        each frame, subset [H, 8]: the hypotheses' matches, drawn by the caller.  Returns a dict: sel [2] int32 (kept H / F hypothesis, -1: none), score [2] float32
+        (SH, SF), H21, F21 [3, 3] float32, inlier_h, inlier_f [n] bool, and of EVERY hypothesis hyp_score [2, H] float32 and hyp_model [2, H, 3, 3] float32 (H first)."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2); xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        norm1 = np.ascontiguousarray(norm1, np.float32).reshape(4); norm2 = np.ascontiguousarray(norm2, np.float32).reshape(4)
+        subset = np.ascontiguousarray(subset, np.int32).reshape(-1, 8)
+        n, H = xy1.shape[0], subset.shape[0]
+        if xy2.shape[0] != n:
+            raise ValueError("xy1 and xy2 have different lengths")
+        ih = np.zeros(max(n, 1), np.uint8); jf = np.zeros(max(n, 1), np.uint8); H21 = np.zeros(9, np.float32); F21 = np.zeros(9, np.float32)
+        score = np.zeros(2, np.float32); sel = np.zeros(2, np.int32); hs = np.zeros((2, max(H, 1)), np.float32); hm = np.zeros((2, max(H, 1), 9), np.float32)
+        ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a.size else None
+        self._check(self.lib.tsorb_match_two_view_ransac(self.ctx, n, ptr(xy1, C.c_float), ptr(xy2, C.c_float), ptr(norm1, C.c_float), ptr(norm2, C.c_float), H,
+                                                         ptr(subset, C.c_int32), float(sigma), ptr(ih, C.c_uint8), ptr(jf, C.c_uint8), ptr(H21, C.c_float), ptr(F21, C.c_float),
+                                                         ptr(score, C.c_float), ptr(sel, C.c_int32), ptr(hs, C.c_float), ptr(hm, C.c_float)), "tsorb_match_two_view_ransac")
+        return dict(sel=sel, score=score, H21=H21.reshape(3, 3), F21=F21.reshape(3, 3), inlier_h=ih[:n].astype(bool), inlier_f=jf[:n].astype(bool),
+                    hyp_score=hs[:, :H].copy(), hyp_model=hm[:, :H].reshape(2, H, 3, 3).copy())
 
     def debug_fast_shape(self, shape=-1):
         """Diagnostics: the shape of the FAST launches (include/tsorb.h); -1 = chosen by the batch size."""
