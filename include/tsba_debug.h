@@ -30,7 +30,9 @@ int  tsba_debug_row_of_kf(void *ctx, int32_t *rowblk);
  * [11..14] this rank's plan of the first pass's level: (target, host) pairs, S blocks, scene candidates, point slots
  * [15] rows of S in reverse Cuthill-McKee order of the keyframes (wide envelopes: loop closures)
  * [16] (n >= 17) ring-shaped map solved with ghost rows for the first separator (one loop closure between the last and the first keyframes)
- * [17] (n >= 19) long-range coupling: band of the preconditioner in pose blocks (0: direct solve)  [18] 6x6 blocks outside the band */
+ * [17] (n >= 19) long-range coupling: band of the preconditioner in pose blocks (0: direct solve)  [18] 6x6 blocks outside the band
+ * [19 + l] (n >= 19 + TSBA_MAX_LEVELS) threads of a k_linearize workgroup at level l under the debug options set now: 128, or 64 where the level's
+ *          largest text group fits one wave (0: the level is not on the device) */
 int  tsba_debug_solver_info(void *ctx, int32_t *out, int n);
 /* Maps with long-range coupling: the conjugate-gradient solves of the last tsba_solve.  out[0] iterations in total, [1] reduced systems
  * solved (LM trials), [2] most iterations of one system, [3] systems that hit the iteration cap. */
@@ -75,7 +77,7 @@ typedef struct tsba_debug_options {
     int32_t sv_per_level;      // bit 0: the separator tree of the single-vector solve phase as one launch per level (k_sv_cre_fwd / _top / _back, production until round 4) instead of one launch for the whole tree (k_sv_cre_tree); bit 1: the back substitution of the factorisation's own solve on maps with long-range blocks as a launch per level (k_cre_back) instead of one launch through the solve phase's products (k_cre_back_tree); bit 2: the update step of a conjugate-gradient iteration (alpha; x, r) as a launch of its own (k_pcg_update) instead of inside the first kernel of the preconditioner application; bit 3: the interiors' back substitution of the solve phase as a launch of its own (k_sv_back_int) instead of in the tree's launch (k_sv_tree_back): A/B runs, bit-identity / parity tests
     int32_t host_pair_lists;   // 0: on the device for problems of at least 4096 scene observations, on the host below; 2: on the device at any size; 1: the slot pairs of the S blocks are built on the host (as every map did until round 4 and every window until round 6) instead of on the device (tsba_devplan.h): A/B runs, list comparison; and single-frame problems (tsba_pose_optim) get their plan from the generic builder on plan threads, the later passes' levels staged during the solve (until round 6), instead of build_plan_single_frame on the calling thread
     int32_t pass_launches;     // 1: a window's pass begins and ends with the launches of rounds 1-4 (k_pass_reset, k_participation, k_gauge_wave, k_musigma | k_outlier, state copy) instead of k_pass_begin | k_pass_end (tsba_kernels_pass.h); PoseOptim: a launch per LM step (k_pose_iter) instead of one per pass (k_pose_pass): A/B runs, agreement tests; 2: PoseOptim (one GPU): the first attempt runs as in production and the host then treats it as abandoned, as if it had reported one give-up (tsba_report.poll_timeouts) -- nothing on the device waits, times out or fails -- so that the retry with a launch per LM step runs under test; every other context: as 1
-    int32_t trial_launches;    // windows: 0 production (k_linearize, k_mid<256> as two launches); 2: the round-5 experiment k_lin_mid -- k_mid inside the speculative linearisation's launch, its last workgroups to finish taking k_mid's blocks of 128 -- measured SLOWER (40.7 against 13.4 + 10.6 us: 736 workgroups signalling completion cost more than the kernel boundary); 1: the two launches with k_mid's blocks of 128 (the experiment's bit-identical comparison partner); 4: production's launches with the text lanes of k_linearize projecting every photometric tap a second time in their evaluation loop (offsets from the constant tables) instead of carrying the fetch loop's projection: the bit-identity partner of that change
+    int32_t trial_launches;    // windows: 0 production (k_linearize, k_mid<256> as two launches); 2: the round-5 experiment k_lin_mid -- k_mid inside the speculative linearisation's launch, its last workgroups to finish taking k_mid's blocks of 128 -- measured SLOWER (40.7 against 13.4 + 10.6 us: 736 workgroups signalling completion cost more than the kernel boundary); 1: the two launches with k_mid's blocks of 128 (the experiment's bit-identical comparison partner); 4: production's launches with the text lanes of k_linearize projecting every photometric tap a second time in their evaluation loop (offsets from the constant tables) instead of carrying the fetch loop's projection: the bit-identity partner of that change; 5: production's launches with every wave of a text workgroup of k_linearize evaluating and transposing in every 64-feature chunk -- a wave that holds no feature of the chunk on the clamped last feature under weight 0 -- instead of going round that work: the partner of the idle-wave skip (equal values; a zero's sign may differ where a group's live features all carry weight 0)
     int32_t assume_cus;        // > 0: the residency test of the kernels whose workgroups poll each other (k_solve_back, k_sv_cre_tree, k_sv_tree_back, k_cre_back_tree) assumes a device of this many compute units (tests: a device too small for the grid takes the launch-per-step path)
     int32_t lds_poison;        // 1 / 2 / 3: before every launch of tsba_solve the LDS of every compute unit is filled with NaNs / 1e300 / 0x5a bytes (what another context's kernels may leave there): results must not change
 } tsba_debug_options;

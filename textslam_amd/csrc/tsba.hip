@@ -771,6 +771,7 @@ static int stage_level(Ctx *c, const tsba_problem *p, int l, double *t_plan, dou
     UV(tg_rec); UV(tg_ppos); UV(pt_pose6); UV(pt_pair4); UV(tx_pair8); UV(pair_i); UV(pair_h); UV(pair_hpos); UV(pair_sc_off); UV(pair_tg_off); UV(pair_tg);
     UV(tg_tobs); UV(tg_kf); UV(tg_text); UV(tg_pair); UV(tg_slot);
     UV(pf_g); UV(pf_f); D.n_pf = (int)H.pf_g.size();
+    for (int g = 0; g < D.n_tg; g++) D.tg_fmax = std::max(D.tg_fmax, (int)(H.tg_rec[8*(size_t)g + 6] - H.tg_rec[8*(size_t)g + 5]));
     if (!H.kf_order.empty()) UV(kf_order); else D.kf_order = nullptr;
     D.far_B = H.far_B; D.n_far = H.n_far();
     D.sb_far = nullptr;
@@ -936,11 +937,28 @@ static int pose_parts(const Ctx *c) { return c->n_kf > 126 ? (c->n_kf + 20)/21 :
 // pairs with a dozen scene blocks (large maps): four pairs per wave
 static bool lin_small_pairs(const Ctx *c, const LevelDev &D) { return !c->dbg.no_small_pairs && D.n_pair > 0 && (long long)D.n_sc <= 24LL*D.n_pair; }
 static bool fused_decisions(const Ctx *c, const LevelDev &D);
-// tsba_debug_options.trial_launches = 4: production's launches with the text lanes of k_linearize projecting every tap twice (lin_body<.., REDO>: the carried projection's partner)
-static bool lin_redo(const Ctx *c) { return c->dbg.trial_launches == 4; }
+// tsba_debug_options.trial_launches = 4 / 5: production's launches with a comparison partner of k_linearize's text lanes (lin_body<.., VAR>) -- 4: every tap projected
+// twice (LIN_REDO: the carried projection's partner); 5: a wave without a feature evaluates the clamped last feature under weight 0 (LIN_ALLW: the idle-wave skip's partner)
+static int lin_variant(const Ctx *c) { return c->dbg.trial_launches == 4 ? LIN_REDO : c->dbg.trial_launches == 5 ? LIN_ALLW : LIN_PROD; }
+// production's launch sequence (148 launches per C4 solve, the decision block in k_mid's launch): production itself and the partners that differ inside k_linearize only
+static bool production_launches(const Ctx *c) { return c->dbg.trial_launches == 0 || lin_variant(c) != LIN_PROD; }
 // windows on one GPU with one-wave k_mid blocks: a speculative k_mid launch carries the decision block (decision_block, tsba_kernels_lin.h) and the k_schur_t<4>
 // behind it reads the record it leaves (SchurDec.on = 3).  tsba_debug_options.trial_launches = 1 / 2 (128-thread blocks, k_lin_mid) keep the decision inside k_schur_t (on = 1)
 static bool decision_in_mid(const Ctx *c, const LevelDev &D) { return fused_decisions(c, D) && mid_threads(c) == 64; }
+// one-wave workgroups (LIN_T1) where a wave takes a whole pair and the level's largest text group fits one wave's feature places (production only: the partners keep both waves)
+static bool lin_one_wave(const Ctx *c, const LevelDev &D) { return !lin_small_pairs(c, D) && lin_variant(c) == LIN_PROD && D.n_tg > 0 && D.tg_fmax <= LIN_T1/(8/LIN_TPL); }
+// k_linearize of a level: the instantiation and the grid by the level's shape (pairs with a dozen scene blocks: four per wave -- without text groups the scene path's
+// registers only; small text groups: one-wave workgroups) and by lin_variant
+static void launch_k_linearize(Ctx *c, const LevelDev &D, int spec) {
+    const int ppw = lin_small_pairs(c, D) ? 4 : 1, var = lin_variant(c), nt = lin_one_wave(c, D) ? LIN_T1 : LIN_T, nwv = nt/64;
+    const dim3 g((((D.n_pair + ppw*nwv - 1)/(ppw*nwv) + D.n_tg + 7)/8)*8);
+#define LIN_LAUNCH(PPW, ...) LAUNCHK((k_linearize<MODE_FULL, PPW, __VA_ARGS__>), g, dim3(nt), 0, c->stream, c->W, D, spec)
+    if (nt == LIN_T1) LIN_LAUNCH(1, true, LIN_PROD, LIN_T1);
+    else if (ppw == 4 && D.n_tg == 0) LIN_LAUNCH(4, false);
+    else if (ppw == 4) { if (var == LIN_REDO) LIN_LAUNCH(4, true, LIN_REDO); else if (var == LIN_ALLW) LIN_LAUNCH(4, true, LIN_ALLW); else LIN_LAUNCH(4, true, LIN_PROD); }
+    else { if (var == LIN_REDO) LIN_LAUNCH(1, true, LIN_REDO); else if (var == LIN_ALLW) LIN_LAUNCH(1, true, LIN_ALLW); else LIN_LAUNCH(1, true, LIN_PROD); }
+#undef LIN_LAUNCH
+}
 static void launch_linearize(Ctx *c, const LevelDev &D, int spec, bool skip_postlin = false) {      // skip_postlin: windows -- the first k_schur_t of the pass does k_postlin's work (SchurDec.on = 2)
     struct XL { Ctx *c; size_t x0; ~XL() { c->x_lin = c->x_acc - x0; } } xl{c, c->x_acc};
     Work &W = c->W;
@@ -956,15 +974,7 @@ static void launch_linearize(Ctx *c, const LevelDev &D, int spec, bool skip_post
         c->lin_base += grid;
         return;
     }
-    if (D.n_pair + D.n_tg > 0) {
-        if (lin_small_pairs(c, D) && D.n_tg == 0) LAUNCHK((k_linearize<MODE_FULL, 4, false>), dim3((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + 7)/8)*8), dim3(LIN_T), 0, c->stream, W, D, spec);
-        else if (lin_small_pairs(c, D)) { const dim3 g((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + D.n_tg + 7)/8)*8);
-            if (lin_redo(c)) LAUNCHK((k_linearize<MODE_FULL, 4, true, true>), g, dim3(LIN_T), 0, c->stream, W, D, spec);
-            else LAUNCHK((k_linearize<MODE_FULL, 4>), g, dim3(LIN_T), 0, c->stream, W, D, spec); }
-        else { const dim3 g((((D.n_pair + LIN_NWV - 1)/LIN_NWV + D.n_tg + 7)/8)*8);
-            if (lin_redo(c)) LAUNCHK((k_linearize<MODE_FULL, 1, true, true>), g, dim3(LIN_T), 0, c->stream, W, D, spec);
-            else LAUNCHK((k_linearize<MODE_FULL, 1>), g, dim3(LIN_T), 0, c->stream, W, D, spec); }
-    }
+    if (D.n_pair + D.n_tg > 0) launch_k_linearize(c, D, spec);
     const MidDec md0{0, 0, 0, tsba_options{}};
     if (mid_threads(c) == MID_TW) LAUNCHK((k_mid<MID_TW, 6, MID_PR_MIN>), dim3(nb_pt + nb_tx + nb_pr), dim3(MID_TW), 0, c->stream, W, D, nb_pt, nb_tx, spec, md0);
     else if (mid_threads(c) == 64) {                  // (a speculative launch: + the decision block, which takes the trial's light decision for the next k_schur_t<4>)
@@ -1169,7 +1179,7 @@ static int lm_trials(Ctx *c, const LevelDev &D, int ps, bool fuse_first, bool *e
         if (it >= 1) { const int rc = stage_ahead(c, ps); if (rc) return rc; }      // (with two iterations queued the device does not run dry while the host stages)
     }
     if (n_trials > 0 && fused_decisions(c, D)) {
-        if (end_decides && decision_in_mid(c, D) && (c->dbg.trial_launches == 0 || lin_redo(c))) *end_decides = true;
+        if (end_decides && decision_in_mid(c, D) && production_launches(c)) *end_decides = true;
         else launch_decide(c, D);
     }
     return TSBA_OK;

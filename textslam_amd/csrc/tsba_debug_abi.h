@@ -161,15 +161,7 @@ int tsba_time_linearize(void *ctx, int level, int n, double *avg_ms, double *alg
     st.need_lin = 1; st.done = 0; st.first = 0;
     CK(hipMemcpy(c->W.st, &st, sizeof(st), hipMemcpyHostToDevice));   // k_linearize never clears need_lin itself
     CK(hipEventRecord(c->ev0, c->stream));
-    for (int k = 0; k < n; k++) {
-        if (lin_small_pairs(c, D) && D.n_tg == 0) hipLaunchKernelGGL((k_linearize<MODE_FULL, 4, false>), dim3((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + 7)/8)*8), dim3(LIN_T), 0, c->stream, c->W, D, 0);
-        else if (lin_small_pairs(c, D)) { const dim3 g((((D.n_pair + 4*LIN_NWV - 1)/(4*LIN_NWV) + D.n_tg + 7)/8)*8);
-            if (lin_redo(c)) hipLaunchKernelGGL((k_linearize<MODE_FULL, 4, true, true>), g, dim3(LIN_T), 0, c->stream, c->W, D, 0);
-            else hipLaunchKernelGGL((k_linearize<MODE_FULL, 4>), g, dim3(LIN_T), 0, c->stream, c->W, D, 0); }
-        else { const dim3 g((((D.n_pair + LIN_NWV - 1)/LIN_NWV + D.n_tg + 7)/8)*8);
-            if (lin_redo(c)) hipLaunchKernelGGL((k_linearize<MODE_FULL, 1, true, true>), g, dim3(LIN_T), 0, c->stream, c->W, D, 0);
-            else hipLaunchKernelGGL((k_linearize<MODE_FULL, 1>), g, dim3(LIN_T), 0, c->stream, c->W, D, 0); }
-    }
+    for (int k = 0; k < n; k++) launch_k_linearize(c, D, 0);
     CK(hipEventRecord(c->ev1, c->stream));
     CK(hipEventSynchronize(c->ev1));
     float ms = 0; CK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
@@ -242,6 +234,8 @@ int tsba_debug_solver_info(void *ctx, int32_t *out, int n) {
     { const LevelDev &D0 = c->lev[c->opt.levels[0]]; out[11] = D0.n_pair; out[12] = D0.n_sb; out[13] = D0.n_sc; out[14] = D0.n_pslot; out[15] = D0.kf_order ? 1 : 0; }
     if (n >= 17) out[16] = c->W.ring;
     if (n >= 19) { out[17] = c->far_B; out[18] = c->n_far; }
+    if (n >= 19 + TSBA_MAX_LEVELS)                       // threads of a k_linearize workgroup by level under the debug options set now (0: level not on the device)
+        for (int l = 0; l < TSBA_MAX_LEVELS; l++) out[19 + l] = l < c->n_levels && c->lev_built[l] ? (lin_one_wave(c, c->lev[l]) ? LIN_T1 : LIN_T) : 0;
     return TSBA_OK;
 }
 // Iterative reduced-system solves of the last tsba_solve on a map with long-range coupling (tsba_pcg.h): out[0] conjugate-gradient iterations in

@@ -407,15 +407,18 @@ __global__ __launch_bounds__(64*LBA_WAVES) void k_label_at(Work W, int n, const 
 // ---- linearisation / cost.  grid = n_pair (scene waves) + n_tg (text waves), 64 threads each.
 #define MODE_FULL 0
 #define MODE_COST 1
-// transpose-sum of N <= 28 per-lane values of ONE wave inside a two-wave workgroup: lane l (< N) returns the total of acc[l].
-// reg: this wave's 28*65 doubles.  Both waves of the workgroup must call it (two workgroup barriers).
+// transpose-sum of N <= 28 per-lane values of ONE wave inside a workgroup of one or two waves: lane l (< N) returns the total of acc[l].
+// reg: this wave's 28*65 doubles.  Every wave of the workgroup must call it (two workgroup barriers).
+// work = false (wave-uniform; a text wave without a feature): the wave meets the two barriers only -- it neither writes nor reads `reg` -- and returns +0.0.
 template <int N>
-__device__ __forceinline__ double wave_sum_to_lane_mw(const double *acc, double *reg, int lane) {
+__device__ __forceinline__ double wave_sum_to_lane_mw(const double *acc, double *reg, int lane, bool work = true) {
+    if (work) {
 #pragma unroll
-    for (int i = 0; i < N; i++) reg[i*65 + lane] = acc[i];
+        for (int i = 0; i < N; i++) reg[i*65 + lane] = acc[i];
+    }
     __syncthreads();
     double s = 0.0;
-    if (lane < N) {
+    if (work && lane < N) {
         const double *row = reg + lane*65;
         double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
 #pragma unroll
@@ -464,15 +467,26 @@ __device__ __forceinline__ void wave_sum_groups16_mw(const double *acc, double *
 #define LIN_NWV (LIN_T/64)
 #define MID_U 4                          // slot records of a point that k_mid keeps in flight per round trip
 // TEXT = false: levels without text planes (the reference's GlobalBA): the scene path alone needs far fewer registers than the text path.
-// REDO (tsba_debug_options.trial_launches = 4: the bit-identity partner of the carried projection): the text lanes' evaluation loop projects every tap again, behind
-// the lane-indexed table loads of its offsets, as it did until the fetch loop started to hand its projection on.
-template <int MODE, int PPW = 1, bool TEXT = true, bool REDO = false>
+// VAR: the text lanes' comparison partners (tsba_debug_options.trial_launches = 4 / 5; LIN_PROD is production).
+// LIN_REDO (4: the partner of the carried projection): the text lanes' evaluation loop projects every tap again, behind the lane-indexed table loads of its
+// offsets, as it did until the fetch loop started to hand its projection on.
+// LIN_ALLW (5: the partner of the idle-wave skip): every wave of a text workgroup evaluates and transposes in every chunk, a wave without a feature on the
+// clamped last feature under weight 0, as all did until a wave without a feature started to go round that work (equal values; a zero's sign may differ).
+#define LIN_PROD 0
+#define LIN_REDO 1
+#define LIN_ALLW 2
+// NT: threads of a workgroup.  LIN_T, or 64 (LIN_T1: one wave -- a scene workgroup takes one pair, a text workgroup's chunk is 64/LPF features) for a level
+// whose largest text group fits one wave (launch_k_linearize): such a level has no second wave to place, no cross-wave sum and half the LDS per workgroup.
+#define LIN_T1 64
+template <int MODE, int PPW = 1, bool TEXT = true, int VAR = LIN_PROD, int NT = LIN_T>
 __device__ __forceinline__ void lin_body(const Work &W, const LevelDev &L, const int spec) {
     // spec = 0: linearise at x (pass start); spec = 1: speculative linearisation at the LM candidate, into the other LinBuf
+    constexpr bool REDO = VAR == LIN_REDO;
     const LmState *st = W.st;
-    constexpr int NWV = LIN_T/64, TPL = LIN_TPL, LPF = 8/LIN_TPL;   // waves per workgroup; taps per lane; lanes per feature
+    constexpr int NWV = NT/64, TPL = LIN_TPL, LPF = 8/LIN_TPL;      // waves per workgroup; taps per lane; lanes per feature
+    constexpr int CHUNK = NT/LPF;                                   // features a text workgroup takes at a time
     __shared__ double lds[NWV*28*65 + NWV*64];
-    __shared__ unsigned s_px[TEXT ? TPL*LIN_T : 1];          // the text path's pixel quads (four bytes): indexed by tap at run time (not registers)
+    __shared__ unsigned s_px[TEXT ? TPL*NT : 1];             // the text path's pixel quads (four bytes): indexed by tap at run time (not registers)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double *reg = lds + wave*28*65, *xw = lds + NWV*28*65;
     // static indices of this workgroup first: in flight together with the LM state
@@ -609,13 +623,18 @@ __device__ __forceinline__ void lin_body(const Work &W, const LevelDev &L, const
         const double inv_sigma = 1.0/sigma;
         const double ifx = 1.0/L.K[0], ify = 1.0/L.K[1];
         double tot = 0.0;                       // lane l < 55 of wave 0: running total of value l
-        // chunks of 64 features (one chunk unless the plane has more).  One accumulator set only: the weighted block of the
+        // chunks of CHUNK (64; one-wave workgroups: 32) features (one chunk unless the plane has more).  One accumulator set only: the weighted block of the
         // thread's half feature is reduced per chunk, so that it stays inside the architectural VGPRs
-        for (int fb = f0; fb == f0 || fb < f1; fb += 64, f += 64) {
+        // A wave whose 64/LPF feature places of a chunk all lie behind the group's last feature (coarse levels: C4's planes have 24 / 12 features at levels
+        // 1 / 2, so wave 1 holds none; a last chunk of at most 32) has nothing to add: it goes round the evaluation and the transposes -- never round a barrier --
+        // and hands +0.0 to the cross-wave sum, where it used to evaluate the clamped last feature under weight 0 beside the waves that are short of fp64 issue.
+        const int wf = __builtin_amdgcn_readfirstlane(wave)*(64/LPF);   // the wave's first feature place of a chunk
+        for (int fb = f0; fb == f0 || fb < f1; fb += CHUNK, f += CHUNK) {
+            const bool work = VAR == LIN_ALLW ? true : (act_g && fb + wf < f1);      // (wave-uniform)
             double blk[55];
 #pragma unroll
             for (int k = 0; k < 55; k++) blk[k] = 0.0;
-            if (act_g) {                                               // (uniform; the shuffle below needs both lanes of a feature)
+            if (act_g && work) {                                       // (uniform; the shuffle below needs both lanes of a feature)
                 const bool in = f < f1;
                 if (fb != f0 && in) {
                     raw = L.tfeat_raw[f]; fu = L.tfeat_uv[2*f]; fv = L.tfeat_uv[2*f+1];
@@ -642,14 +661,14 @@ __device__ __forceinline__ void lin_body(const Work &W, const LevelDev &L, const
                     const double mx = (fu + dx - L.K[2])*ifx, my = (fv + dy - L.K[3])*ify;   // tool.cc:1561
                     double is, iz, u, v;
                     const TapPx q = tap_fetch_keep(T, C.t, th, mx, my, L.K[0], L.K[1], L.K[2], L.K[3], img, L.img_w, L.img_h, is, iz, u, v);
-                    s_px[k*LIN_T + tid] = (unsigned)q.I00 | ((unsigned)q.I01 << 8) | ((unsigned)q.I10 << 16) | ((unsigned)q.I11 << 24);
+                    s_px[k*NT + tid] = (unsigned)q.I00 | ((unsigned)q.I01 << 8) | ((unsigned)q.I10 << 16) | ((unsigned)q.I11 << 24);
                     if constexpr (!REDO) { double *pk = reg + 6*k*65 + lane; pk[0] = mx; pk[65] = my; pk[2*65] = is; pk[3*65] = iz; pk[4*65] = u; pk[5*65] = v; }
                 }
                 LIN_STAMP(1);                                   // (operands there, the taps' pixel quads requested)
                 double s = 0.0;
 #pragma unroll 1
                 for (int k = 0; k < TPL; k++) {
-                    const unsigned q4 = s_px[k*LIN_T + tid];
+                    const unsigned q4 = s_px[k*NT + tid];
                     const TapPx pxk = { (int)(q4 & 0xff), (int)((q4 >> 8) & 0xff), (int)((q4 >> 16) & 0xff), (int)(q4 >> 24) };
                     double rf = refv[0];
 #pragma unroll
@@ -692,9 +711,9 @@ __device__ __forceinline__ void lin_body(const Work &W, const LevelDev &L, const
             }
             LIN_STAMP(2);                                       // (the thread's taps evaluated and weighted)
             // 55 sums over the workgroup's threads: per wave two transposes (28 + 27 values), then the waves (fixed order)
-            const double t0 = wave_sum_to_lane_mw<28>(blk, reg, lane);
-            const double t1 = wave_sum_to_lane_mw<27>(blk + 28, reg, lane);
-            if (lane < 28) xw[wave*64 + lane] = t0;
+            const double t0 = wave_sum_to_lane_mw<28>(blk, reg, lane, work);
+            const double t1 = wave_sum_to_lane_mw<27>(blk + 28, reg, lane, work);
+            if (lane < 28) xw[wave*64 + lane] = t0;                    // (a wave that went round the work: +0.0)
             if (lane < 27) xw[wave*64 + 28 + lane] = t1;
             __syncthreads();
             if (lane < 55) { double part = xw[lane];
@@ -717,8 +736,8 @@ __device__ __forceinline__ void lin_body(const Work &W, const LevelDev &L, const
     }
 }
 
-template <int MODE, int PPW = 1, bool TEXT = true, bool REDO = false>
-__global__ __launch_bounds__(LIN_T, TEXT ? 2 : 3) void k_linearize(Work W, LevelDev L, int spec) { lin_body<MODE, PPW, TEXT, REDO>(W, L, spec); }
+template <int MODE, int PPW = 1, bool TEXT = true, int VAR = LIN_PROD, int NT = LIN_T>
+__global__ __launch_bounds__(NT, TEXT ? 2 : 3) void k_linearize(Work W, LevelDev L, int spec) { lin_body<MODE, PPW, TEXT, VAR, NT>(W, L, spec); }
 
 // ---- per landmark: V, b, host column of W (= -sum Q^T w);  per pair: host-side products.  256-thread blocks.
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }

@@ -24,6 +24,7 @@ struct LmDec { double radius; int done, lcur, fresh, cur; };
 
 struct LevelDev {            // device copies of HostPlan + per-level inputs
     int level, n_sc, n_pair, n_tg, n_pslot, n_tslot, n_sb, n_tfeat, bw_rows;      // bw_rows: rows of S below a pose block that can be non-zero
+    int tg_fmax;             // features of the level's largest text group (0 without groups): which workgroup width k_linearize is launched with
     double K[4];             // K_l
     int img_w, img_h;
     const uint8_t *const *img;      // [n_kf] device pointers

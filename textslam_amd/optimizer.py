@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from .abi import (TsbaProblem, TsbaOptions, TsbaReport, TsbaDebugOptions, BAProblem, options_local, options_pose, options_global,
-                  options_init, options_landmarker, options_theta, STATE_LOCAL, STATE_NOTREACHWIN)
+                  options_init, options_landmarker, options_theta, STATE_LOCAL, STATE_NOTREACHWIN, MAX_LEVELS)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.environ.get("TSBA_LIB", os.path.join(_HERE, "libtsba.so"))     # TSBA_LIB: instrumented build for diagnostics
@@ -264,6 +264,13 @@ class Optimizer:
         keys = ("lds_solver", "band_storage", "band_stream", "interiors", "sep_cr", "band_rows", "small_pairs", "pose_kernel", "large_map", "world", "rank",
                 "n_pair", "n_sblock", "n_scene_candidates", "n_point_slots", "kf_reordered", "ring", "far_band_blocks", "far_blocks")
         return dict(zip(keys, [int(x) for x in v]))
+
+    def linearize_threads(self):
+        """Threads of a k_linearize workgroup per level of the uploaded problem under the debug options set now (tsba_debug_solver_info [19 + l];
+        0: the level is not on the device yet)."""
+        v = (C.c_int32 * (19 + MAX_LEVELS))()
+        self._check(self.lib.tsba_debug_solver_info(self.ctx, v, 19 + MAX_LEVELS), "tsba_debug_solver_info")
+        return [int(x) for x in v[19:19 + self._resident.n_levels]]
 
     def far_blocks(self):
         """The 6x6 blocks outside the band (tsba_debug_far_blocks): keyframes a < b and values [n][6][6] (rows: keyframe a)."""
