@@ -6,7 +6,7 @@
 // NumericDiffCostFunction, and so does this path: 33 residual evaluations per connection, one thread per connection.
 // Normal equations H = sum J^T J are assembled without atomics (a gather per keyframe / per keyframe pair over host-built
 // incidence lists: deterministic), damped in unscaled form H + S^-1 clamp(S^2 diag H) S^-1 / radius, and solved by the BA
-// library's dense solvers, reused as they are (tsba_solve.h: one workgroup in LDS up to 186 unknowns; tsba_chol.h: multi-workgroup
+// library's dense solvers, reused as they are (tsba_solve.h: one workgroup in LDS up to 192 unknowns; tsba_chol.h: multi-workgroup
 // blocked Cholesky on the matrix cores beyond that) on the system padded to a multiple of 6.
 // LM state lives on the device; the host enqueues max_it iterations of a fixed kernel sequence without synchronising.
 #pragma once
