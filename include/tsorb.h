@@ -38,7 +38,13 @@ int tsorb_get_features_per_level(void *ctx, int32_t *n /*[nlevels]*/);
 int tsorb_extract_batch(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride,
                         float *kp, uint8_t *desc, int32_t *count, int cap);
 
-/* Staged form for resident benchmarking: upload once, run the device pipeline any number of times, download. */
+/* Staged form for resident benchmarking: upload once, run the device pipeline any number of times, download.
+ * Geometry: any w, h >= 64 and stride >= w (odd sizes, row-padded images: the pad bytes are never part of any output), with two limits that are the reference's own
+ * divisions by zero, on every level l of the pyramid (w_l = cvRound(w / scale^l), h_l likewise):
+ *   - w_l >= 62 and h_l >= 62: ComputeKeyPointsOctTree's grid has (int)((side - 32) / 30) cells per direction (8 levels at scale 1.2: sides from 221);
+ *   - round((w_l - 32) / (h_l - 32)) >= 1: DistributeOctTree starts from that many nodes, so a search area more than twice as high as wide cannot be distributed.
+ * Outside them, and for n < 1, cap < 1, a NULL pointer or stride < w: TSORB_ERR_ARG, tsorb_last_error names the reason, nothing is launched, no output of
+ * tsorb_extract_batch is touched and the resident batch stays as it was. */
 int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride, int cap);
 int tsorb_run(void *ctx);
 int tsorb_download(void *ctx, float *kp, uint8_t *desc, int32_t *count);

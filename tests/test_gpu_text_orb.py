@@ -181,3 +181,58 @@ def test_adapter_from_cxx(tmp_path, ex320):
         de = np.frombuffer(raw, np.uint8, 32 * n, off).reshape(n, 32); off += 32 * n
         assert n == len(got[d][0]) and np.array_equal(_bits(kp), _bits(got[d][0])) and np.array_equal(de, got[d][1]), d
     assert off == len(raw)
+
+
+# ---- at the cap and off the 32-px tile grid
+def _blocks_image(w, h, seed):
+    """fixture_image's recipe at any size: 8 x 8 blocks of {40, 180} plus uniform noise in [-12, 12]."""
+    rng = np.random.default_rng(seed)
+    blocks = rng.choice(np.array([40.0, 180.0]), size=((h + 7) // 8, (w + 7) // 8))
+    img = np.kron(blocks, np.ones((8, 8)))[:h, :w] + rng.uniform(-12, 12, (h, w))
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def _edge_quads(w, h):
+    """A quad in the middle, one whose corners reach x = w - 1 and y = h - 1, one straddling the 31-px border on the right, the whole frame."""
+    return np.array([
+        [[0.30 * w, 0.28 * h], [0.62 * w + 0.4, 0.33 * h], [0.58 * w, 0.70 * h + 0.7], [0.27 * w, 0.64 * h]],
+        [[0.55 * w, 0.50 * h], [w - 1, 0.45 * h], [w - 1, h - 1], [0.50 * w, h - 1]],
+        [[w - 70.5, 0.20 * h], [w - 12.2, 0.22 * h], [w - 9.0, 0.48 * h], [w - 66.0, 0.50 * h]],
+        [[0, 0], [w - 1, 0], [w - 1, h - 1], [0, h - 1]],
+    ], np.float64)
+
+
+_EDGE_CACHE = {}
+
+
+def _edge_case(w, h):
+    if (w, h) not in _EDGE_CACHE:
+        img = _blocks_image(w, h, 13 + w)
+        _EDGE_CACHE[(w, h)] = (img, R.Frame(img), {})
+    return _EDGE_CACHE[(w, h)]
+
+
+@pytest.mark.parametrize("nfeatures", [500, 60])
+@pytest.mark.parametrize("size", [(640, 480), (637, 479), (323, 243)], ids=lambda s: "%dx%d" % s)
+def test_bit_equal_to_the_restatement_at_the_cap_and_off_the_tile_grid(size, nfeatures):
+    """640 x 480 is tsorb_text_extract's cap: 20 x 15 tiles of 32 px, the tile table (CVO_MAX_T) and the row table (CVO_MAX_H) exactly full; 637 x 479 and 323 x 243
+    have a partial last tile in both directions on every level and odd level sizes.  The frame is resident on a scene extractor with the default pyramid."""
+    from textslam_amd.orbextractor import ORBextractor
+    w, h = size
+    img, frame, refs = _edge_case(w, h)
+    quads = _edge_quads(w, h)
+    if nfeatures not in refs:
+        refs[nfeatures] = frame.extract(quads, nfeatures)
+    ref = refs[nfeatures]
+    levels = np.unique(ref[3][0][:, 5]).size
+    assert levels >= 3 and min(len(r[0]) for r in ref) > 0, (levels, [len(r[0]) for r in ref])       # the whole-frame quad reaches at least three levels; no quad passes empty
+    ex = ORBextractor()
+    try:
+        ex.extract_batch(255 - img); ex.extract_text(0, quads, nfeatures)                # (the scratch planes hold another image's bytes first)
+        ex.extract_batch(img)
+        got = ex.extract_text(0, quads, nfeatures)
+        _same(got, ref, "%d x %d, nfeatures %d," % (w, h, nfeatures))
+        again = ex.extract_text(0, quads[::-1], nfeatures)[::-1]
+        _same(again, ref, "%d x %d reversed, nfeatures %d," % (w, h, nfeatures))
+    finally:
+        ex.close()

@@ -1,8 +1,12 @@
 """CPU tests of the ORB oracle (oracle/tsorb_oracle.c): each OpenCV behaviour it restates is checked against an
 independent formulation (brute-force FAST definition, float bilinear / Gaussian, numpy arctan2) -- the reference ships
 no tests and OpenCV is not installed, so this is what pins the checker."""
+import os
+import sys
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from textslam_amd.orbextractor import synthetic_frame
 
@@ -180,3 +184,30 @@ def test_match_oracle_against_bruteforce(oracle_lib):
             assert out["best_dist2"][q] == (rest.min() if rest.size else 2147483647)
         else:
             assert out["best_idx"][q] == -1 and out["best_dist"][q] == 2147483647
+
+
+def _pyramid_cases():
+    from orb_geometry import GEOMETRIES, OTHER_PYRAMIDS
+    cases = [(name, hw, 1.2, nl) for name, (hw, nl) in GEOMETRIES.items()]
+    cases.append(("e_199x199", (199, 199), 1.2, 8))            # (the pyramid of a size whose last level, 56 px, is too small for a cell: the levels themselves are ordinary)
+    cases += [("%gx%d_%dx%d" % (sc, nl, hw[0], hw[1]), hw, sc, nl) for _, sc, nl, hw in OTHER_PYRAMIDS + [(300, 2.0, 3, (247, 323))]]
+    return cases
+
+
+@pytest.mark.parametrize("name,hw,scale,nlevels", _pyramid_cases(), ids=[c[0] for c in _pyramid_cases()])
+def test_levels_off_the_grid_are_the_chained_resize_in_a_reflected_frame(oracle_lib, name, hw, scale, nlevels):
+    """The shapes tests/test_gpu_orb_geometry.py compares the kernels at: every level of the oracle's pyramid is the numpy restatement of cv::resize
+    (tests/cvorb_ref.py, written independently) of the level before, at the size cvRound(side / scale^l), inside np.pad's 19-px reflection."""
+    import cvorb_ref as R
+    from orb_geometry import level_sizes, noise_frame
+    h, w = hw
+    img = synthetic_frame(7, w, h) if min(h, w) > 131 else noise_frame(7, w, h)
+    sizes = level_sizes(h, w, scale, nlevels)
+    prev = img
+    for l, (lh, lw) in enumerate(sizes):
+        lev = oracle_lib.orb_level(img, l, scale=scale, nlevels=nlevels)
+        assert lev.shape == (lh + 38, lw + 38), (name, l, lev.shape)
+        inner = prev if l == 0 else R.resize_linear(prev, lw, lh)
+        assert np.array_equal(lev[19:-19, 19:-19], inner), (name, l)
+        assert np.array_equal(lev, np.pad(inner, 19, mode="reflect")), (name, l)
+        prev = inner

@@ -1533,14 +1533,27 @@ int tsorb_get_scale_factors(void *ctx, float *sf, float *isf) { OCtx *c = (OCtx 
 int tsorb_get_features_per_level(void *ctx, int32_t *n) { OCtx *c = (OCtx *)ctx; if (!c || !n) return TSORB_ERR_ARG; for (int i = 0; i < c->nlevels; i++) n[i] = c->nfl[i]; return TSORB_OK; }
 
 int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride, int cap) {
-    OCtx *c = (OCtx *)ctx; if (!c || !imgs || n < 1 || w < 64 || h < 64 || stride < w || cap < 1) return TSORB_ERR_ARG;
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_upload: ") + m; return TSORB_ERR_ARG; };
+    if (!imgs) return bad("imgs is NULL");
+    if (n < 1) return bad("n < 1");
+    if (cap < 1) return bad("cap < 1");
+    if (w < 64 || h < 64) return bad("image smaller than 64 x 64");
+    if (stride < w) return bad("stride < w");
+    // every level before anything is freed or launched (a refusal leaves the resident batch as it was): the reference's grid divides by (side - 32)/30 cells and
+    // its quadtree by round(width/height) nodes -- a level under 62 px, or one whose search area is more than twice as high as wide, is a division by zero there
+    for (int l = 0; l < c->nlevels; l++) {
+        const int lw = cv_round_f((float)w*c->isf[l]), lh = cv_round_f((float)h*c->isf[l]);
+        if ((int)((float)(lw - 32)/30.f) < 1 || (int)((float)(lh - 32)/30.f) < 1) return bad("image too small for the requested pyramid (a level under 62 px: no 30-px cell)");
+        if ((int)roundf((float)(lw - 32)/(float)(lh - 32)) < 1) return bad("a level's search area is more than twice as high as wide (the quadtree starts from round(width/height) = 0 nodes)");
+    }
     hipSetDevice(c->device);
     c->out_on_host = false;                                  // (until the next run)
     c->ran = false;
     if (c->uploaded && c->key[0] == n && c->key[1] == w && c->key[2] == h && c->key[3] == stride && c->key[4] == cap) {
         // same geometry as the previous call: only the pixels travel (pinned staging, one asynchronous copy)
-        memcpy(c->h_img, imgs, (size_t)n*h*stride);
-        OCK(hipMemcpyAsync((void *)c->D.img, c->h_img, (size_t)n*h*stride, hipMemcpyHostToDevice, c->stream));
+        memcpy(c->h_img, imgs, c->h_img_sz);
+        OCK(hipMemcpyAsync((void *)c->D.img, c->h_img, c->h_img_sz, hipMemcpyHostToDevice, c->stream));
         return TSORB_OK;
     }
     ofree(c);
@@ -1604,7 +1617,8 @@ int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride
     D.cand_cap = ((D.L[0].maxBX - D.L[0].minB)*(D.L[0].maxBY - D.L[0].minB))/4 + 64; D.node_cap = 64*(c->nfl[0] + 64); D.pool_cap = 16*D.cand_cap;
     int rc;
     uint8_t *img; if ((rc = oalloc(c, &img, (size_t)n*h*stride + 8))) return rc; D.img = img;        // (+ 8: level 1's 8-byte source loads at the end of the last row)
-    c->h_img_sz = (size_t)n*h*stride; OCK(hipHostMalloc((void **)&c->h_img, c->h_img_sz, hipHostMallocDefault));
+    c->h_img_sz = ((size_t)n*h - 1)*stride + w;          // (the last row ends with its pixels: an ROI's stride may run past the caller's buffer there)
+    OCK(hipHostMalloc((void **)&c->h_img, c->h_img_sz, hipHostMallocDefault));
     memcpy(c->h_img, imgs, c->h_img_sz);
     OCK(hipMemcpyAsync(img, c->h_img, c->h_img_sz, hipMemcpyHostToDevice, c->stream));
     if ((rc = oalloc(c, &D.pyr, (size_t)n*po)) || (rc = oalloc(c, &D.blur, (size_t)n*bo))) return rc;

@@ -108,12 +108,19 @@ class ORBextractor:
         self._check(self.lib.tsorb_get_features_per_level(self.ctx, n.ctypes.data_as(C.POINTER(C.c_int32))), "tsorb_get_features_per_level")
         return n
 
-    def upload(self, imgs):
-        imgs = np.ascontiguousarray(imgs, np.uint8)
+    def upload(self, imgs, stride=None):
+        """imgs [n, h, w] uint8.  stride (default w): the images are the first w columns of an [n, h, stride] buffer -- a row-padded cv::Mat -- handed in as
+        the view buf[:, :, :w]; the buffer goes to the library as it lies in memory, pad bytes included (no copy)."""
+        if stride is None:
+            imgs = np.ascontiguousarray(imgs, np.uint8)
         if imgs.ndim == 2:
             imgs = imgs[None]
         n, h, w = imgs.shape
-        self._check(self.lib.tsorb_upload(self.ctx, imgs.ctypes.data_as(C.POINTER(C.c_uint8)), n, w, h, w, self.cap), "tsorb_upload")
+        if stride is None:
+            stride = w
+        elif imgs.dtype != np.uint8 or imgs.strides[1:] != (stride, 1) or (n > 1 and imgs.strides[0] != h * stride):
+            raise ValueError(f"imgs is not the first {w} columns of a uint8 [n, h, {stride}] buffer: strides {imgs.strides}")
+        self._check(self.lib.tsorb_upload(self.ctx, C.cast(imgs.ctypes.data, C.POINTER(C.c_uint8)), n, w, h, int(stride), self.cap), "tsorb_upload")
         self._shape = (n, h, w)
 
     def run(self):
@@ -128,9 +135,9 @@ class ORBextractor:
                                             cnt.ctypes.data_as(C.POINTER(C.c_int32))), "tsorb_download")
         return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy()) for i in range(n)]
 
-    def extract_batch(self, imgs):
-        """imgs [n, h, w] uint8 -> list of (keypoints [k, 6] = x, y, size, angle, response, octave ; descriptors [k, 32])."""
-        self.upload(imgs)
+    def extract_batch(self, imgs, stride=None):
+        """imgs [n, h, w] uint8 (stride: see upload) -> list of (keypoints [k, 6] = x, y, size, angle, response, octave ; descriptors [k, 32])."""
+        self.upload(imgs, stride)
         self.run()
         return self.download()
 
