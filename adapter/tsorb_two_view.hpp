@@ -88,5 +88,65 @@ inline bool find_h_and_f(void *orbCtx, const Keys &vKeys1, const Keys &vKeys2, c
     return two_view_fill<Tr>(c, vbMatchesInliersH, SH, H, vbMatchesInliersF, SF, F);
 }
 
+// ---- ReconstructH / ReconstructF (src/initializer.cc:98-105, :531-802, CheckRT :868-977) over tsorb_match_two_view_reconstruct; docs/twoview_reconstruct_recalled.md
+// states the arithmetic.  On top of the members above, Tr gives
+//   static float at33(const Mat33f &M, int r, int c);           // M.at<float>(r, c)
+//   typedef ... Mat31f;                                         // cv::Mat in the reference
+//   static void assign31(Mat31f &t, const float v[3]);          // t = the 3 x 1, CV_32F
+// and vP3D's elements have the members x, y, z (cv::Point3f).
+
+// What one reconstruction sends and receives
+struct ReconstructCall {
+    std::vector<float> xy1, xy2, p3d; std::vector<uint8_t> inlier, triangulated;
+    float M21[9], K[4], R21[9], t21[3]; int32_t result[6];
+    int n() const { return (int)(xy1.size()/2); }
+};
+
+// the matched pixels as above, vbMatchesInliers as bytes, and the floats of the model and of mK (fx, fy, cx, cy)
+template <class Tr, class Keys, class Matches>
+inline void reconstruct_gather(const Keys &vKeys1, const Keys &vKeys2, const Matches &vMatches12, const std::vector<bool> &vbMatchesInliers,
+                               const typename Tr::Mat33f &M21, const typename Tr::Mat33f &K, ReconstructCall &c) {
+    c.xy1.clear(); c.xy2.clear(); c.inlier.clear();
+    for (size_t i = 0; i < vMatches12.size(); i++) {
+        const size_t i1 = (size_t)vMatches12[i].first, i2 = (size_t)vMatches12[i].second;
+        c.xy1.push_back(vKeys1[i1].pt.x); c.xy1.push_back(vKeys1[i1].pt.y);
+        c.xy2.push_back(vKeys2[i2].pt.x); c.xy2.push_back(vKeys2[i2].pt.y);
+        c.inlier.push_back(i < vbMatchesInliers.size() && vbMatchesInliers[i] ? 1 : 0);
+    }
+    for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) c.M21[3*r + k] = Tr::at33(M21, r, k);
+    c.K[0] = Tr::at33(K, 0, 0); c.K[1] = Tr::at33(K, 1, 1); c.K[2] = Tr::at33(K, 0, 2); c.K[3] = Tr::at33(K, 1, 2);
+}
+
+// the reference's outputs from the call's: on success R21, t21, and vP3D / vbTriangulated sized like mvKeys1 and indexed through mvMatches12[i].first (a keypoint of
+// frame 1 is in at most one match, :45-54); on failure everything is left as it was
+template <class Tr, class Matches, class Points>
+inline bool reconstruct_fill(const ReconstructCall &c, const Matches &vMatches12, size_t nKeys1, typename Tr::Mat33f &R21, typename Tr::Mat31f &t21,
+                             Points &vP3D, std::vector<bool> &vbTriangulated) {
+    if (!c.result[0]) return false;
+    Tr::assign33(R21, c.R21); Tr::assign31(t21, c.t21);
+    vP3D.assign(nKeys1, typename Points::value_type()); vbTriangulated.assign(nKeys1, false);
+    for (size_t i = 0; i < vMatches12.size(); i++) { const size_t k = (size_t)vMatches12[i].first;
+        vP3D[k].x = c.p3d[3*i]; vP3D[k].y = c.p3d[3*i + 1]; vP3D[k].z = c.p3d[3*i + 2];
+        vbTriangulated[k] = c.triangulated[i] != 0; }
+    return true;
+}
+
+// ReconstructH(vbMatchesInliersH, H, mK, R21, t21, vP3D, vbTriangulated, 1.0, 50) (model 0) or ReconstructF(vbMatchesInliersF, F, ...) (model 1) in ONE call.
+// Returns what the reference returns; false also on a device or argument error (tsorb_last_error(orbCtx) says what; keep->result[5] is -1 then).
+template <class Tr, class Keys, class Matches, class Points>
+inline bool reconstruct(void *orbCtx, const Keys &vKeys1, const Keys &vKeys2, const Matches &vMatches12, const std::vector<bool> &vbMatchesInliers, int model,
+                        const typename Tr::Mat33f &M21, const typename Tr::Mat33f &K, float sigma, typename Tr::Mat33f &R21, typename Tr::Mat31f &t21,
+                        Points &vP3D, std::vector<bool> &vbTriangulated, float minParallax = 1.0f, int minTriangulated = 50, ReconstructCall *keep = 0) {
+    ReconstructCall local, &c = keep ? *keep : local;
+    reconstruct_gather<Tr>(vKeys1, vKeys2, vMatches12, vbMatchesInliers, M21, K, c);
+    const size_t n = (size_t)c.n();
+    c.p3d.assign(3*(n ? n : 1), 0.f); c.triangulated.assign(n ? n : 1, 0);
+    for (int i = 0; i < 6; i++) c.result[i] = 0;
+    const int rc = tsorb_match_two_view_reconstruct(orbCtx, (int)n, c.xy1.data(), c.xy2.data(), c.inlier.data(), model, c.M21, c.K, sigma, minParallax, minTriangulated,
+                                                    c.result, c.R21, c.t21, c.p3d.data(), c.triangulated.data(), 0, 0, 0, 0, 0, 0);
+    if (rc != TSORB_OK) { c.result[0] = 0; c.result[5] = -1; return false; }
+    return reconstruct_fill<Tr>(c, vMatches12, vKeys1.size(), R21, t21, vP3D, vbTriangulated);
+}
+
 }  // namespace tsorb_adapter
 #endif

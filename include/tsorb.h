@@ -198,6 +198,38 @@ int tsorb_match_two_view_ransac(void *ctx, int n,
         float *score /*[2]: SH, SF*/, int32_t *sel /*[2]: kept H hypothesis, kept F hypothesis, -1 = none*/,
         float *hyp_score /*[2][n_hyp] or NULL*/, float *hyp_model /*[2][n_hyp][9] or NULL; H rows first*/);
 
+/* ---- The two-view initializer's reconstruction: initializer::ReconstructH (src/initializer.cc:636-802) or ReconstructF (:531-634, DecomposeE :979-999) with CheckRT
+ * (:868-977) and Triangulate (:804-817), as docs/twoview_reconstruct_recalled.md states them: the model's 8 (H, Faugeras) or 4 (F) motion hypotheses, every inlier
+ * match triangulated and checked under every hypothesis, the keep logic.  The RH decision between the two models (:99-102) is the caller's.
+ *   xy1, xy2 [n][2] as above; inlier [n]: vbMatchesInliers of the chosen model (non-zero = inlier); model 0: M21 is H21 (ReconstructH), 1: M21 is F21 (ReconstructF);
+ *   K = fx, fy, cx, cy, the floats of mK; min_parallax and min_triangulated are 1.0 and 50 at the reference's call site.
+ *   The hypotheses: fp64 from the float M21 and K (A = K^-1 H K or E = K^T F K, the 3 x 3 SVD by a one-sided Jacobi iteration, the Faugeras / DecomposeE formulas),
+ *   each R and t rounded to float ONCE.  Their order is fixed by a sign rule, not by an SVD routine's signs (docs): H: v1 and v3 with their largest-magnitude component
+ *   positive; F: t likewise, R1 the rotation with the larger trace, (R1, t), (R2, t), (R1, -t), (R2, -t).
+ *   CheckRT, given the float R, t, K: P2, O2 and R p + t with double accumulation and one float rounding per entry; Triangulate's 4 x 4 from the reference's float
+ *   products, its null vector in fp64, the point rounded to float ONCE; everything after the float point is the reference's arithmetic to the bit.
+ *   result [6] = ok, sel (the kept hypothesis; -1 unless ok), N (inlier count), best nGood, second best nGood (H) or nsimilar (F), exit bits: 1 = H only, d1/d2 or
+ *   d2/d3 below 1.00001 (nothing is evaluated, every hyp_* output is zero), 2 = not enough good points, 4 = no clear winner, 8 = parallax.
+ *   R21 [9], t21 [3], p3d [n][3], triangulated [n]: the kept hypothesis' pose, the points of its counted matches (vP3D; zeros elsewhere) and vbTriangulated, per MATCH
+ *   (the reference indexes them by mvMatches12[i].first: the adapter scatters).  ok = 0 leaves all four zero.
+ *   Of every hypothesis, when not NULL: hyp_good [8] = nGood, hyp_cos [8] = the cosine CheckRT picks (sorted[min(50, nGood - 1)]; 0 when nGood = 0), hyp_parallax [8]
+ *   in degrees, hyp_pose [8][12] = R | t row-major 3 x 4, hyp_p3d [8][n][3] = every evaluated match's float point, hyp_state [8][n] = the exit the match took:
+ *   0 not an inlier, 1 non-finite point (or a NaN cosine: the point is exactly zero), 2 depth in camera 1, 3 depth in camera 2, 4 error in image 1, 5 error in image 2,
+ *   6 good (counted) but low parallax, 7 good and triangulated.  F fills hypotheses 0 .. 3 and zeroes 4 .. 7.
+ * Needs only a context: the resident batch, its pyramid and the match grid are left as they were.
+ * TSORB_ERR_ARG (tsorb_last_error names the function, nothing is launched, no output is touched) for: a NULL context or a NULL required pointer (everything but the
+ * hyp_* outputs), n < 1, n > TSORB_TWOVIEW_MAX_POINTS, model outside {0, 1}, a coordinate, M21 entry or K entry that is not finite, fx or fy <= 0, sigma or
+ * min_parallax not finite or negative, min_triangulated negative. */
+#define TSORB_TWOVIEW_REC_HYP 8        /* 8 hypotheses from H, 4 from F; the arrays below are sized for 8 */
+int tsorb_match_two_view_reconstruct(void *ctx, int n,
+        const float *xy1 /*[n][2]*/, const float *xy2 /*[n][2]*/, const uint8_t *inlier /*[n]: vbMatchesInliers of the chosen model, non-zero = inlier*/,
+        int model /*0: ReconstructH from a homography, 1: ReconstructF from a fundamental matrix*/, const float *M21 /*[9] row-major*/,
+        const float K[4] /*fx fy cx cy: mK's floats*/, float sigma, float min_parallax /*1.0*/, int min_triangulated /*50*/,
+        int32_t *result /*[6]: ok, sel (-1 = none), N = inlier count, best nGood, second best nGood (H) / nsimilar (F), exit bits*/,
+        float *R21 /*[9]*/, float *t21 /*[3]*/, float *p3d /*[n][3]*/, uint8_t *triangulated /*[n]*/,
+        int32_t *hyp_good /*[8] or NULL*/, float *hyp_cos /*[8] or NULL: the cosine CheckRT picks*/, float *hyp_parallax /*[8] or NULL, degrees*/,
+        float *hyp_pose /*[8][12] R|t row-major or NULL*/, uint8_t *hyp_state /*[8][n] or NULL*/, float *hyp_p3d /*[8][n][3] or NULL*/);
+
 /* ---- Text features of a frame.
  * frame::FeatExtracText (src/frame.cc:334-355): for each of n_dete detection quads (level-0 pixels, double x, y; truncated like cv::Point)
  * cv::ORB::create()->detect on the frame masked to the quad (tool::GetMask) and ->compute on the frame itself, OpenCV 3.3 defaults;

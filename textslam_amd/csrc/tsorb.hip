@@ -1464,6 +1464,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
 #include "tswindow.h"
 #include "tspnp.h"
 #include "tstwoview.h"
+#include "tstwoview_rec.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -2155,6 +2156,62 @@ int tsorb_match_two_view_ransac(void *ctx, int n, const float *xy1, const float 
     if (hyp_score) memcpy(hyp_score, r + b_res + b_mdl, 8*H);
     if (hyp_model) memcpy(hyp_model, r + b_res + b_mdl + b_hs, 72*H);
     memcpy(inlier_h, r + b_res + b_mdl + b_hs + b_hm, N); memcpy(inlier_f, r + b_res + b_mdl + b_hs + b_hm + b_inl, N);
+    return TSORB_OK;
+}
+
+// ---- initializer::ReconstructH / ReconstructF with CheckRT and Triangulate (tstwoview_rec.h, docs/twoview_reconstruct_recalled.md).  Needs only a context and shares the
+// blocks of the calls above: one pinned block [xy1 | xy2 | inlier | result | R21, t21 | hyp_good, hyp_cos, hyp_parallax, hyp_pose | p3d | triangulated | hyp_state | hyp_p3d],
+// its image on the device (and behind it every pair's cosine), one copy up, three launches, one copy down (as far as the caller asked for), one synchronisation.
+int tsorb_match_two_view_reconstruct(void *ctx, int n, const float *xy1, const float *xy2, const uint8_t *inlier, int model, const float *M21, const float K[4], float sigma,
+                                     float min_parallax, int min_triangulated, int32_t *result, float *R21, float *t21, float *p3d, uint8_t *triangulated,
+                                     int32_t *hyp_good, float *hyp_cos, float *hyp_parallax, float *hyp_pose, uint8_t *hyp_state, float *hyp_p3d) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_match_two_view_reconstruct: ") + m; return TSORB_ERR_ARG; };
+    if (n < 1) return bad("n < 1");
+    if (n > TSORB_TWOVIEW_MAX_POINTS) return bad("n above TSORB_TWOVIEW_MAX_POINTS");
+    if (model != 0 && model != 1) return bad("model outside {0, 1}");
+    if (!xy1 || !xy2 || !inlier || !M21 || !K || !result || !R21 || !t21 || !p3d || !triangulated) return bad("NULL pointer");
+    if (!std::isfinite(sigma) || sigma < 0.f) return bad("sigma not finite or negative");
+    if (!std::isfinite(min_parallax) || min_parallax < 0.f) return bad("min_parallax not finite or negative");
+    if (min_triangulated < 0) return bad("min_triangulated negative");
+    for (int i = 0; i < 9; i++) if (!std::isfinite(M21[i])) return bad("an M21 entry is not finite");
+    for (int i = 0; i < 4; i++) if (!std::isfinite(K[i])) return bad("a K entry is not finite");
+    if (!(K[0] > 0.f) || !(K[1] > 0.f)) return bad("fx or fy not positive");
+    const size_t N = (size_t)n;
+    for (size_t i = 0; i < 2*N; i++) if (!std::isfinite(xy1[i]) || !std::isfinite(xy2[i])) return bad("a coordinate is not finite");
+    hipSetDevice(c->device);
+    const size_t b_xy = br_al(8*N), b_n = br_al(N), in_sz = 2*b_xy + b_n;
+    const size_t b_res = br_al(24), b_rt = br_al(48), b_h8 = br_al(32), b_pose = br_al(4*12*TSORB_TWOVIEW_REC_HYP), b_p3d = br_al(12*N);
+    const size_t o_rt = b_res, o_good = o_rt + b_rt, o_cos = o_good + b_h8, o_par = o_cos + b_h8, o_pose = o_par + b_h8, o_p3d = o_pose + b_pose, o_tri = o_p3d + b_p3d;
+    const size_t o_state = o_tri + b_n, o_hp = o_state + br_al(8*N), out_sz = o_hp + br_al(96*N), o_cosall = out_sz, dev_sz = in_sz + o_cosall + br_al(32*N) + 16;
+    const size_t down = hyp_p3d ? out_sz : hyp_state ? o_hp : o_state;        // what the caller did not ask for stays on the device
+    if (int rc = br_room(c, dev_sz, in_sz + out_sz)) return rc;
+    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
+    memcpy(h, xy1, 8*N); memcpy(h + b_xy, xy2, 8*N); memcpy(h + 2*b_xy, inlier, N);
+    int n_inl = 0; for (size_t i = 0; i < N; i++) n_inl += inlier[i] != 0;
+    OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
+    RecDev D; char *o = d + in_sz;
+    D.n = n; D.model = model; D.n_inl = n_inl; D.min_tri = min_triangulated; D.xy1 = (const float *)d; D.xy2 = (const float *)(d + b_xy); D.inl = (const uint8_t *)(d + 2*b_xy);
+    for (int i = 0; i < 9; i++) D.M[i] = M21[i];
+    for (int i = 0; i < 4; i++) D.K[i] = K[i];
+    D.sigma = sigma; D.min_par = min_parallax;
+    D.result = (int32_t *)o; D.R21 = (float *)(o + o_rt); D.t21 = D.R21 + 9; D.hyp_good = (int32_t *)(o + o_good); D.hyp_cos = (float *)(o + o_cos); D.hyp_par = (float *)(o + o_par);
+    D.hyp_pose = (float *)(o + o_pose); D.p3d = (float *)(o + o_p3d); D.tri = (uint8_t *)(o + o_tri); D.hyp_state = (uint8_t *)(o + o_state); D.hyp_p3d = (float *)(o + o_hp);
+    D.cosall = (float *)(o + o_cosall); D.sv_exit = (int32_t *)(o + o_cosall + br_al(32*N));
+    const unsigned nb = (unsigned)((n + REC_T - 1)/REC_T);
+    hipLaunchKernelGGL(k_rec_pairs, dim3(nb, model == 0 ? 8 : 4), dim3(REC_T), 0, c->stream, D);
+    hipLaunchKernelGGL(k_rec_stat, dim3(TSORB_TWOVIEW_REC_HYP), dim3(REC_T), 0, c->stream, D);
+    hipLaunchKernelGGL(k_rec_keep, dim3(nb), dim3(REC_T), 0, c->stream, D);
+    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, down, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    const char *r = h + in_sz;
+    memcpy(result, r, 24); memcpy(R21, r + o_rt, 36); memcpy(t21, r + o_rt + 36, 12); memcpy(p3d, r + o_p3d, 12*N); memcpy(triangulated, r + o_tri, N);
+    if (hyp_good) memcpy(hyp_good, r + o_good, 32);
+    if (hyp_cos) memcpy(hyp_cos, r + o_cos, 32);
+    if (hyp_parallax) memcpy(hyp_parallax, r + o_par, 32);
+    if (hyp_pose) memcpy(hyp_pose, r + o_pose, 4*12*TSORB_TWOVIEW_REC_HYP);
+    if (hyp_state) memcpy(hyp_state, r + o_state, 8*N);
+    if (hyp_p3d) memcpy(hyp_p3d, r + o_hp, 96*N);
     return TSORB_OK;
 }
 

@@ -14,13 +14,14 @@ EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_
                     "tsorb_get_features_per_level", "tsorb_extract_batch", "tsorb_upload", "tsorb_run", "tsorb_download",
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
                     "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets", "tsorb_match_pnp_ransac",
-                    "tsorb_match_two_view_ransac"]
+                    "tsorb_match_two_view_ransac", "tsorb_match_two_view_reconstruct"]
 BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
 SETS_MAX = 1024                                                         # TSORB_SETS_MAX of include/tsorb.h
 PNP_MAX_HYP = 128                                                       # TSORB_PNP_MAX_HYP of include/tsorb.h
 PNP_MAX_POINTS = 65536                                                  # TSORB_PNP_MAX_POINTS of include/tsorb.h
 TWOVIEW_MAX_HYP = 256                                                   # TSORB_TWOVIEW_MAX_HYP of include/tsorb.h
 TWOVIEW_MAX_POINTS = 65536                                              # TSORB_TWOVIEW_MAX_POINTS of include/tsorb.h
+TWOVIEW_REC_HYP = 8                                                     # TSORB_TWOVIEW_REC_HYP of include/tsorb.h
 
 
 class TsorbError(RuntimeError):
@@ -64,6 +65,8 @@ def load_library():
         L.tsorb_match_pnp_ransac.restype = C.c_int
         L.tsorb_match_two_view_ransac.argtypes = [vp, C.c_int, fp, fp, fp, fp, C.c_int, ip, C.c_float, up, up, fp, fp, fp, ip, fp, fp]
         L.tsorb_match_two_view_ransac.restype = C.c_int
+        L.tsorb_match_two_view_reconstruct.argtypes = [vp, C.c_int, fp, fp, up, C.c_int, fp, fp, C.c_float, C.c_float, C.c_int, ip, fp, fp, fp, up, ip, fp, fp, fp, up, fp]
+        L.tsorb_match_two_view_reconstruct.restype = C.c_int
         _lib = L
     return _lib
 
@@ -283,6 +286,31 @@ class ORBextractor:
                                                          ptr(score, C.c_float), ptr(sel, C.c_int32), ptr(hs, C.c_float), ptr(hm, C.c_float)), "tsorb_match_two_view_ransac")
         return dict(sel=sel, score=score, H21=H21.reshape(3, 3), F21=F21.reshape(3, 3), inlier_h=ih[:n].astype(bool), inlier_f=jf[:n].astype(bool),
                     hyp_score=hs[:, :H].copy(), hyp_model=hm[:, :H].reshape(2, H, 3, 3).copy())
+
+    # ---- the two-view initializer's reconstruction (initializer::ReconstructH / ReconstructF with CheckRT, docs/twoview_reconstruct_recalled.md)
+    def match_two_view_reconstruct(self, xy1, xy2, inlier, model, M21, K, sigma=1.0, min_parallax=1.0, min_triangulated=50):
+        """xy1, xy2 [n, 2] the matched keypoints (floats), inlier [n] the chosen model's vbMatchesInliers, model 0: M21 is H21, 1: M21 is F21 ([3, 3] floats),
+        K = (fx, fy, cx, cy).  Returns a dict: ok, sel (-1: none), result [6] int32 (ok, sel, N, best nGood, second best nGood / nsimilar, exit bits), R21 [3, 3], t21 [3],
+        p3d [n, 3] float32 and triangulated [n] bool of the kept hypothesis (per match; zeros when nothing is kept), and of EVERY hypothesis hyp_good [8] int32, hyp_cos [8],
+        hyp_parallax [8] float32, hyp_pose [8, 3, 4] = R | t, hyp_state [8, n] uint8 (the exit each match took) and hyp_p3d [8, n, 3] float32."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2); xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        inlier = np.ascontiguousarray(np.asarray(inlier).reshape(-1) != 0, np.uint8)
+        M21 = np.ascontiguousarray(M21, np.float32).reshape(9); K = np.ascontiguousarray(K, np.float32).reshape(4)
+        n, H = xy1.shape[0], TWOVIEW_REC_HYP
+        if xy2.shape[0] != n or inlier.shape[0] != n:
+            raise ValueError("xy1, xy2 and inlier have different lengths")
+        m = max(n, 1)
+        res = np.zeros(6, np.int32); R21 = np.zeros(9, np.float32); t21 = np.zeros(3, np.float32); p3d = np.zeros((m, 3), np.float32); tri = np.zeros(m, np.uint8)
+        hg = np.zeros(H, np.int32); hc = np.zeros(H, np.float32); hp = np.zeros(H, np.float32); pose = np.zeros((H, 12), np.float32)
+        hs = np.zeros((H, m), np.uint8); hx = np.zeros((H, m, 3), np.float32)
+        ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a.size else None
+        self._check(self.lib.tsorb_match_two_view_reconstruct(self.ctx, n, ptr(xy1, C.c_float), ptr(xy2, C.c_float), ptr(inlier, C.c_uint8), int(model), ptr(M21, C.c_float),
+                                                              ptr(K, C.c_float), float(sigma), float(min_parallax), int(min_triangulated), ptr(res, C.c_int32),
+                                                              ptr(R21, C.c_float), ptr(t21, C.c_float), ptr(p3d, C.c_float), ptr(tri, C.c_uint8), ptr(hg, C.c_int32),
+                                                              ptr(hc, C.c_float), ptr(hp, C.c_float), ptr(pose, C.c_float), ptr(hs, C.c_uint8), ptr(hx, C.c_float)),
+                    "tsorb_match_two_view_reconstruct")
+        return dict(ok=bool(res[0]), sel=int(res[1]), result=res, R21=R21.reshape(3, 3), t21=t21, p3d=p3d[:n], triangulated=tri[:n].astype(bool), hyp_good=hg, hyp_cos=hc,
+                    hyp_parallax=hp, hyp_pose=pose.reshape(H, 3, 4), hyp_state=hs[:, :n].copy(), hyp_p3d=hx[:, :n].copy())
 
     def debug_fast_shape(self, shape=-1):
         """Diagnostics: the shape of the FAST launches (include/tsorb.h); -1 = chosen by the batch size."""
