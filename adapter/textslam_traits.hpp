@@ -80,6 +80,13 @@ struct TextSlamTraits {
     }
     // Sim3Solver's index draws (adapter/tsloop_sim3_ransac.hpp): the reference's own generator, Sim3Solver.cc:81
     static int random_int(int lo, int hi) { return DUtils::Random::RandomInt(lo, hi); }
+    // the planes of new text detections (adapter/tsorb_text_theta.hpp): tool.cc:1375 / initializer.cc:130; tracking.cc:1667 / initializer.cc:1013, the reference's own expression
+    static void seed_rand_once() { DUtils::Random::SeedRandOnce(0); }
+    static void tcr_of(const TextSLAM::Mat44 &Tcw, const TextSLAM::Mat44 &Trw, double out[12]) {
+        const TextSLAM::Mat44 Tcr = Tcw * Trw.inverse();
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) out[4*r + c] = Tcr(r, c);
+    }
+    static TextSLAM::Mat31 vec3(double a, double b, double c) { return TextSLAM::Mat31(a, b, c); }
     // nume_BAText.h:25: the cost functors index cv::Mat::data directly, i.e. continuous CV_8UC1 with step == cols
     static const uint8_t *img(const cv::Mat &im) { CV_Assert(im.type() == CV_8UC1 && im.isContinuous()); return im.data; }
     static int img_w(const cv::Mat &im) { return im.cols; }

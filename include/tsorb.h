@@ -230,6 +230,40 @@ int tsorb_match_two_view_reconstruct(void *ctx, int n,
         int32_t *hyp_good /*[8] or NULL*/, float *hyp_cos /*[8] or NULL: the cosine CheckRT picks*/, float *hyp_parallax /*[8] or NULL, degrees*/,
         float *hyp_pose /*[8][12] R|t row-major or NULL*/, uint8_t *hyp_state /*[8][n] or NULL*/, float *hyp_p3d /*[8][n][3] or NULL*/);
 
+/* ---- The planes of new text detections: tracking::InitialTextObjs -> GetTextTheta -> SolveTheta (src/tracking.cc:1631-1734, 1870-1917) and the two-view
+ * initializer's InitialTextObjs -> CalculateTextTheta (src/initializer.cc:111-183, 1004-1061), as docs/texttheta_recalled.md states them: for every plane (a text
+ * detection's features) the triangulation of every feature, then every caller-drawn index triple's closed-form theta and its score over all the plane's features,
+ * and the reference's keep loop.  All planes of a keyframe in ONE call.
+ *   off [n_plane+1]: plane p owns features off[p] .. off[p+1]-1 (off[0] = 0, not decreasing); N = off[n_plane].
+ *   host_xy, targ_xy [N][2]: the feature in the host keyframe (level-0 pixels) and in the target frame, the floats of the cv::Point2f.
+ *   rho [N] or NULL.  NULL (tracking): every feature is triangulated between [I | 0] and Tcr as cv::triangulatePoints does on PixToCam's float points -- the 4 x 4 in
+ *   double, its null vector in fp64 rounded to float as a 4-vector, divided by its last entry in float -- and rho = 1.0/(double)z.  Given (the initializer, rho from
+ *   IniP3D): used as it is, p3d is zero.
+ *   Tcr [12]: rows of [R | t], host -> target (Tcw * Trw.inverse()); K = fx, fy, cx, cy, the doubles of mK.
+ *   hyp_off [n_plane+1]: plane p owns hypotheses hyp_off[p] .. hyp_off[p+1]-1; H = hyp_off[n_plane].  triple [H][3]: feature indices WITHIN the plane, in the order
+ *   drawn (tool::GetRANSACIdx; adapter/tsorb_text_theta.hpp draws them).  Indices may repeat: such a triple gives a NaN theta and is never kept.
+ *   sel [n_plane]: the kept hypothesis within the plane (`BestScore < score` from -1.0 in hypothesis order: the first of the largest scores, a NaN score never), -1:
+ *   none -- also for a plane of fewer than 3 features or without hypotheses; theta [n_plane][3], score [n_plane]: the kept hypothesis' NEGATED theta (what SolveTheta
+ *   returns) and its score, zeros with sel = -1.
+ *   When not NULL: p3d [N][3] the triangulated float points, rho_out [N] the rho that was used, hyp_score [H] and hyp_theta [H][3] of every hypothesis (zeros for a
+ *   plane of fewer than 3 features).
+ * Needs only a context: the resident batch, its pyramid and the match grid are left as they were.  One copy each way, at most three launches; n_plane = 0 launches
+ * nothing.  TSORB_ERR_ARG (tsorb_last_error names the function and the plane, nothing is launched, no output is touched) for: a NULL context, n_plane < 0, a NULL
+ * required pointer (off, hyp_off, Tcr, K, sel, theta, score; host_xy and targ_xy when N > 0; triple when H > 0), off or hyp_off not starting at 0 or decreasing, a
+ * plane of more than TSORB_THETA_MAX_FEAT features, more than TSORB_THETA_MAX_HYP hypotheses in a plane, a triple index outside [0, the plane's feature count). */
+#define TSORB_THETA_MAX_FEAT 1024      /* features per plane (cv::ORB::create() keeps 500 per detection) */
+#define TSORB_THETA_MAX_HYP 65536      /* hypotheses per plane (the reference draws 200) */
+int tsorb_match_text_theta_ransac(void *ctx, int n_plane,
+        const int32_t *off /*[n_plane+1] feature ranges*/,
+        const float *host_xy /*[N][2] level-0 pixels in the host keyframe (Hostfeat / F1->vKeys[].pt)*/,
+        const float *targ_xy /*[N][2] pixels in the target frame (Targfeat / F2->vKeys[].pt)*/,
+        const double *rho /*[N] inverse depths, or NULL: triangulate on the device (tracking's path)*/,
+        const double *Tcr /*[12] rows of [R | t], host -> target*/, const double *K /*fx fy cx cy*/,
+        const int32_t *hyp_off /*[n_plane+1]*/, const int32_t *triple /*[hyp_off[n_plane]][3] indices within the plane, in the order drawn*/,
+        int32_t *sel /*[n_plane] kept hypothesis within the plane, -1: none*/, double *theta /*[n_plane][3]*/, double *score /*[n_plane]*/,
+        float *p3d /*[N][3] or NULL: the triangulated points (rho == NULL)*/, double *rho_out /*[N] or NULL: the rho that was used*/,
+        double *hyp_score /*[H] or NULL*/, double *hyp_theta /*[H][3] or NULL*/);
+
 /* ---- Text features of a frame.
  * frame::FeatExtracText (src/frame.cc:334-355): for each of n_dete detection quads (level-0 pixels, double x, y; truncated like cv::Point)
  * cv::ORB::create()->detect on the frame masked to the quad (tool::GetMask) and ->compute on the frame itself, OpenCV 3.3 defaults;

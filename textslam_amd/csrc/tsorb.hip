@@ -1465,6 +1465,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
 #include "tspnp.h"
 #include "tstwoview.h"
 #include "tstwoview_rec.h"
+#include "tstexttheta.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -2212,6 +2213,63 @@ int tsorb_match_two_view_reconstruct(void *ctx, int n, const float *xy1, const f
     if (hyp_pose) memcpy(hyp_pose, r + o_pose, 4*12*TSORB_TWOVIEW_REC_HYP);
     if (hyp_state) memcpy(hyp_state, r + o_state, 8*N);
     if (hyp_p3d) memcpy(hyp_p3d, r + o_hp, 96*N);
+    return TSORB_OK;
+}
+
+// ---- tracking::GetTextTheta / initializer::CalculateTextTheta for every new text plane (tstexttheta.h, docs/texttheta_recalled.md).  Needs only a context and shares the
+// blocks of the calls above: one pinned block [off | hyp_off | host_xy | targ_xy | rho | triple | sel | theta | score | hyp_score | hyp_theta | rho_out | p3d], its image on
+// the device, one copy up, at most three launches, one copy down (as far as the caller asked for), one synchronisation.
+int tsorb_match_text_theta_ransac(void *ctx, int n_plane, const int32_t *off, const float *host_xy, const float *targ_xy, const double *rho, const double *Tcr, const double *K,
+                                  const int32_t *hyp_off, const int32_t *triple, int32_t *sel, double *theta, double *score, float *p3d, double *rho_out,
+                                  double *hyp_score, double *hyp_theta) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const std::string &m) { c->err = "tsorb_match_text_theta_ransac: " + m; return TSORB_ERR_ARG; };
+    if (n_plane < 0) return bad("n_plane < 0");
+    if (!off || !hyp_off || !Tcr || !K || !sel || !theta || !score) return bad("NULL pointer");
+    if (off[0] != 0 || hyp_off[0] != 0) return bad("off or hyp_off does not start at 0");
+    int max_hyp = 0;
+    for (int p = 0; p < n_plane; p++) { const int64_t n = (int64_t)off[p + 1] - off[p], nh = (int64_t)hyp_off[p + 1] - hyp_off[p];
+        if (n < 0 || nh < 0) return bad("off or hyp_off decreases at plane " + std::to_string(p));
+        if (n > TSORB_THETA_MAX_FEAT) return bad("plane " + std::to_string(p) + " has more than TSORB_THETA_MAX_FEAT features");
+        if (nh > TSORB_THETA_MAX_HYP) return bad("plane " + std::to_string(p) + " has more than TSORB_THETA_MAX_HYP hypotheses");
+        max_hyp = std::max(max_hyp, (int)nh); }
+    const size_t P = (size_t)n_plane, N = (size_t)off[n_plane], H = (size_t)hyp_off[n_plane];
+    if (N && (!host_xy || !targ_xy)) return bad("NULL pointer");
+    if (H && !triple) return bad("NULL pointer");
+    for (int p = 0; p < n_plane; p++) { const int32_t n = off[p + 1] - off[p];
+        for (size_t e = 3*(size_t)hyp_off[p]; e < 3*(size_t)hyp_off[p + 1]; e++)
+            if (triple[e] < 0 || triple[e] >= n) return bad("a triple index of plane " + std::to_string(p) + " is outside the plane"); }
+    if (n_plane == 0) return TSORB_OK;
+    hipSetDevice(c->device);
+    const size_t b_off = br_al(4*(P + 1)), b_xy = br_al(8*N), b_rho = rho ? br_al(8*N) : 0, b_tri = br_al(12*H), in_sz = 2*b_off + 2*b_xy + b_rho + b_tri;
+    const size_t o_theta = br_al(4*P), o_score = o_theta + br_al(24*P), o_hs = o_score + br_al(8*P), o_ht = o_hs + br_al(8*H), o_rho = o_ht + br_al(24*H), o_p3d = o_rho + br_al(8*N),
+                 out_sz = o_p3d + br_al(12*N);
+    const size_t down = p3d ? out_sz : rho_out ? o_p3d : hyp_theta ? o_rho : hyp_score ? o_ht : o_hs;       // what the caller did not ask for stays on the device
+    if (int rc = br_room(c, in_sz + out_sz, in_sz + out_sz)) return rc;
+    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
+    const size_t i_xy1 = 2*b_off, i_xy2 = i_xy1 + b_xy, i_rho = i_xy2 + b_xy, i_tri = i_rho + b_rho;
+    memcpy(h, off, 4*(P + 1)); memcpy(h + b_off, hyp_off, 4*(P + 1));
+    if (N) { memcpy(h + i_xy1, host_xy, 8*N); memcpy(h + i_xy2, targ_xy, 8*N); if (rho) memcpy(h + i_rho, rho, 8*N); }
+    if (H) memcpy(h + i_tri, triple, 12*H);
+    OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
+    TtDev D; char *o = d + in_sz;
+    D.n_plane = n_plane; D.off = (const int32_t *)d; D.hyp_off = (const int32_t *)(d + b_off); D.host_xy = (const float *)(d + i_xy1); D.targ_xy = (const float *)(d + i_xy2);
+    D.rho_in = rho ? (const double *)(d + i_rho) : nullptr; D.triple = (const int32_t *)(d + i_tri);
+    for (int i = 0; i < 12; i++) D.T[i] = Tcr[i];
+    for (int i = 0; i < 4; i++) D.K[i] = K[i];
+    D.sel = (int32_t *)o; D.theta = (double *)(o + o_theta); D.score = (double *)(o + o_score); D.hyp_score = (double *)(o + o_hs); D.hyp_theta = (double *)(o + o_ht);
+    D.rho = (double *)(o + o_rho); D.p3d = (float *)(o + o_p3d);
+    if (N) hipLaunchKernelGGL(k_tt_rho, dim3((unsigned)((N + TT_T - 1)/TT_T)), dim3(TT_T), 0, c->stream, D, (int)N);
+    if (H) hipLaunchKernelGGL(k_tt_score, dim3((unsigned)n_plane, (unsigned)((max_hyp + TT_T - 1)/TT_T)), dim3(TT_T), 0, c->stream, D);
+    hipLaunchKernelGGL(k_tt_select, dim3((unsigned)n_plane), dim3(64), 0, c->stream, D);
+    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, down, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    const char *r = h + in_sz;
+    memcpy(sel, r, 4*P); memcpy(theta, r + o_theta, 24*P); memcpy(score, r + o_score, 8*P);
+    if (hyp_score && H) memcpy(hyp_score, r + o_hs, 8*H);
+    if (hyp_theta && H) memcpy(hyp_theta, r + o_ht, 24*H);
+    if (rho_out && N) memcpy(rho_out, r + o_rho, 8*N);
+    if (p3d && N) memcpy(p3d, r + o_p3d, 12*N);
     return TSORB_OK;
 }
 

@@ -14,7 +14,7 @@ EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_
                     "tsorb_get_features_per_level", "tsorb_extract_batch", "tsorb_upload", "tsorb_run", "tsorb_download",
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
                     "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets", "tsorb_match_pnp_ransac",
-                    "tsorb_match_two_view_ransac", "tsorb_match_two_view_reconstruct"]
+                    "tsorb_match_two_view_ransac", "tsorb_match_two_view_reconstruct", "tsorb_match_text_theta_ransac"]
 BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
 SETS_MAX = 1024                                                         # TSORB_SETS_MAX of include/tsorb.h
 PNP_MAX_HYP = 128                                                       # TSORB_PNP_MAX_HYP of include/tsorb.h
@@ -22,6 +22,8 @@ PNP_MAX_POINTS = 65536                                                  # TSORB_
 TWOVIEW_MAX_HYP = 256                                                   # TSORB_TWOVIEW_MAX_HYP of include/tsorb.h
 TWOVIEW_MAX_POINTS = 65536                                              # TSORB_TWOVIEW_MAX_POINTS of include/tsorb.h
 TWOVIEW_REC_HYP = 8                                                     # TSORB_TWOVIEW_REC_HYP of include/tsorb.h
+TEXT_THETA_MAX_FEAT = 1024                                              # TSORB_THETA_MAX_FEAT of include/tsorb.h
+TEXT_THETA_MAX_HYP = 65536                                              # TSORB_THETA_MAX_HYP of include/tsorb.h
 
 
 class TsorbError(RuntimeError):
@@ -67,6 +69,8 @@ def load_library():
         L.tsorb_match_two_view_ransac.restype = C.c_int
         L.tsorb_match_two_view_reconstruct.argtypes = [vp, C.c_int, fp, fp, up, C.c_int, fp, fp, C.c_float, C.c_float, C.c_int, ip, fp, fp, fp, up, ip, fp, fp, fp, up, fp]
         L.tsorb_match_two_view_reconstruct.restype = C.c_int
+        L.tsorb_match_text_theta_ransac.argtypes = [vp, C.c_int, ip, fp, fp, dp, dp, dp, ip, ip, ip, dp, dp, fp, dp, dp, dp]
+        L.tsorb_match_text_theta_ransac.restype = C.c_int
         _lib = L
     return _lib
 
@@ -311,6 +315,35 @@ class ORBextractor:
                     "tsorb_match_two_view_reconstruct")
         return dict(ok=bool(res[0]), sel=int(res[1]), result=res, R21=R21.reshape(3, 3), t21=t21, p3d=p3d[:n], triangulated=tri[:n].astype(bool), hyp_good=hg, hyp_cos=hc,
                     hyp_parallax=hp, hyp_pose=pose.reshape(H, 3, 4), hyp_state=hs[:, :n].copy(), hyp_p3d=hx[:, :n].copy())
+
+    # ---- the planes of new text detections (tracking::GetTextTheta / initializer::CalculateTextTheta, docs/texttheta_recalled.md)
+    def match_text_theta_ransac(self, off, host_xy, targ_xy, Tcr, K, hyp_off, triple, rho=None):
+        """off [P+1] the planes' feature ranges, host_xy / targ_xy [N, 2] the features in the host keyframe and the target frame (floats), Tcr [3, 4] (or [4, 4]) = R | t host ->
+        target and K = (fx, fy, cx, cy) in double, hyp_off [P+1] the planes' hypothesis ranges, triple [H, 3] feature indices within the plane in the order drawn;
+        rho [N] the inverse depths, or None: triangulated on the device.  Returns a dict: sel [P] int32 (-1: none), theta [P, 3] and score [P] of the kept hypothesis,
+        p3d [N, 3] float32 (zeros when rho is given), rho [N] the rho that was used, and of EVERY hypothesis hyp_score [H] and hyp_theta [H, 3]."""
+        off = np.ascontiguousarray(off, np.int32).reshape(-1); hyp_off = np.ascontiguousarray(hyp_off, np.int32).reshape(-1)
+        host_xy = np.ascontiguousarray(host_xy, np.float32).reshape(-1, 2); targ_xy = np.ascontiguousarray(targ_xy, np.float32).reshape(-1, 2)
+        triple = np.ascontiguousarray(triple, np.int32).reshape(-1, 3)
+        Tcr = np.ascontiguousarray(np.asarray(Tcr, np.float64).reshape(-1, 4)[:3]).reshape(12); K = np.ascontiguousarray(K, np.float64).reshape(4)
+        P = off.shape[0] - 1
+        if P < 0 or hyp_off.shape[0] != P + 1:
+            raise ValueError("off and hyp_off have different lengths")
+        N, H = host_xy.shape[0], triple.shape[0]
+        if targ_xy.shape[0] != N or (P > 0 and (int(off[-1]) != N or int(hyp_off[-1]) != H)):
+            raise ValueError("host_xy, targ_xy or triple does not have the length off / hyp_off give")
+        if rho is not None:
+            rho = np.ascontiguousarray(rho, np.float64).reshape(-1)
+            if rho.shape[0] != N:
+                raise ValueError("rho and host_xy have different lengths")
+        sel = np.full(max(P, 1), -1, np.int32); theta = np.zeros((max(P, 1), 3)); score = np.zeros(max(P, 1))
+        p3d = np.zeros((max(N, 1), 3), np.float32); rho_out = np.zeros(max(N, 1)); hs = np.zeros(max(H, 1)); ht = np.zeros((max(H, 1), 3))
+        ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a is not None and a.size else None
+        self._check(self.lib.tsorb_match_text_theta_ransac(self.ctx, P, ptr(off, C.c_int32), ptr(host_xy, C.c_float), ptr(targ_xy, C.c_float), ptr(rho, C.c_double),
+                                                           ptr(Tcr, C.c_double), ptr(K, C.c_double), ptr(hyp_off, C.c_int32), ptr(triple, C.c_int32), ptr(sel, C.c_int32),
+                                                           ptr(theta, C.c_double), ptr(score, C.c_double), ptr(p3d, C.c_float), ptr(rho_out, C.c_double),
+                                                           ptr(hs, C.c_double), ptr(ht, C.c_double)), "tsorb_match_text_theta_ransac")
+        return dict(sel=sel[:P], theta=theta[:P], score=score[:P], p3d=p3d[:N], rho=rho_out[:N], hyp_score=hs[:H], hyp_theta=ht[:H])
 
     def debug_fast_shape(self, shape=-1):
         """Diagnostics: the shape of the FAST launches (include/tsorb.h); -1 = chosen by the batch size."""
