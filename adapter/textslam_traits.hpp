@@ -87,6 +87,7 @@ struct TextSlamTraits {
         for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) out[4*r + c] = Tcr(r, c);
     }
     static TextSLAM::Mat31 vec3(double a, double b, double c) { return TextSLAM::Mat31(a, b, c); }
+    // a new keyframe's scene points and the initializer's search (adapter/tsorb_new_points.hpp) use row() and vec3() above: nothing else is needed
     // nume_BAText.h:25: the cost functors index cv::Mat::data directly, i.e. continuous CV_8UC1 with step == cols
     static const uint8_t *img(const cv::Mat &im) { CV_Assert(im.type() == CV_8UC1 && im.isContinuous()); return im.data; }
     static int img_w(const cv::Mat &im) { return im.cols; }

@@ -80,7 +80,8 @@ int tsorb_debug_fallbacks(void *ctx);
  *   cand_idx / cand_dist [nq][max_cand]: the candidates in the reference's order with their Hamming distances (cand_cnt = how many
  *   there were, possibly > max_cand), best_idx / best_dist: the first minimum (strict <, as the reference's loop; -1 / INT_MAX if
  *   none), best_dist2: the runner-up distance.  Stateful variants (SearchForInitializ's running vMatchDist filter, the
- *   first-come claim of a feature) stay in the caller, on the candidate lists.  Output pointers may be NULL. */
+ *   first-come claim of a feature) can stay in the caller, on the candidate lists; tsorb_match_search_claim and
+ *   tsorb_match_new_points below run them on the device.  Output pointers may be NULL. */
 int tsorb_match_set_frame(void *ctx, int frame, double min_x, double max_x, double min_y, double max_y);
 int tsorb_match_set_features(void *ctx, const float *kp6, const uint8_t *desc, int n, double min_x, double max_x, double min_y, double max_y);
 int tsorb_match_search(void *ctx, int nq, const float *qxy, const float *qr, const int32_t *qlev, const uint8_t *qdesc, int max_cand,
@@ -263,6 +264,37 @@ int tsorb_match_text_theta_ransac(void *ctx, int n_plane,
         int32_t *sel /*[n_plane] kept hypothesis within the plane, -1: none*/, double *theta /*[n_plane][3]*/, double *score /*[n_plane]*/,
         float *p3d /*[N][3] or NULL: the triangulated points (rho == NULL)*/, double *rho_out /*[N] or NULL: the rho that was used*/,
         double *hyp_score /*[H] or NULL*/, double *hyp_theta /*[H][3] or NULL*/);
+
+/* ---- The stateful window searches: tracking::SearchForTriangular (src/tracking.cc:1347-1411, the first thing TrackNewKeyframe does) and tracking::SearchForInitializ
+ * (:1045-1109, every frame until the map initialises), and behind the first GetForTriangular + CheckTriangular (:1413-1497), as docs/newpoints_recalled.md states them.
+ * Both calls search the context's current grid (tsorb_match_set_frame / tsorb_match_set_features) and leave it, the resident batch and its pyramid as they were.
+ *
+ *   tsorb_match_search_claim: the reference's loop over the queries IN QUERY ORDER.  A query's candidates are tsorb_match_search's (GetFeaturesInArea's order: window
+ *     cells column by column, index order inside a cell; the qlev filter as there).  A candidate i2 is skipped when elig2[i2] == 0 (elig2 [n2] or NULL = all eligible: the
+ *     reference's `F2.vMatches2D3D[i2] < 0`) and when vMatchDist[i2] <= dist (vMatchDist starts at INT_MAX).  Over the rest: the first minimum under strict < in
+ *     CANDIDATE order and the runner-up distance (INT_MAX when there is none).  Accepted when best <= th_low and, with use_ratio, (double)best < (double)second*ratio.
+ *     On acceptance the previous owner of that i2 loses it (match12 = -1), then match12[q] = i2, vMatchIdx21[i2] = q, vMatchDist[i2] = best.
+ *     match12 [nq] = vMatchIdx12 at the end, match_dist [nq] (or NULL) = the accepted distance or -1, n_match = the entries >= 0.
+ *     The caller keeps the reference's per-feature conditions (Fea.octave > 0, vMatches2D3D[i1] >= 0, vTextObjInfo[i1] >= 0) by leaving those features out of the
+ *     queries and maps query numbers back itself.  SearchForTriangular: use_ratio 0, th_low 50, qr = 80*1.2f, qlev = { octave, octave }; SearchForInitializ: use_ratio 1,
+ *     ratio 0.9, qr = Win.  However many candidates a query has, it gets the reference's answer (no list is cut).
+ *   tsorb_match_new_points: the same search, then for every query with match12 >= 0 GetForTriangular's point and CheckTriangular's verdict; the match never visits the
+ *     host.  q_px [nq][2] = F1->vKeys[i1].pt (equal to qxy in the reference; kept separate), the other pixel is the matched feature's of the grid; Trw, Tcw [12] = the
+ *     top three rows of F1->mTcw and F2.mTcw, K = fx, fy, cx, cy of F2.mK, th_reproj 9.  PixToCam in double rounded to float per coordinate; cv::triangulatePoints' 4 x 4
+ *     in double, its null vector in fp64 rounded to float as a 4-vector, divided by its last entry as a float reciprocal and a float product per entry; CheckTriangular
+ *     as written: the finiteness tests, R p + t left to right, (fx X)/Z + cx, u1 < 0 || v1 < 0, the squared error formed in double, rounded to float and compared with
+ *     (float)th_reproj.  There is no depth test and a NaN error passes both comparisons, as in the reference.
+ *     p3d [nq][3], good [nq]: per query (zeros where match12 < 0); n_good = the good ones.  The reference's vNewpts / vMatchNewpts are the good rows in query order.
+ * nq == 0: TSORB_OK, n_match = 0 (n_good = 0), nothing is launched.  TSORB_ERR_ARG (tsorb_last_error names the function, nothing is launched, no output is touched) for:
+ * a NULL context, no grid set, a NULL required pointer (everything but qlev, elig2 and match_dist), nq < 0, a coordinate or radius that is not finite, a negative radius,
+ * th_low outside [0, 256], with use_ratio a ratio that is not finite or negative, a searched set above TSORB_BRUTE_MAX_FEAT features. */
+int tsorb_match_search_claim(void *ctx, int nq, const float *qxy /*[nq][2]*/, const float *qr /*[nq]*/, const int32_t *qlev /*[nq][2] or NULL*/,
+                             const uint8_t *qdesc /*[nq][32]*/, const uint8_t *elig2 /*[n2] or NULL = all*/, int th_low, int use_ratio, double ratio,
+                             int32_t *match12 /*[nq]*/, int32_t *match_dist /*[nq] or NULL*/, int32_t *n_match);
+int tsorb_match_new_points(void *ctx, int nq, const float *qxy /*[nq][2]*/, const float *qr /*[nq]*/, const int32_t *qlev /*[nq][2] or NULL*/,
+                           const uint8_t *qdesc /*[nq][32]*/, const uint8_t *elig2 /*[n2] or NULL = all*/, int th_low, int use_ratio, double ratio,
+                           const float *q_px /*[nq][2]*/, const double *Trw /*[12]*/, const double *Tcw /*[12]*/, const double *K /*fx fy cx cy*/, int th_reproj /*9*/,
+                           int32_t *match12 /*[nq]*/, int32_t *n_match, float *p3d /*[nq][3]*/, uint8_t *good /*[nq]*/, int32_t *n_good);
 
 /* ---- Text features of a frame.
  * frame::FeatExtracText (src/frame.cc:334-355): for each of n_dete detection quads (level-0 pixels, double x, y; truncated like cv::Point)

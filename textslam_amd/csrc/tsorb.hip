@@ -18,6 +18,8 @@
 // (orientation inside the descriptor's launch, results also stored in the pinned block the download hands out).  Levels the LDS quadtree cannot hold are
 // flagged in pinned memory and redone by k_octree_serial behind the run's synchronisation.
 // Window search (tracking::SearchFrom3D*): k_mg_cell / k_mg_scan / k_mg_place build a frame's 64 x 48 grid, k_match searches it, a wave per query.
+// The stateful window searches SearchForTriangular / SearchForInitializ and a new keyframe's scene points (tsclaim.h): k_claim_walk runs match_walk per query, k_claim_chain
+// the reference's claim chain in one workgroup, k_claim_points the triangulation and CheckTriangular.
 // Loop fusion's window searches in many feature sets at once (tswindow.h): k_ws_grid builds every set's grid, k_ws_match runs k_match's walk (match_walk) per query.
 // Integer / fp32 arithmetic is written so that every rounding matches the CPU oracle: no FMA contraction where the
 // reference has separate multiplies and adds (__fmul_rn / __fadd_rn / __dmul_rn ...), rintf = cvRound (half to even).
@@ -1384,8 +1386,12 @@ __global__ __launch_bounds__(256) void k_mg_place(MatchDev M) {           // ran
 // The walk of one query by one wave, stated once: k_match (the context's single grid) and k_ws_match (tswindow.h: a grid per set) both call it.  G is the searched
 // grid by value; inc / o0s are the wave's 64-entry LDS scratch; cand_idx / cand_dist are the query's own rows (max_cand entries, unused slots included).
 struct MatchGrid { const float *kp; const uint8_t *desc; const int *off, *list; double min_x, min_y, iw, ih; };
+// keep(i, d): a further test of a feature that passed the window and the octave, asked with its index and distance (tsclaim.h: eligibility, the running vMatchDist);
+// MwAll keeps every one.
+struct MwAll { __device__ __forceinline__ bool operator()(int, int) const { return true; } };
+template <class Keep = MwAll>
 __device__ __forceinline__ void match_walk(const MatchGrid M, const int lane, int *inc, int *o0s, const float x, const float y, const float r, const int minLevel, const int maxLevel,
-                                           const uint32_t (&qd)[8], const int max_cand, int *cand_idx, int *cand_dist, int *cand_cnt, int *best_idx, int *best_dist, int *best_dist2) {
+                                           const uint32_t (&qd)[8], const int max_cand, int *cand_idx, int *cand_dist, int *cand_cnt, int *best_idx, int *best_dist, int *best_dist2, const Keep keep = Keep()) {
     int nc = 0, bi = -1, bd = 2147483647, bd2 = 2147483647;
     const int c0x = max(0, (int)floor(((double)x - M.min_x - (double)r)*M.iw)), c1x = min(MG_COLS - 1, (int)ceil(((double)x - M.min_x + (double)r)*M.iw));
     const int c0y = max(0, (int)floor(((double)y - M.min_y - (double)r)*M.ih)), c1y = min(MG_ROWS - 1, (int)ceil(((double)y - M.min_y + (double)r)*M.ih));
@@ -1420,6 +1426,7 @@ __device__ __forceinline__ void match_walk(const MatchGrid M, const int lane, in
                     if (!(fabsf(dx) < r && fabsf(dy) < r)) pass = false;
 #pragma unroll
                     for (int w = 0; w < 8; w++) d += __popc(qd[w] ^ f8[w]);
+                    if (pass) pass = keep(i, d);
                 }
                 const unsigned long long pm = __ballot(pass);
                 if (pm) {
@@ -1466,6 +1473,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
 #include "tstwoview.h"
 #include "tstwoview_rec.h"
 #include "tstexttheta.h"
+#include "tsclaim.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -2271,6 +2279,72 @@ int tsorb_match_text_theta_ransac(void *ctx, int n_plane, const int32_t *off, co
     if (rho_out && N) memcpy(rho_out, r + o_rho, 8*N);
     if (p3d && N) memcpy(p3d, r + o_p3d, 12*N);
     return TSORB_OK;
+}
+
+// ---- tracking::SearchForTriangular / SearchForInitializ, and GetForTriangular + CheckTriangular behind the first (tsclaim.h, docs/newpoints_recalled.md).  They search the
+// context's grid and leave it as it is; they share the blocks of the calls above: one pinned block [qxy | qr | qlev | qdesc | elig | q_px | match12 | match_dist | counts |
+// p3d | good], its image on the device followed by the scratch (the queries' lists, vMatchIdx21), one copy up, two or three launches, one copy down, one synchronisation.
+static int claim_call(const char *name, bool points, void *ctx, int nq, const float *qxy, const float *qr, const int32_t *qlev, const uint8_t *qdesc, const uint8_t *elig2,
+                      int th_low, int use_ratio, double ratio, const float *q_px, const double *Trw, const double *Tcw, const double *K, int th_reproj,
+                      int32_t *match12, int32_t *match_dist, int32_t *n_match, float *p3d, uint8_t *good, int32_t *n_good) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const std::string &m) { c->err = std::string(name) + ": " + m; return TSORB_ERR_ARG; };
+    if (!c->m_set) return bad("no grid set (tsorb_match_set_frame / tsorb_match_set_features)");
+    if (nq < 0) return bad("nq < 0");
+    if (!n_match || (points && !n_good)) return bad("NULL pointer");
+    if (th_low < 0 || th_low > 256) return bad("th_low outside [0, 256]");
+    if (use_ratio && (!std::isfinite(ratio) || ratio < 0.0)) return bad("ratio not finite or negative");
+    if (c->M.n > TSORB_BRUTE_MAX_FEAT) return bad("the searched set has more than TSORB_BRUTE_MAX_FEAT features");
+    if (nq > 0 && (!qxy || !qr || !qdesc || !match12 || (points && (!q_px || !Trw || !Tcw || !K || !p3d || !good)))) return bad("NULL pointer");
+    for (int q = 0; q < nq; q++) { if (!std::isfinite(qxy[2*(size_t)q]) || !std::isfinite(qxy[2*(size_t)q + 1])) return bad("query " + std::to_string(q) + ": a coordinate is not finite");
+        if (!std::isfinite(qr[q]) || qr[q] < 0.f) return bad("query " + std::to_string(q) + ": the radius is not finite or negative"); }
+    if (nq == 0) { *n_match = 0; if (points) *n_good = 0; return TSORB_OK; }
+    hipSetDevice(c->device);
+    const size_t Q = (size_t)nq, N2 = (size_t)c->M.n;
+    const size_t i_r = br_al(8*Q), i_lev = i_r + br_al(4*Q), i_d = i_lev + (qlev ? br_al(8*Q) : 0), i_el = i_d + br_al(32*Q), i_px = i_el + (elig2 ? br_al(N2) : 0),
+                 in_sz = i_px + (points ? br_al(8*Q) : 0);
+    const size_t o_dist = br_al(4*Q), o_cnt = o_dist + br_al(4*Q), o_p3d = o_cnt + 16, o_good = o_p3d + (points ? br_al(12*Q) : 0), out_sz = o_good + (points ? br_al(Q) : 0);
+    const size_t s_dist = br_al(4*Q*CL_ROW), s_cnt = 2*s_dist, s_own = s_cnt + br_al(4*Q), scr_sz = s_own + br_al(4*std::max<size_t>(N2, 1));
+    if (int rc = br_room(c, in_sz + out_sz + scr_sz, in_sz + out_sz)) return rc;
+    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
+    memcpy(h, qxy, 8*Q); memcpy(h + i_r, qr, 4*Q); if (qlev) memcpy(h + i_lev, qlev, 8*Q); memcpy(h + i_d, qdesc, 32*Q);
+    if (elig2 && N2) memcpy(h + i_el, elig2, N2);
+    if (points) memcpy(h + i_px, q_px, 8*Q);
+    OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
+    ClaimDev D; char *o = d + in_sz, *s = o + out_sz;
+    D.nq = nq; D.n2 = (int)N2; D.th_low = th_low; D.use_ratio = use_ratio ? 1 : 0; D.ratio = ratio;
+    D.qxy = (const float *)d; D.qr = (const float *)(d + i_r); D.qlev = qlev ? (const int32_t *)(d + i_lev) : nullptr; D.qdesc = (const uint8_t *)(d + i_d);
+    D.elig = elig2 ? (const uint8_t *)(d + i_el) : nullptr; D.q_px = (const float *)(d + i_px);
+    D.row_idx = (int32_t *)s; D.row_dist = (int32_t *)(s + s_dist); D.row_cnt = (int32_t *)(s + s_cnt); D.own = (int32_t *)(s + s_own);
+    D.match12 = (int32_t *)o; D.match_dist = (int32_t *)(o + o_dist); D.count = (int32_t *)(o + o_cnt); D.p3d = (float *)(o + o_p3d); D.good = (uint8_t *)(o + o_good);
+    for (int i = 0; i < 12; i++) { D.Trw[i] = points ? Trw[i] : 0.0; D.Tcw[i] = points ? Tcw[i] : 0.0; }
+    for (int i = 0; i < 4; i++) D.K[i] = points ? K[i] : 0.0;
+    D.th_reproj = th_reproj;
+    const MatchDev &M = c->M;
+    MatchGrid G; G.kp = M.kp; G.desc = M.desc; G.off = M.off; G.list = M.list; G.min_x = M.min_x; G.min_y = M.min_y; G.iw = M.iw; G.ih = M.ih;
+    const size_t lds = (2*N2 + 15) & ~(size_t)15;                           // vMatchDist: 16 bits a feature, at most 128 KB beside the kernel's own 17 KB
+    if (lds > 32768) OCK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_claim_chain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_claim_walk, dim3((unsigned)((nq + 3)/4)), dim3(256), 0, c->stream, G, D);
+    hipLaunchKernelGGL(k_claim_chain, dim3(1), dim3(CL_T), lds, c->stream, G, D);
+    if (points) hipLaunchKernelGGL(k_claim_points, dim3((unsigned)((nq + CL_T - 1)/CL_T)), dim3(CL_T), 0, c->stream, G, D);
+    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
+    const char *r = h + in_sz;
+    memcpy(match12, r, 4*Q); if (match_dist) memcpy(match_dist, r + o_dist, 4*Q);
+    *n_match = ((const int32_t *)(r + o_cnt))[0];
+    if (points) { memcpy(p3d, r + o_p3d, 12*Q); memcpy(good, r + o_good, Q); *n_good = ((const int32_t *)(r + o_cnt))[1]; }
+    return TSORB_OK;
+}
+int tsorb_match_search_claim(void *ctx, int nq, const float *qxy, const float *qr, const int32_t *qlev, const uint8_t *qdesc, const uint8_t *elig2, int th_low, int use_ratio,
+                             double ratio, int32_t *match12, int32_t *match_dist, int32_t *n_match) {
+    return claim_call("tsorb_match_search_claim", false, ctx, nq, qxy, qr, qlev, qdesc, elig2, th_low, use_ratio, ratio, nullptr, nullptr, nullptr, nullptr, 0,
+                      match12, match_dist, n_match, nullptr, nullptr, nullptr);
+}
+int tsorb_match_new_points(void *ctx, int nq, const float *qxy, const float *qr, const int32_t *qlev, const uint8_t *qdesc, const uint8_t *elig2, int th_low, int use_ratio,
+                           double ratio, const float *q_px, const double *Trw, const double *Tcw, const double *K, int th_reproj,
+                           int32_t *match12, int32_t *n_match, float *p3d, uint8_t *good, int32_t *n_good) {
+    return claim_call("tsorb_match_new_points", true, ctx, nq, qxy, qr, qlev, qdesc, elig2, th_low, use_ratio, ratio, q_px, Trw, Tcw, K, th_reproj,
+                      match12, nullptr, n_match, p3d, good, n_good);
 }
 
 } // extern "C"

@@ -24,10 +24,9 @@ struct TtDev {
 // tool::PixToCam: (p.x - cx)/fx in double, stored in a cv::Point2f
 __host__ __device__ __forceinline__ float tt_pix_to_cam(float p, double c, double f) { return (float)(((double)p - c)/f); }
 
-// cvTriangulatePoints' point of one feature (as recalled) between P1 = [I | 0] and P2 = T, and what GetTextTheta makes of it: X = p4d / p4d(3) in float, rho = 1/z.
-// The null vector's sign cancels: the reciprocal and the products change sign together.
-__host__ __device__ inline void tt_triangulate(const double T[12], const double K[4], const float *h, const float *t, float X[3], double &rho) {
-    const double P1[12] = { 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0 };
+// cvTriangulatePoints' point of one feature (as recalled) between the cameras P1 and P2 = T (3 x 4, row-major), and what GetTextTheta / GetForTriangular make of it:
+// X = p4d / p4d(3) in float, rho = 1/z.  The null vector's sign cancels: the reciprocal and the products change sign together.
+__host__ __device__ inline void tt_triangulate_between(const double P1[12], const double T[12], const double K[4], const float *h, const float *t, float X[3], double &rho) {
     const double x1 = (double)tt_pix_to_cam(h[0], K[2], K[0]), y1 = (double)tt_pix_to_cam(h[1], K[3], K[1]);
     const double x2 = (double)tt_pix_to_cam(t[0], K[2], K[0]), y2 = (double)tt_pix_to_cam(t[1], K[3], K[1]);
     double G[4][4], Q[4][4];
@@ -54,6 +53,11 @@ __host__ __device__ inline void tt_triangulate(const double T[12], const double 
 #pragma unroll
     for (int i = 0; i < 3; i++) X[i] = TV_MUL(v[i], r);
     rho = 1.0/(double)X[2];
+}
+// ... between P1 = [I | 0] and P2 = T: GetTextTheta's
+__host__ __device__ inline void tt_triangulate(const double T[12], const double K[4], const float *h, const float *t, float X[3], double &rho) {
+    const double P1[12] = { 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0 };
+    tt_triangulate_between(P1, T, K, h, t, X, rho);
 }
 
 // a feature's host ray (tool::GetRayRho, tracking.cc:352-354) and its target pixel, as the doubles SolveTheta reads

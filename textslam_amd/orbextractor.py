@@ -14,7 +14,8 @@ EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_
                     "tsorb_get_features_per_level", "tsorb_extract_batch", "tsorb_upload", "tsorb_run", "tsorb_download",
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
                     "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets", "tsorb_match_pnp_ransac",
-                    "tsorb_match_two_view_ransac", "tsorb_match_two_view_reconstruct", "tsorb_match_text_theta_ransac"]
+                    "tsorb_match_two_view_ransac", "tsorb_match_two_view_reconstruct", "tsorb_match_text_theta_ransac", "tsorb_match_search_claim",
+                    "tsorb_match_new_points"]
 BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
 SETS_MAX = 1024                                                         # TSORB_SETS_MAX of include/tsorb.h
 PNP_MAX_HYP = 128                                                       # TSORB_PNP_MAX_HYP of include/tsorb.h
@@ -71,6 +72,10 @@ def load_library():
         L.tsorb_match_two_view_reconstruct.restype = C.c_int
         L.tsorb_match_text_theta_ransac.argtypes = [vp, C.c_int, ip, fp, fp, dp, dp, dp, ip, ip, ip, dp, dp, fp, dp, dp, dp]
         L.tsorb_match_text_theta_ransac.restype = C.c_int
+        L.tsorb_match_search_claim.argtypes = [vp, C.c_int, fp, fp, ip, up, up, C.c_int, C.c_int, C.c_double, ip, ip, ip]
+        L.tsorb_match_search_claim.restype = C.c_int
+        L.tsorb_match_new_points.argtypes = [vp, C.c_int, fp, fp, ip, up, up, C.c_int, C.c_int, C.c_double, fp, dp, dp, dp, C.c_int, ip, ip, fp, up, ip]
+        L.tsorb_match_new_points.restype = C.c_int
         _lib = L
     return _lib
 
@@ -344,6 +349,46 @@ class ORBextractor:
                                                            ptr(theta, C.c_double), ptr(score, C.c_double), ptr(p3d, C.c_float), ptr(rho_out, C.c_double),
                                                            ptr(hs, C.c_double), ptr(ht, C.c_double)), "tsorb_match_text_theta_ransac")
         return dict(sel=sel[:P], theta=theta[:P], score=score[:P], p3d=p3d[:N], rho=rho_out[:N], hyp_score=hs[:H], hyp_theta=ht[:H])
+
+    # ---- the stateful window searches (tracking::SearchForTriangular / SearchForInitializ, GetForTriangular + CheckTriangular; docs/newpoints_recalled.md)
+    def _claim_args(self, qxy, qr, qlev, qdesc, elig2):
+        qxy = np.ascontiguousarray(qxy, np.float32).reshape(-1, 2); qr = np.ascontiguousarray(qr, np.float32).reshape(-1); qdesc = np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
+        qlev = None if qlev is None else np.ascontiguousarray(qlev, np.int32).reshape(-1, 2)
+        elig2 = None if elig2 is None else np.ascontiguousarray(np.asarray(elig2).reshape(-1) != 0, np.uint8)
+        nq = qxy.shape[0]
+        if qr.shape[0] != nq or qdesc.shape[0] != nq or (qlev is not None and qlev.shape[0] != nq):
+            raise ValueError("qxy, qr, qlev and qdesc have different lengths")
+        return nq, qxy, qr, qlev, qdesc, elig2
+
+    def match_search_claim(self, qxy, qr, qlev, qdesc, elig2=None, th_low=50, use_ratio=False, ratio=0.9):
+        """The reference's claim chain over the queries in order against the current grid (match_set_frame / match_set_features): qxy [nq, 2], qr [nq], qlev [nq, 2] or
+        None, qdesc [nq, 32]; elig2 [n2] (non-zero = may be matched) or None = all.  SearchForTriangular: the defaults with qr = 80*1.2f and qlev = (octave, octave);
+        SearchForInitializ: use_ratio=True.  Returns a dict: match12 [nq] int32 (-1 = none), match_dist [nq] int32 (-1 = none), n_match."""
+        nq, qxy, qr, qlev, qdesc, elig2 = self._claim_args(qxy, qr, qlev, qdesc, elig2)
+        m12 = np.full(max(nq, 1), -1, np.int32); md = np.full(max(nq, 1), -1, np.int32); nm = np.zeros(1, np.int32)
+        ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a is not None and a.size else None
+        self._check(self.lib.tsorb_match_search_claim(self.ctx, nq, ptr(qxy, C.c_float), ptr(qr, C.c_float), ptr(qlev, C.c_int32), ptr(qdesc, C.c_uint8), ptr(elig2, C.c_uint8),
+                                                      int(th_low), int(bool(use_ratio)), float(ratio), ptr(m12, C.c_int32), ptr(md, C.c_int32), ptr(nm, C.c_int32)),
+                    "tsorb_match_search_claim")
+        return dict(match12=m12[:nq], match_dist=md[:nq], n_match=int(nm[0]))
+
+    def match_new_points(self, qxy, qr, qlev, qdesc, q_px, Trw, Tcw, K, elig2=None, th_low=50, use_ratio=False, ratio=0.9, th_reproj=9):
+        """match_search_claim, then GetForTriangular's point and CheckTriangular's verdict of every match in the same call: q_px [nq, 2] the queries' pixels in the
+        keyframe, Trw / Tcw [3, 4] (or [4, 4]) the keyframe's and the frame's pose, K = (fx, fy, cx, cy) in double.  Returns a dict: match12 [nq] int32, n_match,
+        p3d [nq, 3] float32 and good [nq] bool per query (zeros without a match), n_good."""
+        nq, qxy, qr, qlev, qdesc, elig2 = self._claim_args(qxy, qr, qlev, qdesc, elig2)
+        q_px = np.ascontiguousarray(q_px, np.float32).reshape(-1, 2)
+        if q_px.shape[0] != nq:
+            raise ValueError("q_px and qxy have different lengths")
+        Trw = np.ascontiguousarray(np.asarray(Trw, np.float64).reshape(-1, 4)[:3]).reshape(12); Tcw = np.ascontiguousarray(np.asarray(Tcw, np.float64).reshape(-1, 4)[:3]).reshape(12)
+        K = np.ascontiguousarray(K, np.float64).reshape(4)
+        m12 = np.full(max(nq, 1), -1, np.int32); cnt = np.zeros(2, np.int32); p3d = np.zeros((max(nq, 1), 3), np.float32); good = np.zeros(max(nq, 1), np.uint8)
+        ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a is not None and a.size else None
+        self._check(self.lib.tsorb_match_new_points(self.ctx, nq, ptr(qxy, C.c_float), ptr(qr, C.c_float), ptr(qlev, C.c_int32), ptr(qdesc, C.c_uint8), ptr(elig2, C.c_uint8),
+                                                    int(th_low), int(bool(use_ratio)), float(ratio), ptr(q_px, C.c_float), ptr(Trw, C.c_double), ptr(Tcw, C.c_double),
+                                                    ptr(K, C.c_double), int(th_reproj), ptr(m12, C.c_int32), ptr(cnt[0:1], C.c_int32), ptr(p3d, C.c_float), ptr(good, C.c_uint8),
+                                                    ptr(cnt[1:2], C.c_int32)), "tsorb_match_new_points")
+        return dict(match12=m12[:nq], n_match=int(cnt[0]), p3d=p3d[:nq], good=good[:nq].astype(bool), n_good=int(cnt[1]))
 
     def debug_fast_shape(self, shape=-1):
         """Diagnostics: the shape of the FAST launches (include/tsorb.h); -1 = chosen by the batch size."""
