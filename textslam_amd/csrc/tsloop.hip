@@ -20,14 +20,15 @@
 #include <vector>
 #include <map>
 #include "tsloop_graph.h"
+#include "tsstage.h"
 
 #define SIM_T 256
 #define SIM_NW (SIM_T/64)
 
 struct LCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
-    uint8_t *h_stage = nullptr; size_t h_cap = 0; uint8_t *d_buf = nullptr; size_t d_cap = 0;
-    uint8_t *h_out = nullptr; size_t h_out_cap = 0;                     // tsloop_sim3_batch's pinned block out
+    void *h_stage = nullptr; size_t h_cap = 0; void *d_buf = nullptr; size_t d_cap = 0;       // the calls' pinned block and device block, laid out with tsstage.h
+    void *h_out = nullptr; size_t h_out_cap = 0;                        // tsloop_sim3_batch's pinned block out
 };
 #define CKL(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); return TSLOOP_ERR_DEVICE; } } while (0)
 
@@ -313,21 +314,21 @@ int tsloop_optimize_sim3(void *ctx, tsloop_sim3_problem *p, const tsloop_options
     hipSetDevice(c->device);
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n = (size_t)p->n;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_P1 = 0, o_P2 = o_P1 + al(24*n), o_u1 = o_P2 + al(24*n), o_u2 = o_u1 + al(8*n), o_sim = o_u2 + al(8*n), o_rep = o_sim + al(64),
-                 o_inl = o_rep + al(sizeof(tsloop_report)), tot = o_inl + al(n);
-    if (tot > c->h_cap) { if (c->h_stage) hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_cap = 0; CKL(hipHostMalloc((void **)&c->h_stage, tot, hipHostMallocDefault)); c->h_cap = tot; }
-    if (tot > c->d_cap) { if (c->d_buf) hipFree(c->d_buf); c->d_buf = nullptr; c->d_cap = 0; CKL(hipMalloc((void **)&c->d_buf, tot)); c->d_cap = tot; }
-    uint8_t *h = c->h_stage, *d = c->d_buf;
-    memcpy(h + o_P1, p->P1, 24*n); memcpy(h + o_P2, p->P2, 24*n); memcpy(h + o_u1, p->uv1, 8*n); memcpy(h + o_u2, p->uv2, 8*n);
-    memcpy(h + o_sim, p->sim, 64); memset(h + o_rep, 0, sizeof(tsloop_report)); memcpy(h + o_inl, p->inlier, n);
-    CKL(hipMemcpyAsync(d, h, tot, hipMemcpyHostToDevice, c->stream));                 // one staged copy in, one out
-    Sim3Dev D; D.n = p->n; D.P1 = (const double *)(d + o_P1); D.P2 = (const double *)(d + o_P2); D.uv1 = (const float *)(d + o_u1); D.uv2 = (const float *)(d + o_u2);
-    D.inlier = d + o_inl; memcpy(D.K, p->K, sizeof(D.K)); D.sim = (double *)(d + o_sim); D.rep = (tsloop_report *)(d + o_rep);
+    // in: [P1 | P2 | uv1 | uv2]   in and out: [sim | rep | inlier]
+    Layout L(256);
+    const auto a_P1 = L.take<double>(3*n), a_P2 = L.take<double>(3*n); const auto a_u1 = L.take<float>(2*n), a_u2 = L.take<float>(2*n);
+    const auto a_sim = L.take<double>(8); const auto a_rep = L.take<tsloop_report>(1); const auto a_inl = L.take<uint8_t>(n);
+    CKL(grow_pinned(c->h_stage, c->h_cap, L.mark())); CKL(grow_device(c->d_buf, c->d_cap, L.mark()));
+    void *h = c->h_stage, *d = c->d_buf;
+    a_P1.put(h, p->P1); a_P2.put(h, p->P2); a_u1.put(h, p->uv1); a_u2.put(h, p->uv2);
+    a_sim.put(h, p->sim); memset(a_rep.at(h), 0, a_rep.bytes()); a_inl.put(h, p->inlier);
+    CKL(hipMemcpyAsync(d, h, L.mark(), hipMemcpyHostToDevice, c->stream));            // one staged copy in, one out
+    Sim3Dev D; D.n = p->n; D.P1 = a_P1.at(d); D.P2 = a_P2.at(d); D.uv1 = a_u1.at(d); D.uv2 = a_u2.at(d);
+    D.inlier = a_inl.at(d); memcpy(D.K, p->K, sizeof(D.K)); D.sim = a_sim.at(d); D.rep = a_rep.at(d);
     hipLaunchKernelGGL(k_sim3_lm, dim3(1), dim3(SIM_T), 0, c->stream, D, *o);
-    CKL(hipMemcpyAsync(h + o_sim, d + o_sim, tot - o_sim, hipMemcpyDeviceToHost, c->stream));
+    CKL(hipMemcpyAsync(a_sim.at(h), a_sim.at(d), L.mark() - a_sim.off, hipMemcpyDeviceToHost, c->stream));
     CKL(hipStreamSynchronize(c->stream)); CKL(hipGetLastError());
-    memcpy(p->sim, h + o_sim, 64); memcpy(r, h + o_rep, sizeof(tsloop_report)); memcpy(p->inlier, h + o_inl, n);
+    a_sim.get(h, p->sim); a_rep.get(h, r); a_inl.get(h, p->inlier);
     r->t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return r->termination == 5 ? TSLOOP_ERR_NUMERIC : TSLOOP_OK;
 }
@@ -381,48 +382,45 @@ int tsloop_sim3_batch(void *ctx, tsloop_sim3_batch_problem *p, const tsloop_opti
         } };
     if (na == 0) { fill_idle(); return TSLOOP_OK; }
     hipSetDevice(c->device);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0; auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
-    const size_t o_cand = take(4*na), o_off = take(4*((size_t)nc + 1)), o_hoff = take(4*((size_t)nc + 1)), o_tri = take(12*nh), o_K2 = take(32*(size_t)nc),
-                 o_P1 = take(24*n), o_P2 = take(24*n), o_q1 = take(16*n), o_q2 = take(16*n), o_u1 = take(8*n), o_u2 = take(8*n), in_end = off,      // uploaded
-                 o_ok = take(4*(size_t)nc), o_sel = take(4*(size_t)nc), o_ni = take(4*(size_t)nc), o_hc = take(4*nh), o_sr = take(64*(size_t)nc), o_sim = take(64*(size_t)nc),
-                 o_hs = take(64*nh), o_rep = take(sizeof(tsloop_report)*(size_t)nc), o_inl = take(n), tot = off, out_sz = tot - in_end;             // downloaded
-    if (in_end > c->h_cap) { if (c->h_stage) hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_cap = 0; CKL(hipHostMalloc((void **)&c->h_stage, in_end, hipHostMallocDefault)); c->h_cap = in_end; }
-    if (out_sz > c->h_out_cap) { if (c->h_out) hipHostFree(c->h_out); c->h_out = nullptr; c->h_out_cap = 0; CKL(hipHostMalloc((void **)&c->h_out, out_sz, hipHostMallocDefault)); c->h_out_cap = out_sz; }
-    if (tot > c->d_cap) { if (c->d_buf) hipFree(c->d_buf); c->d_buf = nullptr; c->d_cap = 0; CKL(hipMalloc((void **)&c->d_buf, tot)); c->d_cap = tot; }
-    uint8_t *h = c->h_stage, *d = c->d_buf; auto out_at = [&](size_t o_x) { return (const uint8_t *)c->h_out + (o_x - in_end); };   // output x in the pinned block out
-    memcpy(h + o_cand, act.data(), 4*na); memcpy(h + o_off, p->off, 4*((size_t)nc + 1)); memcpy(h + o_hoff, p->hyp_off, 4*((size_t)nc + 1));
-    memcpy(h + o_tri, p->triple, 12*nh); memcpy(h + o_K2, p->K2, 32*(size_t)nc);
-    memcpy(h + o_P1, p->P1, 24*n); memcpy(h + o_P2, p->P2, 24*n); memcpy(h + o_q1, p->pred1, 16*n); memcpy(h + o_q2, p->pred2, 16*n);
-    memcpy(h + o_u1, p->uv1, 8*n); memcpy(h + o_u2, p->uv2, 8*n);
-    CKL(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));                            // one copy in, one launch, one copy out
+    // in: [cand | off | hyp_off | triple | K2 | P1 | P2 | pred1 | pred2 | uv1 | uv2]   out, behind it on the device and in a pinned block of its own:
+    // [ok | sel | n_inlier | hyp_count | sim_ransac | sim | hyp_sim | rep | inlier]
+    const size_t NC = (size_t)nc;
+    Layout L(256), Lo(256);
+    const auto a_cand = L.take<int32_t>(na), a_off = L.take<int32_t>(NC + 1), a_hoff = L.take<int32_t>(NC + 1), a_tri = L.take<int32_t>(3*nh);
+    const auto a_K2 = L.take<double>(4*NC), a_P1 = L.take<double>(3*n), a_P2 = L.take<double>(3*n), a_q1 = L.take<double>(2*n), a_q2 = L.take<double>(2*n);
+    const auto a_u1 = L.take<float>(2*n), a_u2 = L.take<float>(2*n);
+    const auto a_ok = Lo.take<int32_t>(NC), a_sel = Lo.take<int32_t>(NC), a_ni = Lo.take<int32_t>(NC), a_hc = Lo.take<int32_t>(nh);
+    const auto a_sr = Lo.take<double>(8*NC), a_sim = Lo.take<double>(8*NC), a_hs = Lo.take<double>(8*nh); const auto a_rep = Lo.take<tsloop_report>(NC); const auto a_inl = Lo.take<uint8_t>(n);
+    CKL(grow_pinned(c->h_stage, c->h_cap, L.mark())); CKL(grow_pinned(c->h_out, c->h_out_cap, Lo.mark())); CKL(grow_device(c->d_buf, c->d_cap, L.mark() + Lo.mark()));
+    void *h = c->h_stage, *d = c->d_buf, *dout = (uint8_t *)d + L.mark(); const void *ho = c->h_out;
+    a_cand.put(h, act.data()); a_off.put(h, p->off); a_hoff.put(h, p->hyp_off); a_tri.put(h, p->triple); a_K2.put(h, p->K2);
+    a_P1.put(h, p->P1); a_P2.put(h, p->P2); a_q1.put(h, p->pred1); a_q2.put(h, p->pred2); a_u1.put(h, p->uv1); a_u2.put(h, p->uv2);
+    CKL(hipMemcpyAsync(d, h, L.mark(), hipMemcpyHostToDevice, c->stream));                          // one copy in, one launch, one copy out
     Sim3BatchDev B;
-    B.cand = (const int32_t *)(d + o_cand); B.off = (const int32_t *)(d + o_off); B.hyp_off = (const int32_t *)(d + o_hoff); B.triple = (const int32_t *)(d + o_tri);
-    B.P1 = (const double *)(d + o_P1); B.P2 = (const double *)(d + o_P2); B.pred1 = (const double *)(d + o_q1); B.pred2 = (const double *)(d + o_q2);
-    B.uv1 = (const float *)(d + o_u1); B.uv2 = (const float *)(d + o_u2); B.K2 = (const double *)(d + o_K2);
+    B.cand = a_cand.at(d); B.off = a_off.at(d); B.hyp_off = a_hoff.at(d); B.triple = a_tri.at(d);
+    B.P1 = a_P1.at(d); B.P2 = a_P2.at(d); B.pred1 = a_q1.at(d); B.pred2 = a_q2.at(d); B.uv1 = a_u1.at(d); B.uv2 = a_u2.at(d); B.K2 = a_K2.at(d);
     memcpy(B.K1, p->K1, sizeof(B.K1)); memcpy(B.K, p->K, sizeof(B.K)); B.max_err2 = p->max_err2; B.min_inliers = p->min_inliers; B.optimise = p->optimise ? 1 : 0;
-    B.ok = (int32_t *)(d + o_ok); B.sel = (int32_t *)(d + o_sel); B.ninl = (int32_t *)(d + o_ni); B.hyp_count = (int32_t *)(d + o_hc);
-    B.sim_ransac = (double *)(d + o_sr); B.sim = (double *)(d + o_sim); B.hyp_sim = (double *)(d + o_hs); B.rep = (tsloop_report *)(d + o_rep); B.inlier = d + o_inl;
+    B.ok = a_ok.at(dout); B.sel = a_sel.at(dout); B.ninl = a_ni.at(dout); B.hyp_count = a_hc.at(dout);
+    B.sim_ransac = a_sr.at(dout); B.sim = a_sim.at(dout); B.hyp_sim = a_hs.at(dout); B.rep = a_rep.at(dout); B.inlier = a_inl.at(dout);
     hipLaunchKernelGGL(k_sim3_batch, dim3((unsigned)na), dim3(SIM_T), 0, c->stream, B, *o);
-    CKL(hipMemcpyAsync(c->h_out, d + in_end, out_sz, hipMemcpyDeviceToHost, c->stream));
+    CKL(hipMemcpyAsync(c->h_out, dout, Lo.mark(), hipMemcpyDeviceToHost, c->stream));
     CKL(hipStreamSynchronize(c->stream)); CKL(hipGetLastError());
     const double t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     fill_idle();
     int rc = TSLOOP_OK;
     for (size_t a = 0; a < na; a++) {
         const size_t k = (size_t)act[a];
-        const int ok = ((const int32_t *)out_at(o_ok))[k];
-        p->ok[k] = ok ? 1 : 0; p->sel[k] = ((const int32_t *)out_at(o_sel))[k]; p->n_inlier_ransac[k] = ((const int32_t *)out_at(o_ni))[k];
-        memcpy(p->sim_ransac + 8*k, out_at(o_sr) + 64*k, 64);
-        memcpy(p->inlier + p->off[k], out_at(o_inl) + p->off[k], (size_t)(p->off[k + 1] - p->off[k]));
+        const int ok = a_ok.at(ho)[k];
+        p->ok[k] = ok ? 1 : 0; p->sel[k] = a_sel.at(ho)[k]; p->n_inlier_ransac[k] = a_ni.at(ho)[k];
+        std::copy_n(a_sr.at(ho) + 8*k, 8, p->sim_ransac + 8*k);
+        std::copy(a_inl.at(ho) + p->off[k], a_inl.at(ho) + p->off[k + 1], p->inlier + p->off[k]);
         if (ok && p->optimise) {
-            memcpy(p->sim + 8*k, out_at(o_sim) + 64*k, 64); memcpy(p->rep + k, out_at(o_rep) + sizeof(tsloop_report)*k, sizeof(tsloop_report));
+            std::copy_n(a_sim.at(ho) + 8*k, 8, p->sim + 8*k); p->rep[k] = a_rep.at(ho)[k];
             p->rep[k].t_ms = t_ms;
             if (p->rep[k].termination == 5) rc = TSLOOP_ERR_NUMERIC;
         }
     }
-    if (p->hyp_count) memcpy(p->hyp_count, out_at(o_hc), 4*nh);
-    if (p->hyp_sim) memcpy(p->hyp_sim, out_at(o_hs), 64*nh);
+    a_hc.get(ho, p->hyp_count); a_hs.get(ho, p->hyp_sim);
     return rc;
 }
 
@@ -465,42 +463,41 @@ int tsloop_detect_loop(void *ctx, tsloop_detect_problem *p) {
     if (n_tile*nq > (size_t)INT32_MAX) return bad("more (query, tile of map texts) pairs than a grid holds");
     hipSetDevice(c->device);
     const size_t nsel = std::min((size_t)p->top_n, nk);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0; auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
-    const size_t o_qoff = take(4*(nq + 1)), o_qstr = take(qb), o_qself = take(4*nq), o_moff = take(4*(nm + 1)), o_mstr = take(mb), o_mskip = take(nm),
-                 o_ooff = take(4*(nm + 1)), o_okf = take(4*no), in_end = off,                                                                        // uploaded
-                 o_dist = take(nq*nm), o_hit = take(4*nm), o_tidx = take(4*nq*mm), o_tsc = take(8*nq*mm), o_rrec = take(sizeof(TdRec)*nq*mm), out_begin = off,     // scratch
-                 o_cnt = take(4*nq), o_roff = take(4*(nq + 1)), o_ks = take(4*nk), o_ko = take(4*nk), o_nc = take(4), o_cand = take(4*nsel),
-                 o_rec = take(sizeof(TdRec)*nq*mm), tot = off;                                                                                        // downloaded
+    // in: [q_off | q_str | q_self | m_off | m_str | m_skip | obs_off | obs_kf]   scratch: [dist | hit | tmp_idx | tmp_score | rank_rec]
+    // out, behind it on the device and in a pinned block of its own: [match_cnt | rec_off | kf_score | kf_nobj | n_cand | cand | out_rec]
+    Layout L(256), Lo(256);
+    const auto a_qoff = L.take<int32_t>(nq + 1); const auto a_qstr = L.take<uint8_t>(qb); const auto a_qself = L.take<int32_t>(nq), a_moff = L.take<int32_t>(nm + 1);
+    const auto a_mstr = L.take<uint8_t>(mb), a_mskip = L.take<uint8_t>(nm); const auto a_ooff = L.take<int32_t>(nm + 1), a_okf = L.take<int32_t>(no);
+    const size_t in_end = L.mark();
+    const auto a_dist = L.take<uint8_t>(nq*nm); const auto a_hit = L.take<int32_t>(nm), a_tidx = L.take<int32_t>(nq*mm); const auto a_tsc = L.take<double>(nq*mm); const auto a_rrec = L.take<TdRec>(nq*mm);
+    const auto a_cnt = Lo.take<int32_t>(nq), a_roff = Lo.take<int32_t>(nq + 1), a_ks = Lo.take<int32_t>(nk), a_ko = Lo.take<int32_t>(nk), a_nc = Lo.take<int32_t>(1), a_cand = Lo.take<int32_t>(nsel);
+    const auto a_rec = Lo.take<TdRec>(nq*mm);
     // the packed lists come last: the one copy out takes as many records as the default capacity holds, a second one only what lies beyond them
-    const size_t n_first = nq*std::min(mm, (size_t)64), out_sz = (o_rec - out_begin) + sizeof(TdRec)*n_first;
-    if (in_end > c->h_cap) { if (c->h_stage) hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_cap = 0; CKL(hipHostMalloc((void **)&c->h_stage, in_end, hipHostMallocDefault)); c->h_cap = in_end; }
-    if (out_sz > c->h_out_cap) { if (c->h_out) hipHostFree(c->h_out); c->h_out = nullptr; c->h_out_cap = 0; CKL(hipHostMalloc((void **)&c->h_out, out_sz, hipHostMallocDefault)); c->h_out_cap = out_sz; }
-    if (tot > c->d_cap) { if (c->d_buf) hipFree(c->d_buf); c->d_buf = nullptr; c->d_cap = 0; CKL(hipMalloc((void **)&c->d_buf, tot)); c->d_cap = tot; }
-    uint8_t *h = c->h_stage, *d = c->d_buf; auto out_at = [&](size_t o_x) { return (const uint8_t *)c->h_out + (o_x - out_begin); };
-    memcpy(h + o_qoff, p->q_off, 4*(nq + 1)); if (qb) memcpy(h + o_qstr, p->q_str, qb); memcpy(h + o_qself, p->q_self, 4*nq);
-    memcpy(h + o_moff, p->m_off, 4*(nm + 1)); if (mb) memcpy(h + o_mstr, p->m_str, mb); memcpy(h + o_mskip, p->m_skip, nm);
-    memcpy(h + o_ooff, p->obs_off, 4*(nm + 1)); if (no) memcpy(h + o_okf, p->obs_kf, 4*no);
+    const size_t n_first = nq*std::min(mm, (size_t)64), out_sz = a_rec.off + sizeof(TdRec)*n_first;
+    CKL(grow_pinned(c->h_stage, c->h_cap, in_end)); CKL(grow_pinned(c->h_out, c->h_out_cap, out_sz)); CKL(grow_device(c->d_buf, c->d_cap, L.mark() + Lo.mark()));
+    void *h = c->h_stage, *d = c->d_buf, *dout = (uint8_t *)d + L.mark(); const void *ho = c->h_out;
+    a_qoff.put(h, p->q_off); a_qstr.put(h, p->q_str); a_qself.put(h, p->q_self); a_moff.put(h, p->m_off); a_mstr.put(h, p->m_str); a_mskip.put(h, p->m_skip);
+    a_ooff.put(h, p->obs_off); a_okf.put(h, p->obs_kf);
     CKL(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));                            // one copy in, three launches, one copy out (two after a max_match above the default)
     TdDev D;
     D.n_query = p->n_query; D.n_map = p->n_map; D.n_kf = p->n_kf; D.top_n = p->top_n; D.n_tile = (int32_t)n_tile; D.max_match = p->max_match; D.min_matched_words = p->min_matched_words;
-    D.q_off = (const int32_t *)(d + o_qoff); D.q_str = d + o_qstr; D.q_self = (const int32_t *)(d + o_qself);
-    D.m_off = (const int32_t *)(d + o_moff); D.m_str = d + o_mstr; D.m_skip = d + o_mskip; D.obs_off = (const int32_t *)(d + o_ooff); D.obs_kf = (const int32_t *)(d + o_okf);
+    D.q_off = a_qoff.at(d); D.q_str = a_qstr.at(d); D.q_self = a_qself.at(d); D.m_off = a_moff.at(d); D.m_str = a_mstr.at(d); D.m_skip = a_mskip.at(d);
+    D.obs_off = a_ooff.at(d); D.obs_kf = a_okf.at(d);
     D.min_str_score = p->min_str_score; D.score_thresh_min = p->score_thresh_min;
-    D.dist = d + o_dist; D.hit = (int32_t *)(d + o_hit); D.tmp_idx = (int32_t *)(d + o_tidx); D.tmp_score = (double *)(d + o_tsc);
-    D.rank_rec = (TdRec *)(d + o_rrec); D.match_cnt = (int32_t *)(d + o_cnt); D.rec_off = (int32_t *)(d + o_roff); D.out_rec = (TdRec *)(d + o_rec);
-    D.kf_score = (int32_t *)(d + o_ks); D.kf_nobj = (int32_t *)(d + o_ko); D.n_cand = (int32_t *)(d + o_nc); D.cand = (int32_t *)(d + o_cand);
+    D.dist = a_dist.at(d); D.hit = a_hit.at(d); D.tmp_idx = a_tidx.at(d); D.tmp_score = a_tsc.at(d); D.rank_rec = a_rrec.at(d);
+    D.match_cnt = a_cnt.at(dout); D.rec_off = a_roff.at(dout); D.out_rec = a_rec.at(dout);
+    D.kf_score = a_ks.at(dout); D.kf_nobj = a_ko.at(dout); D.n_cand = a_nc.at(dout); D.cand = a_cand.at(dout);
     hipLaunchKernelGGL(k_td_scan, dim3((unsigned)(n_tile*nq)), dim3(TD_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_td_pick, dim3((unsigned)nq), dim3(TD_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_td_vote, dim3(1), dim3(TD_T), 0, c->stream, D);
-    CKL(hipMemcpyAsync(c->h_out, d + out_begin, out_sz, hipMemcpyDeviceToHost, c->stream));
+    CKL(hipMemcpyAsync(c->h_out, dout, out_sz, hipMemcpyDeviceToHost, c->stream));
     CKL(hipStreamSynchronize(c->stream)); CKL(hipGetLastError());
-    const int32_t *cnt = (const int32_t *)out_at(o_cnt), *roff = (const int32_t *)out_at(o_roff);
-    const TdRec *first = (const TdRec *)out_at(o_rec);
+    const int32_t *cnt = a_cnt.at(ho), *roff = a_roff.at(ho);
+    const TdRec *first = a_rec.at(ho);
     const size_t n_rec = (size_t)roff[nq];
     std::vector<TdRec> rest;                                           // (only after a call with a max_match above the default)
-    if (n_rec > n_first) { rest.resize(n_rec - n_first); CKL(hipMemcpy(rest.data(), d + o_rec + sizeof(TdRec)*n_first, sizeof(TdRec)*rest.size(), hipMemcpyDeviceToHost)); }
-    memcpy(p->match_cnt, cnt, 4*nq);
+    if (n_rec > n_first) { rest.resize(n_rec - n_first); CKL(hipMemcpy(rest.data(), a_rec.at(dout) + n_first, sizeof(TdRec)*rest.size(), hipMemcpyDeviceToHost)); }
+    a_cnt.get(ho, p->match_cnt);
     int over = -1;
     for (size_t q = 0; q < nq; q++) {
         const size_t n = (size_t)cnt[q];
@@ -510,9 +507,9 @@ int tsloop_detect_loop(void *ctx, tsloop_detect_problem *p) {
             p->match_idx[q*mm + j] = r.idx; p->match_dist[q*mm + j] = r.dist; p->match_score[q*mm + j] = r.score;
         }
     }
-    if (nk > 0) { memcpy(p->kf_score, out_at(o_ks), 4*nk); memcpy(p->kf_nobj, out_at(o_ko), 4*nk); }
-    const int32_t nc = *(const int32_t *)out_at(o_nc);
-    *p->n_cand = nc; memcpy(p->cand, out_at(o_cand), 4*(size_t)nc);
+    a_ks.get(ho, p->kf_score); a_ko.get(ho, p->kf_nobj);
+    const int32_t nc = *a_nc.at(ho);
+    *p->n_cand = nc; std::copy_n(a_cand.at(ho), nc, p->cand);
     if (over >= 0) {
         c->err = "tsloop_detect_loop: query " + std::to_string(over) + " has " + std::to_string(cnt[over]) + " matches, more than max_match = " + std::to_string(p->max_match) +
                  " (match_cnt, kf_score, kf_nobj, n_cand and cand are complete; the lists of such queries are not written)";
@@ -555,37 +552,36 @@ int tsloop_optimize_loop(void *ctx, tsloop_graph_problem *p, const tsloop_option
     for (auto &kv : pm) { pair_a.push_back(kv.first.first); pair_b.push_back(kv.first.second); for (int v : kv.second) pair_e.push_back(v); pair_off.push_back((int)pair_e.size()); }
     const int npair = (int)pair_a.size(), n = 7*nf, n6 = (n + 5)/6*6, nb6 = n6/6;
     // ---- device buffers (one allocation)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0; auto take = [&](size_t bytes) { const size_t o_ = off; off += al(bytes); return o_; };
-    const size_t o_x0 = take(64*(size_t)N), o_x1 = take(64*(size_t)N), o_fidx = take(4*(size_t)N), o_free = take(4*(size_t)nf), o_ei = take(4*(size_t)E), o_ej = take(4*(size_t)E),
-                 o_meas = take(64*(size_t)E), o_kfoff = take(4*(size_t)(nf + 1)), o_kfinc = take(4*kf_inc.size() + 4), o_pa = take(4*(size_t)npair + 4), o_pb = take(4*(size_t)npair + 4),
-                 o_poff = take(4*(size_t)(npair + 1)), o_pe = take(4*pair_e.size() + 4), o_sfidx = take(4*(size_t)nb6), o_nfree = take(4), o_st = take(sizeof(LmState)),
-                 o_host_end = off,                                       // everything up to here is uploaded
-                 o_r = take(56*(size_t)E), o_J1 = take(392*(size_t)E), o_J2 = take(392*(size_t)E), o_ce = take(8*(size_t)E), o_cce = take(8*(size_t)E), o_qe = take(8*(size_t)E),
-                 o_sc = take(8*(size_t)n6), o_part = take(32*(size_t)nf), o_g = take(8*(size_t)n6), o_dp = take(8*(size_t)n6), o_Sy = take(8*(size_t)n6),
-                 o_LD = take(8*(size_t)std::max(n6, 32*nb6)), o_dbg = take(8*64), o_S = take(8*((size_t)n6 + 1)*n6), tot = off;
-    if (o_host_end > c->h_cap) { if (c->h_stage) hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_cap = 0; CKL(hipHostMalloc((void **)&c->h_stage, o_host_end, hipHostMallocDefault)); c->h_cap = o_host_end; }
-    if (tot > c->d_cap) { if (c->d_buf) hipFree(c->d_buf); c->d_buf = nullptr; c->d_cap = 0; CKL(hipMalloc((void **)&c->d_buf, tot)); c->d_cap = tot; }
-    uint8_t *h = c->h_stage, *d = c->d_buf;
-    memcpy(h + o_x0, p->pose, 64*(size_t)N); memcpy(h + o_x1, p->pose, 64*(size_t)N);
-    memcpy(h + o_fidx, fidx.data(), 4*(size_t)N); memcpy(h + o_free, free_kf.data(), 4*(size_t)nf);
-    memcpy(h + o_ei, p->edge_i, 4*(size_t)E); memcpy(h + o_ej, p->edge_j, 4*(size_t)E); memcpy(h + o_meas, p->meas, 64*(size_t)E);
-    memcpy(h + o_kfoff, kf_off.data(), 4*(size_t)(nf + 1)); memcpy(h + o_kfinc, kf_inc.data(), 4*kf_inc.size());
-    memcpy(h + o_pa, pair_a.data(), 4*(size_t)npair); memcpy(h + o_pb, pair_b.data(), 4*(size_t)npair); memcpy(h + o_poff, pair_off.data(), 4*(size_t)(npair + 1)); memcpy(h + o_pe, pair_e.data(), 4*pair_e.size());
-    { int *sf = (int *)(h + o_sfidx); for (int k = 0; k < nb6; k++) sf[k] = k; *(int *)(h + o_nfree) = nb6; }
+    // in: [x0 | x1 | fidx | free | ei | ej | meas | kf_off | kf_inc | pair_a | pair_b | pair_off | pair_e | solver fidx | nfree | LmState]
+    // scratch: [r | J1 | J2 | cost | ccost | q | sc | part | g | dp | Sy | LD | dbg | S]   (the lists that can be empty are taken one entry longer)
+    const size_t NK = (size_t)N, NE = (size_t)E, NF = (size_t)nf, NP = (size_t)npair, N6 = (size_t)n6;
+    Layout L(256);
+    const auto a_x0 = L.take<double>(8*NK), a_x1 = L.take<double>(8*NK); const auto a_fidx = L.take<int>(NK), a_free = L.take<int>(NF), a_ei = L.take<int>(NE), a_ej = L.take<int>(NE);
+    const auto a_meas = L.take<double>(8*NE); const auto a_kfoff = L.take<int>(NF + 1), a_kfinc = L.take<int>(kf_inc.size() + 1), a_pa = L.take<int>(NP + 1), a_pb = L.take<int>(NP + 1),
+               a_poff = L.take<int>(NP + 1), a_pe = L.take<int>(pair_e.size() + 1), a_sfidx = L.take<int>((size_t)nb6), a_nfree = L.take<int>(1); const auto a_st = L.take<LmState>(1);
+    const size_t in_end = L.mark();
+    const auto a_r = L.take<double>(7*NE), a_J1 = L.take<double>(49*NE), a_J2 = L.take<double>(49*NE), a_ce = L.take<double>(NE), a_cce = L.take<double>(NE), a_qe = L.take<double>(NE),
+               a_sc = L.take<double>(N6), a_part = L.take<double>(4*NF), a_g = L.take<double>(N6), a_dp = L.take<double>(N6), a_Sy = L.take<double>(N6),
+               a_LD = L.take<double>((size_t)std::max(n6, 32*nb6)); const auto a_dbg = L.take<long long>(64); const auto a_S = L.take<double>((N6 + 1)*N6);
+    CKL(grow_pinned(c->h_stage, c->h_cap, in_end)); CKL(grow_device(c->d_buf, c->d_cap, L.mark()));
+    void *h = c->h_stage, *d = c->d_buf;
+    a_x0.put(h, p->pose); a_x1.put(h, p->pose); a_fidx.put(h, fidx.data()); a_free.put(h, free_kf.data());
+    a_ei.put(h, p->edge_i); a_ej.put(h, p->edge_j); a_meas.put(h, p->meas); a_kfoff.put(h, kf_off.data()); a_poff.put(h, pair_off.data());
+    std::copy(kf_inc.begin(), kf_inc.end(), a_kfinc.at(h)); std::copy(pair_a.begin(), pair_a.end(), a_pa.at(h)); std::copy(pair_b.begin(), pair_b.end(), a_pb.at(h));
+    std::copy(pair_e.begin(), pair_e.end(), a_pe.at(h));
+    { int *sf = a_sfidx.at(h); for (int k = 0; k < nb6; k++) sf[k] = k; *a_nfree.at(h) = nb6; }
     LmState st0; memset(&st0, 0, sizeof(st0));
     st0.first = 1; st0.need_lin = 1; st0.max_it = o->max_it; st0.radius = o->initial_radius; st0.decrease_factor = 2.0;
-    memcpy(h + o_st, &st0, sizeof(st0));
-    CKL(hipMemcpyAsync(d, h, o_host_end, hipMemcpyHostToDevice, c->stream));
+    a_st.put(h, &st0);
+    CKL(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));
     PgDev P; memset(&P, 0, sizeof(P));
     P.n_kf = N; P.n_edge = E; P.nf = nf; P.n = n; P.n6 = n6; P.npair = npair;
-    P.x[0] = (double *)(d + o_x0); P.x[1] = (double *)(d + o_x1); P.fidx_kf = (const int *)(d + o_fidx); P.free_kf = (const int *)(d + o_free);
-    P.ei = (const int *)(d + o_ei); P.ej = (const int *)(d + o_ej); P.meas = (const double *)(d + o_meas);
-    P.r = (double *)(d + o_r); P.J1 = (double *)(d + o_J1); P.J2 = (double *)(d + o_J2); P.cost_e = (double *)(d + o_ce); P.ccost_e = (double *)(d + o_cce); P.q_e = (double *)(d + o_qe);
-    P.kf_off = (const int *)(d + o_kfoff); P.kf_inc = (const int *)(d + o_kfinc); P.pair_a = (const int *)(d + o_pa); P.pair_b = (const int *)(d + o_pb);
-    P.pair_off = (const int *)(d + o_poff); P.pair_e = (const int *)(d + o_pe); P.sc = (double *)(d + o_sc); P.part = (double *)(d + o_part);
-    Work &W = P.W; W.N = n6; W.n_kf = nb6; W.S = (double *)(d + o_S); W.ldS = n6; W.Sy = (double *)(d + o_Sy); W.g = (double *)(d + o_g); W.dp = (double *)(d + o_dp);
-    W.LDbuf = (double *)(d + o_LD); W.fidx = (int *)(d + o_sfidx); W.nfree = (int *)(d + o_nfree); W.dbg = (long long *)(d + o_dbg); W.st = (LmState *)(d + o_st);
+    P.x[0] = a_x0.at(d); P.x[1] = a_x1.at(d); P.fidx_kf = a_fidx.at(d); P.free_kf = a_free.at(d); P.ei = a_ei.at(d); P.ej = a_ej.at(d); P.meas = a_meas.at(d);
+    P.r = a_r.at(d); P.J1 = a_J1.at(d); P.J2 = a_J2.at(d); P.cost_e = a_ce.at(d); P.ccost_e = a_cce.at(d); P.q_e = a_qe.at(d);
+    P.kf_off = a_kfoff.at(d); P.kf_inc = a_kfinc.at(d); P.pair_a = a_pa.at(d); P.pair_b = a_pb.at(d); P.pair_off = a_poff.at(d); P.pair_e = a_pe.at(d);
+    P.sc = a_sc.at(d); P.part = a_part.at(d);
+    Work &W = P.W; W.N = n6; W.n_kf = nb6; W.S = a_S.at(d); W.ldS = n6; W.Sy = a_Sy.at(d); W.g = a_g.at(d); W.dp = a_dp.at(d);
+    W.LDbuf = a_LD.at(d); W.fidx = a_sfidx.at(d); W.nfree = a_nfree.at(d); W.dbg = a_dbg.at(d); W.st = a_st.at(d);
     // ---- solver selection as in the BA library
     const size_t lds_small = solve_lds_doubles(n6)*sizeof(double);
     const bool use_lds = lds_solver_fits(n6);
@@ -624,10 +620,10 @@ int tsloop_optimize_loop(void *ctx, tsloop_graph_problem *p, const tsloop_option
         hipLaunchKernelGGL(k_pg_decide, dim3(1), dim3(1024), 0, c->stream, P, *o);
     }
     LmState st;
-    CKL(hipMemcpyAsync(h + o_st, d + o_st, sizeof(LmState), hipMemcpyDeviceToHost, c->stream));
+    CKL(hipMemcpyAsync(a_st.at(h), a_st.at(d), a_st.bytes(), hipMemcpyDeviceToHost, c->stream));
     CKL(hipStreamSynchronize(c->stream)); CKL(hipGetLastError());
-    memcpy(&st, h + o_st, sizeof(st));
-    CKL(hipMemcpy(p->pose, st.cur ? P.x[1] : P.x[0], 64*(size_t)N, hipMemcpyDeviceToHost));
+    a_st.get(h, &st);
+    CKL(hipMemcpy(p->pose, st.cur ? P.x[1] : P.x[0], a_x0.bytes(), hipMemcpyDeviceToHost));
     r->iters = st.it; r->accepted = st.accepted; r->termination = st.term; r->cost0 = st.cost0; r->cost1 = st.x_cost;
     r->t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return st.term == 5 ? TSLOOP_ERR_NUMERIC : TSLOOP_OK;

@@ -1474,6 +1474,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
 #include "tstwoview_rec.h"
 #include "tstexttheta.h"
 #include "tsclaim.h"
+#include "tsstage.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -1494,6 +1495,7 @@ struct OCtx {
     int key[5] = {0, 0, 0, 0, 0}; uint8_t *h_img = nullptr; void *h_out = nullptr; size_t h_img_sz = 0, h_out_sz = 0;
 };
 static int cv_round_f(float v) { return (int)lrintf(v); }
+template <class T> static bool all_finite(const T *v, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; }
 #define OCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); return TSORB_ERR_DEVICE; } } while (0)
 template <typename T> static int oalloc(OCtx *c, T **p, size_t n) { void *q = nullptr; if (hipMalloc(&q, std::max<size_t>(n, 1)*sizeof(T)) != hipSuccess) { c->err = "hipMalloc failed"; return TSORB_ERR_DEVICE; }
     c->allocs.push_back(q); *p = (T *)q; return 0; }
@@ -1903,18 +1905,20 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
 }
 
 // ---- loopClosing::SearchMatch: every loop candidate's all-pairs matching (tsbrute.h).  Both calls need only a context: the resident batch and the match
-// grid are not touched.  One pinned block up ([in]), one device block ([in | scratch | out]), one pinned block down ([out]).
-static size_t br_al(size_t n) { return (n + 15) & ~(size_t)15; }
-static int br_room(OCtx *c, size_t dev, size_t pin) {
-    if (c->br_dev_cap < dev) { if (c->br_dev) hipFree(c->br_dev); c->br_dev = nullptr; c->br_dev_cap = 0; OCK(hipMalloc(&c->br_dev, dev)); c->br_dev_cap = dev; }
-    if (c->br_pin_cap < pin) { if (c->br_pin) hipHostFree(c->br_pin); c->br_pin = nullptr; c->br_pin_cap = 0; OCK(hipHostMalloc(&c->br_pin, pin, hipHostMallocDefault)); c->br_pin_cap = pin; }
-    return TSORB_OK;
-}
+// grid are not touched.  One pinned block up ([in]), one device block ([in | scratch | out]), one pinned block down ([out]).  Every call from here to the end of the
+// file lays its sub-arrays out with tsstage.h: the takes beneath a call's layout comment are that layout.
 // an offset array: starts at 0, never decreases, no set above TSORB_BRUTE_MAX_FEAT (limit < 0: no limit)
 static const char *br_offsets(const int32_t *off, int n, int limit) {
     if (off[0] != 0) return "an offset array does not start at 0";
     for (int i = 0; i < n; i++) { if (off[i + 1] < off[i]) return "an offset array decreases";
         if (limit >= 0 && off[i + 1] - off[i] > limit) return "a set has more than TSORB_BRUTE_MAX_FEAT features"; }
+    return nullptr;
+}
+// caller-drawn subsets of k indices each: every index in [0, n), none twice in its subset
+static const char *br_subsets(const int32_t *subset, size_t n_hyp, int k, int n) {
+    for (size_t h = 0; h < n_hyp; h++) { const int32_t *s = subset + k*h;
+        for (int i = 0; i < k; i++) { if (s[i] < 0 || s[i] >= n) return "a subset index outside [0, n)";
+            for (int j = 0; j < i; j++) if (s[j] == s[i]) return "an index twice in a subset"; } }
     return nullptr;
 }
 int tsorb_match_brute_text(void *ctx, int n_pair, const int32_t *off1, const uint8_t *desc1, const int32_t *off2, const uint8_t *desc2,
@@ -1933,26 +1937,27 @@ int tsorb_match_brute_text(void *ctx, int n_pair, const int32_t *off1, const uin
     size_t ntile = 0;
     for (int p = 0; p < n_pair; p++) ntile += ((size_t)(off1[p + 1] - off1[p]) + BR_T - 1)/BR_T;
     // in: [off1 | off2 | tiles | pmin | desc1 | desc2]   out: [train | dist | good]
-    const size_t b_off = br_al(4*((size_t)n_pair + 1)), b_tile = br_al(8*ntile), b_pmin = br_al(4*(size_t)n_pair), b_d1 = br_al(32*nq), b_d2 = br_al(32*nt);
-    const size_t in_sz = 2*b_off + b_tile + b_pmin + b_d1 + b_d2, b_i = br_al(4*nq), out_sz = 2*b_i + br_al(nq);
-    if (int rc = br_room(c, in_sz + out_sz, in_sz + out_sz)) return rc;
-    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
-    memcpy(h, off1, 4*((size_t)n_pair + 1)); memcpy(h + b_off, off2, 4*((size_t)n_pair + 1));
-    { int32_t *t = (int32_t *)(h + 2*b_off); size_t k = 0;
+    Layout L(16);
+    const auto a_off1 = L.take<int32_t>((size_t)n_pair + 1), a_off2 = L.take<int32_t>((size_t)n_pair + 1), a_tile = L.take<int32_t>(2*ntile), a_pmin = L.take<int32_t>((size_t)n_pair);
+    const auto a_d1 = L.take<uint8_t>(32*nq), a_d2 = L.take<uint8_t>(32*nt);
+    const size_t in_sz = L.mark();
+    const auto a_train = L.take<int32_t>(nq), a_dist = L.take<int32_t>(nq); const auto a_good = L.take<uint8_t>(nq);
+    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
+    void *h = c->br_pin, *d = c->br_dev;
+    a_off1.put(h, off1); a_off2.put(h, off2);
+    { int32_t *t = a_tile.at(h); size_t k = 0;
       for (int p = 0; p < n_pair; p++) for (int q0 = off1[p]; q0 < off1[p + 1]; q0 += BR_T) { t[2*k] = p; t[2*k + 1] = q0; k++; }
-      int32_t *pm = (int32_t *)(h + 2*b_off + b_tile); for (int p = 0; p < n_pair; p++) pm[p] = INT32_MAX; }
-    memcpy(h + 2*b_off + b_tile + b_pmin, desc1, 32*nq);
-    if (nt) memcpy(h + 2*b_off + b_tile + b_pmin + b_d1, desc2, 32*nt);
+      int32_t *pm = a_pmin.at(h); for (int p = 0; p < n_pair; p++) pm[p] = INT32_MAX; }
+    a_d1.put(h, desc1); a_d2.put(h, desc2);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
     BruteText B;
-    B.off1 = (const int *)d; B.off2 = (const int *)(d + b_off); B.tile = (const int2 *)(d + 2*b_off); B.pmin = (int *)(d + 2*b_off + b_tile);
-    B.desc1 = (const uint8_t *)(d + 2*b_off + b_tile + b_pmin); B.desc2 = B.desc1 + b_d1;
-    B.train = (int *)(d + in_sz); B.dist = (int *)(d + in_sz + b_i); B.good = (uint8_t *)(d + in_sz + 2*b_i);
+    B.off1 = a_off1.at(d); B.off2 = a_off2.at(d); B.tile = (const int2 *)a_tile.at(d); B.pmin = a_pmin.at(d); B.desc1 = a_d1.at(d); B.desc2 = a_d2.at(d);
+    B.train = a_train.at(d); B.dist = a_dist.at(d); B.good = a_good.at(d);
     hipLaunchKernelGGL(k_brute_text, dim3((unsigned)ntile), dim3(BR_T), 0, c->stream, B);
     hipLaunchKernelGGL(k_brute_good, dim3((unsigned)ntile), dim3(BR_T), 0, c->stream, B);
-    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipMemcpyAsync(a_train.at(h), a_train.at(d), L.mark() - in_sz, hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    memcpy(train_idx, h + in_sz, 4*nq); memcpy(dist, h + in_sz + b_i, 4*nq); memcpy(good, h + in_sz + 2*b_i, nq);
+    a_train.get(h, train_idx); a_dist.get(h, dist); a_good.get(h, good);
     return TSORB_OK;
 }
 
@@ -1973,41 +1978,37 @@ int tsorb_match_brute_scene(void *ctx, int w, int h, int n1, const float *xy1, c
     if (const char *m = br_offsets(qoff, n_cand, -1)) return bad(m);
     const size_t N2 = (size_t)off2[n_cand], NQ = (size_t)qoff[n_cand], N1 = (size_t)n1;
     if ((N1 > 0 && (!xy1 || !desc1 || !has3d1 || !match12)) || (N2 > 0 && (!xy2 || !desc2 || !has3d2)) || (NQ > 0 && (!quad_cur || !quad_can))) return bad("NULL pointer");
-    for (size_t i = 0; i < 2*N1; i++) if (!std::isfinite(xy1[i])) return bad("a coordinate is not finite");
-    for (size_t i = 0; i < 2*N2; i++) if (!std::isfinite(xy2[i])) return bad("a coordinate is not finite");
+    if (!all_finite(xy1, 2*N1) || !all_finite(xy2, 2*N2)) return bad("a coordinate is not finite");
     for (size_t i = 0; i < 8*NQ; i++) if (!std::isfinite(quad_cur[i]) || fabs(quad_cur[i]) > 1073741824.0 || !std::isfinite(quad_can[i]) || fabs(quad_can[i]) > 1073741824.0)
         return bad("quad coordinate not finite (or beyond 2^30)");
     if (n1 == 0) { for (int k = 0; k < n_cand; k++) n_match[k] = 0; return TSORB_OK; }
     hipSetDevice(c->device);
     // in: [off2 | qoff | quad_cur | quad_can | xy1 | xy2 | desc1 | desc2 | has3d1 | has3d2]   scratch: [md | own]   out: [match12 | n_match]
-    const size_t b_off = br_al(4*((size_t)n_cand + 1)), b_q = br_al(32*NQ), b_xy1 = br_al(8*N1), b_xy2 = br_al(8*N2), b_d1 = br_al(32*N1), b_d2 = br_al(32*N2),
-                 b_h1 = br_al(N1), b_h2 = br_al(N2);
-    const size_t in_sz = 2*b_off + 2*b_q + b_xy1 + b_xy2 + b_d1 + b_d2 + b_h1 + b_h2, b_md = br_al(4*N2), b_m12 = br_al(4*N1*(size_t)n_cand), out_sz = b_m12 + br_al(4*(size_t)n_cand);
-    if (int rc = br_room(c, in_sz + 2*b_md + out_sz, in_sz + out_sz)) return rc;
-    char *hp = (char *)c->br_pin, *d = (char *)c->br_dev;
-    size_t o = 0;
-    const size_t o_off2 = o; memcpy(hp + o, off2, 4*((size_t)n_cand + 1)); o += b_off;
-    const size_t o_qoff = o; memcpy(hp + o, qoff, 4*((size_t)n_cand + 1)); o += b_off;
-    const size_t o_qcur = o; for (size_t i = 0; i < 8*NQ; i++) ((int32_t *)(hp + o))[i] = (int)quad_cur[i]; o += b_q;          // cv::Point(double, double): truncation
-    const size_t o_qcan = o; for (size_t i = 0; i < 8*NQ; i++) ((int32_t *)(hp + o))[i] = (int)quad_can[i]; o += b_q;
-    const size_t o_xy1 = o; memcpy(hp + o, xy1, 8*N1); o += b_xy1;
-    const size_t o_xy2 = o; if (N2) memcpy(hp + o, xy2, 8*N2); o += b_xy2;
-    const size_t o_d1 = o; memcpy(hp + o, desc1, 32*N1); o += b_d1;
-    const size_t o_d2 = o; if (N2) memcpy(hp + o, desc2, 32*N2); o += b_d2;
-    const size_t o_h1 = o; memcpy(hp + o, has3d1, N1); o += b_h1;
-    const size_t o_h2 = o; if (N2) memcpy(hp + o, has3d2, N2); o += b_h2;
+    Layout L(16);
+    const auto a_off2 = L.take<int32_t>((size_t)n_cand + 1), a_qoff = L.take<int32_t>((size_t)n_cand + 1), a_qcur = L.take<int32_t>(8*NQ), a_qcan = L.take<int32_t>(8*NQ);
+    const auto a_xy1 = L.take<float>(2*N1), a_xy2 = L.take<float>(2*N2);
+    const auto a_d1 = L.take<uint8_t>(32*N1), a_d2 = L.take<uint8_t>(32*N2), a_h1 = L.take<uint8_t>(N1), a_h2 = L.take<uint8_t>(N2);
+    const size_t in_sz = L.mark();
+    const auto a_md = L.take<int32_t>(N2), a_own = L.take<int32_t>(N2);
+    Layout Lo(16);                                                              // the outputs, a layout of their own: behind the scratch on the device, behind the inputs in the pinned block
+    const auto a_m12 = Lo.take<int32_t>(N1*(size_t)n_cand), a_nm = Lo.take<int32_t>((size_t)n_cand);
+    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark() + Lo.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, in_sz + Lo.mark()));
+    void *hp = c->br_pin, *d = c->br_dev, *ho = (char *)hp + in_sz, *dout = (char *)d + L.mark();
+    a_off2.put(hp, off2); a_qoff.put(hp, qoff);
+    { int32_t *cur = a_qcur.at(hp), *can = a_qcan.at(hp);
+      for (size_t i = 0; i < a_qcur.n; i++) { cur[i] = (int)quad_cur[i]; can[i] = (int)quad_can[i]; } }          // cv::Point(double, double): truncation
+    a_xy1.put(hp, xy1); a_xy2.put(hp, xy2); a_d1.put(hp, desc1); a_d2.put(hp, desc2); a_h1.put(hp, has3d1); a_h2.put(hp, has3d2);
     OCK(hipMemcpyAsync(d, hp, in_sz, hipMemcpyHostToDevice, c->stream));
     BruteScene S;
     S.w = w; S.h = h; S.n1 = n1; S.th_low = th_low; S.ratio = ratio;
-    S.xy1 = (const float *)(d + o_xy1); S.desc1 = (const uint8_t *)(d + o_d1); S.has3d1 = (const uint8_t *)(d + o_h1);
-    S.off2 = (const int *)(d + o_off2); S.xy2 = (const float *)(d + o_xy2); S.desc2 = (const uint8_t *)(d + o_d2); S.has3d2 = (const uint8_t *)(d + o_h2);
-    S.qoff = (const int *)(d + o_qoff); S.quad_cur = (const int *)(d + o_qcur); S.quad_can = (const int *)(d + o_qcan);
-    S.md = (int *)(d + in_sz); S.own = (int *)(d + in_sz + b_md);
-    S.match12 = (int *)(d + in_sz + 2*b_md); S.n_match = (int *)(d + in_sz + 2*b_md + b_m12);
+    S.xy1 = a_xy1.at(d); S.desc1 = a_d1.at(d); S.has3d1 = a_h1.at(d);
+    S.off2 = a_off2.at(d); S.xy2 = a_xy2.at(d); S.desc2 = a_d2.at(d); S.has3d2 = a_h2.at(d);
+    S.qoff = a_qoff.at(d); S.quad_cur = a_qcur.at(d); S.quad_can = a_qcan.at(d);
+    S.md = a_md.at(d); S.own = a_own.at(d); S.match12 = a_m12.at(dout); S.n_match = a_nm.at(dout);
     hipLaunchKernelGGL(k_brute_scene, dim3(n_cand), dim3(BR_T), 0, c->stream, S);
-    OCK(hipMemcpyAsync(hp + in_sz, d + in_sz + 2*b_md, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipMemcpyAsync(ho, dout, Lo.mark(), hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    memcpy(match12, hp + in_sz, 4*N1*(size_t)n_cand); memcpy(n_match, hp + in_sz + b_m12, 4*(size_t)n_cand);
+    a_m12.get(ho, match12); a_nm.get(ho, n_match);
     return TSORB_OK;
 }
 
@@ -2028,7 +2029,7 @@ int tsorb_match_search_sets(void *ctx, int n_set, const int32_t *foff, const flo
     const size_t F = (size_t)foff[n_set], NQ = (size_t)nq, ND = (size_t)n_qdesc;
     if (F > 0 && (!kp6 || !desc)) return bad("NULL pointer");
     for (int s = 0; s < n_set; s++) { const double *b = bounds + 4*(size_t)s;
-        if (!std::isfinite(b[0]) || !std::isfinite(b[1]) || !std::isfinite(b[2]) || !std::isfinite(b[3])) return bad("bounds not finite");
+        if (!all_finite(b, 4)) return bad("bounds not finite");
         if (!(b[1] > b[0]) || !(b[3] > b[2])) return bad("bounds with max <= min"); }
     if (!qdi && n_qdesc != nq) return bad("qdi NULL with n_qdesc != nq");
     for (size_t q = 0; q < NQ; q++) {
@@ -2037,41 +2038,38 @@ int tsorb_match_search_sets(void *ctx, int n_set, const int32_t *foff, const flo
         if (!std::isfinite(qxy[2*q]) || !std::isfinite(qxy[2*q + 1]) || !std::isfinite(qr[q])) return bad("a query coordinate or radius is not finite");
     }
     hipSetDevice(c->device);
-    const size_t b_off = br_al(4*((size_t)n_set + 1)), b_grid = br_al(32*(size_t)n_set), b_kp = br_al(24*F), b_desc = br_al(32*F), b_qd = br_al(32*ND), up_sz = b_off + b_grid + b_kp + b_desc + b_qd;
-    const size_t b_cell = br_al(4*(size_t)n_set*(MG_CELLS + 1)), b_list = br_al(4*F);
-    const size_t b_xy = br_al(8*NQ), b_i = br_al(4*NQ), q_sz = b_xy + b_i + 2*b_i + b_i + b_i, b_c = br_al(4*NQ*(size_t)max_cand), out_sz = 2*b_c + 4*b_i;
-    if (int rc = br_room(c, up_sz + b_cell + b_list, up_sz + q_sz + out_sz)) return rc;
-    char *h = (char *)c->br_pin, *d = (char *)c->br_dev, *hq = h + up_sz, *ho = hq + q_sz;
-    memcpy(h, foff, 4*((size_t)n_set + 1));
-    { double *g = (double *)(h + b_off);
+    // up: [foff | grid | kp | desc | qdesc]   behind it on the device: [off | list]   behind it in the pinned block: queries [qxy | qr | qlev | qset | qdi],
+    // results [cand_idx | cand_dist | cand_cnt | best_idx | best_dist | best_dist2]
+    Layout L(16);
+    const auto a_foff = L.take<int32_t>((size_t)n_set + 1); const auto a_grid = L.take<double>(4*(size_t)n_set); const auto a_kp = L.take<float>(6*F);
+    const auto a_desc = L.take<uint8_t>(32*F), a_qd = L.take<uint8_t>(32*ND);
+    const size_t up_sz = L.mark();
+    Layout Ld = L;
+    const auto a_off = Ld.take<int32_t>((size_t)n_set*(MG_CELLS + 1)), a_list = Ld.take<int32_t>(F);
+    const auto a_qxy = L.take<float>(2*NQ), a_qr = L.take<float>(NQ); const auto a_lev = L.take<int32_t>(2*NQ), a_set = L.take<int32_t>(NQ), a_di = L.take<int32_t>(NQ);
+    const auto a_ci = L.take<int32_t>(NQ*(size_t)max_cand), a_cd = L.take<int32_t>(NQ*(size_t)max_cand), a_cc = L.take<int32_t>(NQ), a_bi = L.take<int32_t>(NQ),
+               a_bd = L.take<int32_t>(NQ), a_bd2 = L.take<int32_t>(NQ);
+    OCK(grow_device(c->br_dev, c->br_dev_cap, Ld.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
+    void *h = c->br_pin, *d = c->br_dev;
+    a_foff.put(h, foff);
+    { double *g = a_grid.at(h);
       for (int s = 0; s < n_set; s++) { const double *b = bounds + 4*(size_t)s; g[4*s] = b[0]; g[4*s + 1] = b[2];
           g[4*s + 2] = (double)MG_COLS/(b[1] - b[0]); g[4*s + 3] = (double)MG_ROWS/(b[3] - b[2]); } }                 // frame.cc:124-125, as match_build
-    if (F) { memcpy(h + b_off + b_grid, kp6, 24*F); memcpy(h + b_off + b_grid + b_kp, desc, 32*F); }
-    memcpy(h + b_off + b_grid + b_kp + b_desc, qdesc, 32*ND);
-    memcpy(hq, qxy, 8*NQ); memcpy(hq + b_xy, qr, 4*NQ);
-    { int32_t *lev = (int32_t *)(hq + b_xy + b_i), *st = lev + b_i/2, *di = st + b_i/4;
-      if (qlev) memcpy(lev, qlev, 8*NQ); else for (size_t k = 0; k < 2*NQ; k++) lev[k] = -1;
-      memcpy(st, qset, 4*NQ);
-      if (qdi) memcpy(di, qdi, 4*NQ); else for (size_t k = 0; k < NQ; k++) di[k] = (int32_t)k; }
+    a_kp.put(h, kp6); a_desc.put(h, desc); a_qd.put(h, qdesc);
+    a_qxy.put(h, qxy); a_qr.put(h, qr); a_set.put(h, qset);
+    if (qlev) a_lev.put(h, qlev); else std::fill_n(a_lev.at(h), a_lev.n, -1);
+    if (qdi) a_di.put(h, qdi); else for (size_t k = 0; k < NQ; k++) a_di.at(h)[k] = (int32_t)k;
     OCK(hipMemcpyAsync(d, h, up_sz, hipMemcpyHostToDevice, c->stream));
-    char *pq = nullptr; { void *hd = nullptr; OCK(hipHostGetDevicePointer(&hd, c->br_pin, 0)); pq = (char *)hd + up_sz; }
-    char *po = pq + q_sz;
+    void *p = nullptr; OCK(hipHostGetDevicePointer(&p, c->br_pin, 0));          // the search kernel reads the queries from, and stores the results into, the pinned block
     WindowSets W;
     W.n_set = n_set; W.nq = nq; W.max_cand = max_cand;
-    W.foff = (const int *)d; W.grid = (const double *)(d + b_off); W.kp = (const float *)(d + b_off + b_grid); W.desc = (const uint8_t *)(d + b_off + b_grid + b_kp);
-    W.qdesc = (const uint8_t *)(d + b_off + b_grid + b_kp + b_desc); W.off = (int *)(d + up_sz); W.list = (int *)(d + up_sz + b_cell);
-    W.qxy = (const float *)pq; W.qr = (const float *)(pq + b_xy); W.qlev = (const int *)(pq + b_xy + b_i); W.qset = (const int *)(pq + b_xy + 3*b_i); W.qdi = (const int *)(pq + b_xy + 4*b_i);
-    W.cand_idx = (int *)po; W.cand_dist = (int *)(po + b_c); W.cand_cnt = (int *)(po + 2*b_c); W.best_idx = (int *)(po + 2*b_c + b_i); W.best_dist = (int *)(po + 2*b_c + 2*b_i);
-    W.best_dist2 = (int *)(po + 2*b_c + 3*b_i);
+    W.foff = a_foff.at(d); W.grid = a_grid.at(d); W.kp = a_kp.at(d); W.desc = a_desc.at(d); W.qdesc = a_qd.at(d); W.off = a_off.at(d); W.list = a_list.at(d);
+    W.qxy = a_qxy.at(p); W.qr = a_qr.at(p); W.qlev = a_lev.at(p); W.qset = a_set.at(p); W.qdi = a_di.at(p);
+    W.cand_idx = a_ci.at(p); W.cand_dist = a_cd.at(p); W.cand_cnt = a_cc.at(p); W.best_idx = a_bi.at(p); W.best_dist = a_bd.at(p); W.best_dist2 = a_bd2.at(p);
     hipLaunchKernelGGL(k_ws_grid, dim3(n_set), dim3(WS_T), 0, c->stream, W);
     hipLaunchKernelGGL(k_ws_match, dim3((nq + WS_T/64 - 1)/(WS_T/64)), dim3(WS_T), 0, c->stream, W);
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    if (cand_idx) memcpy(cand_idx, ho, 4*NQ*(size_t)max_cand);
-    if (cand_dist) memcpy(cand_dist, ho + b_c, 4*NQ*(size_t)max_cand);
-    if (cand_cnt) memcpy(cand_cnt, ho + 2*b_c, 4*NQ);
-    if (best_idx) memcpy(best_idx, ho + 2*b_c + b_i, 4*NQ);
-    if (best_dist) memcpy(best_dist, ho + 2*b_c + 2*b_i, 4*NQ);
-    if (best_dist2) memcpy(best_dist2, ho + 2*b_c + 3*b_i, 4*NQ);
+    a_ci.get(h, cand_idx); a_cd.get(h, cand_dist); a_cc.get(h, cand_cnt); a_bi.get(h, best_idx); a_bd.get(h, best_dist); a_bd2.get(h, best_dist2);
     return TSORB_OK;
 }
 
@@ -2087,38 +2085,34 @@ int tsorb_match_pnp_ransac(void *ctx, int n, const float *Pw, const float *uv, c
     if (!Pw || !uv || !K || !subset || !inlier || !result) return bad("NULL pointer");
     if (!std::isfinite(reproj_err) || !(reproj_err > 0.0)) return bad("reproj_err not finite or <= 0");
     if (!(confidence >= 0.0 && confidence <= 1.0)) return bad("confidence outside [0, 1]");
-    for (int i = 0; i < 4; i++) if (!std::isfinite(K[i])) return bad("K is not finite");
+    if (!all_finite(K, 4)) return bad("K is not finite");
     const size_t N = (size_t)n, H = (size_t)n_hyp;
-    for (size_t i = 0; i < 3*N; i++) if (!std::isfinite(Pw[i])) return bad("a point is not finite");
-    for (size_t i = 0; i < 2*N; i++) if (!std::isfinite(uv[i])) return bad("a pixel is not finite");
-    for (size_t h = 0; h < H; h++) { const int32_t *s = subset + 5*h;
-        for (int i = 0; i < 5; i++) { if (s[i] < 0 || s[i] >= n) return bad("a subset index outside [0, n)");
-            for (int j = 0; j < i; j++) if (s[j] == s[i]) return bad("an index twice in a subset"); } }
+    if (!all_finite(Pw, 3*N)) return bad("a point is not finite");
+    if (!all_finite(uv, 2*N)) return bad("a pixel is not finite");
+    if (const char *m = br_subsets(subset, H, 5, n)) return bad(m);
     hipSetDevice(c->device);
-    const size_t b_pw = br_al(12*N), b_uv = br_al(8*N), b_sub = br_al(20*H), in_sz = b_pw + b_uv + b_sub;
-    const size_t b_res = br_al(16), b_pose = br_al(96), b_cnt = br_al(4*H), b_hp = br_al(96*H), out_sz = b_res + b_pose + b_cnt + b_hp + br_al(N);
-    if (int rc = br_room(c, in_sz + out_sz, in_sz + out_sz)) return rc;
-    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
-    memcpy(h, Pw, 12*N); memcpy(h + b_pw, uv, 8*N); memcpy(h + b_pw + b_uv, subset, 20*H);
+    // in: [Pw | uv | subset]   out: [result | pose | count | hyp_pose | inlier]
+    Layout L(16);
+    const auto a_pw = L.take<float>(3*N), a_uv = L.take<float>(2*N); const auto a_sub = L.take<int32_t>(5*H);
+    const size_t in_sz = L.mark();
+    const auto a_res = L.take<int32_t>(4); const auto a_pose = L.take<double>(12); const auto a_cnt = L.take<int32_t>(H); const auto a_hp = L.take<double>(12*H);
+    const auto a_inl = L.take<uint8_t>(N);
+    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
+    void *h = c->br_pin, *d = c->br_dev;
+    a_pw.put(h, Pw); a_uv.put(h, uv); a_sub.put(h, subset);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
     PnpDev D;
-    D.n = n; D.n_hyp = n_hyp; D.Pw = (const float *)d; D.uv = (const float *)(d + b_pw); D.subset = (const int32_t *)(d + b_pw + b_uv);
+    D.n = n; D.n_hyp = n_hyp; D.Pw = a_pw.at(d); D.uv = a_uv.at(d); D.subset = a_sub.at(d);
     for (int i = 0; i < 4; i++) D.K[i] = K[i];
     D.thr = (float)(reproj_err*reproj_err); D.confidence = confidence;
-    D.result = (int32_t *)(d + in_sz); D.pose = (double *)(d + in_sz + b_res); D.count = (int32_t *)(d + in_sz + b_res + b_pose);
-    D.hyp_pose = (double *)(d + in_sz + b_res + b_pose + b_cnt); D.inlier = (uint8_t *)(d + in_sz + b_res + b_pose + b_cnt + b_hp);
+    D.result = a_res.at(d); D.pose = a_pose.at(d); D.count = a_cnt.at(d); D.hyp_pose = a_hp.at(d); D.inlier = a_inl.at(d);
     const unsigned nb = (unsigned)((n + PNP_T - 1)/PNP_T);
     hipLaunchKernelGGL(k_pnp_hyp, dim3((n_hyp + PNP_NW - 1)/PNP_NW), dim3(PNP_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_pnp_count, dim3(nb), dim3(PNP_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_pnp_select, dim3(nb), dim3(PNP_T), 0, c->stream, D);
-    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipMemcpyAsync(a_res.at(h), a_res.at(d), L.mark() - in_sz, hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    const char *o = h + in_sz;
-    memcpy(result, o, 16);
-    if (pose) memcpy(pose, o + b_res, 96);
-    if (hyp_count) memcpy(hyp_count, o + b_res + b_pose, 4*H);
-    if (hyp_pose) memcpy(hyp_pose, o + b_res + b_pose + b_cnt, 96*H);
-    memcpy(inlier, o + b_res + b_pose + b_cnt + b_hp, N);
+    a_res.get(h, result); a_pose.get(h, pose); a_cnt.get(h, hyp_count); a_hp.get(h, hyp_pose); a_inl.get(h, inlier);
     return TSORB_OK;
 }
 
@@ -2134,37 +2128,38 @@ int tsorb_match_two_view_ransac(void *ctx, int n, const float *xy1, const float 
     if (n_hyp < 1 || n_hyp > TSORB_TWOVIEW_MAX_HYP) return bad("n_hyp outside [1, TSORB_TWOVIEW_MAX_HYP]");
     if (!xy1 || !xy2 || !norm1 || !norm2 || !subset || !inlier_h || !inlier_f || !H21 || !F21 || !score || !sel) return bad("NULL pointer");
     if (!std::isfinite(sigma) || !(sigma > 0.f)) return bad("sigma not finite or <= 0");
-    for (int i = 0; i < 4; i++) if (!std::isfinite(norm1[i]) || !std::isfinite(norm2[i])) return bad("a norm entry is not finite");
+    if (!all_finite(norm1, 4) || !all_finite(norm2, 4)) return bad("a norm entry is not finite");
     if (!(norm1[2] > 0.f) || !(norm1[3] > 0.f) || !(norm2[2] > 0.f) || !(norm2[3] > 0.f)) return bad("a norm scale <= 0");
     const size_t N = (size_t)n, H = (size_t)n_hyp;
-    for (size_t i = 0; i < 2*N; i++) if (!std::isfinite(xy1[i]) || !std::isfinite(xy2[i])) return bad("a coordinate is not finite");
-    for (size_t h = 0; h < H; h++) { const int32_t *s = subset + 8*h;
-        for (int i = 0; i < 8; i++) { if (s[i] < 0 || s[i] >= n) return bad("a subset index outside [0, n)");
-            for (int j = 0; j < i; j++) if (s[j] == s[i]) return bad("an index twice in a subset"); } }
+    if (!all_finite(xy1, 2*N) || !all_finite(xy2, 2*N)) return bad("a coordinate is not finite");
+    if (const char *m = br_subsets(subset, H, 8, n)) return bad(m);
     hipSetDevice(c->device);
-    const size_t b_xy = br_al(8*N), b_sub = br_al(32*H), in_sz = 2*b_xy + b_sub;
-    const size_t b_res = br_al(16), b_mdl = br_al(72), b_hs = br_al(8*H), b_hm = br_al(72*H), b_inl = br_al(N), out_sz = b_res + b_mdl + b_hs + b_hm + 2*b_inl;
-    if (int rc = br_room(c, in_sz + out_sz, in_sz + out_sz)) return rc;
-    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
-    memcpy(h, xy1, 8*N); memcpy(h + b_xy, xy2, 8*N); memcpy(h + 2*b_xy, subset, 32*H);
+    // in: [xy1 | xy2 | subset]   out: [sel, score | H21, F21 | hyp_score | hyp_model | inlier_h | inlier_f]
+    struct Pick { int32_t sel[2]; float score[2]; }; struct Models { float H21[9], F21[9]; };
+    Layout L(16);
+    const auto a_xy1 = L.take<float>(2*N), a_xy2 = L.take<float>(2*N); const auto a_sub = L.take<int32_t>(8*H);
+    const size_t in_sz = L.mark();
+    const auto a_pick = L.take<Pick>(1); const auto a_mdl = L.take<Models>(1); const auto a_hs = L.take<float>(2*H), a_hm = L.take<float>(18*H);
+    const auto a_ih = L.take<uint8_t>(N), a_if = L.take<uint8_t>(N);
+    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
+    void *h = c->br_pin, *d = c->br_dev;
+    a_xy1.put(h, xy1); a_xy2.put(h, xy2); a_sub.put(h, subset);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
-    TvDev D; char *o = d + in_sz;
-    D.n = n; D.n_hyp = n_hyp; D.xy1 = (const float *)d; D.xy2 = (const float *)(d + b_xy); D.subset = (const int32_t *)(d + 2*b_xy);
+    TvDev D;
+    D.n = n; D.n_hyp = n_hyp; D.xy1 = a_xy1.at(d); D.xy2 = a_xy2.at(d); D.subset = a_sub.at(d);
     for (int i = 0; i < 4; i++) { D.norm1[i] = norm1[i]; D.norm2[i] = norm2[i]; }
     D.sigma = sigma;
-    D.sel = (int32_t *)o; D.score = (float *)(o + 8); D.model = (float *)(o + b_res); D.hyp_score = (float *)(o + b_res + b_mdl); D.hyp_model = (float *)(o + b_res + b_mdl + b_hs);
-    D.inl_h = (uint8_t *)(o + b_res + b_mdl + b_hs + b_hm); D.inl_f = D.inl_h + b_inl;
+    D.sel = a_pick.at(d)->sel; D.score = a_pick.at(d)->score; D.model = a_mdl.at(d)->H21; D.hyp_score = a_hs.at(d); D.hyp_model = a_hm.at(d);
+    D.inl_h = a_ih.at(d); D.inl_f = a_if.at(d);
     const unsigned nb = (unsigned)((2*n_hyp + TV_NW - 1)/TV_NW);
     hipLaunchKernelGGL(k_tv_fit, dim3(2*(unsigned)n_hyp), dim3(64), 0, c->stream, D);
     hipLaunchKernelGGL(k_tv_score, dim3(nb), dim3(TV_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_tv_select, dim3(1), dim3(TV_T), 0, c->stream, D);
-    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipMemcpyAsync(a_pick.at(h), a_pick.at(d), L.mark() - in_sz, hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    const char *r = h + in_sz;
-    memcpy(sel, r, 8); memcpy(score, r + 8, 8); memcpy(H21, r + b_res, 36); memcpy(F21, r + b_res + 36, 36);
-    if (hyp_score) memcpy(hyp_score, r + b_res + b_mdl, 8*H);
-    if (hyp_model) memcpy(hyp_model, r + b_res + b_mdl + b_hs, 72*H);
-    memcpy(inlier_h, r + b_res + b_mdl + b_hs + b_hm, N); memcpy(inlier_f, r + b_res + b_mdl + b_hs + b_hm + b_inl, N);
+    const Pick *pick = a_pick.at(h); const Models *mdl = a_mdl.at(h);
+    memcpy(sel, pick->sel, sizeof pick->sel); memcpy(score, pick->score, sizeof pick->score); memcpy(H21, mdl->H21, sizeof mdl->H21); memcpy(F21, mdl->F21, sizeof mdl->F21);
+    a_hs.get(h, hyp_score); a_hm.get(h, hyp_model); a_ih.get(h, inlier_h); a_if.get(h, inlier_f);
     return TSORB_OK;
 }
 
@@ -2183,44 +2178,43 @@ int tsorb_match_two_view_reconstruct(void *ctx, int n, const float *xy1, const f
     if (!std::isfinite(sigma) || sigma < 0.f) return bad("sigma not finite or negative");
     if (!std::isfinite(min_parallax) || min_parallax < 0.f) return bad("min_parallax not finite or negative");
     if (min_triangulated < 0) return bad("min_triangulated negative");
-    for (int i = 0; i < 9; i++) if (!std::isfinite(M21[i])) return bad("an M21 entry is not finite");
-    for (int i = 0; i < 4; i++) if (!std::isfinite(K[i])) return bad("a K entry is not finite");
+    if (!all_finite(M21, 9)) return bad("an M21 entry is not finite");
+    if (!all_finite(K, 4)) return bad("a K entry is not finite");
     if (!(K[0] > 0.f) || !(K[1] > 0.f)) return bad("fx or fy not positive");
-    const size_t N = (size_t)n;
-    for (size_t i = 0; i < 2*N; i++) if (!std::isfinite(xy1[i]) || !std::isfinite(xy2[i])) return bad("a coordinate is not finite");
+    const size_t N = (size_t)n, NH = TSORB_TWOVIEW_REC_HYP;
+    if (!all_finite(xy1, 2*N) || !all_finite(xy2, 2*N)) return bad("a coordinate is not finite");
     hipSetDevice(c->device);
-    const size_t b_xy = br_al(8*N), b_n = br_al(N), in_sz = 2*b_xy + b_n;
-    const size_t b_res = br_al(24), b_rt = br_al(48), b_h8 = br_al(32), b_pose = br_al(4*12*TSORB_TWOVIEW_REC_HYP), b_p3d = br_al(12*N);
-    const size_t o_rt = b_res, o_good = o_rt + b_rt, o_cos = o_good + b_h8, o_par = o_cos + b_h8, o_pose = o_par + b_h8, o_p3d = o_pose + b_pose, o_tri = o_p3d + b_p3d;
-    const size_t o_state = o_tri + b_n, o_hp = o_state + br_al(8*N), out_sz = o_hp + br_al(96*N), o_cosall = out_sz, dev_sz = in_sz + o_cosall + br_al(32*N) + 16;
-    const size_t down = hyp_p3d ? out_sz : hyp_state ? o_hp : o_state;        // what the caller did not ask for stays on the device
-    if (int rc = br_room(c, dev_sz, in_sz + out_sz)) return rc;
-    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
-    memcpy(h, xy1, 8*N); memcpy(h + b_xy, xy2, 8*N); memcpy(h + 2*b_xy, inlier, N);
+    // in: [xy1 | xy2 | inlier]   out: [result | R21, t21 | hyp_good | hyp_cos | hyp_parallax | hyp_pose | p3d | triangulated | hyp_state | hyp_p3d]   scratch: [cosall | sv_exit]
+    struct Rt { float R21[9], t21[3]; };
+    Layout L(16);
+    const auto a_xy1 = L.take<float>(2*N), a_xy2 = L.take<float>(2*N); const auto a_inl = L.take<uint8_t>(N);
+    const size_t in_sz = L.mark();
+    const auto a_res = L.take<int32_t>(6); const auto a_rt = L.take<Rt>(1); const auto a_good = L.take<int32_t>(NH); const auto a_cos = L.take<float>(NH), a_par = L.take<float>(NH),
+               a_pose = L.take<float>(12*NH), a_p3d = L.take<float>(3*N); const auto a_tri = L.take<uint8_t>(N), a_state = L.take<uint8_t>(NH*N); const auto a_hp = L.take<float>(3*NH*N);
+    const size_t out_end = L.mark();
+    const auto a_cosall = L.take<float>(NH*N); const auto a_sv = L.take<int32_t>(4);
+    const size_t down = (hyp_p3d ? out_end : hyp_state ? a_hp.off : a_state.off) - in_sz;      // what the caller did not ask for stays on the device
+    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, out_end));
+    void *h = c->br_pin, *d = c->br_dev;
+    a_xy1.put(h, xy1); a_xy2.put(h, xy2); a_inl.put(h, inlier);
     int n_inl = 0; for (size_t i = 0; i < N; i++) n_inl += inlier[i] != 0;
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
-    RecDev D; char *o = d + in_sz;
-    D.n = n; D.model = model; D.n_inl = n_inl; D.min_tri = min_triangulated; D.xy1 = (const float *)d; D.xy2 = (const float *)(d + b_xy); D.inl = (const uint8_t *)(d + 2*b_xy);
+    RecDev D;
+    D.n = n; D.model = model; D.n_inl = n_inl; D.min_tri = min_triangulated; D.xy1 = a_xy1.at(d); D.xy2 = a_xy2.at(d); D.inl = a_inl.at(d);
     for (int i = 0; i < 9; i++) D.M[i] = M21[i];
     for (int i = 0; i < 4; i++) D.K[i] = K[i];
     D.sigma = sigma; D.min_par = min_parallax;
-    D.result = (int32_t *)o; D.R21 = (float *)(o + o_rt); D.t21 = D.R21 + 9; D.hyp_good = (int32_t *)(o + o_good); D.hyp_cos = (float *)(o + o_cos); D.hyp_par = (float *)(o + o_par);
-    D.hyp_pose = (float *)(o + o_pose); D.p3d = (float *)(o + o_p3d); D.tri = (uint8_t *)(o + o_tri); D.hyp_state = (uint8_t *)(o + o_state); D.hyp_p3d = (float *)(o + o_hp);
-    D.cosall = (float *)(o + o_cosall); D.sv_exit = (int32_t *)(o + o_cosall + br_al(32*N));
+    D.result = a_res.at(d); D.R21 = a_rt.at(d)->R21; D.t21 = a_rt.at(d)->t21; D.hyp_good = a_good.at(d); D.hyp_cos = a_cos.at(d); D.hyp_par = a_par.at(d);
+    D.hyp_pose = a_pose.at(d); D.p3d = a_p3d.at(d); D.tri = a_tri.at(d); D.hyp_state = a_state.at(d); D.hyp_p3d = a_hp.at(d); D.cosall = a_cosall.at(d); D.sv_exit = a_sv.at(d);
     const unsigned nb = (unsigned)((n + REC_T - 1)/REC_T);
     hipLaunchKernelGGL(k_rec_pairs, dim3(nb, model == 0 ? 8 : 4), dim3(REC_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_rec_stat, dim3(TSORB_TWOVIEW_REC_HYP), dim3(REC_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_rec_keep, dim3(nb), dim3(REC_T), 0, c->stream, D);
-    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, down, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipMemcpyAsync(a_res.at(h), a_res.at(d), down, hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    const char *r = h + in_sz;
-    memcpy(result, r, 24); memcpy(R21, r + o_rt, 36); memcpy(t21, r + o_rt + 36, 12); memcpy(p3d, r + o_p3d, 12*N); memcpy(triangulated, r + o_tri, N);
-    if (hyp_good) memcpy(hyp_good, r + o_good, 32);
-    if (hyp_cos) memcpy(hyp_cos, r + o_cos, 32);
-    if (hyp_parallax) memcpy(hyp_parallax, r + o_par, 32);
-    if (hyp_pose) memcpy(hyp_pose, r + o_pose, 4*12*TSORB_TWOVIEW_REC_HYP);
-    if (hyp_state) memcpy(hyp_state, r + o_state, 8*N);
-    if (hyp_p3d) memcpy(hyp_p3d, r + o_hp, 96*N);
+    const Rt *rt = a_rt.at(h);
+    a_res.get(h, result); memcpy(R21, rt->R21, sizeof rt->R21); memcpy(t21, rt->t21, sizeof rt->t21); a_p3d.get(h, p3d); a_tri.get(h, triangulated);
+    a_good.get(h, hyp_good); a_cos.get(h, hyp_cos); a_par.get(h, hyp_parallax); a_pose.get(h, hyp_pose); a_state.get(h, hyp_state); a_hp.get(h, hyp_p3d);
     return TSORB_OK;
 }
 
@@ -2249,35 +2243,30 @@ int tsorb_match_text_theta_ransac(void *ctx, int n_plane, const int32_t *off, co
             if (triple[e] < 0 || triple[e] >= n) return bad("a triple index of plane " + std::to_string(p) + " is outside the plane"); }
     if (n_plane == 0) return TSORB_OK;
     hipSetDevice(c->device);
-    const size_t b_off = br_al(4*(P + 1)), b_xy = br_al(8*N), b_rho = rho ? br_al(8*N) : 0, b_tri = br_al(12*H), in_sz = 2*b_off + 2*b_xy + b_rho + b_tri;
-    const size_t o_theta = br_al(4*P), o_score = o_theta + br_al(24*P), o_hs = o_score + br_al(8*P), o_ht = o_hs + br_al(8*H), o_rho = o_ht + br_al(24*H), o_p3d = o_rho + br_al(8*N),
-                 out_sz = o_p3d + br_al(12*N);
-    const size_t down = p3d ? out_sz : rho_out ? o_p3d : hyp_theta ? o_rho : hyp_score ? o_ht : o_hs;       // what the caller did not ask for stays on the device
-    if (int rc = br_room(c, in_sz + out_sz, in_sz + out_sz)) return rc;
-    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
-    const size_t i_xy1 = 2*b_off, i_xy2 = i_xy1 + b_xy, i_rho = i_xy2 + b_xy, i_tri = i_rho + b_rho;
-    memcpy(h, off, 4*(P + 1)); memcpy(h + b_off, hyp_off, 4*(P + 1));
-    if (N) { memcpy(h + i_xy1, host_xy, 8*N); memcpy(h + i_xy2, targ_xy, 8*N); if (rho) memcpy(h + i_rho, rho, 8*N); }
-    if (H) memcpy(h + i_tri, triple, 12*H);
+    // in: [off | hyp_off | host_xy | targ_xy | rho (if given) | triple]   out: [sel | theta | score | hyp_score | hyp_theta | rho_out | p3d]
+    Layout L(16);
+    const auto a_off = L.take<int32_t>(P + 1), a_hoff = L.take<int32_t>(P + 1); const auto a_hxy = L.take<float>(2*N), a_txy = L.take<float>(2*N);
+    const auto a_rin = L.take<double>(rho ? N : 0); const auto a_tri = L.take<int32_t>(3*H);
+    const size_t in_sz = L.mark();
+    const auto a_sel = L.take<int32_t>(P); const auto a_theta = L.take<double>(3*P), a_score = L.take<double>(P), a_hs = L.take<double>(H), a_ht = L.take<double>(3*H),
+               a_rho = L.take<double>(N); const auto a_p3d = L.take<float>(3*N);
+    const size_t down = (p3d ? L.mark() : rho_out ? a_p3d.off : hyp_theta ? a_rho.off : hyp_score ? a_ht.off : a_hs.off) - in_sz;    // what the caller did not ask for stays on the device
+    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
+    void *h = c->br_pin, *d = c->br_dev;
+    a_off.put(h, off); a_hoff.put(h, hyp_off); a_hxy.put(h, host_xy); a_txy.put(h, targ_xy); a_rin.put(h, rho); a_tri.put(h, triple);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
-    TtDev D; char *o = d + in_sz;
-    D.n_plane = n_plane; D.off = (const int32_t *)d; D.hyp_off = (const int32_t *)(d + b_off); D.host_xy = (const float *)(d + i_xy1); D.targ_xy = (const float *)(d + i_xy2);
-    D.rho_in = rho ? (const double *)(d + i_rho) : nullptr; D.triple = (const int32_t *)(d + i_tri);
+    TtDev D;
+    D.n_plane = n_plane; D.off = a_off.at(d); D.hyp_off = a_hoff.at(d); D.host_xy = a_hxy.at(d); D.targ_xy = a_txy.at(d);
+    D.rho_in = rho ? a_rin.at(d) : nullptr; D.triple = a_tri.at(d);
     for (int i = 0; i < 12; i++) D.T[i] = Tcr[i];
     for (int i = 0; i < 4; i++) D.K[i] = K[i];
-    D.sel = (int32_t *)o; D.theta = (double *)(o + o_theta); D.score = (double *)(o + o_score); D.hyp_score = (double *)(o + o_hs); D.hyp_theta = (double *)(o + o_ht);
-    D.rho = (double *)(o + o_rho); D.p3d = (float *)(o + o_p3d);
+    D.sel = a_sel.at(d); D.theta = a_theta.at(d); D.score = a_score.at(d); D.hyp_score = a_hs.at(d); D.hyp_theta = a_ht.at(d); D.rho = a_rho.at(d); D.p3d = a_p3d.at(d);
     if (N) hipLaunchKernelGGL(k_tt_rho, dim3((unsigned)((N + TT_T - 1)/TT_T)), dim3(TT_T), 0, c->stream, D, (int)N);
     if (H) hipLaunchKernelGGL(k_tt_score, dim3((unsigned)n_plane, (unsigned)((max_hyp + TT_T - 1)/TT_T)), dim3(TT_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_tt_select, dim3((unsigned)n_plane), dim3(64), 0, c->stream, D);
-    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, down, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipMemcpyAsync(a_sel.at(h), a_sel.at(d), down, hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    const char *r = h + in_sz;
-    memcpy(sel, r, 4*P); memcpy(theta, r + o_theta, 24*P); memcpy(score, r + o_score, 8*P);
-    if (hyp_score && H) memcpy(hyp_score, r + o_hs, 8*H);
-    if (hyp_theta && H) memcpy(hyp_theta, r + o_ht, 24*H);
-    if (rho_out && N) memcpy(rho_out, r + o_rho, 8*N);
-    if (p3d && N) memcpy(p3d, r + o_p3d, 12*N);
+    a_sel.get(h, sel); a_theta.get(h, theta); a_score.get(h, score); a_hs.get(h, hyp_score); a_ht.get(h, hyp_theta); a_rho.get(h, rho_out); a_p3d.get(h, p3d);
     return TSORB_OK;
 }
 
@@ -2296,27 +2285,28 @@ static int claim_call(const char *name, bool points, void *ctx, int nq, const fl
     if (use_ratio && (!std::isfinite(ratio) || ratio < 0.0)) return bad("ratio not finite or negative");
     if (c->M.n > TSORB_BRUTE_MAX_FEAT) return bad("the searched set has more than TSORB_BRUTE_MAX_FEAT features");
     if (nq > 0 && (!qxy || !qr || !qdesc || !match12 || (points && (!q_px || !Trw || !Tcw || !K || !p3d || !good)))) return bad("NULL pointer");
-    for (int q = 0; q < nq; q++) { if (!std::isfinite(qxy[2*(size_t)q]) || !std::isfinite(qxy[2*(size_t)q + 1])) return bad("query " + std::to_string(q) + ": a coordinate is not finite");
+    for (int q = 0; q < nq; q++) { if (!all_finite(qxy + 2*(size_t)q, 2)) return bad("query " + std::to_string(q) + ": a coordinate is not finite");
         if (!std::isfinite(qr[q]) || qr[q] < 0.f) return bad("query " + std::to_string(q) + ": the radius is not finite or negative"); }
     if (nq == 0) { *n_match = 0; if (points) *n_good = 0; return TSORB_OK; }
     hipSetDevice(c->device);
     const size_t Q = (size_t)nq, N2 = (size_t)c->M.n;
-    const size_t i_r = br_al(8*Q), i_lev = i_r + br_al(4*Q), i_d = i_lev + (qlev ? br_al(8*Q) : 0), i_el = i_d + br_al(32*Q), i_px = i_el + (elig2 ? br_al(N2) : 0),
-                 in_sz = i_px + (points ? br_al(8*Q) : 0);
-    const size_t o_dist = br_al(4*Q), o_cnt = o_dist + br_al(4*Q), o_p3d = o_cnt + 16, o_good = o_p3d + (points ? br_al(12*Q) : 0), out_sz = o_good + (points ? br_al(Q) : 0);
-    const size_t s_dist = br_al(4*Q*CL_ROW), s_cnt = 2*s_dist, s_own = s_cnt + br_al(4*Q), scr_sz = s_own + br_al(4*std::max<size_t>(N2, 1));
-    if (int rc = br_room(c, in_sz + out_sz + scr_sz, in_sz + out_sz)) return rc;
-    char *h = (char *)c->br_pin, *d = (char *)c->br_dev;
-    memcpy(h, qxy, 8*Q); memcpy(h + i_r, qr, 4*Q); if (qlev) memcpy(h + i_lev, qlev, 8*Q); memcpy(h + i_d, qdesc, 32*Q);
-    if (elig2 && N2) memcpy(h + i_el, elig2, N2);
-    if (points) memcpy(h + i_px, q_px, 8*Q);
+    // in: [qxy | qr | qlev (if given) | qdesc | elig (if given) | q_px (points)]   out: [match12 | match_dist | counts | p3d, good (points)]   scratch: [row_idx | row_dist | row_cnt | own]
+    Layout L(16);
+    const auto a_qxy = L.take<float>(2*Q), a_qr = L.take<float>(Q); const auto a_lev = L.take<int32_t>(qlev ? 2*Q : 0); const auto a_qd = L.take<uint8_t>(32*Q), a_el = L.take<uint8_t>(elig2 ? N2 : 0);
+    const auto a_px = L.take<float>(points ? 2*Q : 0);
+    const size_t in_sz = L.mark();
+    const auto a_m12 = L.take<int32_t>(Q), a_dist = L.take<int32_t>(Q), a_cnt = L.take<int32_t>(2); const auto a_p3d = L.take<float>(points ? 3*Q : 0); const auto a_good = L.take<uint8_t>(points ? Q : 0);
+    const size_t out_end = L.mark();
+    const auto a_ridx = L.take<int32_t>(Q*CL_ROW), a_rdist = L.take<int32_t>(Q*CL_ROW), a_rcnt = L.take<int32_t>(Q), a_own = L.take<int32_t>(std::max<size_t>(N2, 1));
+    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, out_end));
+    void *h = c->br_pin, *d = c->br_dev;
+    a_qxy.put(h, qxy); a_qr.put(h, qr); a_lev.put(h, qlev); a_qd.put(h, qdesc); a_el.put(h, elig2); a_px.put(h, q_px);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
-    ClaimDev D; char *o = d + in_sz, *s = o + out_sz;
+    ClaimDev D;
     D.nq = nq; D.n2 = (int)N2; D.th_low = th_low; D.use_ratio = use_ratio ? 1 : 0; D.ratio = ratio;
-    D.qxy = (const float *)d; D.qr = (const float *)(d + i_r); D.qlev = qlev ? (const int32_t *)(d + i_lev) : nullptr; D.qdesc = (const uint8_t *)(d + i_d);
-    D.elig = elig2 ? (const uint8_t *)(d + i_el) : nullptr; D.q_px = (const float *)(d + i_px);
-    D.row_idx = (int32_t *)s; D.row_dist = (int32_t *)(s + s_dist); D.row_cnt = (int32_t *)(s + s_cnt); D.own = (int32_t *)(s + s_own);
-    D.match12 = (int32_t *)o; D.match_dist = (int32_t *)(o + o_dist); D.count = (int32_t *)(o + o_cnt); D.p3d = (float *)(o + o_p3d); D.good = (uint8_t *)(o + o_good);
+    D.qxy = a_qxy.at(d); D.qr = a_qr.at(d); D.qlev = qlev ? a_lev.at(d) : nullptr; D.qdesc = a_qd.at(d); D.elig = elig2 ? a_el.at(d) : nullptr; D.q_px = a_px.at(d);
+    D.row_idx = a_ridx.at(d); D.row_dist = a_rdist.at(d); D.row_cnt = a_rcnt.at(d); D.own = a_own.at(d);
+    D.match12 = a_m12.at(d); D.match_dist = a_dist.at(d); D.count = a_cnt.at(d); D.p3d = a_p3d.at(d); D.good = a_good.at(d);
     for (int i = 0; i < 12; i++) { D.Trw[i] = points ? Trw[i] : 0.0; D.Tcw[i] = points ? Tcw[i] : 0.0; }
     for (int i = 0; i < 4; i++) D.K[i] = points ? K[i] : 0.0;
     D.th_reproj = th_reproj;
@@ -2327,12 +2317,11 @@ static int claim_call(const char *name, bool points, void *ctx, int nq, const fl
     hipLaunchKernelGGL(k_claim_walk, dim3((unsigned)((nq + 3)/4)), dim3(256), 0, c->stream, G, D);
     hipLaunchKernelGGL(k_claim_chain, dim3(1), dim3(CL_T), lds, c->stream, G, D);
     if (points) hipLaunchKernelGGL(k_claim_points, dim3((unsigned)((nq + CL_T - 1)/CL_T)), dim3(CL_T), 0, c->stream, G, D);
-    OCK(hipMemcpyAsync(h + in_sz, d + in_sz, out_sz, hipMemcpyDeviceToHost, c->stream));
+    OCK(hipMemcpyAsync(a_m12.at(h), a_m12.at(d), out_end - in_sz, hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    const char *r = h + in_sz;
-    memcpy(match12, r, 4*Q); if (match_dist) memcpy(match_dist, r + o_dist, 4*Q);
-    *n_match = ((const int32_t *)(r + o_cnt))[0];
-    if (points) { memcpy(p3d, r + o_p3d, 12*Q); memcpy(good, r + o_good, Q); *n_good = ((const int32_t *)(r + o_cnt))[1]; }
+    a_m12.get(h, match12); a_dist.get(h, match_dist); a_p3d.get(h, p3d); a_good.get(h, good);
+    *n_match = a_cnt.at(h)[0];
+    if (points) *n_good = a_cnt.at(h)[1];
     return TSORB_OK;
 }
 int tsorb_match_search_claim(void *ctx, int nq, const float *qxy, const float *qr, const int32_t *qlev, const uint8_t *qdesc, const uint8_t *elig2, int th_low, int use_ratio,
