@@ -10,6 +10,7 @@
  *   tracking::TrackNewTextFeat          /root/reference/src/tracking.cc:1752-1785 -> tsframe_klt_track
  *   mapText::GetObjectInfo              src/mapText.cc:64-107 (tool::CalTextinfo src/tool.cc:1178-1262, CalNormvec :1342-1355,
  *                                       GetBoxAllPixs :1264-1337; callers src/tracking.cc:932-957 and InitialLandmarker) -> tsframe_text_object_info
+ *   cv::undistort + cvtColor            main.cpp:73, src/tracking.cc:69-73 (docs/undistort_recalled.md) -> tsframe_set_camera, tsframe_set_raw_image
  * The pyramid stays resident in HBM: tsframe_level_ptr hands the device pointers to the BA library, so the four levels of a
  * keyframe need no host round trip between GetPyrMat and the photometric residuals.
  * All functions return 0 on success, a negative TSFRAME_ERR_* otherwise; tsframe_last_error gives the text. */
@@ -35,6 +36,33 @@ const char *tsframe_last_error(void *ctx);
 /* frame::GetPyrMat: level 0 = img (w x h, 8-bit), level l = cv::pyrDown(level l-1); per level cv::Sobel x / y (CV_8U) and their
  * addWeighted(.5, .5) blend.  The image is copied through a pinned staging buffer; everything else happens on the device. */
 int tsframe_set_image(void *ctx, const uint8_t *img, int w, int h, int n_levels);
+
+/* The camera-frame entry: cv::undistort(im, imUn, K, dist, K_new) (main.cpp:73), cvtColor BGR2GRAY / RGB2GRAY
+ * (src/tracking.cc:69-73) and frame::GetPyrMat from ONE upload of the raw frame.  The arithmetic is docs/undistort_recalled.md (OpenCV 3.3's
+ * non-IPP path as recalled; everything after the fixed-point map is integer), restated in tests/camera_frame_ref.py.
+ * tsframe_set_camera, once per camera: builds cv::initUndistortRectifyMap's CV_16SC2 map for a w x h image on the device, strip by strip as
+ * cv::undistort does, and keeps it until the next call (which may change the size).  K = fx fy cx cy, dist = k1 k2 p1 p2 k3, K_new = the new
+ * camera matrix (NULL: K, the reference's call).
+ * tsframe_set_raw_image, per frame: raw = h rows of stride bytes, 8-bit BGR, RGB (3 bytes per pixel) or grey (1), row-padded or not; w, h are the
+ * camera's.  The frame goes to the device in one copy through the pinned staging; one kernel remaps it (INTER_LINEAR, BORDER_CONSTANT 0, per
+ * channel), converts the rounded channels to grey and stores level 0; then the chain of tsframe_set_image runs unchanged.  Afterwards every other
+ * call behaves as after tsframe_set_image(grey, w, h, n_levels) with grey = the undistorted grey image (bit for bit), and
+ * tsframe_level_ptr(0, TSFRAME_IMG) is what tsorb_extract_device (include/tsorb.h) takes.  undist_out: NULL, or [h][w][channels] for the undistorted
+ * image before the grey conversion, in raw's channel order (one copy back).
+ * tsframe_get_undist_map, test hook: the resident map, xy [h][w][2] = (short)(iu >> 5), (short)(iv >> 5) and frac [h][w] = (iv & 31) * 32 + (iu & 31).
+ * TSFRAME_ERR_ARG: a NULL pointer (K_new and undist_out may be NULL), w or h < 2 or above 8192, a non-finite K / dist / K_new, fx or fy == 0 in K or
+ * K_new, a format other than the three, stride < w * channels, n_levels outside [1, 8].  TSFRAME_ERR_STATE: a frame or a map request before a camera
+ * is set.  On any of them nothing is launched, the resident planes and map stay as they were, no output is touched, and tsframe_last_error names
+ * the function.  Not covered: k4 - k6, thin-prism and tilt coefficients, a rectification rotation. */
+#define TSFRAME_RAW_BGR 0
+#define TSFRAME_RAW_RGB 1
+#define TSFRAME_RAW_GREY 2
+int tsframe_set_camera(void *ctx, int w, int h, const double K[4] /*fx fy cx cy*/, const double dist[5] /*k1 k2 p1 p2 k3*/,
+                       const double K_new[4] /*NULL: K*/);
+int tsframe_set_raw_image(void *ctx, const uint8_t *raw, int stride, int format, int n_levels,
+                          uint8_t *undist_out /*NULL, or [h][w][channels]: the undistorted image before the grey conversion*/);
+int tsframe_get_undist_map(void *ctx, int16_t *xy /*[h][w][2]*/, uint16_t *frac /*[h][w]*/);
+
 int tsframe_level_size(void *ctx, int level, int *w, int *h);
 /* device pointer of a resident plane (which = TSFRAME_IMG / GRAD / GRADX / GRADY); valid until the next tsframe_set_image */
 int tsframe_level_ptr(void *ctx, int level, int which, const uint8_t **dev);

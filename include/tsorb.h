@@ -46,6 +46,15 @@ int tsorb_extract_batch(void *ctx, const uint8_t *imgs, int n, int w, int h, int
  * Outside them, and for n < 1, cap < 1, a NULL pointer or stride < w: TSORB_ERR_ARG, tsorb_last_error names the reason, nothing is launched, no output of
  * tsorb_extract_batch is touched and the resident batch stays as it was. */
 int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride, int cap);
+/* tsorb_upload / tsorb_extract_batch with the batch already on the context's device, e.g. level 0 of a resident BA pyramid
+ * (tsframe_level_ptr(0, TSFRAME_IMG) of include/tsframe.h after tsframe_set_raw_image: n = 1, stride = w).  The same checks, geometry and same-geometry
+ * fast path as the host forms (one body); the pixels reach the context by a device-to-device copy on its stream, which is waited for before
+ * tsorb_upload_device returns, so the source may change afterwards.  The results are those of the host forms on the same bytes.
+ * TSORB_ERR_ARG, with nothing touched, also for a dev_imgs that hipPointerGetAttributes does not report as device memory of the context's device, or whose
+ * allocation ends before n * h rows of stride bytes (a host pointer is refused, not read). */
+int tsorb_upload_device(void *ctx, const uint8_t *dev_imgs, int n, int w, int h, int stride, int cap);
+int tsorb_extract_device(void *ctx, const uint8_t *dev_imgs, int n, int w, int h, int stride,
+                         float *kp, uint8_t *desc, int32_t *count, int cap);
 int tsorb_run(void *ctx);
 int tsorb_download(void *ctx, float *kp, uint8_t *desc, int32_t *count);
 

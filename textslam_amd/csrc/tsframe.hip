@@ -20,6 +20,8 @@ struct FCtx {
     size_t plane_cap = 0; uint8_t *plane_base = nullptr;
     uint8_t *h_stage = nullptr; size_t h_cap = 0;             // pinned staging (image in, results out)
     uint8_t *d_work = nullptr; size_t d_cap = 0;              // device scratch for the feature calls
+    int cam_w = 0, cam_h = 0; int16_t *map_xy = nullptr; uint16_t *map_frac = nullptr;      // tsframe_set_camera: the fixed-point undistortion map (tsundist.h)
+    uint8_t *d_raw = nullptr, *d_col = nullptr; size_t raw_cap = 0, col_cap = 0;            // tsframe_set_raw_image: the staged raw frame, the undistorted colour plane
 };
 #define CKF(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); return TSFRAME_ERR_DEVICE; } } while (0)
 
@@ -265,6 +267,7 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
 #include "tsklt.h"
 #include "tspts.h"
 #include "tsobj.h"
+#include "tsundist.h"
 
 static int ensure_host(FCtx *c, size_t bytes) {
     if (bytes <= c->h_cap) return 0;
@@ -382,6 +385,33 @@ static int pts_run(FCtx *c, int n_set, const int32_t *xy_off, const float *xy, c
     return TSFRAME_OK;
 }
 
+// The four planes of every level in one allocation (frame::GetPyrMat's sizes: level l = ceil(level l-1 / 2)), kept while it is large enough.
+static int planes_layout(FCtx *c, int w, int h, int n_levels) {
+    size_t tot = 0; int lw = w, lh = h;
+    for (int l = 0; l < n_levels; l++) { c->w[l] = lw; c->h[l] = lh; tot += ((size_t)lw*lh + 255) & ~(size_t)255; lw = (lw + 1)/2; lh = (lh + 1)/2; }
+    if (4*tot > c->plane_cap) {
+        if (c->plane_base) hipFree(c->plane_base);
+        c->plane_base = nullptr; c->plane_cap = 0;
+        CKF(hipMalloc((void **)&c->plane_base, 4*tot));
+        c->plane_cap = 4*tot;
+    }
+    uint8_t *p = c->plane_base;
+    for (int k = 0; k < 4; k++) for (int l = 0; l < n_levels; l++) { c->plane[k][l] = p; p += ((size_t)c->w[l]*c->h[l] + 255) & ~(size_t)255; }
+    c->n_levels = n_levels;
+    return 0;
+}
+// frame::GetPyrMat from the level-0 image that the stream has been given: pyrDown per level, the gradient planes of every level; waits for all of it.
+static int pyramid_from_level0(FCtx *c) {
+    for (int l = 0; l < c->n_levels; l++) {
+        if (l > 0) hipLaunchKernelGGL(k_pyrdown, dim3((c->w[l] + 63)/64, (c->h[l] + 3)/4), dim3(256), 0, c->stream,
+                                      (const uint8_t *)c->plane[TSFRAME_IMG][l - 1], c->w[l - 1], c->h[l - 1], c->plane[TSFRAME_IMG][l], c->w[l], c->h[l]);
+        hipLaunchKernelGGL(k_gradients, dim3((c->w[l] + 63)/64, (c->h[l] + 3)/4), dim3(256), 0, c->stream,
+                           (const uint8_t *)c->plane[TSFRAME_IMG][l], c->w[l], c->h[l], c->plane[TSFRAME_GRADX][l], c->plane[TSFRAME_GRADY][l], c->plane[TSFRAME_GRAD][l]);
+    }
+    CKF(hipStreamSynchronize(c->stream)); CKF(hipGetLastError());
+    return TSFRAME_OK;
+}
+
 extern "C" {
 
 int tsframe_create(int device, void **ctx) {
@@ -397,6 +427,10 @@ void tsframe_destroy(void *ctx) {
     hipSetDevice(c->device);
     if (c->plane_base) hipFree(c->plane_base);
     if (c->d_work) hipFree(c->d_work);
+    if (c->map_xy) hipFree(c->map_xy);
+    if (c->map_frac) hipFree(c->map_frac);
+    if (c->d_raw) hipFree(c->d_raw);
+    if (c->d_col) hipFree(c->d_col);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -406,27 +440,95 @@ const char *tsframe_last_error(void *ctx) { FCtx *c = (FCtx *)ctx; return c ? c-
 int tsframe_set_image(void *ctx, const uint8_t *img, int w, int h, int n_levels) {
     FCtx *c = (FCtx *)ctx; if (!c || !img || w < 2 || h < 2 || n_levels < 1 || n_levels > TSFRAME_MAX_LEVELS) return TSFRAME_ERR_ARG;
     hipSetDevice(c->device);
-    size_t tot = 0; int lw = w, lh = h;
-    for (int l = 0; l < n_levels; l++) { c->w[l] = lw; c->h[l] = lh; tot += ((size_t)lw*lh + 255) & ~(size_t)255; lw = (lw + 1)/2; lh = (lh + 1)/2; }
-    if (4*tot > c->plane_cap) {
-        if (c->plane_base) hipFree(c->plane_base);
-        c->plane_base = nullptr; c->plane_cap = 0;
-        CKF(hipMalloc((void **)&c->plane_base, 4*tot));
-        c->plane_cap = 4*tot;
-    }
-    uint8_t *p = c->plane_base;
-    for (int k = 0; k < 4; k++) for (int l = 0; l < n_levels; l++) { c->plane[k][l] = p; p += ((size_t)c->w[l]*c->h[l] + 255) & ~(size_t)255; }
-    c->n_levels = n_levels;
-    int rc = ensure_host(c, (size_t)w*h); if (rc) return rc;
+    int rc = planes_layout(c, w, h, n_levels); if (rc) return rc;
+    rc = ensure_host(c, (size_t)w*h); if (rc) return rc;
     memcpy(c->h_stage, img, (size_t)w*h);
     CKF(hipMemcpyAsync(c->plane[TSFRAME_IMG][0], c->h_stage, (size_t)w*h, hipMemcpyHostToDevice, c->stream));
-    for (int l = 0; l < n_levels; l++) {
-        if (l > 0) hipLaunchKernelGGL(k_pyrdown, dim3((c->w[l] + 63)/64, (c->h[l] + 3)/4), dim3(256), 0, c->stream,
-                                      (const uint8_t *)c->plane[TSFRAME_IMG][l - 1], c->w[l - 1], c->h[l - 1], c->plane[TSFRAME_IMG][l], c->w[l], c->h[l]);
-        hipLaunchKernelGGL(k_gradients, dim3((c->w[l] + 63)/64, (c->h[l] + 3)/4), dim3(256), 0, c->stream,
-                           (const uint8_t *)c->plane[TSFRAME_IMG][l], c->w[l], c->h[l], c->plane[TSFRAME_GRADX][l], c->plane[TSFRAME_GRADY][l], c->plane[TSFRAME_GRAD][l]);
+    return pyramid_from_level0(c);
+}
+
+/* cv::undistort's map for one camera (docs/undistort_recalled.md U1 - U5), kept on the device until the next call.  The new map is built beside the old
+ * one and takes its place only when the kernel has finished. */
+int tsframe_set_camera(void *ctx, int w, int h, const double K[4], const double dist[5], const double K_new[4]) {
+    FCtx *c = (FCtx *)ctx; if (!c) return TSFRAME_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsframe_set_camera: ") + m; return TSFRAME_ERR_ARG; };
+    if (!K || !dist) return bad("K or dist is NULL");
+    if (w < 2 || h < 2 || w > 8192 || h > 8192) return bad("w or h outside [2, 8192]");
+    const double *Kn = K_new ? K_new : K;
+    for (int i = 0; i < 4; i++) if (!std::isfinite(K[i]) || !std::isfinite(Kn[i])) return bad("K or K_new is not finite");
+    for (int i = 0; i < 5; i++) if (!std::isfinite(dist[i])) return bad("dist is not finite");
+    if (K[0] == 0.0 || K[1] == 0.0 || Kn[0] == 0.0 || Kn[1] == 0.0) return bad("fx or fy is 0 (K or K_new)");
+    hipSetDevice(c->device);
+    UndistCam C; memcpy(C.K, K, sizeof(C.K)); memcpy(C.dist, dist, sizeof(C.dist)); memcpy(C.Kn, Kn, sizeof(C.Kn));
+    C.w = w; C.h = h; C.s0 = std::min(std::max(1, 4096/std::max(w, 1)), h);
+    const size_t n4 = ((size_t)w*h + 3) & ~(size_t)3;            // (k_undist_grey loads four entries at a time)
+    int16_t *xy = nullptr; uint16_t *fr = nullptr;
+    CKF(hipMalloc((void **)&xy, n4*2*sizeof(int16_t)));
+    if (hipMalloc((void **)&fr, n4*sizeof(uint16_t)) != hipSuccess) { hipFree(xy); c->err = "tsframe_set_camera: hipMalloc failed"; return TSFRAME_ERR_DEVICE; }
+    hipError_t e = hipMemsetAsync(xy, 0, n4*2*sizeof(int16_t), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(fr, 0, n4*sizeof(uint16_t), c->stream);
+    if (e == hipSuccess) { hipLaunchKernelGGL(k_undist_map, dim3((h + 63)/64), dim3(64), 0, c->stream, C, xy, fr); e = hipStreamSynchronize(c->stream); }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { hipFree(xy); hipFree(fr); c->err = std::string("tsframe_set_camera: ") + hipGetErrorString(e); return TSFRAME_ERR_DEVICE; }
+    if (c->map_xy) hipFree(c->map_xy);
+    if (c->map_frac) hipFree(c->map_frac);
+    c->map_xy = xy; c->map_frac = fr; c->cam_w = w; c->cam_h = h;
+    return TSFRAME_OK;
+}
+
+int tsframe_get_undist_map(void *ctx, int16_t *xy, uint16_t *frac) {
+    FCtx *c = (FCtx *)ctx; if (!c) return TSFRAME_ERR_ARG;
+    if (!xy || !frac) { c->err = "tsframe_get_undist_map: xy or frac is NULL"; return TSFRAME_ERR_ARG; }
+    if (!c->map_xy) { c->err = "tsframe_get_undist_map: no camera set (tsframe_set_camera first)"; return TSFRAME_ERR_STATE; }
+    hipSetDevice(c->device);
+    const size_t n = (size_t)c->cam_w*c->cam_h;
+    CKF(hipMemcpy(xy, c->map_xy, n*2*sizeof(int16_t), hipMemcpyDeviceToHost));
+    CKF(hipMemcpy(frac, c->map_frac, n*sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return TSFRAME_OK;
+}
+
+/* cv::undistort + cvtColor + frame::GetPyrMat of one raw camera frame: one copy up, k_undist_grey writes level 0 (and the colour plane when asked),
+ * then tsframe_set_image's own chain. */
+int tsframe_set_raw_image(void *ctx, const uint8_t *raw, int stride, int format, int n_levels, uint8_t *undist_out) {
+    FCtx *c = (FCtx *)ctx; if (!c) return TSFRAME_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsframe_set_raw_image: ") + m; return TSFRAME_ERR_ARG; };
+    if (!raw) return bad("raw is NULL");
+    if (format != TSFRAME_RAW_BGR && format != TSFRAME_RAW_RGB && format != TSFRAME_RAW_GREY) return bad("format is none of TSFRAME_RAW_BGR / RGB / GREY");
+    if (n_levels < 1 || n_levels > TSFRAME_MAX_LEVELS) return bad("n_levels outside [1, 8]");
+    if (!c->map_xy) { c->err = "tsframe_set_raw_image: no camera set (tsframe_set_camera first)"; return TSFRAME_ERR_STATE; }
+    const int w = c->cam_w, h = c->cam_h, ch = format == TSFRAME_RAW_GREY ? 1 : 3;
+    if (stride < w*ch) return bad("stride < w * channels");
+    hipSetDevice(c->device);
+    const size_t raw_bytes = (size_t)(h - 1)*stride + (size_t)w*ch, col_bytes = (size_t)w*h*ch;      // (the last row ends with its pixels)
+    if (raw_bytes > c->raw_cap) {
+        if (c->d_raw) hipFree(c->d_raw);
+        c->d_raw = nullptr; c->raw_cap = 0;
+        CKF(hipMalloc((void **)&c->d_raw, raw_bytes));
+        c->raw_cap = raw_bytes;
     }
-    CKF(hipStreamSynchronize(c->stream)); CKF(hipGetLastError());
+    if (undist_out && al256(col_bytes) > c->col_cap) {                                               // (whole dwords at the end of the plane)
+        if (c->d_col) hipFree(c->d_col);
+        c->d_col = nullptr; c->col_cap = 0;
+        CKF(hipMalloc((void **)&c->d_col, al256(col_bytes)));
+        c->col_cap = al256(col_bytes);
+    }
+    int rc = planes_layout(c, w, h, n_levels); if (rc) return rc;
+    rc = ensure_host(c, std::max(raw_bytes, col_bytes)); if (rc) return rc;
+    memcpy(c->h_stage, raw, raw_bytes);
+    CKF(hipMemcpyAsync(c->d_raw, c->h_stage, raw_bytes, hipMemcpyHostToDevice, c->stream));
+    const int npix = w*h; const dim3 grid((npix + 1023)/1024), block(256);
+    const int r_first = format == TSFRAME_RAW_RGB;
+    uint8_t *g0 = c->plane[TSFRAME_IMG][0];
+    if (ch == 3) {
+        if (undist_out) hipLaunchKernelGGL((k_undist_grey<3, true>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, c->d_col);
+        else hipLaunchKernelGGL((k_undist_grey<3, false>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)nullptr);
+    } else {
+        if (undist_out) hipLaunchKernelGGL((k_undist_grey<1, true>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, c->d_col);
+        else hipLaunchKernelGGL((k_undist_grey<1, false>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)nullptr);
+    }
+    if (undist_out) CKF(hipMemcpyAsync(c->h_stage, c->d_col, col_bytes, hipMemcpyDeviceToHost, c->stream));      // (the raw frame has left the staging: same stream)
+    rc = pyramid_from_level0(c); if (rc) return rc;
+    if (undist_out) memcpy(undist_out, c->h_stage, col_bytes);
     return TSFRAME_OK;
 }
 int tsframe_level_size(void *ctx, int level, int *w, int *h) {

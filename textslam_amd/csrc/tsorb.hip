@@ -1544,9 +1544,11 @@ int tsorb_get_scale_factors(void *ctx, float *sf, float *isf) { OCtx *c = (OCtx 
     for (int i = 0; i < c->nlevels; i++) { if (sf) sf[i] = c->sf[i]; if (isf) isf[i] = c->isf[i]; } return TSORB_OK; }
 int tsorb_get_features_per_level(void *ctx, int32_t *n) { OCtx *c = (OCtx *)ctx; if (!c || !n) return TSORB_ERR_ARG; for (int i = 0; i < c->nlevels; i++) n[i] = c->nfl[i]; return TSORB_OK; }
 
-int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride, int cap) {
+// tsorb_upload (imgs on the host: through the pinned staging) and tsorb_upload_device (imgs on the context's device: a device-to-device copy on the
+// context's stream, waited for before the return) -- one body: the checks, the geometry and the same-geometry fast path are the same code.
+static int upload_any(const char *fn, bool on_device, void *ctx, const uint8_t *imgs, int n, int w, int h, int stride, int cap) {
     OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
-    auto bad = [&](const char *m) { c->err = std::string("tsorb_upload: ") + m; return TSORB_ERR_ARG; };
+    auto bad = [&](const char *m) { c->err = std::string(fn) + ": " + m; return TSORB_ERR_ARG; };
     if (!imgs) return bad("imgs is NULL");
     if (n < 1) return bad("n < 1");
     if (cap < 1) return bad("cap < 1");
@@ -1560,14 +1562,27 @@ int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride
         if ((int)roundf((float)(lw - 32)/(float)(lh - 32)) < 1) return bad("a level's search area is more than twice as high as wide (the quadtree starts from round(width/height) = 0 nodes)");
     }
     hipSetDevice(c->device);
-    c->out_on_host = false;                                  // (until the next run)
-    c->ran = false;
-    if (c->uploaded && c->key[0] == n && c->key[1] == w && c->key[2] == h && c->key[3] == stride && c->key[4] == cap) {
-        // same geometry as the previous call: only the pixels travel (pinned staging, one asynchronous copy)
+    const size_t img_sz = ((size_t)n*h - 1)*stride + w;      // (the last row ends with its pixels: an ROI's stride may run past the caller's buffer there)
+    if (on_device) {                                         // device memory of this context's device that holds the whole batch, or nothing is touched
+        hipPointerAttribute_t at; memset(&at, 0, sizeof(at));
+        void *base = nullptr; size_t len = 0;
+        const bool ok = hipPointerGetAttributes(&at, imgs) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device &&
+                        hipMemGetAddressRange((hipDeviceptr_t *)&base, &len, (hipDeviceptr_t)imgs) == hipSuccess &&
+                        (size_t)(imgs - (const uint8_t *)base) + img_sz <= len;
+        (void)hipGetLastError();                             // (a host pointer's query fails: not an error of a later launch)
+        if (!ok) return bad("imgs is not device memory of the context's device that holds n * h rows of stride bytes");
+    }
+    // the pixels: a host batch goes through the pinned staging in one asynchronous copy; a device batch is copied on the stream and waited for (its source may change afterwards)
+    auto pixels = [&]() -> int {
+        if (on_device) { OCK(hipMemcpyAsync((void *)c->D.img, imgs, img_sz, hipMemcpyDeviceToDevice, c->stream)); OCK(hipStreamSynchronize(c->stream)); return TSORB_OK; }
         memcpy(c->h_img, imgs, c->h_img_sz);
         OCK(hipMemcpyAsync((void *)c->D.img, c->h_img, c->h_img_sz, hipMemcpyHostToDevice, c->stream));
         return TSORB_OK;
-    }
+    };
+    c->out_on_host = false;                                  // (until the next run)
+    c->ran = false;
+    if (c->uploaded && c->key[0] == n && c->key[1] == w && c->key[2] == h && c->key[3] == stride && c->key[4] == cap)
+        return pixels();                                     // same geometry as the previous call: only the pixels travel
     ofree(c);
     OrbDev &D = c->D; memset(&D, 0, sizeof(D));
     { void *dp = nullptr; if (hipHostGetDevicePointer(&dp, c->h_fb, 0) != hipSuccess) { c->err = "hipHostGetDevicePointer failed"; return TSORB_ERR_DEVICE; } D.h_fallback = (int *)dp; }
@@ -1629,10 +1644,9 @@ int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride
     D.cand_cap = ((D.L[0].maxBX - D.L[0].minB)*(D.L[0].maxBY - D.L[0].minB))/4 + 64; D.node_cap = 64*(c->nfl[0] + 64); D.pool_cap = 16*D.cand_cap;
     int rc;
     uint8_t *img; if ((rc = oalloc(c, &img, (size_t)n*h*stride + 8))) return rc; D.img = img;        // (+ 8: level 1's 8-byte source loads at the end of the last row)
-    c->h_img_sz = ((size_t)n*h - 1)*stride + w;          // (the last row ends with its pixels: an ROI's stride may run past the caller's buffer there)
+    c->h_img_sz = img_sz;                                // (the staging is kept for a device batch too: the next call of this geometry may come from the host)
     OCK(hipHostMalloc((void **)&c->h_img, c->h_img_sz, hipHostMallocDefault));
-    memcpy(c->h_img, imgs, c->h_img_sz);
-    OCK(hipMemcpyAsync(img, c->h_img, c->h_img_sz, hipMemcpyHostToDevice, c->stream));
+    if ((rc = pixels())) return rc;
     if ((rc = oalloc(c, &D.pyr, (size_t)n*po)) || (rc = oalloc(c, &D.blur, (size_t)n*bo))) return rc;
     if ((rc = oalloc(c, &D.rtab, (size_t)std::max(rt, 4)))) return rc;
     if ((rc = oalloc(c, &D.cellkp, (size_t)n*cell0*CELL_CAP)) || (rc = oalloc(c, &D.cellcnt, (size_t)n*cell0))) return rc;
@@ -1652,6 +1666,8 @@ int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride
     if (c->nlevels > 1) hipLaunchKernelGGL(k_resize_tab, dim3(c->nlevels - 1), dim3(256), 0, c->stream, D);
     c->uploaded = true; return TSORB_OK;
 }
+int tsorb_upload(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride, int cap) { return upload_any("tsorb_upload", false, ctx, imgs, n, w, h, stride, cap); }
+int tsorb_upload_device(void *ctx, const uint8_t *dev_imgs, int n, int w, int h, int stride, int cap) { return upload_any("tsorb_upload_device", true, ctx, dev_imgs, n, w, h, stride, cap); }
 int tsorb_run(void *ctx) {
     OCtx *c = (OCtx *)ctx; if (!c || !c->uploaded) return TSORB_ERR_ARG;
     hipSetDevice(c->device);
@@ -1717,6 +1733,11 @@ int tsorb_download(void *ctx, float *kp, uint8_t *desc, int32_t *count) {
 }
 int tsorb_extract_batch(void *ctx, const uint8_t *imgs, int n, int w, int h, int stride, float *kp, uint8_t *desc, int32_t *count, int cap) {
     int rc = tsorb_upload(ctx, imgs, n, w, h, stride, cap); if (rc) return rc;
+    rc = tsorb_run(ctx); if (rc) return rc;
+    return tsorb_download(ctx, kp, desc, count);
+}
+int tsorb_extract_device(void *ctx, const uint8_t *dev_imgs, int n, int w, int h, int stride, float *kp, uint8_t *desc, int32_t *count, int cap) {
+    int rc = tsorb_upload_device(ctx, dev_imgs, n, w, h, stride, cap); if (rc) return rc;
     rc = tsorb_run(ctx); if (rc) return rc;
     return tsorb_download(ctx, kp, desc, count);
 }

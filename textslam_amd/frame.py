@@ -8,6 +8,7 @@
   Frame.TextJudgeBatch(...)                           tracking::TextJudgeSingle /root/reference/src/tracking.cc:1991-2131 (n planes, one launch)
   Frame.TrackKLT(prev_frame, pts, ...)                tracking::TrackNewTextFeat /root/reference/src/tracking.cc:1752-1785 (all points, one launch)
   Frame.GetObjectInfoBatch(quads, inv_scale, feats)   mapText::GetObjectInfo    src/mapText.cc:64-107 (all new objects, one launch)
+  Frame.SetCamera(w, h, K, dist) / SetRawImage(raw)   cv::undistort + cvtColor + GetPyrMat   main.cpp:73, src/tracking.cc:69-73 (one upload per camera frame)
 
 No CPU fallback: without the HIP library / a GPU every call raises.
 """
@@ -20,8 +21,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libtsframe.so")
 EXPORTED_SYMBOLS = ["tsframe_create", "tsframe_destroy", "tsframe_last_error", "tsframe_set_image", "tsframe_level_size", "tsframe_level_ptr",
                     "tsframe_get_level", "tsframe_pyramid_pts", "tsframe_pyramid_pts_batch", "tsframe_neighbours", "tsframe_box_pixels", "tsframe_text_judge", "tsframe_klt_track",
-                    "tsframe_text_object_info"]
+                    "tsframe_text_object_info", "tsframe_set_camera", "tsframe_set_raw_image", "tsframe_get_undist_map"]
 IMG, GRAD, GRADX, GRADY = 0, 1, 2, 3
+RAW_BGR, RAW_RGB, RAW_GREY = 0, 1, 2                                     # TSFRAME_RAW_* of include/tsframe.h
 JUDGE_PASS, JUDGE_ORIENT, JUDGE_DEPTH, JUDGE_BOX, JUDGE_ZNCC = 0, 1, 2, 3, 4
 
 
@@ -62,6 +64,12 @@ def _load():
     L.tsframe_klt_track.restype = C.c_int
     L.tsframe_text_object_info.argtypes = [vp, C.c_int, dp, dp, ip, ip, dp, dp, dp, C.c_int, dp, up, dp, dp, dp, up, ip, ip, ip, dp, dp]
     L.tsframe_text_object_info.restype = C.c_int
+    L.tsframe_set_camera.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
+    L.tsframe_set_camera.restype = C.c_int
+    L.tsframe_set_raw_image.argtypes = [vp, up, C.c_int, C.c_int, C.c_int, up]
+    L.tsframe_set_raw_image.restype = C.c_int
+    L.tsframe_get_undist_map.argtypes = [vp, C.POINTER(C.c_int16), C.POINTER(C.c_uint16)]
+    L.tsframe_get_undist_map.restype = C.c_int
     return L
 
 
@@ -92,6 +100,38 @@ class Frame:
         img = np.ascontiguousarray(img, np.uint8)
         self._check(self.lib.tsframe_set_image(self.ctx, _up(img), img.shape[1], img.shape[0], iScaleLevels), "tsframe_set_image")
         self.n_levels = iScaleLevels
+
+    def SetCamera(self, w, h, K, dist, K_new=None):
+        """cv::undistort's map for a w x h camera, built and kept on the device (include/tsframe.h: tsframe_set_camera).  K, K_new = (fx, fy, cx, cy),
+        dist = (k1, k2, p1, p2, k3); K_new None: K."""
+        K = np.ascontiguousarray(K, np.float64).reshape(4); dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+        Kn = None if K_new is None else np.ascontiguousarray(K_new, np.float64).reshape(4)
+        self._check(self.lib.tsframe_set_camera(self.ctx, int(w), int(h), _dp(K), _dp(dist), _dp(Kn) if Kn is not None else None), "tsframe_set_camera")
+        self.camera_shape = (int(h), int(w))
+
+    def SetRawImage(self, raw, fmt, iScaleLevels: int, want_undistorted=False):
+        """One raw camera frame -> undistorted, grey, BA pyramid (include/tsframe.h: tsframe_set_raw_image).  raw: uint8 [h, w, 3] (RAW_BGR / RAW_RGB) or
+        [h, w] (RAW_GREY) of the camera's size; a row-padded image is handed in as the view buf[:, :w] of its buffer and goes to the library as it lies in
+        memory (no copy).  Returns the undistorted image in raw's channel order when want_undistorted, else None."""
+        ch = 1 if fmt == RAW_GREY else 3
+        h, w = raw.shape[:2]
+        if raw.dtype != np.uint8 or raw.shape != ((h, w) if ch == 1 else (h, w, 3)) or (h, w) != getattr(self, "camera_shape", (h, w)):
+            raise ValueError("raw is not a uint8 image of the camera's size with %d channel(s): shape %s" % (ch, raw.shape))
+        if raw.strides[1:] != ((1,) if ch == 1 else (3, 1)) or raw.strides[0] < w*ch:
+            raw = np.ascontiguousarray(raw)
+        out = np.zeros(raw.shape, np.uint8) if want_undistorted else None
+        self._check(self.lib.tsframe_set_raw_image(self.ctx, C.cast(raw.ctypes.data, C.POINTER(C.c_uint8)), int(raw.strides[0]), int(fmt), int(iScaleLevels),
+                                                   _up(out) if out is not None else None), "tsframe_set_raw_image")
+        self.n_levels = iScaleLevels
+        return out
+
+    def undist_map(self):
+        """Test hook: the resident map as cv::initUndistortRectifyMap(CV_16SC2) leaves it: (xy int16 [h, w, 2], frac uint16 [h, w])."""
+        h, w = getattr(self, "camera_shape", (1, 1))
+        xy = np.zeros((h, w, 2), np.int16); frac = np.zeros((h, w), np.uint16)
+        self._check(self.lib.tsframe_get_undist_map(self.ctx, xy.ctypes.data_as(C.POINTER(C.c_int16)), frac.ctypes.data_as(C.POINTER(C.c_uint16))),
+                    "tsframe_get_undist_map")
+        return xy, frac
 
     def level_shape(self, level):
         w, h = C.c_int(0), C.c_int(0)

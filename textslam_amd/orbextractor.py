@@ -15,7 +15,7 @@ EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
                     "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets", "tsorb_match_pnp_ransac",
                     "tsorb_match_two_view_ransac", "tsorb_match_two_view_reconstruct", "tsorb_match_text_theta_ransac", "tsorb_match_search_claim",
-                    "tsorb_match_new_points"]
+                    "tsorb_match_new_points", "tsorb_upload_device", "tsorb_extract_device"]
 BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
 SETS_MAX = 1024                                                         # TSORB_SETS_MAX of include/tsorb.h
 PNP_MAX_HYP = 128                                                       # TSORB_PNP_MAX_HYP of include/tsorb.h
@@ -46,6 +46,10 @@ def load_library():
         L.tsorb_get_features_per_level.argtypes = [vp, ip]
         L.tsorb_extract_batch.argtypes = [vp, up, C.c_int, C.c_int, C.c_int, C.c_int, fp, up, ip, C.c_int]
         L.tsorb_upload.argtypes = [vp, up, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.tsorb_upload_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.tsorb_upload_device.restype = C.c_int
+        L.tsorb_extract_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, fp, up, ip, C.c_int]
+        L.tsorb_extract_device.restype = C.c_int
         L.tsorb_run.argtypes = [vp]
         L.tsorb_download.argtypes = [vp, fp, up, ip]
         L.tsorb_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, up, ip, ip]
@@ -134,6 +138,22 @@ class ORBextractor:
             raise ValueError(f"imgs is not the first {w} columns of a uint8 [n, h, {stride}] buffer: strides {imgs.strides}")
         self._check(self.lib.tsorb_upload(self.ctx, C.cast(imgs.ctypes.data, C.POINTER(C.c_uint8)), n, w, h, int(stride), self.cap), "tsorb_upload")
         self._shape = (n, h, w)
+
+    def upload_device(self, dev_ptr, n, h, w, stride=None):
+        """upload() with the batch already on this extractor's device: dev_ptr = the device address (an int) of n frames of h rows of stride bytes,
+        e.g. Frame.level_device_ptr(0) after Frame.SetRawImage (n = 1, stride = w).  The copy is complete when this returns."""
+        stride = w if stride is None else stride
+        self._check(self.lib.tsorb_upload_device(self.ctx, C.c_void_p(dev_ptr), int(n), int(w), int(h), int(stride), self.cap), "tsorb_upload_device")
+        self._shape = (int(n), int(h), int(w))
+
+    def extract_device(self, dev_ptr, n, h, w, stride=None):
+        """extract_batch() with the batch already on this extractor's device (see upload_device), in one library call."""
+        stride = w if stride is None else stride
+        kp = np.zeros((n, self.cap, 6), np.float32); desc = np.zeros((n, self.cap, 32), np.uint8); cnt = np.zeros(n, np.int32)
+        self._check(self.lib.tsorb_extract_device(self.ctx, C.c_void_p(dev_ptr), int(n), int(w), int(h), int(stride), kp.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  desc.ctypes.data_as(C.POINTER(C.c_uint8)), cnt.ctypes.data_as(C.POINTER(C.c_int32)), self.cap), "tsorb_extract_device")
+        self._shape = (int(n), int(h), int(w))
+        return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy()) for i in range(n)]
 
     def run(self):
         self._check(self.lib.tsorb_run(self.ctx), "tsorb_run")
