@@ -12,16 +12,18 @@
 #include "../../include/tsframe.h"
 #include "tsraster.h"
 #include "tsquadstat.h"
+#include "tsstage.h"
 
 struct FCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
     int n_levels = 0, w[TSFRAME_MAX_LEVELS] = {0}, h[TSFRAME_MAX_LEVELS] = {0};
     uint8_t *plane[4][TSFRAME_MAX_LEVELS] = {{nullptr}};     // device planes: img, grad, gx, gy
-    size_t plane_cap = 0; uint8_t *plane_base = nullptr;
-    uint8_t *h_stage = nullptr; size_t h_cap = 0;             // pinned staging (image in, results out)
-    uint8_t *d_work = nullptr; size_t d_cap = 0;              // device scratch for the feature calls
+    // blocks that only grow (tsstage.h):
+    void *plane_base = nullptr; size_t plane_cap = 0;
+    void *h_stage = nullptr; size_t h_cap = 0;                // pinned staging (image in, results out)
+    void *d_work = nullptr; size_t d_cap = 0;                 // device block of the feature calls
     int cam_w = 0, cam_h = 0; int16_t *map_xy = nullptr; uint16_t *map_frac = nullptr;      // tsframe_set_camera: the fixed-point undistortion map (tsundist.h)
-    uint8_t *d_raw = nullptr, *d_col = nullptr; size_t raw_cap = 0, col_cap = 0;            // tsframe_set_raw_image: the staged raw frame, the undistorted colour plane
+    void *d_raw = nullptr, *d_col = nullptr; size_t raw_cap = 0, col_cap = 0;               // tsframe_set_raw_image: the staged raw frame, the undistorted colour plane
 };
 #define CKF(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); return TSFRAME_ERR_DEVICE; } } while (0)
 
@@ -269,24 +271,8 @@ __global__ __launch_bounds__(JUDGE_NT) void k_text_judge(const uint8_t *__restri
 #include "tsobj.h"
 #include "tsundist.h"
 
-static int ensure_host(FCtx *c, size_t bytes) {
-    if (bytes <= c->h_cap) return 0;
-    if (c->h_stage) hipHostFree(c->h_stage);
-    c->h_stage = nullptr; c->h_cap = 0;
-    CKF(hipHostMalloc((void **)&c->h_stage, bytes, hipHostMallocDefault));
-    c->h_cap = bytes; return 0;
-}
-// the feature calls' staging: device scratch of dev_bytes, pinned block of host_bytes (never below the level-0 image, which tsframe_set_image stages there)
-static int ensure_stage(FCtx *c, size_t dev_bytes, size_t host_bytes) {
-    if (dev_bytes > c->d_cap) {
-        if (c->d_work) hipFree(c->d_work);
-        c->d_work = nullptr; c->d_cap = 0;
-        CKF(hipMalloc((void **)&c->d_work, dev_bytes));
-        c->d_cap = dev_bytes;
-    }
-    return ensure_host(c, std::max(host_bytes, (size_t)c->w[0]*c->h[0]));
-}
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// The feature calls below stage through tsstage.h: one Layout over [in || out] serves the pinned block (c->h_stage) and the device block (c->d_work), a take per
+// sub-array of the call's layout comment.  Both blocks are grown to the layout's end; the copy up is the inputs, the copy down starts at the first output.
 
 // The corners of quad * scale as cv::Point(double, double) (truncation) and their clamped bounding box, statement by statement as tool.cc:1269-1298: min / max
 // on strict improvement from w + 1 / -1, then the eight clamps in the reference's order.  An empty box has x1 < x0 or y1 < y0.
@@ -357,28 +343,33 @@ static int pts_run(FCtx *c, int n_set, const int32_t *xy_off, const float *xy, c
     if (total == 0) { memset(level_off, 0, sizeof(int32_t)*(size_t)n_set*(L + 1)); return TSFRAME_OK; }
     hipSetDevice(c->device);
     // one block, inputs then outputs: jobs | xy || cnt | u | v | inten | idx | in; then the large grids' scratch (device only)
-    const size_t cap = total*L, nj = jobs.size();
-    const size_t o_xy = al256(sizeof(PtsJob)*nj), o_cnt = o_xy + al256(8*total), o_u = o_cnt + al256(4*nj), o_v = o_u + al256(8*cap), o_I = o_v + al256(8*cap),
-                 o_idx = o_I + al256(8*cap), o_in = o_idx + al256(4*cap), tot = o_in + al256(cap);
-    int rc = ensure_stage(c, tot + 4*sel_ints, tot); if (rc) return rc;
-    uint8_t *h = c->h_stage, *d = c->d_work;
-    memcpy(h, jobs.data(), sizeof(PtsJob)*nj); memcpy(h + o_xy, xy, 8*total);
-    CKF(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_pts_batch, dim3((unsigned)nj), dim3(PTS_NT), 0, c->stream, (const PtsJob *)d, (const float *)(d + o_xy), (int *)(d + tot), (int *)(d + o_cnt),
-                       (double *)(d + o_u), (double *)(d + o_v), (int *)(d + o_idx), (double *)(d + o_I), d + o_in);
+    const size_t cap = total*L;
+    Layout S(256);
+    const auto a_job = S.take<PtsJob>(jobs.size()); const auto a_xy = S.take<float>(2*total);
+    const size_t in_end = S.mark();
+    const auto a_cnt = S.take<int32_t>(jobs.size()); const auto a_u = S.take<double>(cap), a_v = S.take<double>(cap), a_I = S.take<double>(cap);
+    const auto a_idx = S.take<int32_t>(cap); const auto a_in = S.take<uint8_t>(cap);
+    const size_t tot = S.mark();
+    const auto a_sel = S.take<int32_t>(sel_ints);
+    CKF(grow_device(c->d_work, c->d_cap, S.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, tot));
+    void *h = c->h_stage, *d = c->d_work;
+    a_job.put(h, jobs.data()); a_xy.put(h, xy);
+    CKF(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_pts_batch, dim3((unsigned)a_job.n), dim3(PTS_NT), 0, c->stream, a_job.at(d), a_xy.at(d), a_sel.at(d), a_cnt.at(d),
+                       a_u.at(d), a_v.at(d), a_idx.at(d), a_I.at(d), a_in.at(d));
     CKF(hipGetLastError());
-    CKF(hipMemcpyAsync(h + o_cnt, d + o_cnt, tot - o_cnt, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipMemcpyAsync(a_cnt.at(h), a_cnt.at(d), tot - in_end, hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream));
     // copy-out: level l of set i lies at out0 = xy_off[i]*L + l*n_i with cnt entries; packed behind the set's base
-    const int *cnt = (const int *)(h + o_cnt);
+    const int32_t *cnt = a_cnt.at(h);
     for (int i = 0; i < n_set; i++) {
         int32_t *lo = level_off + (size_t)i*(L + 1);
         const size_t base = (size_t)xy_off[i]*L;
         lo[0] = 0;
         for (int l = 0; l < L; l++) {
             const size_t src = (size_t)jobs[(size_t)i*L + l].out0, dst = base + (size_t)lo[l], m = std::min((size_t)cnt[(size_t)i*L + l], (size_t)(xy_off[i + 1] - xy_off[i]));
-            memcpy(u + dst, h + o_u + 8*src, 8*m); memcpy(v + dst, h + o_v + 8*src, 8*m); memcpy(inten + dst, h + o_I + 8*src, 8*m);
-            memcpy(idx + dst, h + o_idx + 4*src, 4*m); memcpy(in + dst, h + o_in + src, m);
+            std::copy_n(a_u.at(h) + src, m, u + dst); std::copy_n(a_v.at(h) + src, m, v + dst); std::copy_n(a_I.at(h) + src, m, inten + dst);
+            std::copy_n(a_idx.at(h) + src, m, idx + dst); std::copy_n(a_in.at(h) + src, m, in + dst);
             lo[l + 1] = lo[l] + (int32_t)m;
         }
     }
@@ -389,13 +380,8 @@ static int pts_run(FCtx *c, int n_set, const int32_t *xy_off, const float *xy, c
 static int planes_layout(FCtx *c, int w, int h, int n_levels) {
     size_t tot = 0; int lw = w, lh = h;
     for (int l = 0; l < n_levels; l++) { c->w[l] = lw; c->h[l] = lh; tot += ((size_t)lw*lh + 255) & ~(size_t)255; lw = (lw + 1)/2; lh = (lh + 1)/2; }
-    if (4*tot > c->plane_cap) {
-        if (c->plane_base) hipFree(c->plane_base);
-        c->plane_base = nullptr; c->plane_cap = 0;
-        CKF(hipMalloc((void **)&c->plane_base, 4*tot));
-        c->plane_cap = 4*tot;
-    }
-    uint8_t *p = c->plane_base;
+    CKF(grow_device(c->plane_base, c->plane_cap, 4*tot));
+    uint8_t *p = (uint8_t *)c->plane_base;
     for (int k = 0; k < 4; k++) for (int l = 0; l < n_levels; l++) { c->plane[k][l] = p; p += ((size_t)c->w[l]*c->h[l] + 255) & ~(size_t)255; }
     c->n_levels = n_levels;
     return 0;
@@ -441,7 +427,7 @@ int tsframe_set_image(void *ctx, const uint8_t *img, int w, int h, int n_levels)
     FCtx *c = (FCtx *)ctx; if (!c || !img || w < 2 || h < 2 || n_levels < 1 || n_levels > TSFRAME_MAX_LEVELS) return TSFRAME_ERR_ARG;
     hipSetDevice(c->device);
     int rc = planes_layout(c, w, h, n_levels); if (rc) return rc;
-    rc = ensure_host(c, (size_t)w*h); if (rc) return rc;
+    CKF(grow_pinned(c->h_stage, c->h_cap, (size_t)w*h));
     memcpy(c->h_stage, img, (size_t)w*h);
     CKF(hipMemcpyAsync(c->plane[TSFRAME_IMG][0], c->h_stage, (size_t)w*h, hipMemcpyHostToDevice, c->stream));
     return pyramid_from_level0(c);
@@ -500,30 +486,20 @@ int tsframe_set_raw_image(void *ctx, const uint8_t *raw, int stride, int format,
     if (stride < w*ch) return bad("stride < w * channels");
     hipSetDevice(c->device);
     const size_t raw_bytes = (size_t)(h - 1)*stride + (size_t)w*ch, col_bytes = (size_t)w*h*ch;      // (the last row ends with its pixels)
-    if (raw_bytes > c->raw_cap) {
-        if (c->d_raw) hipFree(c->d_raw);
-        c->d_raw = nullptr; c->raw_cap = 0;
-        CKF(hipMalloc((void **)&c->d_raw, raw_bytes));
-        c->raw_cap = raw_bytes;
-    }
-    if (undist_out && al256(col_bytes) > c->col_cap) {                                               // (whole dwords at the end of the plane)
-        if (c->d_col) hipFree(c->d_col);
-        c->d_col = nullptr; c->col_cap = 0;
-        CKF(hipMalloc((void **)&c->d_col, al256(col_bytes)));
-        c->col_cap = al256(col_bytes);
-    }
+    CKF(grow_device(c->d_raw, c->raw_cap, raw_bytes));
+    if (undist_out) CKF(grow_device(c->d_col, c->col_cap, (col_bytes + 255) & ~(size_t)255));        // (whole dwords at the end of the plane)
     int rc = planes_layout(c, w, h, n_levels); if (rc) return rc;
-    rc = ensure_host(c, std::max(raw_bytes, col_bytes)); if (rc) return rc;
+    CKF(grow_pinned(c->h_stage, c->h_cap, std::max(raw_bytes, col_bytes)));                          // the raw frame in, then the colour plane out
     memcpy(c->h_stage, raw, raw_bytes);
     CKF(hipMemcpyAsync(c->d_raw, c->h_stage, raw_bytes, hipMemcpyHostToDevice, c->stream));
     const int npix = w*h; const dim3 grid((npix + 1023)/1024), block(256);
     const int r_first = format == TSFRAME_RAW_RGB;
     uint8_t *g0 = c->plane[TSFRAME_IMG][0];
     if (ch == 3) {
-        if (undist_out) hipLaunchKernelGGL((k_undist_grey<3, true>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, c->d_col);
+        if (undist_out) hipLaunchKernelGGL((k_undist_grey<3, true>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)c->d_col);
         else hipLaunchKernelGGL((k_undist_grey<3, false>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)nullptr);
     } else {
-        if (undist_out) hipLaunchKernelGGL((k_undist_grey<1, true>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, c->d_col);
+        if (undist_out) hipLaunchKernelGGL((k_undist_grey<1, true>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)c->d_col);
         else hipLaunchKernelGGL((k_undist_grey<1, false>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)nullptr);
     }
     if (undist_out) CKF(hipMemcpyAsync(c->h_stage, c->d_col, col_bytes, hipMemcpyDeviceToHost, c->stream));      // (the raw frame has left the staging: same stream)
@@ -610,16 +586,19 @@ int tsframe_neighbours(void *ctx, int level, const double *uv, int n, double mu,
     if (sigma == 0.0) { c->err = "sigma == 0 (tool::CalNormvec returns false)"; return TSFRAME_ERR_ARG; }
     if (n == 0) return TSFRAME_OK;
     hipSetDevice(c->device);
-    const size_t o_uv = 0, o_I = al256(16*(size_t)n), o_N = o_I + al256(64*(size_t)n), o_in = o_N + al256(64*(size_t)n), tot = o_in + al256(n);
-    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
-    uint8_t *d = c->d_work;
-    memcpy(c->h_stage, uv, 16*(size_t)n);
-    CKF(hipMemcpyAsync(d + o_uv, c->h_stage, 16*(size_t)n, hipMemcpyHostToDevice, c->stream));
+    // one block: uv || inten8 | ninten8 | in
+    Layout L(256);
+    const auto a_uv = L.take<double>(2*(size_t)n);
+    const auto a_I = L.take<double>(8*(size_t)n), a_N = L.take<double>(8*(size_t)n); const auto a_in = L.take<uint8_t>((size_t)n);
+    CKF(grow_device(c->d_work, c->d_cap, L.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, L.mark()));
+    void *h = c->h_stage, *d = c->d_work;
+    a_uv.put(h, uv);
+    CKF(hipMemcpyAsync(d, h, a_uv.bytes(), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_neighbours, dim3((8*n + 255)/256), dim3(256), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], c->w[level], c->h[level],
-                       (const double *)(d + o_uv), n, mu, sigma, (double *)(d + o_I), (double *)(d + o_N), d + o_in);
-    CKF(hipMemcpyAsync(c->h_stage + o_I, d + o_I, tot - o_I, hipMemcpyDeviceToHost, c->stream));
+                       a_uv.at(d), n, mu, sigma, a_I.at(d), a_N.at(d), a_in.at(d));
+    CKF(hipMemcpyAsync(a_I.at(h), a_I.at(d), L.mark() - a_I.off, hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream)); CKF(hipGetLastError());
-    memcpy(inten8, c->h_stage + o_I, 64*(size_t)n); memcpy(ninten8, c->h_stage + o_N, 64*(size_t)n); memcpy(in, c->h_stage + o_in, n);
+    a_I.get(h, inten8); a_N.get(h, ninten8); a_in.get(h, in);
     return TSFRAME_OK;
 }
 
@@ -637,24 +616,28 @@ int tsframe_box_pixels(void *ctx, int level, const double *quad, double mu, doub
     *n_out = 0;
     if (xMax < xMin || yMax < yMin) return TSFRAME_OK;
     const size_t npx = (size_t)(xMax - xMin + 1)*(size_t)(yMax - yMin + 1);
-    const size_t o_cnt = 0, o_mask = 256, o_u = o_mask + al256(4*(((size_t)w*h + 31) >> 5)), o_v = o_u + al256(4*npx), o_I = o_v + al256(4*npx), o_N = o_I + al256(8*npx), tot = o_N + al256(8*npx);
-    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
-    uint8_t *d = c->d_work;
-    hipLaunchKernelGGL(k_box_pixels, dim3(1), dim3(1024), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], w, h, B, mu, sigma, (unsigned *)(d + o_mask),
-                       (int *)(d + o_cnt), (int *)(d + o_u), (int *)(d + o_v), (double *)(d + o_I), (double *)(d + o_N));
-    CKF(hipMemcpyAsync(c->h_stage, d + o_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    // one block, outputs only: cnt | mask (the kernel's scratch) | u | v | inten | ninten, the four arrays with room for the whole box
+    Layout L(256);
+    const auto a_cnt = L.take<int32_t>(1); const auto a_mask = L.take<unsigned>(((size_t)w*h + 31) >> 5);
+    const auto a_u = L.take<int32_t>(npx), a_v = L.take<int32_t>(npx); const auto a_I = L.take<double>(npx), a_N = L.take<double>(npx);
+    CKF(grow_device(c->d_work, c->d_cap, L.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, L.mark()));
+    void *hs = c->h_stage, *d = c->d_work;
+    hipLaunchKernelGGL(k_box_pixels, dim3(1), dim3(1024), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], w, h, B, mu, sigma, a_mask.at(d),
+                       a_cnt.at(d), a_u.at(d), a_v.at(d), a_I.at(d), a_N.at(d));
+    CKF(hipMemcpyAsync(a_cnt.at(hs), a_cnt.at(d), a_cnt.bytes(), hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream)); CKF(hipGetLastError());
-    const int n = *(const int *)c->h_stage;
+    const int n = *a_cnt.at(hs);
     *n_out = n;
     if (cap == 0 || n == 0) return TSFRAME_OK;                      // cap == 0: count only
     if (n > cap) { c->err = "tsframe_box_pixels: capacity too small (n_out holds the count)"; return TSFRAME_ERR_ARG; }
-    CKF(hipMemcpyAsync(c->h_stage + o_u, d + o_u, 4*(size_t)n, hipMemcpyDeviceToHost, c->stream));
-    CKF(hipMemcpyAsync(c->h_stage + o_v, d + o_v, 4*(size_t)n, hipMemcpyDeviceToHost, c->stream));
-    CKF(hipMemcpyAsync(c->h_stage + o_I, d + o_I, 8*(size_t)n, hipMemcpyDeviceToHost, c->stream));
-    CKF(hipMemcpyAsync(c->h_stage + o_N, d + o_N, 8*(size_t)n, hipMemcpyDeviceToHost, c->stream));
+    // the first n entries of each array come down: the same offsets, n elements
+    const Span<int32_t> g_u{a_u.off, (size_t)n}, g_v{a_v.off, (size_t)n}; const Span<double> g_I{a_I.off, (size_t)n}, g_N{a_N.off, (size_t)n};
+    CKF(hipMemcpyAsync(g_u.at(hs), g_u.at(d), g_u.bytes(), hipMemcpyDeviceToHost, c->stream));
+    CKF(hipMemcpyAsync(g_v.at(hs), g_v.at(d), g_v.bytes(), hipMemcpyDeviceToHost, c->stream));
+    CKF(hipMemcpyAsync(g_I.at(hs), g_I.at(d), g_I.bytes(), hipMemcpyDeviceToHost, c->stream));
+    CKF(hipMemcpyAsync(g_N.at(hs), g_N.at(d), g_N.bytes(), hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream));
-    memcpy(u, c->h_stage + o_u, 4*(size_t)n); memcpy(v, c->h_stage + o_v, 4*(size_t)n);
-    memcpy(inten, c->h_stage + o_I, 8*(size_t)n); memcpy(ninten, c->h_stage + o_N, 8*(size_t)n);
+    g_u.get(hs, u); g_v.get(hs, v); g_I.get(hs, inten); g_N.get(hs, ninten);
     return TSFRAME_OK;
 }
 
@@ -688,35 +671,34 @@ int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const d
     A.cos_min = cos_min; A.zncc_min = zncc_min;
     // one pinned block, inputs then outputs: planes | dete_xy | pix_off | pix_uv | pix_inten || out | bits
     const size_t nd = words > 0 ? (size_t)n_dete : 0;
-    const size_t o_pl = 0, o_dx = o_pl + al256(sizeof(JudgePlane)*(size_t)n), o_off = o_dx + al256(16*nd), o_uv = o_off + al256(4*((size_t)n + 1)),
-                 o_in = o_uv + al256(4*npix), o_out = o_in + al256(npix), o_bits = o_out + al256(sizeof(JudgeOut)*(size_t)n), tot = o_bits + al256(4*(size_t)n*words);
-    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
-    uint8_t *h = c->h_stage, *d = c->d_work;
-    JudgePlane *hp = (JudgePlane *)(h + o_pl);
+    Layout L(256);
+    const auto a_pl = L.take<JudgePlane>((size_t)n); const auto a_dx = L.take<double>(2*nd); const auto a_off = L.take<int32_t>((size_t)n + 1);
+    const auto a_uv = L.take<int16_t>(2*npix); const auto a_in = L.take<uint8_t>(npix);
+    const size_t in_end = L.mark();
+    const auto a_out = L.take<JudgeOut>((size_t)n); const auto a_bits = L.take<uint32_t>((size_t)n*words);
+    CKF(grow_device(c->d_work, c->d_cap, L.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, L.mark()));
+    void *h = c->h_stage, *d = c->d_work;
+    JudgePlane *hp = a_pl.at(h);
     for (int i = 0; i < n; i++) {
-        memcpy(hp[i].theta, theta + 3*(size_t)i, 24); memcpy(hp[i].T, Tcr + 12*(size_t)i, 96); memcpy(hp[i].ray, box_ray + 8*(size_t)i, 64);
+        std::copy_n(theta + 3*(size_t)i, 3, hp[i].theta); std::copy_n(Tcr + 12*(size_t)i, 12, hp[i].T); std::copy_n(box_ray + 8*(size_t)i, 8, hp[i].ray);
     }
-    if (nd) memcpy(h + o_dx, dete_xy, 16*nd);
-    memcpy(h + o_off, pix_off, 4*((size_t)n + 1));
-    if (npix) { memcpy(h + o_uv, pix_uv, 4*npix); memcpy(h + o_in, pix_inten, npix); }
-    CKF(hipMemcpyAsync(d, h, o_out, hipMemcpyHostToDevice, c->stream));
+    a_dx.put(h, dete_xy); a_off.put(h, pix_off); a_uv.put(h, pix_uv); a_in.put(h, pix_inten);
+    CKF(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));
     if (words > 0 && (size_t)c->w[0]*c->h[0] > (size_t)MS_MASK_WORDS*32)       // the association's mask is level-0 sized: above it, point tests instead
-        hipLaunchKernelGGL(k_text_judge<true>, dim3(n), dim3(JUDGE_NT), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], A, (const JudgePlane *)(d + o_pl),
-                           (const int *)(d + o_off), (const short *)(d + o_uv), (const uint8_t *)(d + o_in), (const double *)(d + o_dx),
-                           (JudgeOut *)(d + o_out), (unsigned *)(d + o_bits));
+        hipLaunchKernelGGL(k_text_judge<true>, dim3(n), dim3(JUDGE_NT), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], A, a_pl.at(d),
+                           a_off.at(d), a_uv.at(d), a_in.at(d), a_dx.at(d), a_out.at(d), a_bits.at(d));
     else
-        hipLaunchKernelGGL(k_text_judge<false>, dim3(n), dim3(JUDGE_NT), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], A, (const JudgePlane *)(d + o_pl),
-                           (const int *)(d + o_off), (const short *)(d + o_uv), (const uint8_t *)(d + o_in), (const double *)(d + o_dx),
-                           (JudgeOut *)(d + o_out), words > 0 ? (unsigned *)(d + o_bits) : nullptr);
+        hipLaunchKernelGGL(k_text_judge<false>, dim3(n), dim3(JUDGE_NT), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], A, a_pl.at(d),
+                           a_off.at(d), a_uv.at(d), a_in.at(d), a_dx.at(d), a_out.at(d), words > 0 ? a_bits.at(d) : nullptr);
     CKF(hipGetLastError());
-    CKF(hipMemcpyAsync(h + o_out, d + o_out, tot - o_out, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipMemcpyAsync(a_out.at(h), a_out.at(d), L.mark() - in_end, hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream));
-    const JudgeOut *ho = (const JudgeOut *)(h + o_out);
+    const JudgeOut *ho = a_out.at(h);
     for (int i = 0; i < n; i++) {
         reason[i] = ho[i].reason; pass[i] = ho[i].reason == TSFRAME_JUDGE_PASS ? 1 : 0; cos[i] = ho[i].cos; zncc[i] = ho[i].zncc;
-        memcpy(box_uv + 8*(size_t)i, ho[i].box, 64);
+        std::copy_n(ho[i].box, 8, box_uv + 8*(size_t)i);
     }
-    if (words > 0) memcpy(dete_bits, h + o_bits, 4*(size_t)n*words);
+    a_bits.get(h, dete_bits);
     return TSFRAME_OK;
 }
 
@@ -750,18 +732,20 @@ int tsframe_klt_track(void *prev_ctx, void *cur_ctx, int n, const float *prev_xy
     A.n = n; A.n_levels = need; A.win = win; A.max_iter = max_iter;
     A.eps2 = (float)eps*(float)eps; A.min_eig = (float)min_eig;
     // one pinned block: prev_xy || next_xy | status
-    const size_t o_out = al256(8*(size_t)n), o_st = o_out + al256(8*(size_t)n), tot = o_st + al256((size_t)n);
-    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
-    uint8_t *h = c->h_stage, *d = c->d_work;
-    memcpy(h, prev_xy, 8*(size_t)n);
-    CKF(hipMemcpyAsync(d, h, 8*(size_t)n, hipMemcpyHostToDevice, c->stream));
+    Layout L(256);
+    const auto a_prev = L.take<float>(2*(size_t)n);
+    const auto a_next = L.take<float>(2*(size_t)n); const auto a_st = L.take<uint8_t>((size_t)n);
+    CKF(grow_device(c->d_work, c->d_cap, L.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, L.mark()));
+    void *h = c->h_stage, *d = c->d_work;
+    a_prev.put(h, prev_xy);
+    CKF(hipMemcpyAsync(d, h, a_prev.bytes(), hipMemcpyHostToDevice, c->stream));
     const dim3 grid((n + KLT_WAVES - 1)/KLT_WAVES), block(64*KLT_WAVES);
-    if (win*win <= 64*8) hipLaunchKernelGGL(k_klt_track<8>, grid, block, 0, c->stream, A, (const float *)d, (float *)(d + o_out), d + o_st);
-    else hipLaunchKernelGGL(k_klt_track<16>, grid, block, 0, c->stream, A, (const float *)d, (float *)(d + o_out), d + o_st);
+    if (win*win <= 64*8) hipLaunchKernelGGL(k_klt_track<8>, grid, block, 0, c->stream, A, a_prev.at(d), a_next.at(d), a_st.at(d));
+    else hipLaunchKernelGGL(k_klt_track<16>, grid, block, 0, c->stream, A, a_prev.at(d), a_next.at(d), a_st.at(d));
     CKF(hipGetLastError());
-    CKF(hipMemcpyAsync(h + o_out, d + o_out, tot - o_out, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipMemcpyAsync(a_next.at(h), a_next.at(d), L.mark() - a_next.off, hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream));
-    memcpy(next_xy, h + o_out, 8*(size_t)n); memcpy(status, h + o_st, (size_t)n);
+    a_next.get(h, next_xy); a_st.get(h, status);
     return TSFRAME_OK;
 }
 
@@ -828,26 +812,28 @@ int tsframe_text_object_info(void *ctx, int n_obj, const double *quad, const dou
     const size_t nreg = want_pix ? pbase[n_obj] : 0;             // slots of the pixel regions (the sum of the clamped level-0 boxes)
     hipSetDevice(c->device);
     // one block, inputs then outputs: jobs | u | v | inten || out | ninten | inten8 | ninten8 | in | pix_u | pix_v | pix_inten | pix_ninten
-    const size_t nj = jobs.size();
-    const size_t o_u = al256(sizeof(ObjJob)*nj), o_v = o_u + al256(8*nfeat), o_I = o_v + al256(8*nfeat), o_out = o_I + al256(8*nfeat), o_n = o_out + al256(sizeof(ObjOut)*nj),
-                 o_i8 = o_n + al256(8*nfeat), o_n8 = o_i8 + al256(64*nfeat), o_in = o_n8 + al256(64*nfeat), o_pu = o_in + al256(nfeat), o_pv = o_pu + al256(4*nreg),
-                 o_pI = o_pv + al256(4*nreg), o_pN = o_pI + al256(8*nreg), tot = o_pN + al256(8*nreg);
-    int rc = ensure_stage(c, tot, tot); if (rc) return rc;
-    uint8_t *h = c->h_stage, *d = c->d_work;
-    memcpy(h, jobs.data(), sizeof(ObjJob)*nj);
+    Layout S(256);
+    const auto a_job = S.take<ObjJob>(jobs.size()); const auto a_u = S.take<double>(nfeat), a_v = S.take<double>(nfeat), a_I = S.take<double>(nfeat);
+    const size_t in_end = S.mark();
+    const auto a_out = S.take<ObjOut>(jobs.size()); const auto a_n = S.take<double>(nfeat), a_i8 = S.take<double>(8*nfeat), a_n8 = S.take<double>(8*nfeat);
+    const auto a_in = S.take<uint8_t>(nfeat);
+    const size_t feat_end = S.mark();                            // a count-only call's copy down ends here
+    const auto a_pu = S.take<int32_t>(nreg), a_pv = S.take<int32_t>(nreg); const auto a_pI = S.take<double>(nreg), a_pN = S.take<double>(nreg);
+    CKF(grow_device(c->d_work, c->d_cap, S.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, S.mark()));
+    void *h = c->h_stage, *d = c->d_work;
+    a_job.put(h, jobs.data());
     for (int i = 0; i < n_obj; i++) {
         const size_t b = (size_t)feat_off[i]*L, m = fbase[i + 1] - fbase[i];
         if (!m) continue;
-        memcpy(h + o_u + 8*fbase[i], u + b, 8*m); memcpy(h + o_v + 8*fbase[i], v + b, 8*m); memcpy(h + o_I + 8*fbase[i], inten + b, 8*m);
+        std::copy_n(u + b, m, a_u.at(h) + fbase[i]); std::copy_n(v + b, m, a_v.at(h) + fbase[i]); std::copy_n(inten + b, m, a_I.at(h) + fbase[i]);
     }
-    CKF(hipMemcpyAsync(d, h, o_out, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_object_info, dim3((unsigned)nj), dim3(OBJ_NT), 0, c->stream, (const ObjJob *)d, (const double *)(d + o_u), (const double *)(d + o_v),
-                       (const double *)(d + o_I), (ObjOut *)(d + o_out), (double *)(d + o_n), (double *)(d + o_i8), (double *)(d + o_n8), d + o_in,
-                       (int *)(d + o_pu), (int *)(d + o_pv), (double *)(d + o_pI), (double *)(d + o_pN));
+    CKF(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_object_info, dim3((unsigned)a_job.n), dim3(OBJ_NT), 0, c->stream, a_job.at(d), a_u.at(d), a_v.at(d), a_I.at(d),
+                       a_out.at(d), a_n.at(d), a_i8.at(d), a_n8.at(d), a_in.at(d), a_pu.at(d), a_pv.at(d), a_pI.at(d), a_pN.at(d));
     CKF(hipGetLastError());
-    CKF(hipMemcpyAsync(h + o_out, d + o_out, (want_pix ? tot : o_pu) - o_out, hipMemcpyDeviceToHost, c->stream));
+    CKF(hipMemcpyAsync(a_out.at(h), a_out.at(d), (want_pix ? S.mark() : feat_end) - in_end, hipMemcpyDeviceToHost, c->stream));
     CKF(hipStreamSynchronize(c->stream));
-    const ObjOut *ho = (const ObjOut *)(h + o_out);
+    const ObjOut *ho = a_out.at(h);
     long long total = 0;
     pix_off[0] = 0;
     for (int i = 0; i < n_obj; i++) {
@@ -857,8 +843,8 @@ int tsframe_text_object_info(void *ctx, int n_obj, const double *quad, const dou
         }
         const size_t b = (size_t)feat_off[i]*L, m = fbase[i + 1] - fbase[i];
         if (m) {
-            memcpy(ninten + b, h + o_n + 8*fbase[i], 8*m); memcpy(inten8 + 8*b, h + o_i8 + 64*fbase[i], 64*m);
-            memcpy(ninten8 + 8*b, h + o_n8 + 64*fbase[i], 64*m); memcpy(in + b, h + o_in + fbase[i], m);
+            std::copy_n(a_n.at(h) + fbase[i], m, ninten + b); std::copy_n(a_i8.at(h) + 8*fbase[i], 8*m, inten8 + 8*b);          // (8 taps per feature)
+            std::copy_n(a_n8.at(h) + 8*fbase[i], 8*m, ninten8 + 8*b); std::copy_n(a_in.at(h) + fbase[i], m, in + b);
         }
         total += std::min((long long)ho[(size_t)i*L].npix, (long long)(pbase[i + 1] - pbase[i]));
         pix_off[i + 1] = (int32_t)std::min(total, (long long)INT32_MAX);
@@ -868,8 +854,8 @@ int tsframe_text_object_info(void *ctx, int n_obj, const double *quad, const dou
     for (int i = 0; i < n_obj; i++) {                            // close the gaps between the regions
         const size_t src = pbase[i], dst = (size_t)pix_off[i], m = (size_t)(pix_off[i + 1] - pix_off[i]);
         if (!m) continue;
-        memcpy(pix_u + dst, h + o_pu + 4*src, 4*m); memcpy(pix_v + dst, h + o_pv + 4*src, 4*m);
-        memcpy(pix_inten + dst, h + o_pI + 8*src, 8*m); memcpy(pix_ninten + dst, h + o_pN + 8*src, 8*m);
+        std::copy_n(a_pu.at(h) + src, m, pix_u + dst); std::copy_n(a_pv.at(h) + src, m, pix_v + dst);
+        std::copy_n(a_pI.at(h) + src, m, pix_inten + dst); std::copy_n(a_pN.at(h) + src, m, pix_ninten + dst);
     }
     return TSFRAME_OK;
 }

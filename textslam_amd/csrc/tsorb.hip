@@ -1488,9 +1488,9 @@ struct OCtx {
     OrbDev D;
     // the SLAM front-end calls once per frame with the same geometry: buffers and pinned staging are kept between calls
     MatchDev M; bool m_set = false; void *m_buf = nullptr; size_t m_cap = 0; void *m_feat = nullptr; size_t m_feat_cap = 0;   // search grid of the current frame
-    void *mq_dev = nullptr, *mq_host = nullptr; size_t mq_cap = 0;
+    void *mq_host = nullptr; size_t mq_cap = 0;                                 // tsorb_match_search: pinned block, read and written by the kernel through its device alias
     bool ran = false;                                                           // the resident batch has been through tsorb_run (its level 0 is in place)
-    CvoDev CV; int cv_w = 0, cv_h = 0, cv_nd = 0; void *cv_geo = nullptr, *cv_det = nullptr, *cv_sel = nullptr, *cv_pin = nullptr; size_t cv_sel_cap = 0, cv_pin_cap = 0;   // tsorb_text_extract's scratch, kept between calls
+    CvoDev CV; int cv_w = 0, cv_h = 0, cv_nd = 0; void *cv_geo = nullptr, *cv_det = nullptr, *cv_sel = nullptr, *cv_pin = nullptr; size_t cv_det_cap = 0, cv_sel_cap = 0, cv_pin_cap = 0;   // tsorb_text_extract's scratch, kept between calls
     void *br_dev = nullptr, *br_pin = nullptr; size_t br_dev_cap = 0, br_pin_cap = 0;                       // tsorb_match_brute_*: device block and pinned staging, kept between calls
     int key[5] = {0, 0, 0, 0, 0}; uint8_t *h_img = nullptr; void *h_out = nullptr; size_t h_img_sz = 0, h_out_sz = 0;
 };
@@ -1535,7 +1535,7 @@ int tsorb_create(void **ctx, int nfeatures, float scale, int nlevels, int ini_th
 int tsorb_destroy(void *ctx) { OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG; hipSetDevice(c->device); ofree(c);
     if (c->h_fb) hipHostFree(c->h_fb);
     if (c->cv_geo) hipFree(c->cv_geo); if (c->cv_det) hipFree(c->cv_det); if (c->cv_sel) hipFree(c->cv_sel); if (c->cv_pin) hipHostFree(c->cv_pin);
-    if (c->m_buf) hipFree(c->m_buf); if (c->m_feat) hipFree(c->m_feat); if (c->mq_dev) hipFree(c->mq_dev); if (c->mq_host) hipHostFree(c->mq_host);
+    if (c->m_buf) hipFree(c->m_buf); if (c->m_feat) hipFree(c->m_feat); if (c->mq_host) hipHostFree(c->mq_host);
     if (c->br_dev) hipFree(c->br_dev); if (c->br_pin) hipHostFree(c->br_pin);
     hipStreamDestroy(c->stream); delete c; return TSORB_OK; }
 const char *tsorb_last_error(void *ctx) { return ctx ? ((OCtx *)ctx)->err.c_str() : "null ctx"; }
@@ -1765,7 +1765,7 @@ int tsorb_debug_level(void *ctx, int frame, int level, int blurred, uint8_t *out
 static int match_build(OCtx *c, const float *kp_dev, const uint8_t *desc_dev, int n, double min_x, double max_x, double min_y, double max_y) {
     if (!(max_x > min_x) || !(max_y > min_y) || n < 0) return TSORB_ERR_ARG;
     const size_t need = sizeof(int)*((size_t)2*std::max(n, 1) + MG_CELLS + 1);
-    if (c->m_cap < need) { if (c->m_buf) hipFree(c->m_buf); c->m_cap = 0; OCK(hipMalloc(&c->m_buf, need)); c->m_cap = need; }
+    OCK(grow_device(c->m_buf, c->m_cap, need));
     MatchDev &M = c->M;
     M.kp = kp_dev; M.desc = desc_dev; M.n = n; M.min_x = min_x; M.min_y = min_y;
     M.iw = (double)MG_COLS/(max_x - min_x); M.ih = (double)MG_ROWS/(max_y - min_y);          // frame.cc:124-125
@@ -1789,7 +1789,7 @@ int tsorb_match_set_features(void *ctx, const float *kp6, const uint8_t *desc, i
     OCtx *c = (OCtx *)ctx; if (!c || n < 0 || (n > 0 && (!kp6 || !desc))) return TSORB_ERR_ARG;
     hipSetDevice(c->device);
     const size_t bk = sizeof(float)*6*(size_t)std::max(n, 1), need = bk + 32*(size_t)std::max(n, 1);
-    if (c->m_feat_cap < need) { if (c->m_feat) hipFree(c->m_feat); c->m_feat_cap = 0; OCK(hipMalloc(&c->m_feat, need)); c->m_feat_cap = need; }
+    OCK(grow_device(c->m_feat, c->m_feat_cap, need));
     if (n > 0) { OCK(hipMemcpyAsync(c->m_feat, kp6, sizeof(float)*6*(size_t)n, hipMemcpyHostToDevice, c->stream));
                  OCK(hipMemcpyAsync((char *)c->m_feat + bk, desc, 32*(size_t)n, hipMemcpyHostToDevice, c->stream)); OCK(hipStreamSynchronize(c->stream)); }
     return match_build(c, (const float *)c->m_feat, (const uint8_t *)c->m_feat + bk, n, min_x, max_x, min_y, max_y);
@@ -1800,29 +1800,23 @@ int tsorb_match_search(void *ctx, int nq, const float *qxy, const float *qr, con
     if (nq == 0) return TSORB_OK;
     hipSetDevice(c->device);
     // one pinned staging block in, one out: [qxy | qr | qlev | qdesc]  ->  [cand_idx | cand_dist | cnt | best | dist | dist2]
-    const size_t b_xy = 8*(size_t)nq, b_r = 4*(size_t)nq, b_lev = 8*(size_t)nq, b_d = 32*(size_t)nq, in_sz = b_xy + b_r + b_lev + b_d;
-    const size_t b_c = 4*(size_t)nq*max_cand, out_sz = 2*b_c + 16*(size_t)nq, tot = in_sz + out_sz;
-    if (c->mq_cap < tot) { if (c->mq_host) hipHostFree(c->mq_host); c->mq_cap = 0;
-        OCK(hipHostMalloc(&c->mq_host, tot, hipHostMallocDefault)); c->mq_cap = tot; }
-    char *h = (char *)c->mq_host, *d = nullptr;
-    memcpy(h, qxy, b_xy); memcpy(h + b_xy, qr, b_r);
-    if (qlev) memcpy(h + b_xy + b_r, qlev, b_lev); else for (size_t k = 0; k < 2*(size_t)nq; k++) ((int32_t *)(h + b_xy + b_r))[k] = -1;
-    memcpy(h + b_xy + b_r + b_lev, qdesc, b_d);
+    // (every size is a multiple of 4: the block is packed)
+    const size_t NQ = (size_t)nq;
+    Layout L(4);
+    const auto a_xy = L.take<float>(2*NQ), a_r = L.take<float>(NQ); const auto a_lev = L.take<int32_t>(2*NQ); const auto a_d = L.take<uint8_t>(32*NQ);
+    const auto a_ci = L.take<int32_t>(NQ*(size_t)max_cand), a_cd = L.take<int32_t>(NQ*(size_t)max_cand), a_cc = L.take<int32_t>(NQ), a_bi = L.take<int32_t>(NQ),
+               a_bd = L.take<int32_t>(NQ), a_bd2 = L.take<int32_t>(NQ);
+    OCK(grow_pinned(c->mq_host, c->mq_cap, L.mark()));
+    void *h = c->mq_host, *d = nullptr;
+    a_xy.put(h, qxy); a_r.put(h, qr); a_d.put(h, qdesc);
+    if (qlev) a_lev.put(h, qlev); else std::fill_n(a_lev.at(h), a_lev.n, -1);
     // (round 6: the kernel reads the queries from, and stores the results into, the pinned block itself -- a wave reads its query's 52 bytes once, the results are a few KB (or
     // the candidate lists' 8 bytes per entry): two copies on the stream cost the call more than the bus does; d = the block's device address)
-    { void *hd = nullptr; OCK(hipHostGetDevicePointer(&hd, c->mq_host, 0)); d = (char *)hd; }
-    int *o_ci = (int *)(d + in_sz), *o_cd = o_ci + (size_t)nq*max_cand, *o_cnt = o_cd + (size_t)nq*max_cand, *o_bi = o_cnt + nq, *o_bd = o_bi + nq, *o_bd2 = o_bd + nq;
-    hipLaunchKernelGGL(k_match, dim3((nq + 3)/4), dim3(256), 0, c->stream, c->M, nq, (const float *)d, (const float *)(d + b_xy), (const int *)(d + b_xy + b_r),
-                       (const uint8_t *)(d + b_xy + b_r + b_lev), max_cand, o_ci, o_cd, o_cnt, o_bi, o_bd, o_bd2);
+    OCK(hipHostGetDevicePointer(&d, c->mq_host, 0));
+    hipLaunchKernelGGL(k_match, dim3((nq + 3)/4), dim3(256), 0, c->stream, c->M, nq, a_xy.at(d), a_r.at(d), a_lev.at(d), a_d.at(d), max_cand,
+                       a_ci.at(d), a_cd.at(d), a_cc.at(d), a_bi.at(d), a_bd.at(d), a_bd2.at(d));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    const char *ho = h + in_sz;
-    if (cand_idx) memcpy(cand_idx, ho, b_c);
-    if (cand_dist) memcpy(cand_dist, ho + b_c, b_c);
-    const int32_t *tail = (const int32_t *)(ho + 2*b_c);
-    if (cand_cnt) memcpy(cand_cnt, tail, 4*(size_t)nq);
-    if (best_idx) memcpy(best_idx, tail + nq, 4*(size_t)nq);
-    if (best_dist) memcpy(best_dist, tail + 2*(size_t)nq, 4*(size_t)nq);
-    if (best_dist2) memcpy(best_dist2, tail + 3*(size_t)nq, 4*(size_t)nq);
+    a_ci.get(h, cand_idx); a_cd.get(h, cand_dist); a_cc.get(h, cand_cnt); a_bi.get(h, best_idx); a_bd.get(h, best_dist); a_bd2.get(h, best_dist2);
     return TSORB_OK;
 }
 
@@ -1845,7 +1839,7 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
     const int nd = n_dete;
     // ---- geometry: cv::ORB's levels, quotas, tiles (docs/cvorb_recalled.md); the planes shared by the detections
     if (c->cv_w != D.w || c->cv_h != D.h) {
-        if (c->cv_geo) hipFree(c->cv_geo); if (c->cv_det) hipFree(c->cv_det); c->cv_geo = c->cv_det = nullptr; c->cv_nd = 0; c->cv_w = c->cv_h = 0;
+        if (c->cv_geo) hipFree(c->cv_geo); c->cv_geo = nullptr; c->cv_w = c->cv_h = 0;
         memset(&C, 0, sizeof(C)); C.w = D.w; C.h = D.h;
         size_t off = 0, boff = 0; int t0 = 0, rt = 0;
         for (int l = 0; l < CVO_NL; l++) { CvoLevel &G = C.L[l];
@@ -1869,25 +1863,26 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
         for (int l = 0; l < CVO_NL - 1; l++) { C.L[l].quota = cv_round_f(nf); sum += C.L[l].quota; nf *= factor; }
         C.L[CVO_NL - 1].quota = std::max(nfeatures - sum, 0);
     }
-    const size_t NT = (size_t)C.ntiles;
-    if (c->cv_nd < nd) {
-        if (c->cv_det) hipFree(c->cv_det); c->cv_det = nullptr; c->cv_nd = 0;
-        const size_t per = 4*(size_t)MS_MASK_WORDS + 16*CVO_NL + C.m_stride + 2*4*NT*CVO_TCAP + 4*NT + 4*(size_t)CVO_NL*CVO_MAX_H + 4*CVO_NL + 8*CVO_NL;
-        OCK(hipMalloc(&c->cv_det, per*(size_t)nd)); c->cv_nd = nd;
-    }
-    {   uint8_t *p = (uint8_t *)c->cv_det; const size_t n = (size_t)c->cv_nd;          // (arrays sized for the largest call so far)
-        C.mask = (unsigned *)p; p += 4*(size_t)MS_MASK_WORDS*n; C.dfoot = (int *)p; p += 16*(size_t)CVO_NL*n; C.M = p; p += C.m_stride*n;
-        C.tkp = (uint32_t *)p; p += 4*NT*CVO_TCAP*n; C.tkey = (uint32_t *)p; p += 4*NT*CVO_TCAP*n; C.tcnt = (int *)p; p += 4*NT*n;
-        C.rowoff = (int *)p; p += 4*(size_t)CVO_NL*CVO_MAX_H*n; C.lvlcnt = (int *)p; p += 4*(size_t)CVO_NL*n; C.thr = (uint32_t *)p; }
-    const size_t need_sel = sizeof(float4)*(size_t)nd*cap;
-    if (c->cv_sel_cap < need_sel) { if (c->cv_sel) hipFree(c->cv_sel); c->cv_sel = nullptr; c->cv_sel_cap = 0; OCK(hipMalloc(&c->cv_sel, need_sel)); c->cv_sel_cap = need_sel; }
+    // ---- the per-detection device arrays, CvoDev's [nd][...] members in its order, sized for the largest call so far (every size is a multiple of 4: packed)
+    {   const size_t NT = (size_t)C.ntiles, n = (size_t)std::max(c->cv_nd, nd);
+        Layout Ld(4);
+        const auto a_mask = Ld.take<unsigned>(MS_MASK_WORDS*n); const auto a_dfoot = Ld.take<int>(4*CVO_NL*n); const auto a_M = Ld.take<uint8_t>(C.m_stride*n);
+        const auto a_tkp = Ld.take<uint32_t>(NT*CVO_TCAP*n), a_tkey = Ld.take<uint32_t>(NT*CVO_TCAP*n);
+        const auto a_tcnt = Ld.take<int>(NT*n), a_rowoff = Ld.take<int>((size_t)CVO_NL*CVO_MAX_H*n), a_lvlcnt = Ld.take<int>(CVO_NL*n); const auto a_thr = Ld.take<uint32_t>(2*CVO_NL*n);
+        OCK(grow_device(c->cv_det, c->cv_det_cap, Ld.mark())); c->cv_nd = (int)n;
+        void *p = c->cv_det;
+        C.mask = a_mask.at(p); C.dfoot = a_dfoot.at(p); C.M = a_M.at(p); C.tkp = a_tkp.at(p); C.tkey = a_tkey.at(p); C.tcnt = a_tcnt.at(p);
+        C.rowoff = a_rowoff.at(p); C.lvlcnt = a_lvlcnt.at(p); C.thr = a_thr.at(p); }
+    OCK(grow_device(c->cv_sel, c->cv_sel_cap, sizeof(float4)*(size_t)nd*cap));
     C.sel = (float4 *)c->cv_sel;
-    // ---- one pinned block: [corners | footprints] in, [count | kp | desc] out
-    const size_t b_in = 160*(size_t)nd, b_cnt = ((4*(size_t)nd + 15)/16)*16, b_kp = 24*(size_t)nd*cap, b_desc = 32*(size_t)nd*cap, tot = b_in + b_cnt + b_kp + b_desc;
-    if (c->cv_pin_cap < tot) { if (c->cv_pin) hipHostFree(c->cv_pin); c->cv_pin = nullptr; c->cv_pin_cap = 0; OCK(hipHostMalloc(&c->cv_pin, tot, hipHostMallocDefault)); c->cv_pin_cap = tot; }
-    char *h = (char *)c->cv_pin, *dp = nullptr;
-    { void *hd = nullptr; OCK(hipHostGetDevicePointer(&hd, c->cv_pin, 0)); dp = (char *)hd; }
-    int *h_quad = (int *)h, *h_foot = (int *)(h + 32*(size_t)nd);
+    // ---- one pinned block: [corners | footprints] in, [count | kp | desc] out; the kernels read and write it through its device alias dp
+    Layout L(16);
+    const auto a_quad = L.take<int>(8*(size_t)nd), a_foot = L.take<int>(4*CVO_NL*(size_t)nd);
+    const auto a_cnt = L.take<int>((size_t)nd); const auto a_kp = L.take<float>(6*(size_t)nd*cap); const auto a_desc = L.take<uint8_t>(32*(size_t)nd*cap);
+    OCK(grow_pinned(c->cv_pin, c->cv_pin_cap, L.mark()));
+    void *h = c->cv_pin, *dp = nullptr;
+    OCK(hipHostGetDevicePointer(&dp, c->cv_pin, 0));
+    int *h_quad = a_quad.at(h), *h_foot = a_foot.at(h);
     for (int d = 0; d < nd; d++) {
         int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
         for (int k = 0; k < 4; k++) { const int x = (int)quad[8*d + 2*k], y = (int)quad[8*d + 2*k + 1];         // cv::Point(double, double): truncation
@@ -1907,8 +1902,7 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
     }
     C.nd = nd; C.cap = cap;
     C.img0 = D.pyr + (size_t)frame*D.pyr_frame + D.L[0].pyr_off + (size_t)EDGE*D.L[0].bw + EDGE; C.pitch0 = D.L[0].bw;
-    C.quad = (const int *)dp; C.foot = (const int *)(dp + 32*(size_t)nd);
-    C.o_cnt = (int *)(dp + b_in); C.o_kp = (float *)(dp + b_in + b_cnt); C.o_desc = (uint8_t *)(dp + b_in + b_cnt + b_kp);
+    C.quad = a_quad.at(dp); C.foot = a_foot.at(dp); C.o_cnt = a_cnt.at(dp); C.o_kp = a_kp.at(dp); C.o_desc = a_desc.at(dp);
     hipLaunchKernelGGL(k_cvo_mask, dim3(nd), dim3(256), 0, c->stream, C);
     for (int l = 1; l < CVO_NL; l++) hipLaunchKernelGGL(k_cvo_resize, dim3((C.L[l].w + 63)/64, (C.L[l].h + 3)/4, 1 + nd), dim3(256), 0, c->stream, C, l);
     hipLaunchKernelGGL(k_cvo_blur, dim3(C.ntiles), dim3(256), 0, c->stream, C);
@@ -1917,11 +1911,11 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
     hipLaunchKernelGGL(k_cvo_place, dim3(C.ntiles, nd), dim3(CVO_TCAP), 0, c->stream, C);
     hipLaunchKernelGGL(k_cvo_describe, dim3(CVO_DESC_BLOCKS, nd), dim3(256), 0, c->stream, C);
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
-    const int *o_cnt = (const int *)(h + b_in); const char *o_kp = h + b_in + b_cnt, *o_desc = h + b_in + b_cnt + b_kp;
+    const int *o_cnt = a_cnt.at(h); const float *o_kp = a_kp.at(h); const uint8_t *o_desc = a_desc.at(h);
     int rc = TSORB_OK;
     for (int d = 0; d < nd; d++) { const int n = o_cnt[d]; count[d] = n;
         if (n > cap) { rc = bad("a detection has more keypoints than cap (count[] is complete, nothing written for it)"); continue; }
-        memcpy(kp + 6*(size_t)d*cap, o_kp + 24*(size_t)d*cap, 24*(size_t)n); memcpy(desc + 32*(size_t)d*cap, o_desc + 32*(size_t)d*cap, 32*(size_t)n); }
+        std::copy_n(o_kp + 6*(size_t)d*cap, 6*(size_t)n, kp + 6*(size_t)d*cap); std::copy_n(o_desc + 32*(size_t)d*cap, 32*(size_t)n, desc + 32*(size_t)d*cap); }
     return rc;
 }
 

@@ -1,4 +1,4 @@
-// tsstage.h -- how a one-call entry point (tsorb_match_*, tsloop_*) stages its data.  Host only.
+// tsstage.h -- how a one-call entry point (tsorb_match_*, tsorb_text_extract, tsloop_*, libtsframe's feature calls) stages its data.  Host only.
 //
 // Such a call keeps one pinned block and one device block on its context, grown on demand (grow_pinned / grow_device), and lays its
 // sub-arrays [in | scratch | out] into them at aligned offsets: a Layout hands out Spans in the order of the call's layout comment.  A
@@ -21,7 +21,7 @@ template <class T> struct Span {
     void get(const void *base, T *dst) const { if (n && dst) memcpy(dst, at(base), bytes()); }          // copy down; an array the caller omitted is skipped
 };
 
-// a running offset, rounded up to `align` after every take (16 in libtsorb, 256 in libtsloop); a copy of a Layout continues from the same offset on its own
+// a running offset, rounded up to `align` after every take (16 in libtsorb, 256 in libtsloop and libtsframe, 4 for a packed block of 32-bit words); a copy of a Layout continues from the same offset on its own
 struct Layout {
     explicit Layout(size_t align) : align_(align) {}
     template <class T> Span<T> take(size_t n) { const Span<T> s{cur_, n}; cur_ = (s.end() + align_ - 1)/align_*align_; return s; }
