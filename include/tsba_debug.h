@@ -56,7 +56,17 @@ int  tsba_time_linearize(void *ctx, int level, int n, double *avg_ms, double *al
  * over n repetitions on the S, g left by the last solve / tsba_debug_reduced_system; HIP events on the library's stream. */
 int  tsba_debug_time_solve(void *ctx, int n, double *avg_ms);
 
-/* Test / diagnostics switches of one context (never read from the environment; all zero = production behaviour).  They select
+/* Test hook: the window's reduced-system solver on a GIVEN system, under the context's solve_variant.  Needs an uploaded window on one GPU whose reduced
+ * system is stored dense (solver_info [1] == 0), else TSBA_ERR_STATE.  nfree in 1 .. n_kf; S [6 nfree][6 nfree] row-major, only the lower triangle is
+ * read; g [6 nfree]; free block b stands for keyframe b, the other keyframes are constant.  assembly_failed: the failure flag an assembly would have
+ * raised.  dp [6 n_kf]: the step S dp = -g by keyframe (zeros for the constant keyframes and for a failed step).  failed[0]: the solver's failure flag
+ * in the LM state (non-positive or NaN pivot, or assembly_failed); failed[1]: what the workgroups that poll the step would have read as its flag:
+ * 0 solved, 1 failed, -2 neither (never published), -1 where the schedule does not poll (solve_variant 1 - 4).  Where the schedule polls, the solver
+ * runs as the solver workgroup of k_solve_back does, the slots NaN beforehand.  The context is left as it was: a tsba_solve afterwards gives the bits
+ * of a fresh context. */
+int  tsba_debug_solve_given(void *ctx, int nfree, const double *S, const double *g, int assembly_failed, double *dp, int32_t failed[2]);
+
+/* Test / diagnostics switches of one context(never read from the environment; all zero = production behaviour).  They select
  * between solver paths that are all exact -- none of them changes what is computed, only by which kernels. */
 typedef struct tsba_debug_options {
     int32_t band_parts;        /* > 0: number of interiors of the partitioned band solver (1 = single-workgroup streaming solver) */

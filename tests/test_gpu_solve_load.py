@@ -9,7 +9,7 @@ The windows are those of test_small_window_solver_schedules_agree: 4, 5, 7, 20 (
 behind step 0), fewer rows than one round of the panel lanes, rows past the loader waves' first batch and past one round of the panel lanes (28 free poses:
 168 rows), and 10 / 20 blocks of the back-substitution's register sets.
 
-(A numerically failed factorisation -- a non-positive pivot -- is not among the cases: no existing test has a recipe that produces one.)"""
+(A numerically failed factorisation -- a non-positive pivot -- under the same schedules: tests/test_gpu_window_failed_steps.py.)"""
 import numpy as np
 import pytest
 

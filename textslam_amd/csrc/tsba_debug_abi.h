@@ -337,7 +337,62 @@ int tsba_debug_time_solve(void *ctx, int n, double *avg_ms) {     // n back-to-b
     return TSBA_OK;
 }
 
-int tsba_debug_copy_S(void *ctx, double *out) {      // (6 n_kf + 1) x (6 n_kf): factored S and the rhs row after a solve
+// Test hook: the window's reduced-system solver on a system the caller gives.  S [6 nfree][6 nfree] row-major (only the lower triangle is read, as the
+// solver does), g [6 nfree]: free block b becomes keyframe b, the other keyframes are constant.  Runs what a trial of the context's schedule runs on the
+// solver's side: where the back-substitution blocks poll the step (W.dp_poll: production, solve_variant 5, 6) k_solve_back with no back block -- a grid of
+// the solver workgroup alone, solve_body<false, true> with its load by rows and its published stores, the slots NaN beforehand as a decision leaves them --
+// otherwise launch_solve (k_solve_t, k_solve_la, the multi-workgroup dense Cholesky).  assembly_failed: the flag an assembly raises (LmState.step_fail on entry).
+// dp [6 n_kf] by keyframe (= by free block for the first nfree, the constant keyframes' zeros behind them).  failed[0] = LmState.step_fail afterwards;
+// failed[1] = what the polling blocks would have read in the flag's slot dp[6 n_kf]: 0 solved, 1 failed, -2 anything else (never published), -1 where
+// the schedule does not poll.  The context's S, g, dp, free blocks and LM state are put back: a tsba_solve afterwards is that of a fresh context.
+int tsba_debug_solve_given(void *ctx, int nfree, const double *S, const double *g, int assembly_failed, double *dp, int32_t *failed) {
+    Ctx *c = (Ctx *)ctx; if (!c || !S || !g || !dp || !failed) return TSBA_ERR_ARG;
+    if (!c->uploaded) return TSBA_ERR_STATE;
+    Work &W = c->W;
+    if (W.band || c->pose_only || is_multi(c)) { set_err(c, "tsba_debug_solve_given: needs a window on one GPU whose reduced system is stored dense"); return TSBA_ERR_STATE; }
+    if (nfree < 1 || nfree > c->n_kf) { set_err(c, "tsba_debug_solve_given: nfree out of range"); return TSBA_ERR_ARG; }
+    hipSetDevice(c->device);
+    { int rca = set_solver_attrs(c); if (rca) return rca; }
+    CK(hipStreamSynchronize(c->stream));
+    const size_t N = (size_t)W.N, ld = (size_t)W.ldS, n = 6*(size_t)nfree;
+    std::vector<double> S0(c->S_count), g0(N), dp0(N + 2), nans(N + 1, __builtin_nan(""));
+    std::vector<int> fi0(c->n_kf), fi(c->n_kf, -1); int nf0[2], nf[2] = {nfree, 0}; LmState st0; const int bw0 = c->cur_bw_rows;
+    CK(hipMemcpy(S0.data(), c->S_alloc, sizeof(double)*S0.size(), hipMemcpyDeviceToHost)); CK(hipMemcpy(g0.data(), W.g, sizeof(double)*N, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(dp0.data(), W.dp, sizeof(double)*(N + 2), hipMemcpyDeviceToHost)); CK(hipMemcpy(fi0.data(), W.fidx, sizeof(int)*c->n_kf, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(nf0, W.nfree, sizeof(nf0), hipMemcpyDeviceToHost)); CK(hipMemcpy(&st0, W.st, sizeof(st0), hipMemcpyDeviceToHost));
+    std::vector<double> Sh(S0), gh(g0);
+    for (size_t i = 0; i < n; i++) { gh[i] = g[i]; for (size_t j = 0; j <= i; j++) Sh[i*ld + j] = S[i*n + j]; }
+    for (int b = 0; b < nfree; b++) fi[b] = b;
+    LmState st = st0; st.done = 0; st.step_fail = assembly_failed ? 1 : 0;
+    CK(hipMemcpy(c->S_alloc, Sh.data(), sizeof(double)*Sh.size(), hipMemcpyHostToDevice)); CK(hipMemcpy(W.g, gh.data(), sizeof(double)*N, hipMemcpyHostToDevice));
+    CK(hipMemcpy(W.fidx, fi.data(), sizeof(int)*c->n_kf, hipMemcpyHostToDevice)); CK(hipMemcpy(W.nfree, nf, sizeof(nf), hipMemcpyHostToDevice));
+    CK(hipMemcpy(W.st, &st, sizeof(st), hipMemcpyHostToDevice));
+    if (W.dp_poll) CK(hipMemcpy(W.dp, nans.data(), sizeof(double)*(N + 1), hipMemcpyHostToDevice));       // ("not there yet", as a decision leaves the slots)
+    int use_lds; const int lds = solve_lds_bytes(c, &use_lds);
+    if (W.dp_poll) {
+        const LevelDev &D = c->lev[c->opt.levels[0]]; const int ldsb = solve_back_lds_bytes(lds, W.N), v = c->dbg.solve_variant;
+        if (v == 6) LAUNCHK((k_solve_back<true, true>), dim3(1), dim3(SOLVE_THREADS), ldsb, c->stream, W, D, 0, 0, 0);
+        else if (v == 5) LAUNCHK(k_solve_back<false>, dim3(1), dim3(SOLVE_THREADS), ldsb, c->stream, W, D, 0, 0, 0);
+        else LAUNCHK(k_solve_back<true>, dim3(1), dim3(SOLVE_THREADS), ldsb, c->stream, W, D, 0, 0, 0);
+    } else {
+        if (!use_lds) c->cur_bw_rows = W.N;                        // (the multi-workgroup Cholesky: a given system is dense)
+        launch_solve(c);
+    }
+    const hipError_t e1 = hipStreamSynchronize(c->stream), e2 = hipGetLastError();
+    c->cur_bw_rows = bw0;
+    CK(e1); CK(e2);
+    std::vector<double> out(N + 1);
+    CK(hipMemcpy(out.data(), W.dp, sizeof(double)*(N + 1), hipMemcpyDeviceToHost)); CK(hipMemcpy(&st, W.st, sizeof(st), hipMemcpyDeviceToHost));
+    memcpy(dp, out.data(), sizeof(double)*N);
+    failed[0] = st.step_fail;
+    failed[1] = !W.dp_poll ? -1 : out[N] == 0.0 ? 0 : out[N] == 1.0 ? 1 : -2;
+    CK(hipMemcpy(c->S_alloc, S0.data(), sizeof(double)*S0.size(), hipMemcpyHostToDevice)); CK(hipMemcpy(W.g, g0.data(), sizeof(double)*N, hipMemcpyHostToDevice));
+    CK(hipMemcpy(W.dp, dp0.data(), sizeof(double)*(N + 2), hipMemcpyHostToDevice)); CK(hipMemcpy(W.fidx, fi0.data(), sizeof(int)*c->n_kf, hipMemcpyHostToDevice));
+    CK(hipMemcpy(W.nfree, nf0, sizeof(nf0), hipMemcpyHostToDevice)); CK(hipMemcpy(W.st, &st0, sizeof(st0), hipMemcpyHostToDevice));
+    return TSBA_OK;
+}
+
+int tsba_debug_copy_S(void *ctx, double *out) {     // (6 n_kf + 1) x (6 n_kf): factored S and the rhs row after a solve
     Ctx *c = (Ctx *)ctx; if (!c || !c->uploaded) return TSBA_ERR_STATE;
     hipSetDevice(c->device); hipStreamSynchronize(c->stream);
     const Work &W = c->W; const long long N = W.N;

@@ -53,6 +53,7 @@ def load_library():
     L.tsba_debug_far_blocks.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp]
     L.tsba_debug_row_of_kf.argtypes = [vp, C.POINTER(C.c_int32)]
     L.tsba_debug_time_solve.argtypes = [vp, C.c_int, dp]
+    L.tsba_debug_solve_given.argtypes = [vp, C.c_int, dp, dp, C.c_int, dp, C.POINTER(C.c_int32)]
     ip32 = C.POINTER(C.c_int32)
     L.tsba_debug_reduced_blocks.argtypes = [vp, C.c_double, ip32, ip32, ip32, dp, dp, dp, dp]
     L.tsba_debug_lm_trace.argtypes = [vp, C.c_int, dp, C.c_int]
@@ -256,6 +257,19 @@ class Optimizer:
                                                        free.ctypes.data_as(C.POINTER(C.c_int32)), _dp(dpv)),
                     "tsba_debug_reduced_system")
         return {"S": S, "g": g, "cost": cost.value, "free": free, "dp": dpv}
+
+    def solve_given(self, S, g, assembly_failed=False):
+        """The window's reduced-system solver on a given system (tsba_debug_solve_given): S [n, n] (only the lower triangle is read), g [n],
+        n = 6 x free blocks <= 6 n_kf of the uploaded window; free block b stands for keyframe b.  -> dict(dp [n] by free block, rest: the constant
+        keyframes' slots behind it, failed: the failure flag in the LM state, published: the flag as the polling blocks read it -- 0 / 1, -2 if
+        never published, -1 where the schedule under the debug options set at the upload does not poll)."""
+        S = np.ascontiguousarray(S, np.float64); g = np.ascontiguousarray(g, np.float64)
+        n = g.shape[0]
+        assert n % 6 == 0 and S.shape == (n, n)
+        out = np.full(6*self._resident.n_kf, np.nan)
+        fl = (C.c_int32 * 2)()
+        self._check(self.lib.tsba_debug_solve_given(self.ctx, n//6, _dp(S), _dp(g), int(bool(assembly_failed)), _dp(out), fl), "tsba_debug_solve_given")
+        return {"dp": out[:n].copy(), "rest": out[n:].copy(), "failed": int(fl[0]), "published": int(fl[1])}
 
     def solver_info(self):
         """Which kernel paths the uploaded problem takes (tsba_debug_solver_info)."""
