@@ -8,7 +8,8 @@
 //   static KeyPoint keypoint(float x, float y, float size, float angle, float response, int octave);   // cv::KeyPoint(x, y, size, angle, response, octave)
 //   static Mat descriptors(const uint8_t *rows, int n);                                                // cv::Mat(n, 32, CV_8U, (void *)rows).clone(); n == 0: cv::Mat()
 // (over the real types these two lines are the whole Traits; tests/cxx/text_orb_from_cxx.cpp has them over mock types.)
-// The -3-px boundary test of frame.cc:244 (tool::BoundFeatDele_T) stays where it is, on the returned vectors.
+// These are the RAW text features.  The -3-px boundary test of frame.cc:244 (tool::BoundFeatDele_T) and frame::FeatFusion run on the device in
+// tsorb_fuse_frame (adapter/tsorb_fuse_frame.hpp), which makes this extraction part of its own call; a caller of this header alone keeps both on the host.
 #ifndef TSORB_TEXT_EXTRACT_HPP
 #define TSORB_TEXT_EXTRACT_HPP
 #include <stdint.h>

@@ -319,9 +319,42 @@ int tsorb_match_new_points(void *ctx, int nq, const float *qxy /*[nq][2]*/, cons
  *          the standard library; here a cut keeps EVERY point whose response is >= the n-th largest response (the superset of all those outcomes);
  *   order  OpenCV's order inside a level is what nth_element and partition left; here it is level-major and, inside a level, raster order of the
  *          level coordinates (y, then x).
- * The -3-px boundary test of frame.cc:244 (tool::BoundFeatDele_T) stays with the caller. */
+ * These are the RAW text features: the -3-px boundary test of frame.cc:244 (tool::BoundFeatDele_T) and frame::FeatFusion are tsorb_fuse_frame below, which runs
+ * this extraction itself. */
 int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad /*[n_dete][4][2]*/, int nfeatures, int cap,
                        float *kp, uint8_t *desc, int32_t *count);
+
+/* ---- The frame's searched set: steps 3 - 4 of frame::FeatExtract, frame::FeatFusion and frame::AssignFeaturesToGrid (src/frame.cc:229-325, :372-394) in one call on
+ * frame `frame` of the resident batch.  Everything the tracker searches indexes this fused set (vKeys / mDescr, vMatches2D3D, vTextObjInfo); tsorb_match_set_frame
+ * alone grids the scene features only.
+ *   raw text features  exactly tsorb_text_extract(ctx, frame, n_dete, quad, nfeatures, cap_text, ..): the same launches, writing device scratch; raw_count [n_dete].
+ *   filter             tool::BoundFeatDele_T (src/tool.cc:456-508): raw keypoint (x, y) of detection d is kept iff CheckPtsIn(shrunk_d) && CheckPtsIn(bb_d), with
+ *                      shrunk_d = (x0 - win, y0 - win), (x1 + win, y1 - win), (x2 + win, y2 + win), (x3 - win, y3 + win) formed in double and truncated like
+ *                      cv::Point(double, double), bb_d = (minx, miny), (maxx, miny), (maxx, maxy), (minx, maxy) of bbox[d] = vTextDeteMin x, y, vTextDeteMax x, y truncated
+ *                      the same way, and CheckPtsIn = cv::pointPolygonTest(int contour, Point2f, true) > 0 as docs/pointpolygon_recalled.md states it.  win = -3 is
+ *                      the reference's WinText.  (BoundFeatDele_S never runs in the reference, FLAG_NOSCENEMASK is hard-coded: the scene rows are not filtered.)
+ *   fusion             rows [0, n_scene) = the resident frame's keypoints and descriptors as tsorb_download returns them, then the kept rows of detection 0, 1, .. in
+ *                      raw order.  kp [cap][6], desc [cap][32]; obj [cap] = vTextObjInfo (-1 for a scene row, d for a text row); src [cap] (or NULL) = the row itself
+ *                      for a scene row, the row's index among its detection's raw keypoints for a text row (IdxNewText); text_off [n_dete + 1]: detection d's rows
+ *                      are text_off[d] .. text_off[d + 1] - 1 (vKeysTextIdx[d]); n_out = { n_scene, n }.  Only the first n rows are written.
+ *   grid               on success the fused set is the context's searched set, with the bounds as in tsorb_match_set_features: tsorb_match_search, _search_claim and
+ *                      _new_points afterwards answer with fused indices, byte for byte what they answer after tsorb_match_set_features(kp, desc, n, bounds).
+ * The resident batch (scene outputs, pyramid, what tsorb_download returns) is left as it was; a later tsorb_text_extract gives the same bytes.
+ * n_dete == 0: the fused set is the scene set, no pointer of the detection arrays is read.
+ * Capacity: a detection with more than cap_text raw keypoints, or n > cap: TSORB_ERR_ARG with raw_count and n_out written, nothing else written, and the searched set
+ * what it was.  raw_count is complete in both cases, and so is n_out when only cap was too small; a detection that does not fit cap_text has no rows to test, so n then
+ * counts the others only (cap_text = the largest raw_count and cap = n_scene + the sum of raw_count always suffice for a second call).
+ * TSORB_ERR_ARG (tsorb_last_error names the function, nothing is launched, no output is touched) also for: a NULL context, no batch resident or frame outside it, a NULL
+ * required pointer (src and raw_count may be NULL; quad and bbox with n_dete == 0), n_dete < 0, nfeatures < 1, cap_text < 1, cap < 1, a quad or bbox value or win that
+ * is not finite or lies beyond 2^30, bounds with max <= min or not finite, level 0 larger than 640 x 480 (tsorb_text_extract's cap).
+ * One pinned block up, the 13 launches of the text extraction, k_fuse_keep / k_fuse_offsets / k_fuse_gather (csrc/tsfuse.h), one pinned block down, one wait, then the
+ * grid's launches. */
+int tsorb_fuse_frame(void *ctx, int frame, int n_dete,
+                     const double *quad /*[n_dete][4][2] vTextDete, level-0 pixels*/, const double *bbox /*[n_dete][4] = vTextDeteMin x, y, vTextDeteMax x, y*/,
+                     double win /*-3: WinText of frame.cc:237*/, int nfeatures /*500*/, int cap_text /*raw rows per detection*/, int cap /*fused rows*/,
+                     double min_x, double max_x, double min_y, double max_y /*mnMinX .. of the grid*/,
+                     float *kp /*[cap][6]*/, uint8_t *desc /*[cap][32]*/, int32_t *obj /*[cap] vTextObjInfo*/, int32_t *src /*[cap] or NULL*/,
+                     int32_t *text_off /*[n_dete + 1]*/, int32_t *raw_count /*[n_dete] or NULL*/, int32_t *n_out /*[2] = n_scene, n*/);
 
 #ifdef __cplusplus
 }

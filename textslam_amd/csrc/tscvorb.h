@@ -47,7 +47,7 @@ struct CvoDev {
     uint32_t *tkp, *tkey; int *tcnt;    // [nd][ntiles][CVO_TCAP] x | y << 10 | score << 20, the response's ordered key; [nd][ntiles]
     int *rowoff, *lvlcnt; uint32_t *thr;        // [nd][CVO_NL][CVO_MAX_H], [nd][CVO_NL], [nd][CVO_NL][2] first cut (score), second cut (key)
     float4 *sel;                        // [nd][cap] x, y (level coordinates), response, level
-    int *o_cnt; float *o_kp; uint8_t *o_desc;   // (pinned) [nd], [nd][cap][6], [nd][cap][32]
+    int *o_cnt; float *o_kp; uint8_t *o_desc;   // [nd], [nd][cap][6], [nd][cap][32]: the pinned block (tsorb_text_extract) or device scratch (tsorb_fuse_frame)
     int umax[16], gk[7];
 };
 
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(CVO_TCAP) void k_cvo_place(CvoDev C) {
 }
 
 // grid (CVO_DESC_BLOCKS, nd), eight keypoints per workgroup pass, 32 lanes each: lanes 0 .. 15 the rows +-v of IC_Angle's patch on the MASKED level (detect),
-// lane i byte i of the descriptor on the blurred UNMASKED level (compute).  Results go straight into the pinned block the host hands out.
+// lane i byte i of the descriptor on the blurred UNMASKED level (compute).  Results go straight into the arrays the host hands out (cvo_launch's output pointers).
 __global__ __launch_bounds__(256) void k_cvo_describe(CvoDev C) {
     const int d = blockIdx.y, lane = threadIdx.x & 31, sub = threadIdx.x >> 5;
     int total = 0;

@@ -1475,6 +1475,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *
 #include "tstexttheta.h"
 #include "tsclaim.h"
 #include "tsstage.h"
+#include "tsfuse.h"
 
 struct OCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
@@ -1492,6 +1493,7 @@ struct OCtx {
     bool ran = false;                                                           // the resident batch has been through tsorb_run (its level 0 is in place)
     CvoDev CV; int cv_w = 0, cv_h = 0, cv_nd = 0; void *cv_geo = nullptr, *cv_det = nullptr, *cv_sel = nullptr, *cv_pin = nullptr; size_t cv_det_cap = 0, cv_sel_cap = 0, cv_pin_cap = 0;   // tsorb_text_extract's scratch, kept between calls
     void *br_dev = nullptr, *br_pin = nullptr; size_t br_dev_cap = 0, br_pin_cap = 0;                       // tsorb_match_brute_*: device block and pinned staging, kept between calls
+    void *fz_dev = nullptr, *fz_pin = nullptr, *fz_set[2] = {nullptr, nullptr}; size_t fz_dev_cap = 0, fz_pin_cap = 0, fz_set_cap[2] = {0, 0}; int fz_cur = 1;   // tsorb_fuse_frame: device scratch, pinned staging, the fused set (two blocks taken in turn: a call that fails leaves the set the grid reads alone)
     int key[5] = {0, 0, 0, 0, 0}; uint8_t *h_img = nullptr; void *h_out = nullptr; size_t h_img_sz = 0, h_out_sz = 0;
 };
 static int cv_round_f(float v) { return (int)lrintf(v); }
@@ -1537,6 +1539,7 @@ int tsorb_destroy(void *ctx) { OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_A
     if (c->cv_geo) hipFree(c->cv_geo); if (c->cv_det) hipFree(c->cv_det); if (c->cv_sel) hipFree(c->cv_sel); if (c->cv_pin) hipHostFree(c->cv_pin);
     if (c->m_buf) hipFree(c->m_buf); if (c->m_feat) hipFree(c->m_feat); if (c->mq_host) hipHostFree(c->mq_host);
     if (c->br_dev) hipFree(c->br_dev); if (c->br_pin) hipHostFree(c->br_pin);
+    if (c->fz_dev) hipFree(c->fz_dev); if (c->fz_pin) hipHostFree(c->fz_pin); if (c->fz_set[0]) hipFree(c->fz_set[0]); if (c->fz_set[1]) hipFree(c->fz_set[1]);
     hipStreamDestroy(c->stream); delete c; return TSORB_OK; }
 const char *tsorb_last_error(void *ctx) { return ctx ? ((OCtx *)ctx)->err.c_str() : "null ctx"; }
 int tsorb_get_levels(void *ctx) { return ctx ? ((OCtx *)ctx)->nlevels : TSORB_ERR_ARG; }
@@ -1821,22 +1824,16 @@ int tsorb_match_search(void *ctx, int nq, const float *qxy, const float *qr, con
 }
 
 // ---- frame::FeatExtracText: cv::ORB detect on the masked frame + compute on the frame, every detection of a frame in one call (tscvorb.h)
-int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int nfeatures, int cap, float *kp, uint8_t *desc, int32_t *count) {
-    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
-    auto bad = [&](const char *m) { c->err = std::string("tsorb_text_extract: ") + m; return TSORB_ERR_ARG; };
-    if (!c->uploaded || !c->ran) return bad("no batch resident (tsorb_extract_batch, or tsorb_upload + tsorb_run, first)");
+// The staged inputs of the text extraction, [corners | footprints], laid into a pinned block by the caller
+struct CvoIn { Span<int> quad, foot; };
+static CvoIn cvo_take_inputs(Layout &L, int nd) { CvoIn in; in.quad = L.take<int>(8*(size_t)nd); in.foot = L.take<int>(4*CVO_NL*(size_t)nd); return in; }
+// The launch sequence of the text extraction for nd >= 1 checked detections of the resident frame `frame`: the geometry and the scratch of the context, the
+// truncated corners and the footprints into the pinned block h (its device alias dp), then the 13 launches.  k_cvo_place writes o_cnt [nd], k_cvo_describe o_kp
+// [nd][cap][6] and o_desc [nd][cap][32]: device addresses of any memory (tsorb_text_extract: the pinned block itself, tsorb_fuse_frame: device scratch).  Nothing
+// waits for the stream here.
+static int cvo_launch(OCtx *c, int frame, int nd, const double *quad, int nfeatures, int cap, void *h, void *dp, const CvoIn &in, int *o_cnt, float *o_kp, uint8_t *o_desc) {
     OrbDev &D = c->D;
-    if (frame < 0 || frame >= D.n) return bad("frame outside the resident batch");
-    if (n_dete < 0) return bad("n_dete < 0");
-    if (nfeatures < 1) return bad("nfeatures < 1");
-    if (cap < 1) return bad("cap < 1");
-    if (D.w > CVO_MAX_W || D.h > CVO_MAX_H) return bad("level 0 larger than 640 x 480");
-    if (n_dete == 0) return TSORB_OK;
-    if (!quad || !kp || !desc || !count) return bad("NULL pointer");
-    for (int i = 0; i < 8*n_dete; i++) if (!std::isfinite(quad[i]) || fabs(quad[i]) > 1073741824.0) return bad("quad coordinate not finite (or beyond 2^30)");
-    hipSetDevice(c->device);
     CvoDev &C = c->CV;
-    const int nd = n_dete;
     // ---- geometry: cv::ORB's levels, quotas, tiles (docs/cvorb_recalled.md); the planes shared by the detections
     if (c->cv_w != D.w || c->cv_h != D.h) {
         if (c->cv_geo) hipFree(c->cv_geo); c->cv_geo = nullptr; c->cv_w = c->cv_h = 0;
@@ -1875,14 +1872,7 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
         C.rowoff = a_rowoff.at(p); C.lvlcnt = a_lvlcnt.at(p); C.thr = a_thr.at(p); }
     OCK(grow_device(c->cv_sel, c->cv_sel_cap, sizeof(float4)*(size_t)nd*cap));
     C.sel = (float4 *)c->cv_sel;
-    // ---- one pinned block: [corners | footprints] in, [count | kp | desc] out; the kernels read and write it through its device alias dp
-    Layout L(16);
-    const auto a_quad = L.take<int>(8*(size_t)nd), a_foot = L.take<int>(4*CVO_NL*(size_t)nd);
-    const auto a_cnt = L.take<int>((size_t)nd); const auto a_kp = L.take<float>(6*(size_t)nd*cap); const auto a_desc = L.take<uint8_t>(32*(size_t)nd*cap);
-    OCK(grow_pinned(c->cv_pin, c->cv_pin_cap, L.mark()));
-    void *h = c->cv_pin, *dp = nullptr;
-    OCK(hipHostGetDevicePointer(&dp, c->cv_pin, 0));
-    int *h_quad = a_quad.at(h), *h_foot = a_foot.at(h);
+    int *h_quad = in.quad.at(h), *h_foot = in.foot.at(h);
     for (int d = 0; d < nd; d++) {
         int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
         for (int k = 0; k < 4; k++) { const int x = (int)quad[8*d + 2*k], y = (int)quad[8*d + 2*k + 1];         // cv::Point(double, double): truncation
@@ -1902,7 +1892,7 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
     }
     C.nd = nd; C.cap = cap;
     C.img0 = D.pyr + (size_t)frame*D.pyr_frame + D.L[0].pyr_off + (size_t)EDGE*D.L[0].bw + EDGE; C.pitch0 = D.L[0].bw;
-    C.quad = a_quad.at(dp); C.foot = a_foot.at(dp); C.o_cnt = a_cnt.at(dp); C.o_kp = a_kp.at(dp); C.o_desc = a_desc.at(dp);
+    C.quad = in.quad.at(dp); C.foot = in.foot.at(dp); C.o_cnt = o_cnt; C.o_kp = o_kp; C.o_desc = o_desc;
     hipLaunchKernelGGL(k_cvo_mask, dim3(nd), dim3(256), 0, c->stream, C);
     for (int l = 1; l < CVO_NL; l++) hipLaunchKernelGGL(k_cvo_resize, dim3((C.L[l].w + 63)/64, (C.L[l].h + 3)/4, 1 + nd), dim3(256), 0, c->stream, C, l);
     hipLaunchKernelGGL(k_cvo_blur, dim3(C.ntiles), dim3(256), 0, c->stream, C);
@@ -1910,12 +1900,102 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
     hipLaunchKernelGGL(k_cvo_select, dim3(CVO_NL, nd), dim3(256), 0, c->stream, C);
     hipLaunchKernelGGL(k_cvo_place, dim3(C.ntiles, nd), dim3(CVO_TCAP), 0, c->stream, C);
     hipLaunchKernelGGL(k_cvo_describe, dim3(CVO_DESC_BLOCKS, nd), dim3(256), 0, c->stream, C);
+    return TSORB_OK;
+}
+int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int nfeatures, int cap, float *kp, uint8_t *desc, int32_t *count) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_text_extract: ") + m; return TSORB_ERR_ARG; };
+    if (!c->uploaded || !c->ran) return bad("no batch resident (tsorb_extract_batch, or tsorb_upload + tsorb_run, first)");
+    OrbDev &D = c->D;
+    if (frame < 0 || frame >= D.n) return bad("frame outside the resident batch");
+    if (n_dete < 0) return bad("n_dete < 0");
+    if (nfeatures < 1) return bad("nfeatures < 1");
+    if (cap < 1) return bad("cap < 1");
+    if (D.w > CVO_MAX_W || D.h > CVO_MAX_H) return bad("level 0 larger than 640 x 480");
+    if (n_dete == 0) return TSORB_OK;
+    if (!quad || !kp || !desc || !count) return bad("NULL pointer");
+    for (int i = 0; i < 8*n_dete; i++) if (!std::isfinite(quad[i]) || fabs(quad[i]) > 1073741824.0) return bad("quad coordinate not finite (or beyond 2^30)");
+    hipSetDevice(c->device);
+    const int nd = n_dete;
+    // ---- one pinned block: [corners | footprints] in, [count | kp | desc] out; the kernels read and write it through its device alias dp
+    Layout L(16);
+    const CvoIn in = cvo_take_inputs(L, nd);
+    const auto a_cnt = L.take<int>((size_t)nd); const auto a_kp = L.take<float>(6*(size_t)nd*cap); const auto a_desc = L.take<uint8_t>(32*(size_t)nd*cap);
+    OCK(grow_pinned(c->cv_pin, c->cv_pin_cap, L.mark()));
+    void *h = c->cv_pin, *dp = nullptr;
+    OCK(hipHostGetDevicePointer(&dp, c->cv_pin, 0));
+    { const int rc0 = cvo_launch(c, frame, nd, quad, nfeatures, cap, h, dp, in, a_cnt.at(dp), a_kp.at(dp), a_desc.at(dp)); if (rc0) return rc0; }
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
     const int *o_cnt = a_cnt.at(h); const float *o_kp = a_kp.at(h); const uint8_t *o_desc = a_desc.at(h);
     int rc = TSORB_OK;
     for (int d = 0; d < nd; d++) { const int n = o_cnt[d]; count[d] = n;
         if (n > cap) { rc = bad("a detection has more keypoints than cap (count[] is complete, nothing written for it)"); continue; }
         std::copy_n(o_kp + 6*(size_t)d*cap, 6*(size_t)n, kp + 6*(size_t)d*cap); std::copy_n(o_desc + 32*(size_t)d*cap, 32*(size_t)n, desc + 32*(size_t)d*cap); }
+    return rc;
+}
+
+// ---- frame::FeatExtract's boundary test + frame::FeatFusion + frame::AssignFeaturesToGrid (src/frame.cc:234-325, :372-394; tsfuse.h): the frame's searched set
+int tsorb_fuse_frame(void *ctx, int frame, int n_dete, const double *quad, const double *bbox, double win, int nfeatures, int cap_text, int cap,
+                     double min_x, double max_x, double min_y, double max_y, float *kp, uint8_t *desc, int32_t *obj, int32_t *src, int32_t *text_off,
+                     int32_t *raw_count, int32_t *n_out) {
+    OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
+    auto bad = [&](const char *m) { c->err = std::string("tsorb_fuse_frame: ") + m; return TSORB_ERR_ARG; };
+    if (!c->uploaded || !c->ran) return bad("no batch resident (tsorb_extract_batch, or tsorb_upload + tsorb_run, first)");
+    OrbDev &D = c->D;
+    if (frame < 0 || frame >= D.n) return bad("frame outside the resident batch");
+    if (n_dete < 0) return bad("n_dete < 0");
+    if (nfeatures < 1) return bad("nfeatures < 1");
+    if (cap_text < 1) return bad("cap_text < 1");
+    if (cap < 1) return bad("cap < 1");
+    if (D.w > CVO_MAX_W || D.h > CVO_MAX_H) return bad("level 0 larger than 640 x 480");
+    if (!kp || !desc || !obj || !text_off || !n_out || (n_dete > 0 && (!quad || !bbox))) return bad("NULL pointer");
+    const double lim = 1073741824.0;
+    if (!std::isfinite(win) || fabs(win) > lim) return bad("win not finite (or beyond 2^30)");
+    if (!std::isfinite(min_x) || !std::isfinite(max_x) || !std::isfinite(min_y) || !std::isfinite(max_y) || !(max_x > min_x) || !(max_y > min_y)) return bad("bounds with max <= min (or not finite)");
+    for (int i = 0; i < 8*n_dete; i++) if (!std::isfinite(quad[i]) || fabs(quad[i]) > lim) return bad("quad coordinate not finite (or beyond 2^30)");
+    for (int i = 0; i < 4*n_dete; i++) if (!std::isfinite(bbox[i]) || fabs(bbox[i]) > lim) return bad("bbox value not finite (or beyond 2^30)");
+    hipSetDevice(c->device);
+    const size_t nd = (size_t)n_dete, CT = (size_t)cap_text, CP = (size_t)cap;
+    // ---- one pinned block up, one down: [corners | footprints | shrunk quad, bounding box]  ->  [text_off, n_out, verdicts | raw_count | obj | src | kp | desc]
+    Layout L(16);
+    const CvoIn in = cvo_take_inputs(L, n_dete); const auto a_poly = L.take<int>(16*nd);
+    const auto a_head = L.take<int>(nd + 5), a_raw = L.take<int>(nd), a_obj = L.take<int>(CP), a_src = L.take<int>(CP); const auto a_kp = L.take<float>(6*CP); const auto a_desc = L.take<uint8_t>(32*CP);
+    OCK(grow_pinned(c->fz_pin, c->fz_pin_cap, L.mark()));
+    // ---- device scratch: [raw count | raw kp | raw desc | kept indices | kept counts | text_off, n_out, verdicts]; the fused set in the block the grid does not read now
+    Layout Ls(16);
+    const auto s_cnt = Ls.take<int>(nd); const auto s_kp = Ls.take<float>(6*nd*CT); const auto s_desc = Ls.take<uint8_t>(32*nd*CT); const auto s_idx = Ls.take<int>(nd*CT), s_keep = Ls.take<int>(nd), s_head = Ls.take<int>(nd + 5);
+    OCK(grow_device(c->fz_dev, c->fz_dev_cap, Ls.mark()));
+    const int nxt = 1 - c->fz_cur;
+    Layout Lf(16);
+    const auto f_kp = Lf.take<float>(6*CP); const auto f_desc = Lf.take<uint8_t>(32*CP);
+    OCK(grow_device(c->fz_set[nxt], c->fz_set_cap[nxt], Lf.mark()));
+    void *h = c->fz_pin, *dp = nullptr, *sp = c->fz_dev, *fp = c->fz_set[nxt];
+    OCK(hipHostGetDevicePointer(&dp, c->fz_pin, 0));
+    if (n_dete > 0) {
+        int *h_poly = a_poly.at(h);
+        for (int d = 0; d < n_dete; d++) { fuse_shrunk_quad(quad + 8*(size_t)d, win, h_poly + 16*(size_t)d); fuse_bbox_quad(bbox + 4*(size_t)d, h_poly + 16*(size_t)d + 8); }
+        const int rc0 = cvo_launch(c, frame, n_dete, quad, nfeatures, cap_text, h, dp, in, s_cnt.at(sp), s_kp.at(sp), s_desc.at(sp)); if (rc0) return rc0;
+    }
+    FuseDev F;
+    F.nd = n_dete; F.cap_text = cap_text; F.cap = cap;
+    F.poly = a_poly.at(dp); F.raw_cnt = s_cnt.at(sp); F.raw_kp = s_kp.at(sp); F.raw_desc = s_desc.at(sp);
+    F.sc_cnt = D.out_cnt + frame; F.sc_kp = D.out_kp + (size_t)frame*D.cap*6; F.sc_desc = D.out_desc + (size_t)frame*D.cap*32;
+    F.keep_idx = s_idx.at(sp); F.keep_cnt = s_keep.at(sp); F.head = s_head.at(sp); F.set_kp = f_kp.at(fp); F.set_desc = f_desc.at(fp);
+    F.o_head = a_head.at(dp); F.o_raw = a_raw.at(dp); F.o_obj = a_obj.at(dp); F.o_src = a_src.at(dp); F.o_kp = a_kp.at(dp); F.o_desc = a_desc.at(dp);
+    if (n_dete > 0) hipLaunchKernelGGL(k_fuse_keep, dim3(n_dete), dim3(256), 0, c->stream, F);
+    hipLaunchKernelGGL(k_fuse_offsets, dim3(1), dim3(256), 0, c->stream, F);
+    hipLaunchKernelGGL(k_fuse_gather, dim3((unsigned)((8*CP + 255)/256)), dim3(256), 0, c->stream, F);
+    OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());           // the one wait: n is needed for the grid's launches
+    const int *o_head = a_head.at(h);
+    const int n_scene = o_head[nd + 1], n = o_head[nd + 2];
+    a_raw.get(h, raw_count); n_out[0] = n_scene; n_out[1] = n;
+    if (!o_head[nd + 3]) return bad("a detection has more raw keypoints than cap_text (raw_count[] is complete, n_out counts the detections that fit; nothing else written)");
+    if (!o_head[nd + 4]) return bad("more fused rows than cap (raw_count[] and n_out are complete; nothing else written)");
+    std::copy_n(o_head, nd + 1, text_off);
+    std::copy_n(a_kp.at(h), 6*(size_t)n, kp); std::copy_n(a_desc.at(h), 32*(size_t)n, desc); std::copy_n(a_obj.at(h), (size_t)n, obj);
+    if (src) std::copy_n(a_src.at(h), (size_t)n, src);
+    const int rc = match_build(c, F.set_kp, F.set_desc, n, min_x, max_x, min_y, max_y);
+    if (rc == TSORB_OK) c->fz_cur = nxt;
     return rc;
 }
 

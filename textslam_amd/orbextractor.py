@@ -15,7 +15,7 @@ EXPORTED_SYMBOLS = ["tsorb_create", "tsorb_destroy", "tsorb_last_error", "tsorb_
                     "tsorb_debug_level", "tsorb_debug_fast_shape", "tsorb_debug_pyramid", "tsorb_debug_fallbacks", "tsorb_match_set_frame", "tsorb_match_set_features", "tsorb_match_search",
                     "tsorb_text_extract", "tsorb_match_brute_text", "tsorb_match_brute_scene", "tsorb_match_search_sets", "tsorb_match_pnp_ransac",
                     "tsorb_match_two_view_ransac", "tsorb_match_two_view_reconstruct", "tsorb_match_text_theta_ransac", "tsorb_match_search_claim",
-                    "tsorb_match_new_points", "tsorb_upload_device", "tsorb_extract_device"]
+                    "tsorb_match_new_points", "tsorb_upload_device", "tsorb_extract_device", "tsorb_fuse_frame"]
 BRUTE_MAX_FEAT = 65536                                                  # TSORB_BRUTE_MAX_FEAT of include/tsorb.h
 SETS_MAX = 1024                                                         # TSORB_SETS_MAX of include/tsorb.h
 PNP_MAX_HYP = 128                                                       # TSORB_PNP_MAX_HYP of include/tsorb.h
@@ -80,6 +80,9 @@ def load_library():
         L.tsorb_match_search_claim.restype = C.c_int
         L.tsorb_match_new_points.argtypes = [vp, C.c_int, fp, fp, ip, up, up, C.c_int, C.c_int, C.c_double, fp, dp, dp, dp, C.c_int, ip, ip, fp, up, ip]
         L.tsorb_match_new_points.restype = C.c_int
+        L.tsorb_fuse_frame.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                       fp, up, ip, ip, ip, ip, ip]
+        L.tsorb_fuse_frame.restype = C.c_int
         _lib = L
     return _lib
 
@@ -214,6 +217,29 @@ class ORBextractor:
                                                 kp.ctypes.data_as(C.POINTER(C.c_float)), desc.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                 cnt.ctypes.data_as(C.POINTER(C.c_int32))), "tsorb_text_extract")
         return [(kp[i, :cnt[i]].copy(), desc[i, :cnt[i]].copy()) for i in range(n)]
+
+    # ---- the frame's searched set (frame::FeatExtract's boundary test + frame::FeatFusion + AssignFeaturesToGrid, docs/pointpolygon_recalled.md)
+    def fuse_frame(self, frame, quads, bbox, bounds, win=-3.0, nfeatures=500, cap_text=None, cap=None):
+        """The fused scene + text feature set of frame `frame` of the resident batch, left as the searched set of match_search / match_search_claim /
+        match_new_points.  quads [n, 4, 2] = vTextDete, bbox [n, 4] = vTextDeteMin x, y, vTextDeteMax x, y, bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY).
+        cap_text = raw rows per detection (default nfeatures + 64), cap = fused rows (default: the extractor's rows per frame + n * cap_text).
+        Returns a dict: kp [n, 6], desc [n, 32], obj [n] int32 (vTextObjInfo: -1 = scene), src [n] int32 (the row itself for a scene row, the index among the
+        detection's raw keypoints for a text row), text_off [n_dete + 1] int32, raw_count [n_dete] int32, n_scene."""
+        quads = np.ascontiguousarray(quads, np.float64).reshape(-1, 4, 2); bbox = np.ascontiguousarray(bbox, np.float64).reshape(-1, 4)
+        nd = quads.shape[0]
+        if bbox.shape[0] != nd:
+            raise ValueError("quads and bbox have different lengths")
+        cap_text = int(nfeatures) + 64 if cap_text is None else int(cap_text)
+        cap = self.cap + nd * max(cap_text, 0) if cap is None else int(cap)
+        kp = np.zeros((max(cap, 1), 6), np.float32); desc = np.zeros((max(cap, 1), 32), np.uint8)
+        obj = np.zeros(max(cap, 1), np.int32); src = np.zeros(max(cap, 1), np.int32)
+        off = np.zeros(nd + 1, np.int32); raw = np.zeros(max(nd, 1), np.int32); n_out = np.zeros(2, np.int32)
+        ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a.size else None
+        self._check(self.lib.tsorb_fuse_frame(self.ctx, int(frame), nd, ptr(quads, C.c_double), ptr(bbox, C.c_double), float(win), int(nfeatures), cap_text, cap,
+                                              *[float(b) for b in bounds], ptr(kp, C.c_float), ptr(desc, C.c_uint8), ptr(obj, C.c_int32), ptr(src, C.c_int32),
+                                              ptr(off, C.c_int32), ptr(raw, C.c_int32), ptr(n_out, C.c_int32)), "tsorb_fuse_frame")
+        n = int(n_out[1])
+        return dict(kp=kp[:n].copy(), desc=desc[:n].copy(), obj=obj[:n].copy(), src=src[:n].copy(), text_off=off, raw_count=raw[:nd].copy(), n_scene=int(n_out[0]))
 
     # ---- loop closing's all-pairs matching (loopClosing::SearchMatch_Text / SearchMatch_Other), every loop candidate in one call
     def match_brute_text(self, pairs):
