@@ -15,6 +15,7 @@ KEYS = ("cand_cnt", "best_idx", "best_dist", "best_dist2", "cand_idx", "cand_dis
 B0 = (0.0, 640.0, 0.0, 480.0)
 B5 = (-8.5, 331.25, -4.0, 244.0)
 SIZES = (0, 1, 70, 300, 1500)                       # 1500: more than one placement chunk of 256
+CHUNK_EDGE = (256, 257)                              # exactly one placement chunk, and one feature past it
 N_DENSE, DENSE_X, DENSE_Y = 150, (326.0, 334.0), (236.0, 244.0)       # 150 features of one further set inside the cell (33, 24) of a 10 x 10-px grid
 FIXED = [[-500.0, -500.0], [5.0, 5.0], [639.0, 479.0], [320.0, 240.0], [2000.0, 100.0], [0.0, 479.0], [639.0, 0.0], [320.0, -30.0]]     # tests/test_gpu_orb.py's
 
@@ -55,6 +56,7 @@ def world():
     sets = [(*_features(rng, n, B0), B0) for n in SIZES]
     sets.append((*_features(rng, 400, B5), B5))
     sets.append((*_features(rng, 350, B0, dense=N_DENSE), B0))
+    sets += [(*_features(rng, n, B0), B0) for n in CHUNK_EDGE]
     qset, qxy, qr, qlev, qd = [], [], [], [], []
     for s, (kp, desc, b) in enumerate(sets):
         n = len(kp)
@@ -139,6 +141,19 @@ def test_all_shapes_in_one_call(ex, world, oracle_lib, with_lev, max_cand):
     w = world
     got = ex.match_search_sets(w["sets"], w["qset"], w["qxy"], w["qr"], w["table"], qdi=w["qdi"], qlev=w["qlev"] if with_lev else None, max_cand=max_cand)
     _same(got, _ref(oracle_lib, w, with_lev, max_cand), (with_lev, max_cand))
+
+
+@pytest.mark.parametrize("max_cand", [256, 4])
+def test_every_set_as_the_single_grid(ex, world, oracle_lib, max_cand):
+    """The context's grid is built by the same chunked builder: every set of the world through match_set_features + match_search against the oracle's rows of that set
+    (the empty grid, a grid smaller than a chunk, the chunk boundary, a cell whose list crosses chunks, features outside the grid, an origin off zero)."""
+    w = world
+    ref = _ref(oracle_lib, w, True, max_cand)
+    for s, (kp, desc, b) in enumerate(w["sets"]):
+        m = np.flatnonzero(w["qset"] == s)
+        ex.match_set_features(kp, desc, b)
+        got = ex.match_search(w["qxy"][m], w["qr"][m], w["qlev"][m], w["qd"][m], max_cand=max_cand)
+        _same(got, {k: ref[k][m] for k in KEYS}, (s, max_cand))
 
 
 def test_descriptors_by_index_or_expanded(ex, world, oracle_lib):

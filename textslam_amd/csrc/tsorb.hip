@@ -17,10 +17,10 @@
 // inside one workgroup from the input image / from level 3), k_fast_blur (the blur's tiles behind the detector's workgroups), k_octree, k_orient_describe
 // (orientation inside the descriptor's launch, results also stored in the pinned block the download hands out).  Levels the LDS quadtree cannot hold are
 // flagged in pinned memory and redone by k_octree_serial behind the run's synchronisation.
-// Window search (tracking::SearchFrom3D*): k_mg_cell / k_mg_scan / k_mg_place build a frame's 64 x 48 grid, k_match searches it, a wave per query.
+// Window search (tracking::SearchFrom3D*, tswindow.h): k_grid builds a frame's 64 x 48 grid in one workgroup, k_match searches it, a wave per query.
 // The stateful window searches SearchForTriangular / SearchForInitializ and a new keyframe's scene points (tsclaim.h): k_claim_walk runs match_walk per query, k_claim_chain
 // the reference's claim chain in one workgroup, k_claim_points the triangulation and CheckTriangular.
-// Loop fusion's window searches in many feature sets at once (tswindow.h): k_ws_grid builds every set's grid, k_ws_match runs k_match's walk (match_walk) per query.
+// Loop fusion's window searches in many feature sets at once (tswindow.h): k_ws_grid builds every set's grid as k_grid does, k_ws_match runs k_match's walk (match_walk) per query.
 // Integer / fp32 arithmetic is written so that every rounding matches the CPU oracle: no FMA contraction where the
 // reference has separate multiplies and adds (__fmul_rn / __fadd_rn / __dmul_rn ...), rintf = cvRound (half to even).
 #include <hip/hip_runtime.h>
@@ -1321,151 +1321,6 @@ __global__ __launch_bounds__(256) void k_orient_describe(OrbDev D) {
 
 // ------------------------------------------------------------------------------------------------ host side
 
-// ================================================================== window / projection search
-// frame::AssignFeaturesToGrid / PosInGrid (frame.cc:372-407), frame::GetFeaturesInArea (frame.cc:415-468),
-// tracking::DescriptorDistance (tracking.cc:2762-2778): the feature grid of the searched frame is built on the device (stable
-// counting sort: a cell lists its features in index order, as the reference's push_back does), one thread per query walks the
-// cells in the reference's order, filters by octave and window, and scores the candidates with a 256-bit Hamming distance.
-#define MG_COLS 64
-#define MG_ROWS 48
-#define MG_CELLS (MG_COLS*MG_ROWS)
-struct MatchDev {
-    const float *kp; const uint8_t *desc; int n;      // [n][6], [n][32]
-    double min_x, min_y, iw, ih;
-    int *cell, *off, *list;                           // [n], [MG_CELLS + 1], [n]
-};
-// frame::PosInGrid (frame.cc:395-407) in the reference's doubles: the feature's cell (column-major, as the window walk counts them), -1 outside the grid
-__device__ __forceinline__ int mg_cell_of(const float fx, const float fy, const double min_x, const double min_y, const double iw, const double ih) {
-    const int px = (int)round(((double)fx - min_x)*iw), py = (int)round(((double)fy - min_y)*ih);
-    return (px < 0 || px >= MG_COLS || py < 0 || py >= MG_ROWS) ? -1 : px*MG_ROWS + py;
-}
-__global__ __launch_bounds__(256) void k_mg_cell(MatchDev M) {
-    const int i = blockIdx.x*256 + threadIdx.x;
-    if (i >= M.n) return;
-    const int c = mg_cell_of(M.kp[6*i], M.kp[6*i+1], M.min_x, M.min_y, M.iw, M.ih);
-    M.cell[i] = c;
-    if (c >= 0) atomicAdd(&M.off[c + 1], 1);
-}
-__global__ __launch_bounds__(1024) void k_mg_scan(MatchDev M) {          // inclusive scan of the 3072 cell counts, one workgroup
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    int v[3], s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { v[k] = M.off[1 + 3*t + k]; s += v[k]; }
-    part[t] = s; __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) { int a = t >= d ? part[t - d] : 0; __syncthreads(); part[t] += a; __syncthreads(); }
-    int run = part[t] - s;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { run += v[k]; M.off[1 + 3*t + k] = run; }
-}
-__global__ __launch_bounds__(256) void k_mg_place(MatchDev M) {           // rank inside the cell = features of the cell with a smaller index
-    // (64 features per workgroup, four threads each: the features before the workgroup's last one through LDS, 1024 at a time, a quarter of a tile per thread -- every thread
-    // walking all of them in global memory was 40 us for 1000 features)
-    __shared__ int s_cell[1024];
-    const int i = blockIdx.x*64 + (threadIdx.x >> 2), part = threadIdx.x & 3, iend = min((int)(blockIdx.x + 1)*64, M.n);
-    const int c = i < M.n ? M.cell[i] : -1;
-    int rank = 0;
-    for (int t0 = 0; t0 < iend; t0 += 1024) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) { const int j = t0 + threadIdx.x + 256*u; s_cell[threadIdx.x + 256*u] = j < iend ? M.cell[j] : -2; }
-        __syncthreads();
-        const int n = min(1024, i - t0), j0 = 256*part, j1 = min(n, j0 + 256);         // the features of this tile before feature i; this thread's quarter of the tile
-        if (c >= 0) for (int j = j0; j < j1; j += 8) {
-#pragma unroll
-            for (int u = 0; u < 8; u++) rank += (j + u < j1 && s_cell[j + u] == c) ? 1 : 0; }
-        __syncthreads();
-    }
-    rank += __shfl_xor(rank, 1, 4); rank += __shfl_xor(rank, 2, 4);
-    if (c >= 0 && part == 0) M.list[M.off[c] + rank] = i;
-}
-// One WAVE per query (until round 6: one thread per query walking its window's cells one after the other -- two dependent loads per cell, two more per feature, 81 cells for a
-// 40-px radius: 289 us for 1000 queries, 0.37 ms per call of tracking::SearchFrom3D's search).  The window's cells on the lanes in the reference's order (column by column,
-// frame.cc:415-468), their feature counts as a wave scan; then the window's features on the lanes, again in that order (a lane finds its feature's cell in the scan), the
-// reference's filters and the Hamming distance per lane; the survivors keep their order through a ballot, best / second best as the two smallest of the multiset with the
-// first minimum's index (what the reference's sequential scan ends with).
-// The walk of one query by one wave, stated once: k_match (the context's single grid) and k_ws_match (tswindow.h: a grid per set) both call it.  G is the searched
-// grid by value; inc / o0s are the wave's 64-entry LDS scratch; cand_idx / cand_dist are the query's own rows (max_cand entries, unused slots included).
-struct MatchGrid { const float *kp; const uint8_t *desc; const int *off, *list; double min_x, min_y, iw, ih; };
-// keep(i, d): a further test of a feature that passed the window and the octave, asked with its index and distance (tsclaim.h: eligibility, the running vMatchDist);
-// MwAll keeps every one.
-struct MwAll { __device__ __forceinline__ bool operator()(int, int) const { return true; } };
-template <class Keep = MwAll>
-__device__ __forceinline__ void match_walk(const MatchGrid M, const int lane, int *inc, int *o0s, const float x, const float y, const float r, const int minLevel, const int maxLevel,
-                                           const uint32_t (&qd)[8], const int max_cand, int *cand_idx, int *cand_dist, int *cand_cnt, int *best_idx, int *best_dist, int *best_dist2, const Keep keep = Keep()) {
-    int nc = 0, bi = -1, bd = 2147483647, bd2 = 2147483647;
-    const int c0x = max(0, (int)floor(((double)x - M.min_x - (double)r)*M.iw)), c1x = min(MG_COLS - 1, (int)ceil(((double)x - M.min_x + (double)r)*M.iw));
-    const int c0y = max(0, (int)floor(((double)y - M.min_y - (double)r)*M.ih)), c1y = min(MG_ROWS - 1, (int)ceil(((double)y - M.min_y + (double)r)*M.ih));
-    if (!(c0x >= MG_COLS || c1x < 0 || c0y >= MG_ROWS || c1y < 0)) {
-        const bool check = (minLevel > 0) || (maxLevel >= 0);
-        const int ny = c1y - c0y + 1, ncell = (c1x - c0x + 1)*ny;
-        const unsigned long long lt = (1ull << lane) - 1ull;
-        for (int e0 = 0; e0 < ncell; e0 += 64) {             // 64 cells of the window at a time
-            const int e = e0 + lane; int o0 = 0, cnt = 0;
-            if (e < ncell) { const int ix = c0x + e/ny, iy = c0y + e - (e/ny)*ny, c = ix*MG_ROWS + iy; o0 = M.off[c]; cnt = M.off[c+1] - o0; }
-            int incl = cnt;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-            const int tot = __shfl(incl, 63, 64);
-            inc[lane] = incl; o0s[lane] = o0 - (incl - cnt);                                 // (list position of the cell's first feature minus the features before the cell)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            for (int j0 = 0; j0 < tot; j0 += 64) {            // 64 features of those cells at a time, in order
-                const int j = j0 + lane; bool pass = false; int i = 0, d = 0;
-                if (j < tot) {
-                    int lo = 0;                                // the first cell whose inclusive count exceeds j
-#pragma unroll
-                    for (int step = 32; step > 0; step >>= 1) if (inc[lo + step - 1] <= j) lo += step;
-                    i = M.list[o0s[lo] + j];
-                    const float fx = M.kp[6*i], fy = M.kp[6*i+1]; const int oct = (int)M.kp[6*i+5];
-                    const uint32_t *fd = (const uint32_t *)(M.desc + 32*(size_t)i);
-                    uint32_t f8[8];
-#pragma unroll
-                    for (int w = 0; w < 8; w++) f8[w] = fd[w];
-                    pass = true;
-                    if (check) { if (oct < minLevel) pass = false; if (maxLevel >= 0 && oct > maxLevel) pass = false; }
-                    const float dx = fx - x, dy = fy - y;
-                    if (!(fabsf(dx) < r && fabsf(dy) < r)) pass = false;
-#pragma unroll
-                    for (int w = 0; w < 8; w++) d += __popc(qd[w] ^ f8[w]);
-                    if (pass) pass = keep(i, d);
-                }
-                const unsigned long long pm = __ballot(pass);
-                if (pm) {
-                    const int rank = nc + __popcll(pm & lt);
-                    if (pass && rank < max_cand) { cand_idx[rank] = i; cand_dist[rank] = d; }
-                    nc += __popcll(pm);
-                    // the chunk's two smallest distances and the first lane of the smallest
-                    int m1 = pass ? d : 2147483647;
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) m1 = min(m1, __shfl_xor(m1, o, 64));
-                    const unsigned long long at1 = __ballot(pass && d == m1);
-                    const int first = __ffsll((long long)at1) - 1;
-                    int m2 = (pass && lane != first) ? d : 2147483647;
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) m2 = min(m2, __shfl_xor(m2, o, 64));
-                    const int i1 = __shfl(i, first, 64);
-                    // merged behind what came before (a later equal minimum does not take the index: strict < in the reference)
-                    if (m1 < bd) { bd2 = min(bd, m2); bd = m1; bi = i1; } else bd2 = min(bd2, m1);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // (the next 64 cells overwrite the scan)
-        }
-    }
-    for (int k = nc + lane; k < max_cand; k += 64) { cand_idx[k] = -1; cand_dist[k] = -1; }     // unused slots
-    if (lane == 0) { *cand_cnt = nc; *best_idx = bi; *best_dist = bd; *best_dist2 = bd2; }
-}
-__global__ __launch_bounds__(256) void k_match(MatchDev M, int nq, const float *qxy, const float *qr, const int *qlev, const uint8_t *qdesc, int max_cand,
-                                               int *cand_idx, int *cand_dist, int *cand_cnt, int *best_idx, int *best_dist, int *best_dist2) {
-    __shared__ int s_inc[4][64], s_o0[4][64];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, q = blockIdx.x*4 + wv;
-    if (q >= nq) return;                                     // (a whole wave)
-    uint32_t qd[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) qd[k] = ((const uint32_t *)qdesc)[8*(size_t)q + k];
-    MatchGrid G; G.kp = M.kp; G.desc = M.desc; G.off = M.off; G.list = M.list; G.min_x = M.min_x; G.min_y = M.min_y; G.iw = M.iw; G.ih = M.ih;
-    match_walk(G, lane, s_inc[wv], s_o0[wv], qxy[2*q], qxy[2*q+1], qr[q], qlev ? qlev[2*q] : -1, qlev ? qlev[2*q+1] : -1, qd, max_cand,
-               cand_idx + (size_t)q*max_cand, cand_dist + (size_t)q*max_cand, cand_cnt + q, best_idx + q, best_dist + q, best_dist2 + q);
-}
-
 #include "tscvorb.h"
 #include "tsbrute.h"
 #include "tswindow.h"
@@ -1488,7 +1343,7 @@ struct OCtx {
     int pyr_shape = -1, pyr_split = P1_SPLIT; PyrOne Q[3 + MAXL/2 + 1]; int q_inst[3 + MAXL/2 + 1], n_pairs = 0;           // (tsorb_debug_pyramid) k_pyramid_one's launches: [0] levels 0 .. split from the image, [1] the rest from level split, [2] every level from the image; instance 0 = small buffers, 1 = large, -1 = does not fit
     OrbDev D;
     // the SLAM front-end calls once per frame with the same geometry: buffers and pinned staging are kept between calls
-    MatchDev M; bool m_set = false; void *m_buf = nullptr; size_t m_cap = 0; void *m_feat = nullptr; size_t m_feat_cap = 0;   // search grid of the current frame
+    MatchGrid M; int m_n = 0; bool m_set = false; void *m_buf = nullptr; size_t m_cap = 0; void *m_feat = nullptr; size_t m_feat_cap = 0;   // search grid of the current frame
     void *mq_host = nullptr; size_t mq_cap = 0;                                 // tsorb_match_search: pinned block, read and written by the kernel through its device alias
     bool ran = false;                                                           // the resident batch has been through tsorb_run (its level 0 is in place)
     CvoDev CV; int cv_w = 0, cv_h = 0, cv_nd = 0; void *cv_geo = nullptr, *cv_det = nullptr, *cv_sel = nullptr, *cv_pin = nullptr; size_t cv_det_cap = 0, cv_sel_cap = 0, cv_pin_cap = 0;   // tsorb_text_extract's scratch, kept between calls
@@ -1767,17 +1622,13 @@ int tsorb_debug_level(void *ctx, int frame, int level, int blurred, uint8_t *out
 // ---- window / projection search
 static int match_build(OCtx *c, const float *kp_dev, const uint8_t *desc_dev, int n, double min_x, double max_x, double min_y, double max_y) {
     if (!(max_x > min_x) || !(max_y > min_y) || n < 0) return TSORB_ERR_ARG;
-    const size_t need = sizeof(int)*((size_t)2*std::max(n, 1) + MG_CELLS + 1);
-    OCK(grow_device(c->m_buf, c->m_cap, need));
-    MatchDev &M = c->M;
-    M.kp = kp_dev; M.desc = desc_dev; M.n = n; M.min_x = min_x; M.min_y = min_y;
-    M.iw = (double)MG_COLS/(max_x - min_x); M.ih = (double)MG_ROWS/(max_y - min_y);          // frame.cc:124-125
-    M.off = (int *)c->m_buf; M.cell = M.off + MG_CELLS + 1; M.list = M.cell + std::max(n, 1);
-    OCK(hipMemsetAsync(M.off, 0, sizeof(int)*(MG_CELLS + 1), c->stream));
-    if (n > 0) hipLaunchKernelGGL(k_mg_cell, dim3((n + 255)/256), dim3(256), 0, c->stream, M);
-    hipLaunchKernelGGL(k_mg_scan, dim3(1), dim3(1024), 0, c->stream, M);
-    if (n > 0) hipLaunchKernelGGL(k_mg_place, dim3((n + 63)/64), dim3(256), 0, c->stream, M);
-    c->m_set = true; return TSORB_OK;
+    OCK(grow_device(c->m_buf, c->m_cap, sizeof(int)*((size_t)std::max(n, 1) + MG_CELLS + 1)));
+    MatchGrid &M = c->M;
+    double g[4]; grid_scale(min_x, max_x, min_y, max_y, g);
+    M.kp = kp_dev; M.desc = desc_dev; M.min_x = g[0]; M.min_y = g[1]; M.iw = g[2]; M.ih = g[3];
+    M.off = (int *)c->m_buf; M.list = M.off + MG_CELLS + 1;
+    hipLaunchKernelGGL(k_grid, dim3(1), dim3(WS_T), 0, c->stream, M, n);
+    c->m_n = n; c->m_set = true; return TSORB_OK;
 }
 int tsorb_match_set_frame(void *ctx, int frame, double min_x, double max_x, double min_y, double max_y) {
     OCtx *c = (OCtx *)ctx; if (!c || !c->uploaded) return TSORB_ERR_ARG;
@@ -2147,9 +1998,7 @@ int tsorb_match_search_sets(void *ctx, int n_set, const int32_t *foff, const flo
     OCK(grow_device(c->br_dev, c->br_dev_cap, Ld.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
     void *h = c->br_pin, *d = c->br_dev;
     a_foff.put(h, foff);
-    { double *g = a_grid.at(h);
-      for (int s = 0; s < n_set; s++) { const double *b = bounds + 4*(size_t)s; g[4*s] = b[0]; g[4*s + 1] = b[2];
-          g[4*s + 2] = (double)MG_COLS/(b[1] - b[0]); g[4*s + 3] = (double)MG_ROWS/(b[3] - b[2]); } }                 // frame.cc:124-125, as match_build
+    for (int s = 0; s < n_set; s++) { const double *b = bounds + 4*(size_t)s; grid_scale(b[0], b[1], b[2], b[3], a_grid.at(h) + 4*(size_t)s); }
     a_kp.put(h, kp6); a_desc.put(h, desc); a_qd.put(h, qdesc);
     a_qxy.put(h, qxy); a_qr.put(h, qr); a_set.put(h, qset);
     if (qlev) a_lev.put(h, qlev); else std::fill_n(a_lev.at(h), a_lev.n, -1);
@@ -2378,13 +2227,13 @@ static int claim_call(const char *name, bool points, void *ctx, int nq, const fl
     if (!n_match || (points && !n_good)) return bad("NULL pointer");
     if (th_low < 0 || th_low > 256) return bad("th_low outside [0, 256]");
     if (use_ratio && (!std::isfinite(ratio) || ratio < 0.0)) return bad("ratio not finite or negative");
-    if (c->M.n > TSORB_BRUTE_MAX_FEAT) return bad("the searched set has more than TSORB_BRUTE_MAX_FEAT features");
+    if (c->m_n > TSORB_BRUTE_MAX_FEAT) return bad("the searched set has more than TSORB_BRUTE_MAX_FEAT features");
     if (nq > 0 && (!qxy || !qr || !qdesc || !match12 || (points && (!q_px || !Trw || !Tcw || !K || !p3d || !good)))) return bad("NULL pointer");
     for (int q = 0; q < nq; q++) { if (!all_finite(qxy + 2*(size_t)q, 2)) return bad("query " + std::to_string(q) + ": a coordinate is not finite");
         if (!std::isfinite(qr[q]) || qr[q] < 0.f) return bad("query " + std::to_string(q) + ": the radius is not finite or negative"); }
     if (nq == 0) { *n_match = 0; if (points) *n_good = 0; return TSORB_OK; }
     hipSetDevice(c->device);
-    const size_t Q = (size_t)nq, N2 = (size_t)c->M.n;
+    const size_t Q = (size_t)nq, N2 = (size_t)c->m_n;
     // in: [qxy | qr | qlev (if given) | qdesc | elig (if given) | q_px (points)]   out: [match12 | match_dist | counts | p3d, good (points)]   scratch: [row_idx | row_dist | row_cnt | own]
     Layout L(16);
     const auto a_qxy = L.take<float>(2*Q), a_qr = L.take<float>(Q); const auto a_lev = L.take<int32_t>(qlev ? 2*Q : 0); const auto a_qd = L.take<uint8_t>(32*Q), a_el = L.take<uint8_t>(elig2 ? N2 : 0);
@@ -2405,13 +2254,11 @@ static int claim_call(const char *name, bool points, void *ctx, int nq, const fl
     for (int i = 0; i < 12; i++) { D.Trw[i] = points ? Trw[i] : 0.0; D.Tcw[i] = points ? Tcw[i] : 0.0; }
     for (int i = 0; i < 4; i++) D.K[i] = points ? K[i] : 0.0;
     D.th_reproj = th_reproj;
-    const MatchDev &M = c->M;
-    MatchGrid G; G.kp = M.kp; G.desc = M.desc; G.off = M.off; G.list = M.list; G.min_x = M.min_x; G.min_y = M.min_y; G.iw = M.iw; G.ih = M.ih;
     const size_t lds = (2*N2 + 15) & ~(size_t)15;                           // vMatchDist: 16 bits a feature, at most 128 KB beside the kernel's own 17 KB
     if (lds > 32768) OCK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_claim_chain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_claim_walk, dim3((unsigned)((nq + 3)/4)), dim3(256), 0, c->stream, G, D);
-    hipLaunchKernelGGL(k_claim_chain, dim3(1), dim3(CL_T), lds, c->stream, G, D);
-    if (points) hipLaunchKernelGGL(k_claim_points, dim3((unsigned)((nq + CL_T - 1)/CL_T)), dim3(CL_T), 0, c->stream, G, D);
+    hipLaunchKernelGGL(k_claim_walk, dim3((unsigned)((nq + 3)/4)), dim3(256), 0, c->stream, c->M, D);
+    hipLaunchKernelGGL(k_claim_chain, dim3(1), dim3(CL_T), lds, c->stream, c->M, D);
+    if (points) hipLaunchKernelGGL(k_claim_points, dim3((unsigned)((nq + CL_T - 1)/CL_T)), dim3(CL_T), 0, c->stream, c->M, D);
     OCK(hipMemcpyAsync(a_m12.at(h), a_m12.at(d), out_end - in_sz, hipMemcpyDeviceToHost, c->stream));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
     a_m12.get(h, match12); a_dist.get(h, match_dist); a_p3d.get(h, p3d); a_good.get(h, good);

@@ -4,10 +4,12 @@ C ABI (ctypes, host clock around calls that end in a stream synchronisation), me
 
     python tools/diag/gpu_window_sets.py [--rounds 200] [--commit TEXT] [--out profiles/window_sets_timing.txt]
     python tools/diag/gpu_window_sets.py --stats [--stats-out profiles/window_sets_kernel_stats.txt]     the same workload under rocprofv3 --kernel-trace --stats
-    python tools/diag/gpu_window_sets.py --single-compare PARENT_LIB [--single-out profiles/window_sets_single_parent_vs_branch.txt]
-        tsorb_match_search alone (1000 queries of 40-px radius in a 1000-feature frame, bench.py's also.orb_window_search) with the parent commit's libtsorb.so and with
-        this tree's, alternating child processes: does the existing search pay for the shared device function?
-    python tools/diag/gpu_window_sets.py --single LIB        (the child of --single-compare: prints its medians, microseconds)"""
+    python tools/diag/gpu_window_sets.py --single-compare PARENT_LIB [--single-out profiles/grid_build_parent_vs_branch.txt]
+        the single grid with the parent commit's libtsorb.so and with this tree's, alternating child processes.  Shape "search": tsorb_match_search alone (1000 queries of
+        40-px radius in a 1000-feature frame, bench.py's also.orb_window_search).  Shapes "build N": the grid build on the timed path -- tsorb_match_set_features of N
+        features, then a tsorb_match_search of 64 queries whose synchronisation waits for the build; N = 1000 and 1400 (the bench's frame, the fused set of the documented
+        tsorb_fuse_frame shape) are gated against the parent's own spread, 4000 and 65536 are reported.
+    python tools/diag/gpu_window_sets.py --single LIB        (the child of --single-compare: prints its medians per shape, microseconds)"""
 import argparse
 import ctypes as C
 import glob
@@ -27,7 +29,7 @@ ap.add_argument("--stats", action="store_true")
 ap.add_argument("--stats-out", default=os.path.join(ROOT, "profiles", "window_sets_kernel_stats.txt"))
 ap.add_argument("--single", default=None)
 ap.add_argument("--single-compare", default=None)
-ap.add_argument("--single-out", default=os.path.join(ROOT, "profiles", "window_sets_single_parent_vs_branch.txt"))
+ap.add_argument("--single-out", default=os.path.join(ROOT, "profiles", "grid_build_parent_vs_branch.txt"))
 ap.add_argument("--no-write", action="store_true")
 args = ap.parse_args()
 VP, I32, U8, F32, F64 = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -71,52 +73,69 @@ def pct(t):
     return float(np.median(t)), float(t[int(0.1 * (len(t) - 1))]), float(t[int(0.9 * (len(t) - 1))])
 
 
-# ------------------------------------------------------------------ the existing single search, one library
+# ------------------------------------------------------------------ the single grid, one library
+BUILD_N = (1000, 1400, 4000, 65536)
+GATED = ("search", "build 1000", "build 1400")
+
+
 def single(lib_path, groups=5, calls=300):
     L, ctx = open_lib(lib_path)
     rng = np.random.default_rng(1)
-    kp, desc = features(rng, 1000)
-    nq = 1000
-    qxy = (kp[rng.integers(0, 1000, nq), :2] + rng.normal(0, 3, (nq, 2))).astype(np.float32); qr = np.full(nq, 40.0, np.float32)
-    qd = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
-    out = [np.zeros(nq, np.int32) for _ in range(4)]
-    assert L.tsorb_match_set_features(ctx, p(kp, F32), p(desc, U8), 1000, *BOUNDS) == 0
-    call = lambda: L.tsorb_match_search(ctx, nq, p(qxy, F32), p(qr, F32), None, p(qd, U8), 0, None, None, p(out[0], I32), p(out[1], I32), p(out[2], I32), p(out[3], I32))
-    for _ in range(50):
-        assert call() == 0
-    meds = []
-    for _ in range(groups):
-        t = []
-        for _ in range(calls):
-            t0 = time.perf_counter(); call(); t.append(time.perf_counter() - t0)
-        meds.append(pct(t)[0])
+
+    def shape(name, n, nq, build):
+        kp, desc = features(rng, n)
+        qxy = (kp[rng.integers(0, n, nq), :2] + rng.normal(0, 3, (nq, 2))).astype(np.float32); qr = np.full(nq, 40.0, np.float32)
+        qd = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+        out = [np.zeros(nq, np.int32) for _ in range(4)]
+        set_ = lambda: L.tsorb_match_set_features(ctx, p(kp, F32), p(desc, U8), n, *BOUNDS)
+        search = lambda: L.tsorb_match_search(ctx, nq, p(qxy, F32), p(qr, F32), None, p(qd, U8), 0, None, None, p(out[0], I32), p(out[1], I32), p(out[2], I32), p(out[3], I32))
+        call = (lambda: set_() | search()) if build else search
+        assert set_() == 0
+        for _ in range(50):
+            assert call() == 0
+        meds = []
+        for _ in range(groups):
+            t = []
+            for _ in range(calls):
+                t0 = time.perf_counter(); call(); t.append(time.perf_counter() - t0)
+            meds.append(pct(t)[0])
+        print("shape %s: medians_us " % name + " ".join("%.2f" % m for m in meds) + " checksum %d" % int(out[0].sum() + out[2].astype(np.int64).sum()), flush=True)
+    shape("search", 1000, 1000, False)
+    for n in BUILD_N:
+        shape("build %d" % n, n, 64, True)
     L.tsorb_destroy(ctx)
-    print("medians_us " + " ".join("%.2f" % m for m in meds) + " checksum %d" % int(out[0].sum() + out[2].astype(np.int64).sum()))
 
 
 def single_compare(parent_lib):
     branch_lib = os.path.join(ROOT, "textslam_amd", "libtsorb.so")
-    rows = {"parent": [], "branch": []}; sums = set()
+    names = ["search"] + ["build %d" % n for n in BUILD_N]
+    rows = {(label, nm): [] for label in ("parent", "branch") for nm in names}; sums = {nm: set() for nm in names}
     for rnd in range(5):
         for label, lib in (("parent", parent_lib), ("branch", branch_lib)):
             res = subprocess.run([sys.executable, os.path.abspath(__file__), "--single", lib], capture_output=True, text=True, timeout=200)
             if res.returncode != 0:
                 sys.exit(res.stdout + res.stderr)
-            w = res.stdout.split()
-            rows[label].append([float(x) for x in w[1:w.index("checksum")]]); sums.add(w[-1])
-    pa = np.array(rows["parent"]).reshape(-1); br = np.array(rows["branch"]).reshape(-1)
-    lines = ["tsorb_match_search alone, 1000 queries of 40-px radius in a 1000-feature frame (640 x 480), max_cand 0: the library of the parent commit against this tree's",
-             "(%s), tools/diag/gpu_window_sets.py --single-compare, one job on one MI355X; child processes parent, branch alternating, five of each; each prints" % commit_text(),
-             "5 medians of 300 calls after 50 warm-up calls (C ABI through ctypes, host clock); microseconds.  The results' checksums agree: %s." % (len(sums) == 1)]
-    for label in ("parent", "branch"):
-        for k, r in enumerate(rows[label]):
-            lines.append("%s process %d: %s" % (label, k + 1, "  ".join("%7.2f" % x for x in r)))
-    lo, hi = pa.min(), pa.max()
-    lines.append("parent: median of its medians %.2f, spread of its own medians %.2f .. %.2f (the noise of this job)" % (np.median(pa), lo, hi))
-    lines.append("branch: median of its medians %.2f, its medians %.2f .. %.2f" % (np.median(br), br.min(), br.max()))
-    inside = lo <= np.median(br) <= hi
-    lines.append("branch median %s the parent's spread: %s" % ("inside" if inside else ("BELOW" if np.median(br) < lo else "ABOVE"),
-                 "the shared device function costs the existing search nothing measurable" if np.median(br) <= hi else "the shared function is not free"))
+            for line in res.stdout.splitlines():
+                nm, rest = line[len("shape "):].split(": ", 1); w = rest.split()
+                rows[(label, nm)].append([float(x) for x in w[1:w.index("checksum")]]); sums[nm].add(w[-1])
+    lines = ["the single grid: the library of the parent commit against this tree's (%s), tools/diag/gpu_window_sets.py --single-compare, one job on one MI355X;" % commit_text(),
+             "child processes parent, branch alternating, five of each; each prints per shape 5 medians of 300 timed units after 50 warm-up units (C ABI through ctypes, host",
+             "clock); microseconds.  640 x 480, 40-px radius, max_cand 0.  search: one tsorb_match_search of 1000 queries in a 1000-feature frame (the grid built before).",
+             "build N: tsorb_match_set_features of N features + one tsorb_match_search of 64 queries, which waits for the build.  Gated: %s; the others are reported." % ", ".join(GATED)]
+    ok = True
+    for nm in names:
+        pa = np.array(rows[("parent", nm)]).reshape(-1); br = np.array(rows[("branch", nm)]).reshape(-1)
+        lines.append("---- %s (the results' checksums agree: %s)" % (nm, len(sums[nm]) == 1))
+        for label in ("parent", "branch"):
+            for k, r in enumerate(rows[(label, nm)]):
+                lines.append("%s process %d: %s" % (label, k + 1, "  ".join("%8.2f" % x for x in r)))
+        lo, hi = pa.min(), pa.max()
+        lines.append("parent: median of its medians %.2f, spread of its own medians %.2f .. %.2f (the noise of this job)" % (np.median(pa), lo, hi))
+        lines.append("branch: median of its medians %.2f, its medians %.2f .. %.2f" % (np.median(br), br.min(), br.max()))
+        where = "inside" if lo <= np.median(br) <= hi else ("BELOW" if np.median(br) < lo else "ABOVE")
+        lines.append("branch median %s the parent's spread (%s)" % (where, "gated" if nm in GATED else "reported only"))
+        ok = ok and len(sums[nm]) == 1 and (nm not in GATED or where != "ABOVE")
+    lines.append("gates: %s" % ("hold" if ok else "FAIL"))
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if not args.no_write:
