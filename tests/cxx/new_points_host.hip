@@ -18,10 +18,6 @@
 #include <chrono>
 #include <vector>
 #include "../../include/tsorb.h"
-#include "../../textslam_amd/csrc/tspnp.h"
-#include "../../textslam_amd/csrc/tstwoview.h"
-#include "../../textslam_amd/csrc/tstwoview_rec.h"
-#include "../../textslam_amd/csrc/tstexttheta.h"
 #define TSCLAIM_HOST_ONLY
 #include "../../textslam_amd/csrc/tsclaim.h"
 

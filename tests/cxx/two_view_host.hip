@@ -15,7 +15,6 @@
 #include <chrono>
 #include <vector>
 #include "../../include/tsorb.h"
-#include "../../textslam_amd/csrc/tspnp.h"
 #include "../../textslam_amd/csrc/tstwoview.h"
 
 template <class V> static bool rd(FILE *f, V *p, size_t n) { return n == 0 || fread(p, sizeof(V), n, f) == n; }

@@ -14,8 +14,6 @@
 #include <chrono>
 #include <vector>
 #include "../../include/tsorb.h"
-#include "../../textslam_amd/csrc/tspnp.h"
-#include "../../textslam_amd/csrc/tstwoview.h"
 #include "../../textslam_amd/csrc/tstwoview_rec.h"
 
 template <class V> static bool rd(FILE *f, V *p, size_t n) { return n == 0 || fread(p, sizeof(V), n, f) == n; }

@@ -1,7 +1,6 @@
 // tsclaim.h -- the stateful window searches tracking::SearchForTriangular (src/tracking.cc:1347-1411) and tracking::SearchForInitializ (:1045-1109) and, behind the first,
 // GetForTriangular + CheckTriangular (:1413-1497) on the device (tsorb_match_search_claim, tsorb_match_new_points, include/tsorb.h; docs/newpoints_recalled.md is the
-// arithmetic).  Included by tsorb.hip after tstexttheta.h, whose tt_triangulate_between and tt_pix_to_cam it uses, and after match_walk.  Three launches, no workgroup
-// waits for another:
+// arithmetic).  The point is tstexttheta.h's tt_triangulate_between; the walks are tsorb.hip's match_walk.  Three launches, no workgroup waits for another:
 //   k_claim_walk    a wave per query: match_walk over the context's grid, eligible features only.  The first CL_ROW candidates (index, distance) of every query stay in
 //                   device scratch in the reference's order, with the number there were.
 //   k_claim_chain   ONE workgroup, the reference's loop over the queries in order.  vMatchDist lives in LDS as 16 bits a feature (0 = not eligible: hidden from every
@@ -15,6 +14,7 @@
 // Everything that decides anything is __host__ __device__: tests/cxx/new_points_host.hip runs it on the CPU.  fp64, one rounding per operation, no contraction.
 #pragma once
 #pragma clang fp contract(off)
+#include "tstexttheta.h"
 
 #define CL_T     256                 /* threads of k_claim_chain and k_claim_points; k_claim_walk: four waves = four queries */
 #define CL_ROW   256                 /* candidates of a query kept in scratch (a 96-px window of one octave in a 1000-feature frame holds about 35, the initializer's 100-px window over 1000 octave-0 features 120 - 175; with a row of 128 its re-walks made that call 6.7 ms) */

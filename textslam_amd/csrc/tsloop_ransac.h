@@ -9,6 +9,7 @@
 //   (e) the LM of tsloop_optimize_sim3 (sim3_lm_body) on the candidate's slice, from the selection
 // Every loop is bounded by H <= TSLOOP_RANSAC_MAX_HYP, the candidate's match count, JACOBI_SWEEPS or max_it.
 #pragma once
+#include "tsjacobi.h"
 
 #define JACOBI_SWEEPS 24          // a 4 x 4 converges quadratically: 6-8 sweeps reach an exactly diagonal matrix; the bound only has to be finite
 #define HYP_STRIDE 32             // doubles per hypothesis in LDS: T12 (3 x 4) | T21 (3 x 4) | q t s
@@ -20,25 +21,6 @@ struct Sim3BatchDev {
     double K1[4], K[4]; double max_err2; int32_t min_inliers, optimise;
     int32_t *ok, *sel, *ninl, *hyp_count; double *sim_ransac, *sim, *hyp_sim; tsloop_report *rep; uint8_t *inlier;
 };
-
-// one Jacobi rotation of the pair (p, q): A <- J^T A J, V <- V J
-template <int p, int q>
-__host__ __device__ __forceinline__ void jacobi_rotate(double A[4][4], double V[4][4]) {
-    const double apq = A[p][q];
-    if (apq == 0.0) return;
-    const double g = 100.0*fabs(apq);
-    if (fabs(A[p][p]) + g == fabs(A[p][p]) && fabs(A[q][q]) + g == fabs(A[q][q])) { A[p][q] = 0.0; A[q][p] = 0.0; return; }      // negligible beside both diagonals
-    const double theta = (A[q][q] - A[p][p])/(2.0*apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0)/(fabs(theta) + sqrt(theta*theta + 1.0));
-    const double c = 1.0/sqrt(t*t + 1.0), s = t*c;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = c*akp - s*akq; A[k][q] = s*akp + c*akq; }
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const double apk = A[p][k], aqk = A[q][k]; A[p][k] = c*apk - s*aqk; A[q][k] = s*apk + c*aqk; }
-    A[p][q] = 0.0; A[q][p] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = c*vkp - s*vkq; V[k][q] = s*vkp + c*vkq; }
-}
 
 // (the per-hypothesis and per-match arithmetic is __host__ __device__: a host program can call exactly what the kernel runs)
 // Horn 1987 from three matches a1[i] <-> a2[i] (points as the columns of the reference's Mat33): out = T12 (3 x 4, row-major) | T21 | qw qx qy qz t s
@@ -68,8 +50,8 @@ __host__ __device__ __forceinline__ void horn_sim3(const double a1[3][3], const 
     for (int sweep = 0; sweep < JACOBI_SWEEPS; sweep++) {
         const double offd = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[0][3]) + fabs(A[1][2]) + fabs(A[1][3]) + fabs(A[2][3]);
         if (!(offd > 0.0)) break;                                       // diagonal (or NaN: nothing to gain)
-        jacobi_rotate<0, 1>(A, V); jacobi_rotate<0, 2>(A, V); jacobi_rotate<0, 3>(A, V);
-        jacobi_rotate<1, 2>(A, V); jacobi_rotate<1, 3>(A, V); jacobi_rotate<2, 3>(A, V);
+        jac_sym_rotate<4, 0, 1>(A, V); jac_sym_rotate<4, 0, 2>(A, V); jac_sym_rotate<4, 0, 3>(A, V);
+        jac_sym_rotate<4, 1, 2>(A, V); jac_sym_rotate<4, 1, 3>(A, V); jac_sym_rotate<4, 2, 3>(A, V);
     }
     double q[4] = { V[0][0], V[1][0], V[2][0], V[3][0] }, best = A[0][0];          // the first maximum, as maxCoeff
 #pragma unroll

@@ -1,5 +1,5 @@
 // tspnp.h -- tracking::CheckMatch's cv::solvePnPRansac on the device (tsorb_match_pnp_ransac, include/tsorb.h; docs/pnpransac_recalled.md is the arithmetic).
-// Included by tsorb.hip.  Three launches, no workgroup waits for another:
+// Three launches, no workgroup waits for another:
 //   k_pnp_hyp     one hypothesis per wave (four per 256-thread workgroup): EPnP on the subset's five matches.  The 10 x 12 M, the 12 x 12 MtM and its eigenvectors
 //                 live in LDS; MtM and the cyclic Jacobi iteration (round-robin order: six disjoint rotations per step) are spread over the wave's lanes, the rest
 //                 runs in fp64 on lane 0 and, for the three starts of the betas, lanes 0 .. 2 (their small systems unrolled to constant indices: registers, no
@@ -11,19 +11,13 @@
 // The per-hypothesis and per-match arithmetic is __host__ __device__ with the lane and the lane count as arguments: a host program calls it with (0, 1) and runs
 // exactly what the kernel runs (the items of a phase are independent of each other, so their order does not matter).  Every loop is bounded.
 #pragma once
+#include "tsjacobi.h"
 
 #define PNP_T 256
 #define PNP_NW (PNP_T/64)
 #define PNP_SWEEPS 40             // a 12 x 12 is diagonal after 8 - 11 sweeps; the bound only has to be finite
+#define PNP_POLAR_ORTHO 1e-17     // pnp_polar3 turns a pair of columns while |g_p . g_q| > PNP_POLAR_ORTHO |g_p| |g_q|: to working precision, and no second test
 #define PNP_DEGENERATE 1e-12      // scatter eigenvalue ratio below which the five points count as coplanar / collinear / coincident: the hypothesis is NaN
-
-#ifdef __HIP_DEVICE_COMPILE__
-#define PNP_SYNC() __syncthreads()
-#define PNP_ALL(x) __syncthreads_and(x)
-#else
-#define PNP_SYNC() do { } while (0)
-#define PNP_ALL(x) (x)
-#endif
 
 struct PnpWs {                    // one hypothesis' workspace: LDS on the device, the stack on the host
     double A[144], V[144];        // MtM (then its diagonal form) and the accumulated rotations: column j of V = eigenvector j
@@ -42,46 +36,13 @@ struct PnpDev {
     int32_t *result, *count; double *pose, *hyp_pose; uint8_t *inlier;
 };
 
-__host__ __device__ __forceinline__ double pnp_nan() { return __builtin_nan(""); }
-
-// the rotation that annihilates a_pq (Rutishauser; the rule of tsloop_ransac.h's jacobi_rotate): c = 1, s = 0 when there is nothing to do
-__host__ __device__ __forceinline__ void pnp_rotation(double app, double aqq, double apq, double &c, double &s) {
-    c = 1.0; s = 0.0;
-    if (apq == 0.0) return;
-    const double g = 100.0*fabs(apq);
-    if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) return;          // negligible beside both diagonals: set to zero by the caller
-    const double theta = (aqq - app)/(2.0*apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0)/(fabs(theta) + sqrt(theta*theta + 1.0));
-    c = 1.0/sqrt(t*t + 1.0); s = t*c;
-}
-
-// largest-magnitude component (the first on ties) made positive
-__host__ __device__ __forceinline__ void pnp_sign(double *v, int n) {
-    int k = 0;
-    for (int i = 1; i < n; i++) if (fabs(v[i]) > fabs(v[k])) k = i;
-    if (v[k] < 0.0) for (int i = 0; i < n; i++) v[i] = -v[i];
-}
-
-// one rotation of the pair (p, q) of a symmetric 3 x 3: S <- J^T S J, Q <- Q J (constant indices: the arrays stay in registers)
-template <int p, int q>
-__host__ __device__ __forceinline__ void pnp_sym3_rotate(double S[3][3], double Q[3][3]) {
-    double c, s; pnp_rotation(S[p][p], S[q][q], S[p][q], c, s);
-#pragma unroll
-    for (int k = 0; k < 3; k++) { const double akp = S[k][p], akq = S[k][q]; S[k][p] = c*akp - s*akq; S[k][q] = s*akp + c*akq; }
-#pragma unroll
-    for (int k = 0; k < 3; k++) { const double apk = S[p][k], aqk = S[q][k]; S[p][k] = c*apk - s*aqk; S[q][k] = s*apk + c*aqk; }
-    S[p][q] = 0.0; S[q][p] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { const double vkp = Q[k][p], vkq = Q[k][q]; Q[k][p] = c*vkp - s*vkq; Q[k][q] = s*vkp + c*vkq; }
-}
-
 // eigenvalues (descending, the first of equal ones first) and eigenvectors (rows of U, sign rule) of a symmetric 3 x 3: cyclic Jacobi
 __host__ __device__ inline void pnp_sym3_eig(double S[3][3], double d[3], double U[3][3]) {
     double Q[3][3] = { {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0} };
 #pragma unroll 1
     for (int sweep = 0; sweep < PNP_SWEEPS; sweep++) {
         if (!(fabs(S[0][1]) + fabs(S[0][2]) + fabs(S[1][2]) > 0.0)) break;
-        pnp_sym3_rotate<0, 1>(S, Q); pnp_sym3_rotate<0, 2>(S, Q); pnp_sym3_rotate<1, 2>(S, Q);
+        jac_sym_rotate<3, 0, 1>(S, Q); jac_sym_rotate<3, 0, 2>(S, Q); jac_sym_rotate<3, 1, 2>(S, Q);
     }
     // descending order by three compare-and-swaps on (value, column) pairs: the first of equal ones first
     double e0 = S[0][0], e1 = S[1][1], e2 = S[2][2];
@@ -92,7 +53,7 @@ __host__ __device__ inline void pnp_sym3_eig(double S[3][3], double d[3], double
     d[0] = e0; d[1] = e1; d[2] = e2;
 #pragma unroll
     for (int k = 0; k < 3; k++) { U[0][k] = c0[k]; U[1][k] = c1[k]; U[2][k] = c2[k]; }
-    pnp_sign(U[0], 3); pnp_sign(U[1], 3); pnp_sign(U[2], 3);
+    jac_sign(U[0], 3); jac_sign(U[1], 3); jac_sign(U[2], 3);
 }
 
 // choose_control_points + compute_barycentric_coordinates + fill_M on the subset's five matches (one lane)
@@ -107,7 +68,7 @@ __host__ __device__ inline void pnp_setup(PnpWs &W, const float *Pw, const float
     pnp_sym3_eig(S, d, U);
     const bool degenerate = !(d[2] > PNP_DEGENERATE*d[0]);
     double k[3];
-    for (int i = 0; i < 3; i++) k[i] = degenerate ? pnp_nan() : sqrt(d[i]/5.0);
+    for (int i = 0; i < 3; i++) k[i] = degenerate ? ts_nan() : sqrt(d[i]/5.0);
     for (int a = 0; a < 3; a++) { W.cw[a] = c0[a]; for (int i = 0; i < 3; i++) W.cw[3*(i + 1) + a] = c0[a] + k[i]*U[i][a]; }
     // CC = (k_j u_j) as columns, so row j of its inverse is u_j / k_j
     for (int i = 0; i < 5; i++) { double *a = W.al + 4*i;
@@ -125,34 +86,27 @@ __host__ __device__ inline void pnp_mtm(PnpWs &W, int lane, int nl) {
         W.A[e] = s; W.V[e] = i == j ? 1.0 : 0.0; }
 }
 
-// pair i (0 .. 5) of step r (0 .. 10) of the round-robin order over 12 indices: 11 stays, the others turn
-__host__ __device__ __forceinline__ void pnp_pair(int r, int i, int &p, int &q) {
-    int a, b;
-    if (i == 0) { a = 11; b = r; } else { a = (r + i)%11; b = (r + 11 - i)%11; }
-    p = a < b ? a : b; q = a < b ? b : a;
-}
-
-// cyclic Jacobi on the symmetric 12 x 12 in W.A: A <- J^T A J, V <- V J, six disjoint rotations per step (lanes)
+// cyclic Jacobi on the symmetric 12 x 12 in W.A: A <- J^T A J, V <- V J, the six disjoint rotations of a round-robin step over 12 indices (jac_pair<11>) at a time (lanes)
 __host__ __device__ inline void pnp_jacobi12(PnpWs &W, int lane, int nl) {
 #pragma unroll 1
     for (int sweep = 0; sweep < PNP_SWEEPS; sweep++) {
         double off = 0.0;
         for (int i = 0; i < 12; i++) for (int j = i + 1; j < 12; j++) off += fabs(W.A[12*i + j]);
-        if (PNP_ALL(!(off > 0.0))) break;                                   // diagonal (or NaN: nothing to gain); uniform over the workgroup
+        if (TS_ALL(!(off > 0.0))) break;                                   // diagonal (or NaN: nothing to gain); uniform over the workgroup
 #pragma unroll 1
         for (int r = 0; r < 11; r++) {
-            for (int i = lane; i < 6; i += nl) { int p, q; pnp_pair(r, i, p, q);
-                pnp_rotation(W.A[13*p], W.A[13*q], W.A[12*p + q], W.cs[2*i], W.cs[2*i + 1]); }
-            PNP_SYNC();
-            for (int e = lane; e < 144; e += nl) { const int i = (e%72)/12, k = e%12; int p, q; pnp_pair(r, i, p, q);
+            for (int i = lane; i < 6; i += nl) { int p, q; jac_pair<11>(r, i, p, q);
+                jac_sym_rotation(W.A[13*p], W.A[13*q], W.A[12*p + q], W.cs[2*i], W.cs[2*i + 1]); }
+            TS_BARRIER();
+            for (int e = lane; e < 144; e += nl) { const int i = (e%72)/12, k = e%12; int p, q; jac_pair<11>(r, i, p, q);
                 double *X = e < 72 ? W.A : W.V; const double c = W.cs[2*i], s = W.cs[2*i + 1];
                 const double xkp = X[12*k + p], xkq = X[12*k + q]; X[12*k + p] = c*xkp - s*xkq; X[12*k + q] = s*xkp + c*xkq; }
-            PNP_SYNC();
-            for (int e = lane; e < 72; e += nl) { const int i = e/12, k = e%12; int p, q; pnp_pair(r, i, p, q);
+            TS_BARRIER();
+            for (int e = lane; e < 72; e += nl) { const int i = e/12, k = e%12; int p, q; jac_pair<11>(r, i, p, q);
                 const double c = W.cs[2*i], s = W.cs[2*i + 1];
                 const double apk = W.A[12*p + k], aqk = W.A[12*q + k];
                 W.A[12*p + k] = k == q ? 0.0 : c*apk - s*aqk; W.A[12*q + k] = k == p ? 0.0 : s*apk + c*aqk; }
-            PNP_SYNC();
+            TS_BARRIER();
         }
     }
 }
@@ -168,7 +122,7 @@ __host__ __device__ inline void pnp_basis(PnpWs &W) {
     for (int j = 1; j < 12; j++) { const double pj = v0[j]*v0[j] + v1[j]*v1[j]; if (pj > best) { best = pj; k = j; } }
     const double a = v0[k], b = v1[k], rr = sqrt(a*a + b*b);
     for (int j = 0; j < 12; j++) { const double x = v0[j], y = v1[j]; v1[j] = (a*x + b*y)/rr; v0[j] = (b*x - a*y)/rr; }
-    pnp_sign(v0, 12); pnp_sign(W.v + 24, 12); pnp_sign(W.v + 36, 12);
+    jac_sign(v0, 12); jac_sign(W.v + 24, 12); jac_sign(W.v + 36, 12);
     double (*dv)[6][3] = (double (*)[6][3])W.M;                               // 72 doubles in M's place (MtM has been formed)
     for (int i = 0; i < 4; i++) { int p = 0, q = 1; const double *v = W.v + 12*i;
         for (int j = 0; j < 6; j++) { for (int c = 0; c < 3; c++) dv[i][j][c] = v[3*p + c] - v[3*q + c];
@@ -223,37 +177,16 @@ __host__ __device__ __forceinline__ void pnp_lstsq6(double (&A)[6][NC], int nc, 
         x[k] = k < nc ? s/A[k][k] : 0.0; }
 }
 
-// one step of the one-sided Jacobi iteration on the columns (p, q) of G: returns whether it turned them (constant indices: the arrays stay in registers)
-template <int p, int q>
-__host__ __device__ __forceinline__ bool pnp_polar3_turn(double G[3][3], double Q[3][3]) {
-    double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; i++) { al += G[i][p]*G[i][p]; be += G[i][q]*G[i][q]; ga += G[i][p]*G[i][q]; }
-    if (!(fabs(ga) > 1e-17*sqrt(al*be))) return false;                      // orthogonal to working precision (or NaN)
-    const double zeta = (be - al)/(2.0*ga);
-    const double t = (zeta >= 0.0 ? 1.0 : -1.0)/(fabs(zeta) + sqrt(zeta*zeta + 1.0));
-    const double c = 1.0/sqrt(t*t + 1.0), s = t*c;
-#pragma unroll
-    for (int i = 0; i < 3; i++) { const double gp = G[i][p], gq = G[i][q]; G[i][p] = c*gp - s*gq; G[i][q] = s*gp + c*gq; }
-#pragma unroll
-    for (int i = 0; i < 3; i++) { const double vp = Q[i][p], vq = Q[i][q]; Q[i][p] = c*vp - s*vq; Q[i][q] = s*vp + c*vq; }
-    return true;
-}
-
 // R = U V^T of the 3 x 3 B = U S V^T by one-sided Jacobi (the columns of B turned until they are orthogonal): independent of the order and signs of the triplets
 __host__ __device__ inline void pnp_polar3(const double B[3][3], double R[3][3]) {
-    double G[3][3], Q[3][3] = { {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0} };
+    double G[3][3], Q[3][3];
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) G[i][j] = B[i][j];
-#pragma unroll 1
-    for (int sweep = 0; sweep < PNP_SWEEPS; sweep++) {
-        const bool t01 = pnp_polar3_turn<0, 1>(G, Q), t02 = pnp_polar3_turn<0, 2>(G, Q), t12 = pnp_polar3_turn<1, 2>(G, Q);
-        if (!(t01 || t02 || t12)) break;
-    }
+    jac_orthogonalize(G, Q, PNP_POLAR_ORTHO, 0.0);
 #pragma unroll
-    for (int j = 0; j < 3; j++) { const double nrm = sqrt((G[0][j]*G[0][j] + G[1][j]*G[1][j]) + G[2][j]*G[2][j]);
+    for (int j = 0; j < 3; j++) { const double nrm = sqrt(jac_length2(G, j));
 #pragma unroll
         for (int i = 0; i < 3; i++) G[i][j] /= nrm; }
 #pragma unroll
@@ -323,19 +256,19 @@ __host__ __device__ inline void pnp_start(PnpWs &W, const double K[4], int s) {
 // epnp::compute_pose on the subset: W.pose = R | t (3 x 4 row-major) of the start with the smallest error, in the reference's order of comparisons
 __host__ __device__ inline void pnp_hypothesis(PnpWs &W, const float *Pw, const float *uv, const int32_t *idx, const double K[4], int lane, int nl) {
     if (lane == 0) pnp_setup(W, Pw, uv, idx, K);
-    PNP_SYNC();
+    TS_BARRIER();
     pnp_mtm(W, lane, nl);
-    PNP_SYNC();
+    TS_BARRIER();
     pnp_jacobi12(W, lane, nl);
     if (lane == 0) pnp_basis(W);
-    PNP_SYNC();
+    TS_BARRIER();
     for (int s = lane; s < 3; s += nl) pnp_start(W, K, s);
-    PNP_SYNC();
+    TS_BARRIER();
     if (lane == 0) { int N = 0;
         if (W.err[1] < W.err[0]) N = 1;
         if (W.err[2] < W.err[N]) N = 2;
         for (int j = 0; j < 12; j++) W.pose[j] = W.Rt[12*N + j]; }
-    PNP_SYNC();
+    TS_BARRIER();
 }
 
 // PnPRansacCallback::computeError for one match: projectPoints in double stored as float, float differences, their squares added in float

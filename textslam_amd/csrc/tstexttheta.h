@@ -1,6 +1,5 @@
 // tstexttheta.h -- tracking::GetTextTheta / SolveTheta and initializer::CalculateTextTheta on the device (tsorb_match_text_theta_ransac, include/tsorb.h;
-// docs/texttheta_recalled.md is the arithmetic).  Included by tsorb.hip after tstwoview_rec.h, whose rec_turn4 (and through it tv_rotation, TV_SWEEPS) and TV_MUL it
-// uses.  Three launches, no workgroup waits for another:
+// docs/texttheta_recalled.md is the arithmetic).  Three launches, no workgroup waits for another:
 //   k_tt_rho      one thread per feature.  rho given: it is copied and the point is zero.  Otherwise cv::triangulatePoints between [I | 0] and Tcr: the 4 x 4 in
 //                 double, its null vector by the one-sided iteration on the four columns in fp64 in registers (a lane turning until ITS matrix has converged), the
 //                 4-vector rounded to float, the division by its last entry as a float reciprocal and a float product per entry, rho = 1.0/(double)z.
@@ -12,6 +11,7 @@
 // Everything that decides anything is __host__ __device__: tests/cxx/text_theta_host.hip runs it on the CPU.  fp64 throughout, one rounding per operation, no contraction.
 #pragma once
 #pragma clang fp contract(off)
+#include "tsjacobi.h"
 
 #define TT_T 256
 #define TT_TH 5.991f               // SolveTheta's `const float th = 5.991`, compared and subtracted as a double
@@ -29,29 +29,16 @@ __host__ __device__ __forceinline__ float tt_pix_to_cam(float p, double c, doubl
 __host__ __device__ inline void tt_triangulate_between(const double P1[12], const double T[12], const double K[4], const float *h, const float *t, float X[3], double &rho) {
     const double x1 = (double)tt_pix_to_cam(h[0], K[2], K[0]), y1 = (double)tt_pix_to_cam(h[1], K[3], K[1]);
     const double x2 = (double)tt_pix_to_cam(t[0], K[2], K[0]), y2 = (double)tt_pix_to_cam(t[1], K[3], K[1]);
-    double G[4][4], Q[4][4];
+    double G[4][4], vd[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         G[0][j] = x1*P1[8 + j] - P1[j]; G[1][j] = y1*P1[8 + j] - P1[4 + j];
-        G[2][j] = x2*T[8 + j] - T[j];   G[3][j] = y2*T[8 + j] - T[4 + j];
-#pragma unroll
-        for (int i = 0; i < 4; i++) Q[i][j] = i == j ? 1.0 : 0.0; }
-#pragma unroll 1
-    for (int sweep = 0; sweep < TV_SWEEPS; sweep++) {                      // the pair order of rec_triangulate; a NaN never turns
-        const bool a = rec_turn4<0, 1>(G, Q), b = rec_turn4<2, 3>(G, Q), c = rec_turn4<0, 2>(G, Q), d = rec_turn4<1, 3>(G, Q), e = rec_turn4<0, 3>(G, Q), f = rec_turn4<1, 2>(G, Q);
-        if (!(a || b || c || d || e || f)) break;
-    }
-    double d[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) d[j] = ((G[0][j]*G[0][j] + G[1][j]*G[1][j]) + G[2][j]*G[2][j]) + G[3][j]*G[3][j];
-    const int j01 = d[1] < d[0] ? 1 : 0, j23 = d[3] < d[2] ? 3 : 2; const double m01 = j01 ? d[1] : d[0], m23 = j23 == 3 ? d[3] : d[2];
-    const int jmin = m23 < m01 ? j23 : j01;                                // the smallest singular value, the first of equal ones
-    float v[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) v[i] = (float)(jmin == 0 ? Q[i][0] : jmin == 1 ? Q[i][1] : jmin == 2 ? Q[i][2] : Q[i][3]);
+        G[2][j] = x2*T[8 + j] - T[j];   G[3][j] = y2*T[8 + j] - T[4 + j]; }
+    jac_null4(G, vd);
+    const float v[4] = { (float)vd[0], (float)vd[1], (float)vd[2], (float)vd[3] };
     const float r = (float)(1.0/(double)v[3]);                             // Mat /= scalar: the reciprocal in double, rounded to float, a float product per entry
 #pragma unroll
-    for (int i = 0; i < 3; i++) X[i] = TV_MUL(v[i], r);
+    for (int i = 0; i < 3; i++) X[i] = TS_FMUL(v[i], r);
     rho = 1.0/(double)X[2];
 }
 // ... between P1 = [I | 0] and P2 = T: GetTextTheta's

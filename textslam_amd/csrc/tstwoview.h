@@ -1,5 +1,5 @@
 // tstwoview.h -- initializer::FindHomography / FindFundamental on the device (tsorb_match_two_view_ransac, include/tsorb.h; docs/twoview_recalled.md is the arithmetic).
-// Included by tsorb.hip after tspnp.h, whose pnp_sign, PNP_SYNC, PNP_ALL and PNP_DEGENERATE it uses.  Three launches, no workgroup waits for another:
+// Three launches, no workgroup waits for another:
 //   k_tv_fit     one fit per wave and workgroup, 2 n_hyp fits: the H fits first, then the F fits.  The 16 x 9 (H) or 8 x 9 (F) system A and the
 //                accumulated rotations V live in LDS; the null vector is the right singular vector of A's smallest singular value by a one-sided (Hestenes) Jacobi
 //                iteration on A's nine columns in fp64 -- the round-robin order over 9 indices and a bye (9 steps of 4 disjoint pairs a sweep), a lane per pair for
@@ -10,29 +10,16 @@
 //   k_tv_select  one workgroup: the scores go to LDS, lane 0 of waves 0 and 1 run the two keep loops over them (strictly greater from 0.0: the first of equal scores stays, a NaN is never kept),
 //                then all threads re-form the kept hypotheses' masks with the same device functions.
 // Everything that decides anything is __host__ __device__ with the lane and the lane count as arguments: a host program calls it with (0, 1) and runs what the kernel
-// runs (the items of a phase are independent of each other).  Every loop is bounded.  Float arithmetic whose bits matter goes through TV_MUL / TV_ADD / TV_SUB / TV_DIV:
-// one rounding each, no contraction (the library and the host builds also use -ffp-contract=off).
+// runs (the items of a phase are independent of each other).  Every loop is bounded.  Float arithmetic whose bits matter goes through tsjacobi.h's TS_FMUL / TS_FADD / TS_FSUB /
+// TS_FDIV: one rounding each, no contraction (the library and the host builds also use -ffp-contract=off).
 #pragma once
 #pragma clang fp contract(off)
+#include "tsjacobi.h"
 
 #define TV_T 256
 #define TV_NW (TV_T/64)
 #define TV_SWEEPS 40              // nine columns are orthogonal after 6 - 9 sweeps; the bound only has to be finite
-#define TV_ORTHO 1e-14            // |a_p . a_q| <= TV_ORTHO |a_p| |a_q|: the pair counts as orthogonal
-#define TV_TINY 1e-17             // ... and so does one whose rotation angle (below |a_p . a_q| / (|a_p|^2 + |a_q|^2)) could not change a double of V
-#define TV_DEGENERATE PNP_DEGENERATE   // second smallest eigenvalue of AtA over the largest at or below which the subset is degenerate: the model is NaN
-
-#ifdef __HIP_DEVICE_COMPILE__
-#define TV_MUL(a, b) __fmul_rn(a, b)
-#define TV_ADD(a, b) __fadd_rn(a, b)
-#define TV_SUB(a, b) __fsub_rn(a, b)
-#define TV_DIV(a, b) __fdiv_rn(a, b)
-#else
-#define TV_MUL(a, b) ((float)(a)*(float)(b))
-#define TV_ADD(a, b) ((float)(a) + (float)(b))
-#define TV_SUB(a, b) ((float)(a) - (float)(b))
-#define TV_DIV(a, b) ((float)(a)/(float)(b))
-#endif
+#define TV_DEGENERATE 1e-12       // second smallest eigenvalue of AtA over the largest at or below which the subset is degenerate: the model is NaN
 
 struct TvWs {                     // one fit's workspace: LDS on the device, the stack on the host
     double A[144], V[81];         // the system (16 or 8 rows of 9) and the accumulated rotations: A_now = A_0 V
@@ -48,7 +35,7 @@ struct TvDev {
 };
 
 // initializer::Normalize's point: (x - mean) * s, two float roundings
-__host__ __device__ __forceinline__ float tv_normalized(float x, float mean, float s) { return TV_MUL(TV_SUB(x, mean), s); }
+__host__ __device__ __forceinline__ float tv_normalized(float x, float mean, float s) { return TS_FMUL(TS_FSUB(x, mean), s); }
 
 // ComputeH21's 16 x 9 (model 0) or ComputeF21's 8 x 9 (model 1) from the subset's eight matches: the reference's float products, then doubles; V = I (lanes)
 __host__ __device__ inline void tv_setup(TvWs &W, int model, const float *xy1, const float *xy2, const float *n1, const float *n2, const int32_t *idx, int lane, int nl) {
@@ -57,52 +44,37 @@ __host__ __device__ inline void tv_setup(TvWs &W, int model, const float *xy1, c
         const float u2 = tv_normalized(xy2[2*i], n2[0], n2[2]), v2 = tv_normalized(xy2[2*i + 1], n2[1], n2[3]);
         if (model == 0) { double *a = W.A + 18*j, *b = a + 9;
             a[0] = 0.0; a[1] = 0.0; a[2] = 0.0; a[3] = (double)-u1; a[4] = (double)-v1; a[5] = -1.0;
-            a[6] = (double)TV_MUL(v2, u1); a[7] = (double)TV_MUL(v2, v1); a[8] = (double)v2;
+            a[6] = (double)TS_FMUL(v2, u1); a[7] = (double)TS_FMUL(v2, v1); a[8] = (double)v2;
             b[0] = (double)u1; b[1] = (double)v1; b[2] = 1.0; b[3] = 0.0; b[4] = 0.0; b[5] = 0.0;
-            b[6] = (double)TV_MUL(-u2, u1); b[7] = (double)TV_MUL(-u2, v1); b[8] = (double)-u2;
+            b[6] = (double)TS_FMUL(-u2, u1); b[7] = (double)TS_FMUL(-u2, v1); b[8] = (double)-u2;
         } else { double *a = W.A + 9*j;
-            a[0] = (double)TV_MUL(u2, u1); a[1] = (double)TV_MUL(u2, v1); a[2] = (double)u2;
-            a[3] = (double)TV_MUL(v2, u1); a[4] = (double)TV_MUL(v2, v1); a[5] = (double)v2;
+            a[0] = (double)TS_FMUL(u2, u1); a[1] = (double)TS_FMUL(u2, v1); a[2] = (double)u2;
+            a[3] = (double)TS_FMUL(v2, u1); a[4] = (double)TS_FMUL(v2, v1); a[5] = (double)v2;
             a[6] = (double)u1; a[7] = (double)v1; a[8] = 1.0; } }
     for (int e = lane; e < 81; e += nl) W.V[e] = e/9 == e%9 ? 1.0 : 0.0;
 }
 
-// pair i (1 .. 4) of step r (0 .. 8) of the round-robin order over 9 indices and a bye (pair 0 would be the bye's)
-__host__ __device__ __forceinline__ void tv_pair(int r, int i, int &p, int &q) {
-    const int a = (r + i)%9, b = (r + 9 - i)%9;
-    p = a < b ? a : b; q = a < b ? b : a;
-}
-
-// the rotation that makes two columns with squared lengths al, be and product ga orthogonal; false (c = 1, s = 0) when they count as orthogonal already (or NaN)
-__host__ __device__ __forceinline__ bool tv_rotation(double al, double be, double ga, double &c, double &s) {
-    c = 1.0; s = 0.0;
-    if (!(fabs(ga) > TV_ORTHO*sqrt(al*be)) || !(fabs(ga) > TV_TINY*(al + be))) return false;
-    const double zeta = (be - al)/(2.0*ga);
-    const double t = (zeta >= 0.0 ? 1.0 : -1.0)/(fabs(zeta) + sqrt(zeta*zeta + 1.0));
-    c = 1.0/sqrt(t*t + 1.0); s = t*c;
-    return true;
-}
-
-// one-sided Jacobi on the m x 9 in W.A: its columns turned until they are orthogonal, V <- V J, four disjoint pairs per step (lanes)
+// one-sided Jacobi on the m x 9 in W.A: its columns turned until they are orthogonal, V <- V J, the four disjoint pairs i = 1 .. 4 of a round-robin step over 9 indices
+// and a bye (jac_pair<9>) at a time (lanes)
 __host__ __device__ inline void tv_jacobi9(TvWs &W, int m, int lane, int nl) {
 #pragma unroll 1
     for (int sweep = 0; sweep < TV_SWEEPS; sweep++) {
         for (int i = 1 + lane; i < 5; i += nl) W.flag[i] = 0;
 #pragma unroll 1
         for (int r = 0; r < 9; r++) {
-            for (int i = 1 + lane; i < 5; i += nl) { int p, q; tv_pair(r, i, p, q);
+            for (int i = 1 + lane; i < 5; i += nl) { int p, q; jac_pair<9>(r, i, p, q);
                 double al = 0.0, be = 0.0, ga = 0.0;
                 for (int k = 0; k < m; k++) { const double ap = W.A[9*k + p], aq = W.A[9*k + q]; al += ap*ap; be += aq*aq; ga += ap*aq; }
-                if (tv_rotation(al, be, ga, W.cs[2*i], W.cs[2*i + 1])) W.flag[i] = 1; }
-            PNP_SYNC();
-            for (int e = lane; e < 4*(m + 9); e += nl) { const int i = 1 + e/(m + 9), k = e%(m + 9); int p, q; tv_pair(r, i, p, q);
+                if (jac_rotation(al, be, ga, JAC_ORTHO, JAC_TINY, W.cs[2*i], W.cs[2*i + 1])) W.flag[i] = 1; }
+            TS_BARRIER();
+            for (int e = lane; e < 4*(m + 9); e += nl) { const int i = 1 + e/(m + 9), k = e%(m + 9); int p, q; jac_pair<9>(r, i, p, q);
                 double *X = k < m ? W.A + 9*k : W.V + 9*(k - m); const double c = W.cs[2*i], s = W.cs[2*i + 1];
                 const double xp = X[p], xq = X[q]; X[p] = c*xp - s*xq; X[q] = s*xp + c*xq; }
-            PNP_SYNC();
+            TS_BARRIER();
         }
         const bool any = (W.flag[1] | W.flag[2] | W.flag[3] | W.flag[4]) != 0;
         if (lane == 0) W.sweeps = sweep + 1;
-        if (PNP_ALL(!any)) break;                                            // nothing turned in a whole sweep (a NaN never turns); uniform over the workgroup
+        if (TS_ALL(!any)) break;                                            // nothing turned in a whole sweep (a NaN never turns); uniform over the workgroup
     }
 }
 
@@ -118,41 +90,20 @@ __host__ __device__ inline void tv_null_vector(const TvWs &W, int m, double v[9]
     double nn = 0.0;
     for (int j = 0; j < 9; j++) { v[j] = W.V[9*j + jmin]; nn += v[j]*v[j]; }
     nn = sqrt(nn);
-    for (int j = 0; j < 9; j++) v[j] = degenerate ? pnp_nan() : v[j]/nn;
-    pnp_sign(v, 9);
-}
-
-// one step of the one-sided iteration on the columns (p, q) of a 3 x 3 (constant indices: registers)
-template <int p, int q>
-__host__ __device__ __forceinline__ bool tv_turn3(double G[3][3], double Q[3][3]) {
-    double al = 0.0, be = 0.0, ga = 0.0, c, s;
-#pragma unroll
-    for (int i = 0; i < 3; i++) { al += G[i][p]*G[i][p]; be += G[i][q]*G[i][q]; ga += G[i][p]*G[i][q]; }
-    if (!tv_rotation(al, be, ga, c, s)) return false;
-#pragma unroll
-    for (int i = 0; i < 3; i++) { const double gp = G[i][p], gq = G[i][q]; G[i][p] = c*gp - s*gq; G[i][q] = s*gp + c*gq; }
-#pragma unroll
-    for (int i = 0; i < 3; i++) { const double vp = Q[i][p], vq = Q[i][q]; Q[i][p] = c*vp - s*vq; Q[i][q] = s*vp + c*vq; }
-    return true;
+    for (int j = 0; j < 9; j++) v[j] = degenerate ? ts_nan() : v[j]/nn;
+    jac_sign(v, 9);
 }
 
 // ComputeF21's second SVD: F = U diag(w) V^T with the smallest w (the first of equal ones) set to 0.  G = F Q has orthogonal columns u_j w_j, so the answer is
 // G with that column zeroed, times Q^T: independent of the order and signs of the triplets
 __host__ __device__ inline void tv_rank2(const double F[9], double Fn[9]) {
-    double G[3][3], Q[3][3] = { {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0} };
+    double G[3][3], Q[3][3];
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) G[i][j] = F[3*i + j];
-#pragma unroll 1
-    for (int sweep = 0; sweep < TV_SWEEPS; sweep++) {
-        const bool t01 = tv_turn3<0, 1>(G, Q), t02 = tv_turn3<0, 2>(G, Q), t12 = tv_turn3<1, 2>(G, Q);
-        if (!(t01 || t02 || t12)) break;
-    }
-    double d[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) d[j] = (G[0][j]*G[0][j] + G[1][j]*G[1][j]) + G[2][j]*G[2][j];
-    const int jmin = d[1] < d[0] ? (d[2] < d[1] ? 2 : 1) : (d[2] < d[0] ? 2 : 0);
+    jac_orthogonalize(G, Q, JAC_ORTHO, JAC_TINY);
+    const int jmin = jac_shortest(G);
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -161,7 +112,7 @@ __host__ __device__ inline void tv_rank2(const double F[9], double Fn[9]) {
 
 // T = [[sX, 0, -meanX sX], [0, sY, -meanY sY], [0, 0, 1]] as the reference's floats: t[0 .. 3] = sX, sY, T02, T12
 __host__ __device__ __forceinline__ void tv_T(const float nrm[4], double t[4]) {
-    t[0] = (double)nrm[2]; t[1] = (double)nrm[3]; t[2] = (double)TV_MUL(-nrm[0], nrm[2]); t[3] = (double)TV_MUL(-nrm[1], nrm[3]);
+    t[0] = (double)nrm[2]; t[1] = (double)nrm[3]; t[2] = (double)TS_FMUL(-nrm[0], nrm[2]); t[3] = (double)TS_FMUL(-nrm[1], nrm[3]);
 }
 
 // M T1 for a 3 x 3 M (fp64)
@@ -187,10 +138,10 @@ __host__ __device__ inline void tv_model(TvWs &W, int model, const float *n1, co
 
 __host__ __device__ inline void tv_fit(TvWs &W, int model, const float *xy1, const float *xy2, const float *n1, const float *n2, const int32_t *idx, int lane, int nl) {
     tv_setup(W, model, xy1, xy2, n1, n2, idx, lane, nl);
-    PNP_SYNC();
+    TS_BARRIER();
     tv_jacobi9(W, model == 0 ? 16 : 8, lane, nl);
     if (lane == 0) tv_model(W, model, n1, n2);
-    PNP_SYNC();
+    TS_BARRIER();
 }
 
 // H12i = the inverse of the FLOAT H21i: adjugate over determinant in fp64, rounded to float; a zero determinant gives zeros (cv::Mat::inv() as recalled)
@@ -201,22 +152,22 @@ __host__ __device__ inline void tv_h_inverse(const float h[9], float hi[9]) {
     for (int j = 0; j < 9; j++) hi[j] = det == 0.0 ? 0.f : (float)(adj[j]/det);
 }
 
-__host__ __device__ __forceinline__ float tv_inv_sigma2(float sigma) { return (float)(1.0/(double)TV_MUL(sigma, sigma)); }
-__host__ __device__ __forceinline__ float tv_dot3(float a, float x, float b, float y, float c) { return TV_ADD(TV_ADD(TV_MUL(a, x), TV_MUL(b, y)), c); }
+__host__ __device__ __forceinline__ float tv_inv_sigma2(float sigma) { return (float)(1.0/(double)TS_FMUL(sigma, sigma)); }
+__host__ __device__ __forceinline__ float tv_dot3(float a, float x, float b, float y, float c) { return TS_FADD(TS_FADD(TS_FMUL(a, x), TS_FMUL(b, y)), c); }
 
 // CheckHomography for one match: the two score terms (0 where the reference adds nothing; a term is never negative, so adding it changes no bit) and bIn
 __host__ __device__ inline bool tv_terms_h(const float *h, const float *hi, float u1, float v1, float u2, float v2, float iss, float &t1, float &t2) {
     const float th = 5.991f; bool in = true;
     const float w2 = (float)(1.0/(double)tv_dot3(hi[6], u2, hi[7], v2, hi[8]));
-    const float u2in1 = TV_MUL(tv_dot3(hi[0], u2, hi[1], v2, hi[2]), w2), v2in1 = TV_MUL(tv_dot3(hi[3], u2, hi[4], v2, hi[5]), w2);
-    const float du1 = TV_SUB(u1, u2in1), dv1 = TV_SUB(v1, v2in1);
-    const float chi1 = TV_MUL(TV_ADD(TV_MUL(du1, du1), TV_MUL(dv1, dv1)), iss);
-    if (chi1 > th) { in = false; t1 = 0.f; } else t1 = TV_SUB(th, chi1);
+    const float u2in1 = TS_FMUL(tv_dot3(hi[0], u2, hi[1], v2, hi[2]), w2), v2in1 = TS_FMUL(tv_dot3(hi[3], u2, hi[4], v2, hi[5]), w2);
+    const float du1 = TS_FSUB(u1, u2in1), dv1 = TS_FSUB(v1, v2in1);
+    const float chi1 = TS_FMUL(TS_FADD(TS_FMUL(du1, du1), TS_FMUL(dv1, dv1)), iss);
+    if (chi1 > th) { in = false; t1 = 0.f; } else t1 = TS_FSUB(th, chi1);
     const float w1 = (float)(1.0/(double)tv_dot3(h[6], u1, h[7], v1, h[8]));
-    const float u1in2 = TV_MUL(tv_dot3(h[0], u1, h[1], v1, h[2]), w1), v1in2 = TV_MUL(tv_dot3(h[3], u1, h[4], v1, h[5]), w1);
-    const float du2 = TV_SUB(u2, u1in2), dv2 = TV_SUB(v2, v1in2);
-    const float chi2 = TV_MUL(TV_ADD(TV_MUL(du2, du2), TV_MUL(dv2, dv2)), iss);
-    if (chi2 > th) { in = false; t2 = 0.f; } else t2 = TV_SUB(th, chi2);
+    const float u1in2 = TS_FMUL(tv_dot3(h[0], u1, h[1], v1, h[2]), w1), v1in2 = TS_FMUL(tv_dot3(h[3], u1, h[4], v1, h[5]), w1);
+    const float du2 = TS_FSUB(u2, u1in2), dv2 = TS_FSUB(v2, v1in2);
+    const float chi2 = TS_FMUL(TS_FADD(TS_FMUL(du2, du2), TS_FMUL(dv2, dv2)), iss);
+    if (chi2 > th) { in = false; t2 = 0.f; } else t2 = TS_FSUB(th, chi2);
     return in;
 }
 
@@ -225,12 +176,12 @@ __host__ __device__ inline bool tv_terms_f(const float *f, float u1, float v1, f
     const float th = 3.841f, thScore = 5.991f; bool in = true;
     const float a2 = tv_dot3(f[0], u1, f[1], v1, f[2]), b2 = tv_dot3(f[3], u1, f[4], v1, f[5]), c2 = tv_dot3(f[6], u1, f[7], v1, f[8]);
     const float num2 = tv_dot3(a2, u2, b2, v2, c2);
-    const float chi1 = TV_MUL(TV_DIV(TV_MUL(num2, num2), TV_ADD(TV_MUL(a2, a2), TV_MUL(b2, b2))), iss);
-    if (chi1 > th) { in = false; t1 = 0.f; } else t1 = TV_SUB(thScore, chi1);
+    const float chi1 = TS_FMUL(TS_FDIV(TS_FMUL(num2, num2), TS_FADD(TS_FMUL(a2, a2), TS_FMUL(b2, b2))), iss);
+    if (chi1 > th) { in = false; t1 = 0.f; } else t1 = TS_FSUB(thScore, chi1);
     const float a1 = tv_dot3(f[0], u2, f[3], v2, f[6]), b1 = tv_dot3(f[1], u2, f[4], v2, f[7]), c1 = tv_dot3(f[2], u2, f[5], v2, f[8]);
     const float num1 = tv_dot3(a1, u1, b1, v1, c1);
-    const float chi2 = TV_MUL(TV_DIV(TV_MUL(num1, num1), TV_ADD(TV_MUL(a1, a1), TV_MUL(b1, b1))), iss);
-    if (chi2 > th) { in = false; t2 = 0.f; } else t2 = TV_SUB(thScore, chi2);
+    const float chi2 = TS_FMUL(TS_FDIV(TS_FMUL(num1, num1), TS_FADD(TS_FMUL(a1, a1), TS_FMUL(b1, b1))), iss);
+    if (chi2 > th) { in = false; t2 = 0.f; } else t2 = TS_FSUB(thScore, chi2);
     return in;
 }
 
@@ -243,7 +194,7 @@ __host__ __device__ inline float tv_score_serial(int model, const float *m, int 
     float hi[9] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, s = 0.f; const float iss = tv_inv_sigma2(sigma);
     if (model == 0) tv_h_inverse(m, hi);
     for (int i = 0; i < n; i++) { float t1, t2; const bool in = tv_terms(model, m, hi, xy1 + 2*i, xy2 + 2*i, iss, t1, t2);
-        s = TV_ADD(s, t1); s = TV_ADD(s, t2);
+        s = TS_FADD(s, t1); s = TS_FADD(s, t2);
         if (mask) mask[i] = in ? 1 : 0; }
     return s;
 }

@@ -1,5 +1,5 @@
 // tstwoview_rec.h -- initializer::ReconstructH / ReconstructF on the device (tsorb_match_two_view_reconstruct, include/tsorb.h; docs/twoview_reconstruct_recalled.md is
-// the arithmetic).  Included by tsorb.hip after tstwoview.h, whose tv_rotation, tv_turn3, TV_MUL ... and TV_SWEEPS it uses.  Three launches, no workgroup waits for another:
+// the arithmetic).  Three launches, no workgroup waits for another:
 //   k_rec_pairs   one thread per (hypothesis, match), a workgroup per (256 matches, hypothesis).  Lane 0 forms the workgroup's hypothesis (the 3 x 3 SVD by the one-sided
 //                 iteration in registers, the Faugeras / DecomposeE formulas in fp64, R and t rounded to float once) and CheckRT's P2 and O2; then every lane
 //                 triangulates its match: the 4 x 4 of the reference's float products, its null vector by the one-sided iteration on the four columns in fp64 --
@@ -12,6 +12,7 @@
 // Everything that decides anything is __host__ __device__ with the lane and the lane count as arguments: tests/cxx/two_view_reconstruct_host.hip calls it with (0, 1).
 #pragma once
 #pragma clang fp contract(off)
+#include "tsjacobi.h"
 
 #define REC_T 256
 #define REC_NW (REC_T/64)
@@ -33,12 +34,6 @@
 #define REC_EXIT_TIE 4            // no clear winner
 #define REC_EXIT_PARALLAX 8
 
-#ifdef __HIP_DEVICE_COMPILE__
-#define REC_COUNT(x) atomicAdd(&(x), 1u)
-#else
-#define REC_COUNT(x) ((x)++)
-#endif
-
 struct RecHyp { float R[9], t[3]; };               // a motion hypothesis, rounded to float once
 struct RecCam { float P2[12], O2[3]; };            // CheckRT's P2 = K [R | t] and O2 = -R^T t
 
@@ -48,13 +43,6 @@ struct RecDev {
     float *cosall; int32_t *sv_exit;               // device only: every pair's cosine [8][n]; ReconstructH's singular-value exit was taken
 };
 
-// pnp_sign's rule on three components: the one of largest magnitude positive, the first on ties
-__host__ __device__ __forceinline__ bool rec_negative3(double a, double b, double c) {
-    const double fa = fabs(a), fb = fabs(b), fc = fabs(c);
-    const bool k1 = fb > fa; const double m = k1 ? fb : fa, lead = k1 ? b : a;
-    return (fc > m ? c : lead) < 0.0;
-}
-
 template <int a, int b>
 __host__ __device__ __forceinline__ void rec_order3(double G[3][3], double Q[3][3], double d[3]) {       // column a before column b when it is at least as long
     if (d[a] < d[b]) { double x = d[a]; d[a] = d[b]; d[b] = x;
@@ -62,19 +50,15 @@ __host__ __device__ __forceinline__ void rec_order3(double G[3][3], double Q[3][
         for (int i = 0; i < 3; i++) { x = G[i][a]; G[i][a] = G[i][b]; G[i][b] = x; x = Q[i][a]; Q[i][a] = Q[i][b]; Q[i][b] = x; } }
 }
 
-// A = U diag(d) V^T, d descending: G = A Q with orthogonal columns (the one-sided iteration of tstwoview.h), d_j = |G_j|, v_j = Q_j; u_j = G_j / d_j is left to the caller
+// A = U diag(d) V^T, d descending: G = A Q with orthogonal columns (tsjacobi.h's one-sided iteration), d_j = |G_j|, v_j = Q_j; u_j = G_j / d_j is left to the caller
 __host__ __device__ inline void rec_svd3(const double A[9], double G[3][3], double Q[3][3], double d[3]) {
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
-        for (int j = 0; j < 3; j++) { G[i][j] = A[3*i + j]; Q[i][j] = i == j ? 1.0 : 0.0; }
-#pragma unroll 1
-    for (int sweep = 0; sweep < TV_SWEEPS; sweep++) {
-        const bool t01 = tv_turn3<0, 1>(G, Q), t02 = tv_turn3<0, 2>(G, Q), t12 = tv_turn3<1, 2>(G, Q);
-        if (!(t01 || t02 || t12)) break;
-    }
+        for (int j = 0; j < 3; j++) G[i][j] = A[3*i + j];
+    jac_orthogonalize(G, Q, JAC_ORTHO, JAC_TINY);
 #pragma unroll
-    for (int j = 0; j < 3; j++) d[j] = sqrt((G[0][j]*G[0][j] + G[1][j]*G[1][j]) + G[2][j]*G[2][j]);
+    for (int j = 0; j < 3; j++) d[j] = sqrt(jac_length2(G, j));
     rec_order3<0, 1>(G, Q, d); rec_order3<1, 2>(G, Q, d); rec_order3<0, 1>(G, Q, d);
 }
 
@@ -109,10 +93,10 @@ __host__ __device__ inline bool rec_hyp_h(const float H[9], const float K[4], in
         A[c] = (h0 - cx*h2)/fx; A[3 + c] = (h1 - cy*h2)/fy; A[6 + c] = h2; }
     rec_svd3(A, G, Q, d);
     const float d1f = (float)d[0], d2f = (float)d[1], d3f = (float)d[2];
-    if ((double)TV_DIV(d1f, d2f) < REC_RATIO || (double)TV_DIV(d2f, d3f) < REC_RATIO) return true;
+    if ((double)TS_FDIV(d1f, d2f) < REC_RATIO || (double)TS_FDIV(d2f, d3f) < REC_RATIO) return true;
     double u[3][3], v[3][3];                                               // u[j], v[j]: the j-th left / right singular vector
 #pragma unroll
-    for (int j = 0; j < 3; j++) { const bool neg = j != 1 && rec_negative3(Q[0][j], Q[1][j], Q[2][j]);
+    for (int j = 0; j < 3; j++) { const bool neg = j != 1 && jac_negative3(Q[0][j], Q[1][j], Q[2][j]);
 #pragma unroll
         for (int i = 0; i < 3; i++) { v[j][i] = neg ? -Q[i][j] : Q[i][j]; u[j][i] = (neg ? -G[i][j] : G[i][j])/d[j]; } }
     const double sg = rec_det3(u[0], u[1], u[2])*rec_det3(v[0], v[1], v[2]) < 0.0 ? -1.0 : 1.0;
@@ -157,7 +141,7 @@ __host__ __device__ inline void rec_hyp_f(const float F[9], const float K[4], in
 #pragma unroll
     for (int k = 0; k < 3; k++) { const double a = u[1][k]*v[0][k] - u[0][k]*v[1][k], b = u[2][k]*v[2][k]; tra += a + b; trb += b - a; }
     const bool first = ((h & 1) == 0) == (tra >= trb);                     // this hypothesis takes U W V^T
-    const bool neg = rec_negative3(u[2][0], u[2][1], u[2][2]) != ((h & 2) != 0);
+    const bool neg = jac_negative3(u[2][0], u[2][1], u[2][2]) != ((h & 2) != 0);
     double w0[3], w1[3], tt[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) { w0[k] = first ? u[1][k] : -u[1][k]; w1[k] = first ? -u[0][k] : u[0][k]; tt[k] = neg ? -u[2][k] : u[2][k]; }
@@ -173,45 +157,18 @@ __host__ __device__ inline void rec_camera(const RecHyp &hp, const float K[4], R
     for (int i = 0; i < 3; i++) cam.O2[i] = (float)(-(((double)hp.R[i]*(double)hp.t[0] + (double)hp.R[3 + i]*(double)hp.t[1]) + (double)hp.R[6 + i]*(double)hp.t[2]));
 }
 
-__host__ __device__ __forceinline__ float rec_th2(float sigma) { return (float)(4.0*(double)TV_MUL(sigma, sigma)); }
-
-template <int p, int q>
-__host__ __device__ __forceinline__ bool rec_turn4(double G[4][4], double Q[4][4]) {
-    double al = 0.0, be = 0.0, ga = 0.0, c, s;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { al += G[i][p]*G[i][p]; be += G[i][q]*G[i][q]; ga += G[i][p]*G[i][q]; }
-    if (!tv_rotation(al, be, ga, c, s)) return false;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const double gp = G[i][p], gq = G[i][q]; G[i][p] = c*gp - s*gq; G[i][q] = s*gp + c*gq; }
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const double vp = Q[i][p], vq = Q[i][q]; Q[i][p] = c*vp - s*vq; Q[i][q] = s*vp + c*vq; }
-    return true;
-}
+__host__ __device__ __forceinline__ float rec_th2(float sigma) { return (float)(4.0*(double)TS_FMUL(sigma, sigma)); }
 
 // initializer::Triangulate (:804-817): the rows are the reference's float products and differences; from that float matrix on fp64 -- the right singular vector of
 // the smallest singular value (the first of equal ones) -- and X = v[0 .. 2] / v[3] rounded to float once
 __host__ __device__ inline void rec_triangulate(const RecCam &cam, const float K[4], float x1, float y1, float x2, float y2, float X[3]) {
     const float P1[12] = { K[0], 0.f, K[2], 0.f, 0.f, K[1], K[3], 0.f, 0.f, 0.f, 1.f, 0.f };
-    double G[4][4], Q[4][4];
+    double G[4][4], v[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        G[0][j] = (double)TV_SUB(TV_MUL(x1, P1[8 + j]), P1[j]); G[1][j] = (double)TV_SUB(TV_MUL(y1, P1[8 + j]), P1[4 + j]);
-        G[2][j] = (double)TV_SUB(TV_MUL(x2, cam.P2[8 + j]), cam.P2[j]); G[3][j] = (double)TV_SUB(TV_MUL(y2, cam.P2[8 + j]), cam.P2[4 + j]);
-#pragma unroll
-        for (int i = 0; i < 4; i++) Q[i][j] = i == j ? 1.0 : 0.0; }
-#pragma unroll 1
-    for (int sweep = 0; sweep < TV_SWEEPS; sweep++) {                      // this lane's own matrix: the loop ends when IT has converged (a NaN never turns)
-        const bool a = rec_turn4<0, 1>(G, Q), b = rec_turn4<2, 3>(G, Q), c = rec_turn4<0, 2>(G, Q), d = rec_turn4<1, 3>(G, Q), e = rec_turn4<0, 3>(G, Q), f = rec_turn4<1, 2>(G, Q);
-        if (!(a || b || c || d || e || f)) break;
-    }
-    double d[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) d[j] = ((G[0][j]*G[0][j] + G[1][j]*G[1][j]) + G[2][j]*G[2][j]) + G[3][j]*G[3][j];
-    const int j01 = d[1] < d[0] ? 1 : 0, j23 = d[3] < d[2] ? 3 : 2; const double m01 = j01 ? d[1] : d[0], m23 = j23 == 3 ? d[3] : d[2];
-    const int jmin = m23 < m01 ? j23 : j01;
-    double v[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) v[i] = jmin == 0 ? Q[i][0] : jmin == 1 ? Q[i][1] : jmin == 2 ? Q[i][2] : Q[i][3];
+        G[0][j] = (double)TS_FSUB(TS_FMUL(x1, P1[8 + j]), P1[j]); G[1][j] = (double)TS_FSUB(TS_FMUL(y1, P1[8 + j]), P1[4 + j]);
+        G[2][j] = (double)TS_FSUB(TS_FMUL(x2, cam.P2[8 + j]), cam.P2[j]); G[3][j] = (double)TS_FSUB(TS_FMUL(y2, cam.P2[8 + j]), cam.P2[4 + j]); }
+    jac_null4(G, v);
 #pragma unroll
     for (int i = 0; i < 3; i++) X[i] = (float)(v[i]/v[3]);
 }
@@ -219,20 +176,20 @@ __host__ __device__ inline void rec_triangulate(const RecCam &cam, const float K
 __host__ __device__ __forceinline__ float rec_norm3(float x, float y, float z) {       // cv::norm (NORM_L2) of a CV_32F 3-vector: double accumulation (as recalled)
     return (float)sqrt(((double)x*(double)x + (double)y*(double)y) + (double)z*(double)z);
 }
-__host__ __device__ __forceinline__ float rec_project(float f, float x, float invz, float c) { return TV_ADD(TV_MUL(TV_MUL(f, x), invz), c); }
+__host__ __device__ __forceinline__ float rec_project(float f, float x, float invz, float c) { return TS_FADD(TS_FMUL(TS_FMUL(f, x), invz), c); }
 __host__ __device__ __forceinline__ float rec_err(float ax, float px, float ay, float py) {
-    const float dx = TV_SUB(ax, px), dy = TV_SUB(ay, py); return TV_ADD(TV_MUL(dx, dx), TV_MUL(dy, dy));
+    const float dx = TS_FSUB(ax, px), dy = TS_FSUB(ay, py); return TS_FADD(TS_FMUL(dx, dx), TS_FMUL(dy, dy));
 }
 
 // CheckRT's loop body after Triangulate (:911-963) on the FLOAT point X: the exit it takes and the cosine, the reference's arithmetic to the bit
 __host__ __device__ inline int rec_check(const RecHyp &hp, const RecCam &cam, const float K[4], float th2, float x1, float y1, float x2, float y2, const float X[3], float &cosv) {
     cosv = 0.f;
     if (!__builtin_isfinite(X[0]) || !__builtin_isfinite(X[1]) || !__builtin_isfinite(X[2])) return REC_ST_NONFINITE;
-    const float a0 = TV_SUB(X[0], 0.f), a1 = TV_SUB(X[1], 0.f), a2 = TV_SUB(X[2], 0.f);                               // normal1 = p3dC1 - O1
-    const float b0 = TV_SUB(X[0], cam.O2[0]), b1 = TV_SUB(X[1], cam.O2[1]), b2 = TV_SUB(X[2], cam.O2[2]);             // normal2 = p3dC1 - O2
+    const float a0 = TS_FSUB(X[0], 0.f), a1 = TS_FSUB(X[1], 0.f), a2 = TS_FSUB(X[2], 0.f);                               // normal1 = p3dC1 - O1
+    const float b0 = TS_FSUB(X[0], cam.O2[0]), b1 = TS_FSUB(X[1], cam.O2[1]), b2 = TS_FSUB(X[2], cam.O2[2]);             // normal2 = p3dC1 - O2
     const float dist1 = rec_norm3(a0, a1, a2), dist2 = rec_norm3(b0, b1, b2);
     const double dot = ((double)a0*(double)b0 + (double)a1*(double)b1) + (double)a2*(double)b2;                       // Mat::dot: double accumulation (as recalled)
-    const float c = (float)(dot/(double)TV_MUL(dist1, dist2));
+    const float c = (float)(dot/(double)TS_FMUL(dist1, dist2));
     if (c != c) return REC_ST_NONFINITE;                                   // stated difference: the reference would hand a NaN to std::sort
     cosv = c;
     const bool low = (double)c < REC_COS_LOW;
@@ -265,22 +222,22 @@ __host__ __device__ inline uint32_t rec_select(const uint8_t *state, const float
 #pragma unroll 1
     for (int pass = 0; pass < 4; pass++) { const int shift = 24 - 8*pass;
         for (int b = lane; b < 256; b += nl) hist[b] = 0;
-        PNP_SYNC();
+        TS_BARRIER();
         for (int i = lane; i < n; i += nl) if (state[i] >= REC_ST_GOOD) { const uint32_t key = rec_key(cosv[i]);
-            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) REC_COUNT(hist[(key >> shift) & 255u]); }
-        PNP_SYNC();
+            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) TS_COUNT(hist[(key >> shift) & 255u]); }
+        TS_BARRIER();
         int acc = 0, bsel = 255, before = 0; bool found = false;           // every lane reads all 256 bins (independent broadcast reads) and arrives at the same bin
         for (int b = 0; b < 256; b++) { const int cnt = (int)hist[b];
             if (!found && rem < acc + cnt) { found = true; bsel = b; before = acc; }
             acc += cnt; }
         rem -= before; prefix |= (uint32_t)bsel << shift;
-        PNP_SYNC();
+        TS_BARRIER();
     }
     return prefix;
 }
 
 // CheckRT's parallax (:971): acos of the float, * 180 in float, / CV_PI in double, stored in a float
-__host__ __device__ __forceinline__ float rec_parallax(float c) { return (float)((double)TV_MUL(acosf(c), 180.f)/REC_PI); }
+__host__ __device__ __forceinline__ float rec_parallax(float c) { return (float)((double)TS_FMUL(acosf(c), 180.f)/REC_PI); }
 
 // the keep logic of ReconstructH (:755-801) or ReconstructF (:560-633) over the hypotheses' counts and parallaxes, comparison for comparison.
 // res = ok, sel (-1 unless ok), N, best nGood, second best nGood (H) / nsimilar (F), exit bits

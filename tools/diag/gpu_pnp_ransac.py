@@ -34,7 +34,7 @@ SRC = os.path.join(ROOT, "tests", "cxx", "pnp_host.hip")
 
 
 def build_host():
-    deps = [SRC, os.path.join(ROOT, "textslam_amd", "csrc", "tspnp.h"), os.path.join(ROOT, "include", "tsorb.h")]
+    deps = [SRC, os.path.join(ROOT, "textslam_amd", "csrc", "tspnp.h"), os.path.join(ROOT, "textslam_amd", "csrc", "tsjacobi.h"), os.path.join(ROOT, "include", "tsorb.h")]
     if not os.path.exists(HOST) or any(os.path.getmtime(d) > os.path.getmtime(HOST) for d in deps):
         os.makedirs(os.path.dirname(HOST), exist_ok=True)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-O2", "-ffp-contract=off", "-o", HOST, SRC])

@@ -36,7 +36,7 @@ import text_theta_io as IO                                            # noqa: E4
 
 
 def build_host():
-    deps = [SRC, os.path.join(ROOT, "include", "tsorb.h")] + [os.path.join(ROOT, "textslam_amd", "csrc", h) for h in ("tstexttheta.h", "tstwoview_rec.h", "tstwoview.h", "tspnp.h")]
+    deps = [SRC, os.path.join(ROOT, "include", "tsorb.h")] + [os.path.join(ROOT, "textslam_amd", "csrc", h) for h in ("tstexttheta.h", "tsjacobi.h")]
     if not os.path.exists(HOST) or any(os.path.getmtime(d) > os.path.getmtime(HOST) for d in deps):
         os.makedirs(os.path.dirname(HOST), exist_ok=True)
         IO.build_host(HOST, sanitize=False)

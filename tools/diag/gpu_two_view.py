@@ -38,7 +38,7 @@ import two_view_io as IO                                              # noqa: E4
 
 
 def build_host():
-    deps = [SRC, os.path.join(ROOT, "textslam_amd", "csrc", "tstwoview.h"), os.path.join(ROOT, "textslam_amd", "csrc", "tspnp.h"), os.path.join(ROOT, "include", "tsorb.h")]
+    deps = [SRC, os.path.join(ROOT, "textslam_amd", "csrc", "tstwoview.h"), os.path.join(ROOT, "textslam_amd", "csrc", "tsjacobi.h"), os.path.join(ROOT, "include", "tsorb.h")]
     if not os.path.exists(HOST) or any(os.path.getmtime(d) > os.path.getmtime(HOST) for d in deps):
         os.makedirs(os.path.dirname(HOST), exist_ok=True)
         IO.build_host(HOST, sanitize=False)
