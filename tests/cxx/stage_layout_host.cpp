@@ -1,9 +1,10 @@
-// The layout half of textslam_amd/csrc/tsstage.h on the CPU, no HIP header: built with -fsanitize=address,undefined by tests/test_stage_layout.py.
+// The HIP-free half of textslam_amd/csrc/tsstage.h (Span, Layout, Block) on the CPU, no HIP header: built with -fsanitize=address,undefined by tests/test_stage_layout.py.
 // Every check prints what failed and the program exits with 1; "stage layout host: ok" is the last line of a clean run.
 #include "../../textslam_amd/csrc/tsstage.h"
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 static int failures = 0;
@@ -100,9 +101,63 @@ static void run(size_t align) {
     free(other); free(block);
 }
 
+// ---- the owner of a block that only grows, over malloc / free; Mem counts what is live and fails on request
+struct Mem {
+    static int live, fail_next;
+    static int alloc(void **p, size_t n) {
+        if (fail_next) { fail_next = 0; *p = nullptr; return 7; }
+        *p = malloc(n); if (!*p) return 7;
+        live++; return 0;
+    }
+    static void release(void *p) { free(p); live--; }
+};
+int Mem::live = 0, Mem::fail_next = 0;
+static_assert(!std::is_copy_constructible<Block<Mem>>::value && !std::is_copy_assignable<Block<Mem>>::value, "a copied context would free its blocks twice");
+struct TwoBlocks { Block<Mem> a, b; int x = 0; };                          // a context: not copyable either
+static_assert(!std::is_copy_constructible<TwoBlocks>::value, "a context with a block cannot be copied");
+
+static void fill(Block<Mem> &b, unsigned char v) { memset(b.as<unsigned char>(), v, b.cap()); }           // every byte of the capacity: AddressSanitizer holds it to the size
+static void run_blocks() {
+    {
+        Block<Mem> b;
+        CHECK(b.as() == nullptr && b.cap() == 0 && Mem::live == 0);             // starts empty
+        CHECK(b.grow(0) == 0 && b.as() == nullptr && Mem::live == 0);           // nothing needed: nothing allocated
+        CHECK(b.grow(100) == 0 && b.as() != nullptr && b.cap() == 100 && Mem::live == 1);
+        fill(b, 0x11);
+        void *p0 = b.as();
+        CHECK(b.grow(40) == 0 && b.as() == p0 && b.cap() == 100);               // a smaller request keeps pointer and capacity
+        CHECK(b.grow(100, 4000) == 0 && b.as() == p0 && b.cap() == 100);        // room counts only when the block must move
+        CHECK(b.as<unsigned char>()[99] == 0x11);
+        CHECK(b.grow(101) == 0 && b.cap() == 101 && Mem::live == 1);            // larger: freed, then allocated again -- one block live
+        fill(b, 0x22);
+        CHECK(b.grow(300, 1000) == 0 && b.cap() == 1000 && Mem::live == 1);     // capacity == max(need, room)
+        fill(b, 0x33);
+        CHECK(b.grow(2000, 1500) == 0 && b.cap() == 2000 && Mem::live == 1);
+        fill(b, 0x44);
+        CHECK(b.as<int32_t>() == (int32_t *)b.as() && (const void *)b.as<const double>() == b.as());
+        // a failed allocation: null and 0, the old block gone (freed first); the next grow works again
+        Mem::fail_next = 1;
+        CHECK(b.grow(5000) == 7 && b.as() == nullptr && b.cap() == 0 && Mem::live == 0);
+        CHECK(b.grow(10) == 0 && b.as() != nullptr && b.cap() == 10 && Mem::live == 1);
+        fill(b, 0x55);
+        Mem::fail_next = 1;
+        CHECK(b.grow(5) == 0 && b.cap() == 10 && Mem::fail_next == 1);          // (no allocation attempted)
+        Mem::fail_next = 0;
+        Block<Mem> never;                                                       // destroyed empty: nothing to free
+        TwoBlocks *ctx = new TwoBlocks();
+        CHECK(ctx->a.grow(64) == 0 && ctx->b.grow(1, 32) == 0 && ctx->b.cap() == 32 && Mem::live == 3);
+        fill(ctx->a, 0x66); fill(ctx->b, 0x77);
+        delete ctx;                                                             // the blocks go with the context
+        CHECK(Mem::live == 1);
+    }
+    CHECK(Mem::live == 0);                      // destructors only; LeakSanitizer judges the same at exit
+}
+
 int main() {
+    run(4);
     run(16);
     run(256);
+    run_blocks();
     if (failures) { printf("stage layout host: %d check(s) failed\n", failures); return 1; }
     printf("stage layout host: ok\n");
     return 0;

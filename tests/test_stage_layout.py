@@ -1,10 +1,15 @@
-"""The staging layout of the one-call entry points (textslam_amd/csrc/tsstage.h: Span, Layout) on the CPU -- no GPU, no HIP header.
+"""The staging layout of the one-call entry points and the owner of their blocks (textslam_amd/csrc/tsstage.h: Span, Layout, Block) on the CPU -- no GPU, no HIP header.
 
 tests/cxx/stage_layout_host.cpp is built with plain g++ and the address and undefined-behaviour sanitizers and run as a child process.  It checks, for the
 alignments of libtsorb (16) and libtsloop (256): every span's offset is a multiple of the alignment; spans do not overlap and mark() covers them all; a
 zero-length span takes no room and is a no-op in put and get, null pointers included; put then get through a heap block of exactly mark() bytes returns every
 array unchanged (odd counts 1, 3, 17; element sizes 1, 4, 8, 12, 24 -- AddressSanitizer is what holds the block to "exactly"); a null source or destination
-touches nothing; at() on a second base gives the same offset."""
+touches nothing; at() on a second base gives the same offset.
+
+The owner of a block that only grows (Block) runs there too, over a malloc / free policy that counts its live blocks and fails on request: growing from empty; a
+smaller grow keeps pointer and capacity; a larger one frees first and returns a block whose every byte can be written; capacity == max(need, room); a failed
+allocation leaves null and 0 and the next grow succeeds; a context's blocks are released by its destructor alone (the leak check at exit is the judge); a block,
+and a struct that holds one, is not copyable (static_assert)."""
 import os
 import subprocess
 import pytest
@@ -27,9 +32,11 @@ def test_layout_under_sanitizers(host_exe):
 
 
 def test_layout_header_needs_no_hip():
-    """The layout half compiles with g++ alone; the two grow functions (hipMalloc / hipHostMalloc) are behind the HIP compiler's guard."""
+    """The layout half and the owner template compile with g++ alone; the two memory policies (hipMalloc / hipHostMalloc) are behind the HIP compiler's guard."""
     src = open(os.path.join(ROOT, "textslam_amd", "csrc", "tsstage.h")).read()
     head, guard, room = src.partition("#ifdef __HIPCC__")
     assert guard and "#include <hip" not in src
-    assert "grow_device" in room and "grow_pinned" in room and "struct Layout" in head and "struct Span" in head
-    assert "hipMalloc" not in head and "hipHostMalloc" not in head and "hipError_t" not in head
+    assert "struct DeviceMem" in room and "struct PinnedMem" in room and "DeviceBlock" in room and "PinnedBlock" in room
+    assert "struct Block" in head and "struct Layout" in head and "struct Span" in head
+    assert "hipMalloc" not in head and "hipHostMalloc" not in head and "hipError_t" not in head and "hipFree" not in head and "hipHostFree" not in head
+    assert "hipMalloc(" in room and "hipFree(" in room and "hipHostMalloc(" in room and "hipHostFree(" in room

@@ -37,6 +37,7 @@
 #include "tsba_device.h"
 #include "tsraster.h"
 #include "tsquadstat.h"
+#include "tsstage.h"
 #include "tsba_plan.h"
 
 #include "tsba_types.h"
@@ -127,28 +128,28 @@ struct Ctx {
     bool sep_cr = false;                  // separator system by cyclic reduction on the compact block pool (tsba_bandcr.h)
     int band_parts = 1; double *Lb = nullptr, *Tbuf = nullptr, *Bpart = nullptr, *Ssep = nullptr, *Lcol_sep = nullptr, *CRcontrib = nullptr, *CRfac = nullptr; int *CRgate = nullptr; int cre_epoch = 0; int nsep_ld = 0; Work Wsep;   // partitioned band solver (tsba_bandp.h)
     double *Lcol = nullptr; int band_stream = 0;  // streaming band solver (tsba_band.h): L by block column; 1 = every built level fits it     // storage behind W.S (dense or band)
-    float *lbl_dev = nullptr, *lbl_host = nullptr; size_t lbl_cap = 0;   // text label image staging
-    int32_t *lat_dev = nullptr, *lat_host = nullptr; size_t lat_cap = 0;   // tsba_text_label_at: queries (kf [cap] | px [cap][2]) and labels [cap], device and pinned; grows on demand
+    DeviceBlock lbl_dev; PinnedBlock lbl_host;   // text label image staging
+    DeviceBlock lat_dev; PinnedBlock lat_host;   // tsba_text_label_at: queries and labels [kf | px | label], device and pinned
     unsigned long long *hprog = nullptr; unsigned int pass_seq = 0;   // pinned progress word written by k_postlin / k_decide
     std::vector<struct Slab> slabs; int cur_slab = 0;
     int run_slab = 0; size_t run_off = 0, run_len = 0;   // pending contiguous host-to-device range
     int cur_bw_rows = 1 << 30;                     // band bound of the level being solved (set by launch_pass_init)
     // device cache of keyframe pyramid planes (tsba_problem.kf_id): one slot per keyframe, all levels of a keyframe contiguous
-    struct ImgCache { uint8_t *dev = nullptr, *stage = nullptr; size_t stage_cap = 0, slot = 0, lvl_off[TSBA_MAX_LEVELS] = {0,0,0,0};
+    struct ImgCache { uint8_t *dev = nullptr; PinnedBlock stage; size_t slot = 0, lvl_off[TSBA_MAX_LEVELS] = {0,0,0,0};
                       int w[TSBA_MAX_LEVELS] = {0,0,0,0}, h[TSBA_MAX_LEVELS] = {0,0,0,0}; unsigned lvl_mask = 0;
                       long long id[TSBA_IMG_CACHE_KF]; unsigned long long used[TSBA_IMG_CACHE_KF]; bool full[TSBA_IMG_CACHE_KF]; unsigned long long tick = 0;
                       long long hits = 0, misses = 0; } ic;
-    WbBuf wb{}; Work Wk{}; double *wb_alloc = nullptr; size_t wb_bytes = 0;      // low-rank correction for loop closures (tsba_wb.h): its buffers, the k x k dense system as a second Work
-    EcgBuf ecg{}; double *ecg_alloc = nullptr; size_t ecg_bytes = 0;      // enlarged conjugate gradients (tsba_pcg.h)
+    WbBuf wb{}; Work Wk{}; DeviceBlock wb_alloc;      // low-rank correction for loop closures (tsba_wb.h): its buffers, the k x k dense system as a second Work
+    EcgBuf ecg{}; DeviceBlock ecg_alloc;      // enlarged conjugate gradients (tsba_pcg.h)
     bool pack_in_solve = false, packed = false;   // one-shot calls: tsba_solve packs the results behind its last kernel (enqueue_pack); packed: the block in dl_host is that solve's
-    unsigned char *dl_dev = nullptr, *dl_host = nullptr; size_t dl_bytes = 0;       // results of a solve as one block (k_pack_results): one device-to-host copy per download
-    MsBuf sv{}; double *sv_alloc = nullptr; size_t sv_bytes = 0; bool sv_prepared = false;      // single-vector solve phase (tsba_bandsv.h); sv_prepared: k_sv_linv has run on the current factorisation
-    MsBuf ms{}; double *ms_alloc = nullptr; size_t ms_bytes = 0; int ms_cap = 0;      // multi-right-hand-side solve phase of the partitioned band solver (tsba_bandms.h)
+    DeviceBlock dl_dev; PinnedBlock dl_host;       // results of a solve as one block (k_pack_results): one device-to-host copy per download
+    MsBuf sv{}; DeviceBlock sv_alloc; bool sv_prepared = false;      // single-vector solve phase (tsba_bandsv.h); sv_prepared: k_sv_linv has run on the current factorisation
+    MsBuf ms{}; DeviceBlock ms_alloc; int ms_T = 0;      // multi-right-hand-side solve phase of the partitioned band solver (tsba_bandms.h)
     std::vector<int32_t> rb_r, rb_c; std::vector<double> rb_v;      // tsba_debug_reduced_blocks: the blocks between its two calls
     int cov_text = -1; double *cov_log = nullptr;     // tsba_theta_optim: V of this plane at the end of every pass [TSBA_MAX_LEVELS][6]
     // tsba_theta_optim_batch: an arena of its own (the resident problem of tsba_upload, its slabs and its plane cache are never touched).  dev = staged
     // block | scratch | output records; host = the pinned staging block (headers, frames, features, image planes); out = the pinned output records
-    unsigned char *tb_dev = nullptr, *tb_host = nullptr, *tb_out = nullptr; size_t tb_dev_cap = 0, tb_host_cap = 0, tb_out_cap = 0;
+    DeviceBlock tb_dev; PinnedBlock tb_host, tb_out;
     int far_B = 0, n_far = 0, pcg_parts = 0; unsigned int pcg_seq = 0;      // band + long-range blocks (tsba_pcg.h): band of M in pose blocks, blocks outside it, partial sums per vector kernel
     int rank = 0, world = 1; bool force_multi = false;
     tsba_debug_options dbg{};                      // test / diagnostics switches (tsba_debug_set), all zero in production
@@ -163,6 +164,15 @@ struct Ctx {
 };
 
 static void set_err(Ctx *c, const std::string &s) { c->err = s; }
+// Room for `need` bytes in one of the context's blocks that only grow (tsstage.h); where it must move it gets max(need, room) bytes, after a wait for the stream, which
+// may still use the old one.  what names the block in the error text; nullptr where a failure only makes the caller take another path and nothing is reported.
+template <class B> static int reserve(Ctx *c, B &b, const char *what, size_t need, size_t room = 0) {
+    if (need <= b.cap()) return TSBA_OK;
+    if (b.cap()) hipStreamSynchronize(c->stream);
+    const hipError_t e = b.grow(need, room);
+    if (e != hipSuccess && what) set_err(c, std::string(what) + ": " + hipGetErrorString(e));
+    return e == hipSuccess ? TSBA_OK : TSBA_ERR_DEVICE;
+}
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, once per (kernel, device) and size class instead of before every solve (a global-BA solve made ~45 of these
 // calls).  And with a retry: beside another host thread that was initialising an RCCL communicator the call has been seen to fail with "invalid device function" for a
 // kernel it had accepted a thousand times (the runtime's function table while another library's code objects are being registered; the busy-context suite of round 6's
@@ -342,26 +352,17 @@ int tsba_destroy(void *ctx) {
     hipSetDevice(c->device);
     lgroup_forget(c);
     free_problem(c);
-    hipStreamSynchronize(c->stream);
+    hipStreamSynchronize(c->stream); if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     for (Slab &sl : c->slabs) { hipFree(sl.dev); if (sl.host) hipHostFree(sl.host); }
     c->slabs.clear();
     if (c->comm && c->p_destroy) c->p_destroy(c->comm);
     hipHostFree(c->st_host); hipFree(c->st_log); if (c->hprog) hipHostFree(c->hprog);
-    if (c->lbl_dev) hipFree(c->lbl_dev); if (c->lbl_host) hipHostFree(c->lbl_host);
-    if (c->lat_dev) hipFree(c->lat_dev); if (c->lat_host) hipHostFree(c->lat_host);
-    if (c->ic.dev) hipFree(c->ic.dev); if (c->ic.stage) hipHostFree(c->ic.stage);
-    if (c->tb_dev) hipFree(c->tb_dev); if (c->tb_host) hipHostFree(c->tb_host); if (c->tb_out) hipHostFree(c->tb_out);
-    if (c->ms_alloc) hipFree(c->ms_alloc);
-    if (c->sv_alloc) hipFree(c->sv_alloc);
-    if (c->dl_dev) hipFree(c->dl_dev);
-    if (c->dl_host) hipHostFree(c->dl_host);
-    if (c->ecg_alloc) hipFree(c->ecg_alloc);
-    if (c->wb_alloc) hipFree(c->wb_alloc);
+    if (c->ic.dev) hipFree(c->ic.dev);
     for (int l = 0; l < TSBA_MAX_LEVELS; l++) if (c->ev_stage[l]) hipEventDestroy(c->ev_stage[l]);
     if (c->ev_upload) hipEventDestroy(c->ev_upload);
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
     hipEventDestroy(c->ev0); hipEventDestroy(c->ev1); hipStreamDestroy(c->stream);
-    delete c; return TSBA_OK;
+    delete c; return TSBA_OK;                     // the blocks that only grow (tsstage.h) go with the context
 }
 int tsba_abi_version(void) { return TSBA_ABI_VERSION; }
 const char *tsba_last_error(void *ctx) { return ctx ? ((Ctx *)ctx)->err.c_str() : "null ctx"; }
@@ -578,14 +579,13 @@ static int assign_plane_cache(Ctx *c, const tsba_problem *p, const tsba_options 
     IC.hits += p->n_kf - (long long)miss.size(); IC.misses += (long long)miss.size();
     if (!miss.empty()) {
         const size_t need = miss.size()*off;
-        if (IC.stage_cap < need) { if (IC.stage) hipHostFree(IC.stage); IC.stage = nullptr; IC.stage_cap = 0;
-            if (hipHostMalloc((void **)&IC.stage, need, hipHostMallocDefault) != hipSuccess) { IC.stage = nullptr;
-                for (int k : miss) IC.full[ic_slot[(size_t)k]] = false;          // (their planes were never copied)
-                set_err(c, "hipHostMalloc (plane cache staging)"); return TSBA_ERR_DEVICE; }
-            IC.stage_cap = need; }
+        if (int rc = reserve(c, IC.stage, "plane cache staging", need)) {
+            for (int k : miss) IC.full[ic_slot[(size_t)k]] = false;          // (their planes were never copied)
+            return rc; }
+        uint8_t *stage = IC.stage.as<uint8_t>();
         for (size_t m = 0; m < miss.size(); m++) { const int k = miss[m];
-            for (int l = 0; l < p->n_levels; l++) if (mask >> l & 1) memcpy(IC.stage + m*off + lo[l], p->img[l][k], (size_t)p->img_w[l]*p->img_h[l]);
-            hipMemcpyAsync(IC.dev + (size_t)ic_slot[(size_t)k]*off, IC.stage + m*off, off, hipMemcpyHostToDevice, c->stream); }
+            for (int l = 0; l < p->n_levels; l++) if (mask >> l & 1) memcpy(stage + m*off + lo[l], p->img[l][k], (size_t)p->img_w[l]*p->img_h[l]);
+            hipMemcpyAsync(IC.dev + (size_t)ic_slot[(size_t)k]*off, stage + m*off, off, hipMemcpyHostToDevice, c->stream); }
     }
     c->use_img_cache = true;
     return 0;
@@ -1305,12 +1305,15 @@ int tsba_solve(void *ctx, tsba_report *r) {
 // the results of a solve -- LM state, the current poses / inverse depths / plane parameters, the three flag arrays -- gathered into one block on the
 // device (which of the two parameter buffers is current is device-side state) and brought over by ONE copy into pinned memory: seven synchronous
 // copies into pageable memory, the first of them only to learn an index, were 0.22 ms of a 3.8 ms local-BA call
-struct DlLayout { size_t o_pose, o_rho, o_theta, o_sg, o_to, o_tf, total; };
-static DlLayout dl_layout(const Ctx *c) {
-    DlLayout L; auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    L.o_pose = up(sizeof(LmState)); L.o_rho = L.o_pose + up(sizeof(double)*7*(size_t)c->n_kf); L.o_theta = L.o_rho + up(sizeof(double)*(size_t)c->n_pt);
-    L.o_sg = L.o_theta + up(sizeof(double)*3*(size_t)c->n_text); L.o_to = L.o_sg + up((size_t)c->n_sgood); L.o_tf = L.o_to + up((size_t)c->n_tobs); L.total = L.o_tf + up((size_t)c->n_tfgood);
-    return L;
+struct DlLayout { size_t o_pose, o_rho, o_theta, o_sg, o_to, o_tf, total; };        // what the kernel gets: the spans' offsets
+struct DlSpans { Span<LmState> st; Span<double> pose, rho, theta; Span<uint8_t> sg, to, tf; DlLayout dev; };
+static DlSpans dl_layout(const Ctx *c) {
+    // [LmState | pose | rho | theta | sgood | tobs_good | tfgood]
+    Layout L(16); DlSpans S;
+    S.st = L.take<LmState>(1); S.pose = L.take<double>(7*(size_t)c->n_kf); S.rho = L.take<double>((size_t)c->n_pt); S.theta = L.take<double>(3*(size_t)c->n_text);
+    S.sg = L.take<uint8_t>((size_t)c->n_sgood); S.to = L.take<uint8_t>((size_t)c->n_tobs); S.tf = L.take<uint8_t>((size_t)c->n_tfgood);
+    S.dev = {S.pose.off, S.rho.off, S.theta.off, S.sg.off, S.to.off, S.tf.off, L.mark()};
+    return S;
 }
 __global__ __launch_bounds__(256) void k_pack_results(Work W, DlLayout L, unsigned char *out, int n_kf, int n_pt, int n_text, int n_sg, int n_to, int n_tf) {
     const LmState *st = W.st; const int cur = st->cur & 1;
@@ -1328,23 +1331,14 @@ __global__ __launch_bounds__(256) void k_pack_results(Work W, DlLayout L, unsign
 // call: 5 KB, a window: 60 KB) as the kernel's own stores into pinned host memory, larger ones through the device block and one copy: tsba_download then
 // only copies out of the pinned block (no launch, no second synchronisation: 0.06 ms of a 0.66 ms tsba_pose_optim call).
 #define TSBA_PACK_DIRECT_MAX ((size_t)256 << 10)
-static int dl_reserve(Ctx *c, const DlLayout &L) {
-    if (L.total > c->dl_bytes) {
-        CK(hipStreamSynchronize(c->stream));
-        if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_host) hipHostFree(c->dl_host);
-        c->dl_dev = nullptr; c->dl_host = nullptr; c->dl_bytes = 0;
-        const size_t cap = L.total + L.total/4;
-        CK(hipMalloc((void **)&c->dl_dev, cap)); CK(hipHostMalloc((void **)&c->dl_host, cap, hipHostMallocDefault)); c->dl_bytes = cap;
-    }
-    return TSBA_OK;
-}
 static int enqueue_pack(Ctx *c) {                 // (no synchronisation: the caller's)
-    const DlLayout L = dl_layout(c);
-    int rc = dl_reserve(c, L); if (rc) return rc;
+    const DlLayout L = dl_layout(c).dev;
+    if (int rc = reserve(c, c->dl_dev, "results block", L.total, L.total + L.total/4)) return rc;
+    if (int rc = reserve(c, c->dl_host, "results block (pinned)", L.total, L.total + L.total/4)) return rc;
     const bool direct = L.total <= TSBA_PACK_DIRECT_MAX;
     const size_t work = std::max<size_t>({7*(size_t)c->n_kf, (size_t)c->n_pt, 3*(size_t)c->n_text, (size_t)c->n_sgood, (size_t)c->n_tobs, (size_t)c->n_tfgood, 64});
-    LAUNCHK(k_pack_results, dim3((unsigned)std::min<size_t>(direct ? 64 : 1024, (work + 255)/256)), dim3(256), 0, c->stream, c->W, L, direct ? c->dl_host : c->dl_dev, c->n_kf, c->n_pt, c->n_text, c->n_sgood, c->n_tobs, c->n_tfgood);
-    if (!direct) CK(hipMemcpyAsync(c->dl_host, c->dl_dev, L.total, hipMemcpyDeviceToHost, c->stream));
+    LAUNCHK(k_pack_results, dim3((unsigned)std::min<size_t>(direct ? 64 : 1024, (work + 255)/256)), dim3(256), 0, c->stream, c->W, L, direct ? c->dl_host.as<unsigned char>() : c->dl_dev.as<unsigned char>(), c->n_kf, c->n_pt, c->n_text, c->n_sgood, c->n_tobs, c->n_tfgood);
+    if (!direct) CK(hipMemcpyAsync(c->dl_host.as(), c->dl_dev.as(), L.total, hipMemcpyDeviceToHost, c->stream));
     return TSBA_OK;
 }
 int tsba_download(void *ctx, tsba_problem *p) {
@@ -1352,16 +1346,12 @@ int tsba_download(void *ctx, tsba_problem *p) {
     if (!c->uploaded) { set_err(c, "no problem uploaded"); return TSBA_ERR_STATE; }
     hipSetDevice(c->device);
     static_assert(sizeof(LmState) % 4 == 0, "LmState is copied as words");
-    const DlLayout L = dl_layout(c);
+    const DlSpans S = dl_layout(c);
     if (c->packed) c->packed = false;             // (the solve that has just ended left the block in pinned memory)
     else { int rc = enqueue_pack(c); if (rc) return rc;
         CK(hipStreamSynchronize(c->stream)); CK(hipGetLastError()); }
-    memcpy(p->pose, c->dl_host + L.o_pose, sizeof(double)*7*(size_t)c->n_kf);
-    if (c->n_pt) memcpy(p->rho, c->dl_host + L.o_rho, sizeof(double)*(size_t)c->n_pt);
-    if (c->n_text) memcpy(p->theta, c->dl_host + L.o_theta, sizeof(double)*3*(size_t)c->n_text);
-    if (c->n_sgood) memcpy(p->sgood, c->dl_host + L.o_sg, (size_t)c->n_sgood);
-    if (c->n_tobs) memcpy(p->tobs_good, c->dl_host + L.o_to, (size_t)c->n_tobs);
-    if (c->n_tfgood) memcpy(p->tfgood, c->dl_host + L.o_tf, (size_t)c->n_tfgood);
+    const void *h = c->dl_host.as();
+    S.pose.get(h, p->pose); S.rho.get(h, p->rho); S.theta.get(h, p->theta); S.sg.get(h, p->sgood); S.to.get(h, p->tobs_good); S.tf.get(h, p->tfgood);
     return TSBA_OK;
 }
 
@@ -1461,15 +1451,6 @@ static int theta_batch_check(Ctx *c, tsba_problem *const *probs, int n, const ts
     }
     return TSBA_OK;
 }
-static int tb_reserve(Ctx *c, unsigned char **buf, size_t *cap, size_t need, bool pinned) {
-    if (need <= *cap) return TSBA_OK;
-    CK(hipStreamSynchronize(c->stream));
-    if (*buf) { if (pinned) hipHostFree(*buf); else hipFree(*buf); }
-    *buf = nullptr; *cap = 0;
-    const size_t nc = need + need/4;
-    if (pinned) CK(hipHostMalloc((void **)buf, nc, hipHostMallocDefault)); else CK(hipMalloc((void **)buf, nc));
-    *cap = nc; return TSBA_OK;
-}
 int tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const tsba_options *o, double *cov, tsba_report *reps) {
     Ctx *c = (Ctx *)ctx;
     if (!c) return TSBA_ERR_ARG;
@@ -1478,30 +1459,31 @@ int tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const t
     int rc = theta_batch_check(c, probs, n, o); if (rc) return rc;
     hipSetDevice(c->device);
     auto t0 = std::chrono::steady_clock::now();
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // ---- layout of the staged block: headers | frames | feature uv | feature ref | image planes (each host plane once per call)
+    // ---- the staged block: [headers | frames | feature uv | feature ref | image planes (each host plane once per call)]; behind it on the device: [scratch | output records]
     int n_obs = 0; size_t n_feat = 0;
     for (int i = 0; i < n; i++) { const tsba_problem *p = probs[i]; n_obs += p->n_tobs;
         for (int l = 0; l < p->n_levels && l < TSBA_MAX_LEVELS; l++) if (p->tfeat_off[l]) n_feat += (size_t)p->tfeat_off[l][1]; }
-    const size_t o_hdr = 0, o_obs = up(sizeof(ThHdr)*n), o_uv = o_obs + up(sizeof(ThObs)*std::max(n_obs, 1)), o_ref = o_uv + up(sizeof(double)*2*std::max<size_t>(n_feat, 1));
-    const size_t o_img = o_ref + up(sizeof(double)*8*std::max<size_t>(n_feat, 1));
-    struct Plane { const uint8_t *src; size_t off, len; };
+    Layout L(256);
+    const auto a_hdr = L.take<ThHdr>((size_t)n); const auto a_obs = L.take<ThObs>((size_t)std::max(n_obs, 1));
+    const auto a_uv = L.take<double>(2*std::max<size_t>(n_feat, 1)), a_ref = L.take<double>(8*std::max<size_t>(n_feat, 1));
+    struct Plane { const uint8_t *src; Span<uint8_t> at; size_t end; };          // end: where the next plane begins (the gap up to it is zeroed)
     std::vector<Plane> planes;                                                  // host planes in first-use order
     std::map<const uint8_t *, size_t> seen;
-    size_t img_end = o_img;
     if (!o->img_on_device)
         for (int i = 0; i < n; i++) { const tsba_problem *p = probs[i];
             for (int ps = 0; ps < o->n_passes; ps++) { const int l = o->levels[ps];
                 for (int t = 0; t < p->n_tobs; t++) { const uint8_t *src = p->img[l][p->tobs_kf[t]];
                     if (seen.count(src)) continue;
-                    const size_t len = (size_t)p->img_w[l]*p->img_h[l];
-                    seen[src] = img_end; planes.push_back({src, img_end, len}); img_end += up(len + 2); } } }      // (+2: tap_fetch's 2-byte loads)
-    const size_t staged = img_end, o_scr = up(staged), o_out = o_scr + up(sizeof(double)*THETA_SCR*std::max(n_obs, 1)), dev_total = o_out + up(sizeof(ThOut)*n);
-    rc = tb_reserve(c, &c->tb_host, &c->tb_host_cap, staged, true); if (rc) return rc;
-    rc = tb_reserve(c, &c->tb_dev, &c->tb_dev_cap, dev_total, false); if (rc) return rc;
-    rc = tb_reserve(c, &c->tb_out, &c->tb_out_cap, sizeof(ThOut)*n, true); if (rc) return rc;
-    unsigned char *hb = c->tb_host, *db = c->tb_dev;
-    ThHdr *hh = (ThHdr *)(hb + o_hdr); ThObs *ho = (ThObs *)(hb + o_obs); double *huv = (double *)(hb + o_uv), *href = (double *)(hb + o_ref);
+                    const auto a = L.take<uint8_t>((size_t)p->img_w[l]*p->img_h[l] + 2);                         // (+2: tap_fetch's 2-byte loads)
+                    seen[src] = a.off; planes.push_back({src, a, L.mark()}); } } }
+    const size_t staged = L.mark();
+    const auto a_scr = L.take<double>((size_t)THETA_SCR*std::max(n_obs, 1)); const auto a_out = L.take<ThOut>((size_t)n);
+    Layout Lo(256); const auto h_out = Lo.take<ThOut>((size_t)n);               // the output records in the pinned out block
+    if ((rc = reserve(c, c->tb_host, "theta batch staging", staged, staged + staged/4))) return rc;
+    if ((rc = reserve(c, c->tb_dev, "theta batch device block", L.mark(), L.mark() + L.mark()/4))) return rc;
+    if ((rc = reserve(c, c->tb_out, "theta batch output records", h_out.bytes(), h_out.bytes() + h_out.bytes()/4))) return rc;
+    unsigned char *hb = c->tb_host.as<unsigned char>(), *db = c->tb_dev.as<unsigned char>();
+    ThHdr *hh = a_hdr.at(hb); ThObs *ho = a_obs.at(hb); double *huv = a_uv.at(hb), *href = a_ref.at(hb);
     int ob = 0; size_t fb = 0;
     for (int i = 0; i < n; i++) {
         const tsba_problem *p = probs[i]; ThHdr &H = hh[i];
@@ -1525,21 +1507,21 @@ int tsba_theta_optim_batch(void *ctx, tsba_problem *const *probs, int n, const t
                 ho[ob + t].img[l] = o->img_on_device ? src : (const uint8_t *)(db + seen[src]); } }
         ob += p->n_tobs;
     }
-    for (size_t q = 0; q < planes.size(); q++) {                   // the image planes: a memcpy each into the pinned block (one copy to the device for all)
-        const size_t end = q + 1 < planes.size() ? planes[q + 1].off : img_end;
-        memcpy(hb + planes[q].off, planes[q].src, planes[q].len); memset(hb + planes[q].off + planes[q].len, 0, end - planes[q].off - planes[q].len);
+    for (const Plane &P : planes) {                                // the image planes: a memcpy each into the pinned block (one copy to the device for all)
+        const size_t len = P.at.n - 2;
+        memcpy(P.at.at(hb), P.src, len); memset(P.at.at(hb) + len, 0, P.end - P.at.off - len);
     }
     CK(hipMemcpyAsync(db, hb, staged, hipMemcpyHostToDevice, c->stream));
     auto t1 = std::chrono::steady_clock::now();
-    ThArgs A; A.hdr = (const ThHdr *)(db + o_hdr); A.obs = (const ThObs *)(db + o_obs); A.fuv = (const double *)(db + o_uv); A.fref = (const double *)(db + o_ref);
-    A.scr = (double *)(db + o_scr); A.out = (ThOut *)(db + o_out);
+    ThArgs A; A.hdr = a_hdr.at(db); A.obs = a_obs.at(db); A.fuv = a_uv.at(db); A.fref = a_ref.at(db);
+    A.scr = a_scr.at(db); A.out = a_out.at(db);
     void (*const kern)(ThArgs, tsba_options) = k_theta_batch<THETA_WG>;
     LAUNCHK(kern, dim3(n), dim3(THETA_WG), 0, c->stream, A, *o);
     CK(hipGetLastError());
-    CK(hipMemcpyAsync(c->tb_out, db + o_out, sizeof(ThOut)*n, hipMemcpyDeviceToHost, c->stream));
+    CK(hipMemcpyAsync(h_out.at(c->tb_out.as()), a_out.at(db), h_out.bytes(), hipMemcpyDeviceToHost, c->stream));
     CK(hipStreamSynchronize(c->stream));
     auto t2 = std::chrono::steady_clock::now();
-    const ThOut *out = (const ThOut *)c->tb_out;
+    const ThOut *out = h_out.at(c->tb_out.as());
     for (int i = 0; i < n; i++) {
         tsba_problem *p = probs[i]; const ThOut &R = out[i]; tsba_report &r = reps[i];
         memset(&r, 0, sizeof(r));

@@ -183,12 +183,12 @@ int tsba_text_label_image(void *ctx, int kf, int level, float *out) {
     const LevelDev &D = c->lev[level];
     if (D.img_w <= 0 || D.img_h <= 0) { set_err(c, "no image geometry for this level"); return TSBA_ERR_ARG; }
     const size_t npx = (size_t)D.img_w*D.img_h;
-    if (c->lbl_cap < npx) { if (c->lbl_dev) hipFree(c->lbl_dev); if (c->lbl_host) hipHostFree(c->lbl_host); c->lbl_cap = 0;
-        CK(hipMalloc((void **)&c->lbl_dev, npx*sizeof(float))); CK(hipHostMalloc((void **)&c->lbl_host, npx*sizeof(float), hipHostMallocDefault)); c->lbl_cap = npx; }
-    hipLaunchKernelGGL(k_label, dim3(1), dim3(LBL_THREADS), 0, c->stream, c->W, kf, D.img_w, D.img_h, D.K[0], D.K[1], D.K[2], D.K[3], c->lbl_dev);
-    CK(hipMemcpyAsync(c->lbl_host, c->lbl_dev, npx*sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = reserve(c, c->lbl_dev, "label image", npx*sizeof(float))) return rc;
+    if (int rc = reserve(c, c->lbl_host, "label image (pinned)", npx*sizeof(float))) return rc;
+    hipLaunchKernelGGL(k_label, dim3(1), dim3(LBL_THREADS), 0, c->stream, c->W, kf, D.img_w, D.img_h, D.K[0], D.K[1], D.K[2], D.K[3], c->lbl_dev.as<float>());
+    CK(hipMemcpyAsync(c->lbl_host.as(), c->lbl_dev.as(), npx*sizeof(float), hipMemcpyDeviceToHost, c->stream));
     CK(hipStreamSynchronize(c->stream)); CK(hipGetLastError());
-    memcpy(out, c->lbl_host, npx*sizeof(float));
+    memcpy(out, c->lbl_host.as(), npx*sizeof(float));
     return TSBA_OK;
 }
 
@@ -205,16 +205,20 @@ int tsba_text_label_at(void *ctx, int level, int n, const int32_t *kf, const int
     for (int i = 0; i < n; i++) if (kf[i] < 0 || kf[i] >= c->n_kf) { set_err(c, "tsba_text_label_at: keyframe out of range"); return TSBA_ERR_ARG; }
     hipSetDevice(c->device);
     const size_t nq = (size_t)n;
-    if (c->lat_cap < nq) { if (c->lat_dev) hipFree(c->lat_dev); if (c->lat_host) hipHostFree(c->lat_host); c->lat_dev = c->lat_host = nullptr; c->lat_cap = 0;
-        const size_t cap = std::max<size_t>(64, nq + nq/2);
-        CK(hipMalloc((void **)&c->lat_dev, 4*cap*sizeof(int32_t))); CK(hipHostMalloc((void **)&c->lat_host, 4*cap*sizeof(int32_t), hipHostMallocDefault)); c->lat_cap = cap; }
-    memcpy(c->lat_host, kf, nq*sizeof(int32_t)); memcpy(c->lat_host + nq, px, 2*nq*sizeof(int32_t));
-    CK(hipMemcpyAsync(c->lat_dev, c->lat_host, 3*nq*sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_label_at, dim3((unsigned)((nq + LBA_WAVES - 1)/LBA_WAVES)), dim3(64*LBA_WAVES), 0, c->stream, c->W, n, c->lat_dev, c->lat_dev + nq,
-                       D.img_w, D.img_h, D.K[0], D.K[1], D.K[2], D.K[3], c->lat_dev + 3*nq);
-    CK(hipMemcpyAsync(c->lat_host + 3*nq, c->lat_dev + 3*nq, nq*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    // in: [kf | px]   out: [label]
+    Layout L(4);
+    const auto a_kf = L.take<int32_t>(nq), a_px = L.take<int32_t>(2*nq); const size_t in_end = L.mark(); const auto a_lbl = L.take<int32_t>(nq);
+    const size_t room = 4*std::max<size_t>(64, nq + nq/2)*sizeof(int32_t);           // (headroom: the query count differs from frame to frame)
+    if (int rc = reserve(c, c->lat_dev, "label queries", L.mark(), room)) return rc;
+    if (int rc = reserve(c, c->lat_host, "label queries (pinned)", L.mark(), room)) return rc;
+    void *h = c->lat_host.as(), *d = c->lat_dev.as();
+    a_kf.put(h, kf); a_px.put(h, px);
+    CK(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_label_at, dim3((unsigned)((nq + LBA_WAVES - 1)/LBA_WAVES)), dim3(64*LBA_WAVES), 0, c->stream, c->W, n, a_kf.at(d), a_px.at(d),
+                       D.img_w, D.img_h, D.K[0], D.K[1], D.K[2], D.K[3], a_lbl.at(d));
+    CK(hipMemcpyAsync(a_lbl.at(h), a_lbl.at(d), a_lbl.bytes(), hipMemcpyDeviceToHost, c->stream));
     CK(hipStreamSynchronize(c->stream)); CK(hipGetLastError());
-    memcpy(label, c->lat_host + 3*nq, nq*sizeof(int32_t));
+    a_lbl.get(h, label);
     return TSBA_OK;
 }
 

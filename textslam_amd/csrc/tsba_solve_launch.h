@@ -2,14 +2,7 @@
 // unit (needs Ctx, LAUNCHK, grid_resident, solve_lds_bytes).  launch_solve: the direct solvers, one launcher each.  launch_ms_solve /
 // launch_sv_solve: the solve phases on the factor the last launch_solve left.  launch_solve_full: + conjugate gradients where the map has
 // blocks outside the band, with the preconditioner that pcg_choose picks.
-// A device buffer that only grows, to exactly `need` bytes (the stream may still use the old one: synchronise before the free).  what names it
-// in the error text; nullptr where a failure only makes the caller take another path and nothing is reported.
-static int grow(Ctx *c, double **buf, size_t *bytes, size_t need, const char *what) {
-    if (need <= *bytes) return TSBA_OK;
-    if (*buf) { hipStreamSynchronize(c->stream); hipFree(*buf); } *buf = nullptr; *bytes = 0;
-    if (hipMalloc((void **)buf, need) != hipSuccess) { if (what) set_err(c, std::string("hipMalloc (") + what + ")"); return TSBA_ERR_DEVICE; }
-    *bytes = need; return TSBA_OK;
-}
+// Its device buffers only grow, to exactly the bytes needed (reserve, tsba.hip).
 
 // ---- the direct solvers.  Multi-workgroup blocked Cholesky (tsba_chol.h) of the system in `W` (band bound bw rows below a pose block; bw = N: dense)
 static void launch_dense_chol(Ctx *c, Work &W, int bw) {
@@ -49,16 +42,16 @@ static bool ms_available(const Ctx *c) { return c->band_stream && c->band_parts 
 static int ms_reserve(Ctx *c, int T) {           // buffers for T columns (kept until a larger request or another problem size)
     const size_t n6 = (size_t)c->W.N, labels = (size_t)cr_mmax(0, c->band_parts, 0) + 1, sdim = (size_t)std::max(6, c->cur_bw_rows);
     const size_t per = 4*n6 + 6*labels*sdim;
-    if (int rc = grow(c, &c->ms_alloc, &c->ms_bytes, per*(size_t)T*sizeof(double), "multi-right-hand-side buffers")) return rc;
-    double *q = c->ms_alloc; MsBuf &M = c->ms; M.T = T;
+    if (int rc = reserve(c, c->ms_alloc, "multi-right-hand-side buffers", per*(size_t)T*sizeof(double))) return rc;
+    double *q = c->ms_alloc.as<double>(); MsBuf &M = c->ms; M.T = T;
     M.R = q; q += n6*T; M.Wm = q; q += n6*T; M.V = q; q += n6*T; M.X = q; q += n6*T;
     M.G = q; q += labels*sdim*T; M.Z = q; q += labels*sdim*T; M.Xs = q; q += labels*sdim*T; M.Cg = q; q += 2*labels*sdim*T; M.G2 = q;
-    c->ms_cap = T; return TSBA_OK;
+    c->ms_T = T; return TSBA_OK;
 }
 static int sv_reserve(Ctx *c) {
     const size_t n6 = ((size_t)c->W.N + 1) & ~(size_t)1, labels = (size_t)cr_mmax(0, c->band_parts, 0) + 1, sdim = (size_t)std::max(6, c->cur_bw_rows);
-    if (int rc = grow(c, &c->sv_alloc, &c->sv_bytes, (4*n6 + 7*labels*sdim + 3*labels*sdim*sdim)*sizeof(double), "solve-phase buffers")) return rc;
-    double *q = c->sv_alloc; MsBuf &M = c->sv; M.T = 1;
+    if (int rc = reserve(c, c->sv_alloc, "solve-phase buffers", (4*n6 + 7*labels*sdim + 3*labels*sdim*sdim)*sizeof(double))) return rc;
+    double *q = c->sv_alloc.as<double>(); MsBuf &M = c->sv; M.T = 1;
     M.Li = q; q += labels*sdim*sdim; M.Pp = q; q += 2*labels*sdim*sdim;
     M.R = q; q += n6; M.Wm = q; q += n6; M.V = q; q += n6; M.X = q; q += n6;
     M.G = q; q += labels*sdim; M.Z = q; q += labels*sdim; M.Xs = q; q += labels*sdim; M.Cg = q; q += 2*labels*sdim; M.G2 = q; q += labels*sdim; M.Lid = q;
@@ -250,16 +243,16 @@ static PcgChoice pcg_choose(Ctx *c, const LevelDev &D) {
     // It halves the iterations where the coupling outside the band is a few hundred blocks (outlying eigenvalues, captured 32 at a time), but an
     // application costs 0.8 ms at 5000 keyframes against 0.13 ms of the single-vector solve phase (tsba_bandsv.h) -- measured when the single-vector
     // iteration still re-ran the factorisation (0.57 ms), ms per solve single / enlarged: two loop closures 410 / 303, 1 % long-range points 247 / 320
-    ch.ecg = msa && c->dbg.pcg_block == 2 && ms_reserve(c, std::max(ECG_T, c->ms_cap)) == TSBA_OK && grow(c, &c->ecg_alloc, &c->ecg_bytes, ecg_need, nullptr) == TSBA_OK;
+    ch.ecg = msa && c->dbg.pcg_block == 2 && ms_reserve(c, std::max(ECG_T, c->ms_T)) == TSBA_OK && reserve(c, c->ecg_alloc, nullptr, ecg_need) == TSBA_OK;
     if (ch.ecg) return ch;
     // Loop closures (E touches a few dozen keyframes): the band solve corrected by the low-rank part exactly (tsba_wb.h) is the preconditioner --
     // set up once per trial (one solve phase with k columns, the k x k matrix), then a band solve and a k x k Cholesky per application
-    ch.wb = D.n_wb > 0 && msa && c->dbg.far_solver != 3 && ms_reserve(c, std::max(6*D.n_wb, c->ms_cap)) == TSBA_OK && grow(c, &c->wb_alloc, &c->wb_bytes, wb_need, nullptr) == TSBA_OK;
+    ch.wb = D.n_wb > 0 && msa && c->dbg.far_solver != 3 && ms_reserve(c, std::max(6*D.n_wb, c->ms_T)) == TSBA_OK && reserve(c, c->wb_alloc, nullptr, wb_need) == TSBA_OK;
     // M^-1 on the residual: the solve phase of the partitioned band solver on the factor this trial's first solve left (tsba_bandms.h); where
     // that is not available (a single interior, the sequential separator solve) the factorisation is run again with the residual as right-hand side
     // (measured at 5000 keyframes, one column: 1.3 ms per application against 0.57 ms for the factorisation re-run -- the solve phase pays for 64
     // columns whether it has them or not; it is the default only for the block variants.  pcg_refactor = 2 selects it for the single-vector iteration)
-    if (!ch.wb && msa && rf == 2 && ms_reserve(c, std::max(1, c->ms_cap)) == TSBA_OK) ch.minv = PcgChoice::MS1;
+    if (!ch.wb && msa && rf == 2 && ms_reserve(c, std::max(1, c->ms_T)) == TSBA_OK) ch.minv = PcgChoice::MS1;
     else if (ch.svok && (rf == 0 || rf == 3)) ch.minv = PcgChoice::SV;      // (the single-vector solve phase, tsba_bandsv.h: the default)
     else ch.minv = PcgChoice::REFACTOR;
     ch.fused_dot = ch.minv == PcgChoice::SV && !ch.wb && c->band_parts <= 144 && rf == 0;
@@ -268,7 +261,7 @@ static PcgChoice pcg_choose(Ctx *c, const LevelDev &D) {
 }
 static void launch_ecg(Ctx *c, const LevelDev &D, const PcgChoice &ch) {
     Work &W = c->W; const int nbp = c->pcg_parts, B = std::max(6, c->cur_bw_rows)/6, nch = (c->n_kf + ECG_CH - 1)/ECG_CH; const size_t n6 = (size_t)W.N;
-    EcgBuf &E = c->ecg; MsBuf M = c->ms; M.T = ECG_T; double *q = c->ecg_alloc;
+    EcgBuf &E = c->ecg; MsBuf M = c->ms; M.T = ECG_T; double *q = c->ecg_alloc.as<double>();
     E.P = q; q += n6*ECG_T; E.Q = q; q += n6*ECG_T; E.part = q; q += (size_t)nch*2*(ECG_T*ECG_T + 1); E.Cm = q; q += ECG_T*ECG_T; E.Lm = q; q += ECG_T*ECG_T + ECG_T;
     E.Y = q; q += ECG_T*ECG_T; E.y1 = q; q += ECG_T; E.scal = q; E.nchunk = nch;
     LAUNCHK(k_ecg_begin, dim3(nbp), dim3(PCG_ET), 0, c->stream, W, M);
@@ -292,7 +285,7 @@ static void launch_ecg(Ctx *c, const LevelDev &D, const PcgChoice &ch) {
 struct WbTrial { double *K2; bool factored; };      // the k x k matrix of this trial's low-rank correction; factored: c->Wk holds its Cholesky factor
 // low-rank correction, once per trial: one solve phase with k = 6 n_wb columns, then the k x k matrix (c->Wk: the dense system that factors a copy of it)
 static WbTrial launch_wb_setup(Ctx *c, const LevelDev &D, const PcgChoice &ch) {
-    Work &W = c->W, &Wk = c->Wk; WbBuf &Bw = c->wb; const int kk = 6*D.n_wb; double *q = c->wb_alloc;
+    Work &W = c->W, &Wk = c->Wk; WbBuf &Bw = c->wb; const int kk = 6*D.n_wb; double *q = c->wb_alloc.as<double>();
     Bw.k = kk; Bw.n_u = D.n_wb; Bw.wb_kf = D.wb_kf; Bw.wb_idx = D.wb_idx;
     Bw.Gm = q; q += (size_t)kk*kk; Bw.T1 = q; q += (size_t)kk*kk; double *K2 = q; q += (size_t)kk*kk; Bw.xu = q; q += kk; Bw.vu = q; q += kk; Bw.z = q; q += W.N;
     memset(&Wk, 0, sizeof(Wk)); Wk.N = kk; Wk.n_kf = D.n_wb; Wk.ldS = kk; Wk.band = 0; Wk.st = W.st;

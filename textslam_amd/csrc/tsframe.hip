@@ -19,11 +19,11 @@ struct FCtx {
     int n_levels = 0, w[TSFRAME_MAX_LEVELS] = {0}, h[TSFRAME_MAX_LEVELS] = {0};
     uint8_t *plane[4][TSFRAME_MAX_LEVELS] = {{nullptr}};     // device planes: img, grad, gx, gy
     // blocks that only grow (tsstage.h):
-    void *plane_base = nullptr; size_t plane_cap = 0;
-    void *h_stage = nullptr; size_t h_cap = 0;                // pinned staging (image in, results out)
-    void *d_work = nullptr; size_t d_cap = 0;                 // device block of the feature calls
+    DeviceBlock plane_base;
+    PinnedBlock h_stage;                // pinned staging (image in, results out)
+    DeviceBlock d_work;                 // device block of the feature calls
     int cam_w = 0, cam_h = 0; int16_t *map_xy = nullptr; uint16_t *map_frac = nullptr;      // tsframe_set_camera: the fixed-point undistortion map (tsundist.h)
-    void *d_raw = nullptr, *d_col = nullptr; size_t raw_cap = 0, col_cap = 0;               // tsframe_set_raw_image: the staged raw frame, the undistorted colour plane
+    DeviceBlock d_raw, d_col;               // tsframe_set_raw_image: the staged raw frame, the undistorted colour plane
 };
 #define CKF(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); return TSFRAME_ERR_DEVICE; } } while (0)
 
@@ -351,8 +351,8 @@ static int pts_run(FCtx *c, int n_set, const int32_t *xy_off, const float *xy, c
     const auto a_idx = S.take<int32_t>(cap); const auto a_in = S.take<uint8_t>(cap);
     const size_t tot = S.mark();
     const auto a_sel = S.take<int32_t>(sel_ints);
-    CKF(grow_device(c->d_work, c->d_cap, S.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, tot));
-    void *h = c->h_stage, *d = c->d_work;
+    CKF(c->d_work.grow(S.mark())); CKF(c->h_stage.grow(tot));
+    void *h = c->h_stage.as(), *d = c->d_work.as();
     a_job.put(h, jobs.data()); a_xy.put(h, xy);
     CKF(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_pts_batch, dim3((unsigned)a_job.n), dim3(PTS_NT), 0, c->stream, a_job.at(d), a_xy.at(d), a_sel.at(d), a_cnt.at(d),
@@ -380,8 +380,8 @@ static int pts_run(FCtx *c, int n_set, const int32_t *xy_off, const float *xy, c
 static int planes_layout(FCtx *c, int w, int h, int n_levels) {
     size_t tot = 0; int lw = w, lh = h;
     for (int l = 0; l < n_levels; l++) { c->w[l] = lw; c->h[l] = lh; tot += ((size_t)lw*lh + 255) & ~(size_t)255; lw = (lw + 1)/2; lh = (lh + 1)/2; }
-    CKF(grow_device(c->plane_base, c->plane_cap, 4*tot));
-    uint8_t *p = (uint8_t *)c->plane_base;
+    CKF(c->plane_base.grow(4*tot));
+    uint8_t *p = c->plane_base.as<uint8_t>();
     for (int k = 0; k < 4; k++) for (int l = 0; l < n_levels; l++) { c->plane[k][l] = p; p += ((size_t)c->w[l]*c->h[l] + 255) & ~(size_t)255; }
     c->n_levels = n_levels;
     return 0;
@@ -411,15 +411,10 @@ int tsframe_create(int device, void **ctx) {
 void tsframe_destroy(void *ctx) {
     FCtx *c = (FCtx *)ctx; if (!c) return;
     hipSetDevice(c->device);
-    if (c->plane_base) hipFree(c->plane_base);
-    if (c->d_work) hipFree(c->d_work);
+    if (c->stream) { hipStreamSynchronize(c->stream); hipStreamDestroy(c->stream); }
     if (c->map_xy) hipFree(c->map_xy);
     if (c->map_frac) hipFree(c->map_frac);
-    if (c->d_raw) hipFree(c->d_raw);
-    if (c->d_col) hipFree(c->d_col);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                               // the blocks go with the context
 }
 const char *tsframe_last_error(void *ctx) { FCtx *c = (FCtx *)ctx; return c ? c->err.c_str() : "null context"; }
 
@@ -427,9 +422,9 @@ int tsframe_set_image(void *ctx, const uint8_t *img, int w, int h, int n_levels)
     FCtx *c = (FCtx *)ctx; if (!c || !img || w < 2 || h < 2 || n_levels < 1 || n_levels > TSFRAME_MAX_LEVELS) return TSFRAME_ERR_ARG;
     hipSetDevice(c->device);
     int rc = planes_layout(c, w, h, n_levels); if (rc) return rc;
-    CKF(grow_pinned(c->h_stage, c->h_cap, (size_t)w*h));
-    memcpy(c->h_stage, img, (size_t)w*h);
-    CKF(hipMemcpyAsync(c->plane[TSFRAME_IMG][0], c->h_stage, (size_t)w*h, hipMemcpyHostToDevice, c->stream));
+    CKF(c->h_stage.grow((size_t)w*h));
+    memcpy(c->h_stage.as(), img, (size_t)w*h);
+    CKF(hipMemcpyAsync(c->plane[TSFRAME_IMG][0], c->h_stage.as(), (size_t)w*h, hipMemcpyHostToDevice, c->stream));
     return pyramid_from_level0(c);
 }
 
@@ -486,25 +481,25 @@ int tsframe_set_raw_image(void *ctx, const uint8_t *raw, int stride, int format,
     if (stride < w*ch) return bad("stride < w * channels");
     hipSetDevice(c->device);
     const size_t raw_bytes = (size_t)(h - 1)*stride + (size_t)w*ch, col_bytes = (size_t)w*h*ch;      // (the last row ends with its pixels)
-    CKF(grow_device(c->d_raw, c->raw_cap, raw_bytes));
-    if (undist_out) CKF(grow_device(c->d_col, c->col_cap, (col_bytes + 255) & ~(size_t)255));        // (whole dwords at the end of the plane)
+    CKF(c->d_raw.grow(raw_bytes));
+    if (undist_out) CKF(c->d_col.grow((col_bytes + 255) & ~(size_t)255));        // (whole dwords at the end of the plane)
     int rc = planes_layout(c, w, h, n_levels); if (rc) return rc;
-    CKF(grow_pinned(c->h_stage, c->h_cap, std::max(raw_bytes, col_bytes)));                          // the raw frame in, then the colour plane out
-    memcpy(c->h_stage, raw, raw_bytes);
-    CKF(hipMemcpyAsync(c->d_raw, c->h_stage, raw_bytes, hipMemcpyHostToDevice, c->stream));
+    CKF(c->h_stage.grow(std::max(raw_bytes, col_bytes)));                          // the raw frame in, then the colour plane out
+    memcpy(c->h_stage.as(), raw, raw_bytes);
+    CKF(hipMemcpyAsync(c->d_raw.as(), c->h_stage.as(), raw_bytes, hipMemcpyHostToDevice, c->stream));
     const int npix = w*h; const dim3 grid((npix + 1023)/1024), block(256);
     const int r_first = format == TSFRAME_RAW_RGB;
     uint8_t *g0 = c->plane[TSFRAME_IMG][0];
     if (ch == 3) {
-        if (undist_out) hipLaunchKernelGGL((k_undist_grey<3, true>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)c->d_col);
-        else hipLaunchKernelGGL((k_undist_grey<3, false>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)nullptr);
+        if (undist_out) hipLaunchKernelGGL((k_undist_grey<3, true>), grid, block, 0, c->stream, c->d_raw.as<const uint8_t>(), w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, c->d_col.as<uint8_t>());
+        else hipLaunchKernelGGL((k_undist_grey<3, false>), grid, block, 0, c->stream, c->d_raw.as<const uint8_t>(), w, h, stride, r_first, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)nullptr);
     } else {
-        if (undist_out) hipLaunchKernelGGL((k_undist_grey<1, true>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)c->d_col);
-        else hipLaunchKernelGGL((k_undist_grey<1, false>), grid, block, 0, c->stream, (const uint8_t *)c->d_raw, w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)nullptr);
+        if (undist_out) hipLaunchKernelGGL((k_undist_grey<1, true>), grid, block, 0, c->stream, c->d_raw.as<const uint8_t>(), w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, c->d_col.as<uint8_t>());
+        else hipLaunchKernelGGL((k_undist_grey<1, false>), grid, block, 0, c->stream, c->d_raw.as<const uint8_t>(), w, h, stride, 0, (const int16_t *)c->map_xy, (const uint16_t *)c->map_frac, npix, g0, (uint8_t *)nullptr);
     }
-    if (undist_out) CKF(hipMemcpyAsync(c->h_stage, c->d_col, col_bytes, hipMemcpyDeviceToHost, c->stream));      // (the raw frame has left the staging: same stream)
+    if (undist_out) CKF(hipMemcpyAsync(c->h_stage.as(), c->d_col.as(), col_bytes, hipMemcpyDeviceToHost, c->stream));      // (the raw frame has left the staging: same stream)
     rc = pyramid_from_level0(c); if (rc) return rc;
-    if (undist_out) memcpy(undist_out, c->h_stage, col_bytes);
+    if (undist_out) memcpy(undist_out, c->h_stage.as(), col_bytes);
     return TSFRAME_OK;
 }
 int tsframe_level_size(void *ctx, int level, int *w, int *h) {
@@ -590,8 +585,8 @@ int tsframe_neighbours(void *ctx, int level, const double *uv, int n, double mu,
     Layout L(256);
     const auto a_uv = L.take<double>(2*(size_t)n);
     const auto a_I = L.take<double>(8*(size_t)n), a_N = L.take<double>(8*(size_t)n); const auto a_in = L.take<uint8_t>((size_t)n);
-    CKF(grow_device(c->d_work, c->d_cap, L.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, L.mark()));
-    void *h = c->h_stage, *d = c->d_work;
+    CKF(c->d_work.grow(L.mark())); CKF(c->h_stage.grow(L.mark()));
+    void *h = c->h_stage.as(), *d = c->d_work.as();
     a_uv.put(h, uv);
     CKF(hipMemcpyAsync(d, h, a_uv.bytes(), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_neighbours, dim3((8*n + 255)/256), dim3(256), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], c->w[level], c->h[level],
@@ -620,8 +615,8 @@ int tsframe_box_pixels(void *ctx, int level, const double *quad, double mu, doub
     Layout L(256);
     const auto a_cnt = L.take<int32_t>(1); const auto a_mask = L.take<unsigned>(((size_t)w*h + 31) >> 5);
     const auto a_u = L.take<int32_t>(npx), a_v = L.take<int32_t>(npx); const auto a_I = L.take<double>(npx), a_N = L.take<double>(npx);
-    CKF(grow_device(c->d_work, c->d_cap, L.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, L.mark()));
-    void *hs = c->h_stage, *d = c->d_work;
+    CKF(c->d_work.grow(L.mark())); CKF(c->h_stage.grow(L.mark()));
+    void *hs = c->h_stage.as(), *d = c->d_work.as();
     hipLaunchKernelGGL(k_box_pixels, dim3(1), dim3(1024), 0, c->stream, (const uint8_t *)c->plane[TSFRAME_IMG][level], w, h, B, mu, sigma, a_mask.at(d),
                        a_cnt.at(d), a_u.at(d), a_v.at(d), a_I.at(d), a_N.at(d));
     CKF(hipMemcpyAsync(a_cnt.at(hs), a_cnt.at(d), a_cnt.bytes(), hipMemcpyDeviceToHost, c->stream));
@@ -676,8 +671,8 @@ int tsframe_text_judge(void *ctx, int level, int n, const double *theta, const d
     const auto a_uv = L.take<int16_t>(2*npix); const auto a_in = L.take<uint8_t>(npix);
     const size_t in_end = L.mark();
     const auto a_out = L.take<JudgeOut>((size_t)n); const auto a_bits = L.take<uint32_t>((size_t)n*words);
-    CKF(grow_device(c->d_work, c->d_cap, L.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, L.mark()));
-    void *h = c->h_stage, *d = c->d_work;
+    CKF(c->d_work.grow(L.mark())); CKF(c->h_stage.grow(L.mark()));
+    void *h = c->h_stage.as(), *d = c->d_work.as();
     JudgePlane *hp = a_pl.at(h);
     for (int i = 0; i < n; i++) {
         std::copy_n(theta + 3*(size_t)i, 3, hp[i].theta); std::copy_n(Tcr + 12*(size_t)i, 12, hp[i].T); std::copy_n(box_ray + 8*(size_t)i, 8, hp[i].ray);
@@ -735,8 +730,8 @@ int tsframe_klt_track(void *prev_ctx, void *cur_ctx, int n, const float *prev_xy
     Layout L(256);
     const auto a_prev = L.take<float>(2*(size_t)n);
     const auto a_next = L.take<float>(2*(size_t)n); const auto a_st = L.take<uint8_t>((size_t)n);
-    CKF(grow_device(c->d_work, c->d_cap, L.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, L.mark()));
-    void *h = c->h_stage, *d = c->d_work;
+    CKF(c->d_work.grow(L.mark())); CKF(c->h_stage.grow(L.mark()));
+    void *h = c->h_stage.as(), *d = c->d_work.as();
     a_prev.put(h, prev_xy);
     CKF(hipMemcpyAsync(d, h, a_prev.bytes(), hipMemcpyHostToDevice, c->stream));
     const dim3 grid((n + KLT_WAVES - 1)/KLT_WAVES), block(64*KLT_WAVES);
@@ -819,8 +814,8 @@ int tsframe_text_object_info(void *ctx, int n_obj, const double *quad, const dou
     const auto a_in = S.take<uint8_t>(nfeat);
     const size_t feat_end = S.mark();                            // a count-only call's copy down ends here
     const auto a_pu = S.take<int32_t>(nreg), a_pv = S.take<int32_t>(nreg); const auto a_pI = S.take<double>(nreg), a_pN = S.take<double>(nreg);
-    CKF(grow_device(c->d_work, c->d_cap, S.mark())); CKF(grow_pinned(c->h_stage, c->h_cap, S.mark()));
-    void *h = c->h_stage, *d = c->d_work;
+    CKF(c->d_work.grow(S.mark())); CKF(c->h_stage.grow(S.mark()));
+    void *h = c->h_stage.as(), *d = c->d_work.as();
     a_job.put(h, jobs.data());
     for (int i = 0; i < n_obj; i++) {
         const size_t b = (size_t)feat_off[i]*L, m = fbase[i + 1] - fbase[i];

@@ -27,8 +27,8 @@
 
 struct LCtx {
     int device = 0; hipStream_t stream = nullptr; std::string err;
-    void *h_stage = nullptr; size_t h_cap = 0; void *d_buf = nullptr; size_t d_cap = 0;       // the calls' pinned block and device block, laid out with tsstage.h
-    void *h_out = nullptr; size_t h_out_cap = 0;                        // tsloop_sim3_batch's pinned block out
+    PinnedBlock h_stage; DeviceBlock d_buf;       // the calls' pinned block and device block, laid out with tsstage.h
+    PinnedBlock h_out;                            // tsloop_sim3_batch's pinned block out
 };
 #define CKL(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { c->err = std::string(#x) + ": " + hipGetErrorString(e_); return TSLOOP_ERR_DEVICE; } } while (0)
 
@@ -299,11 +299,8 @@ int tsloop_create(int device, void **ctx) {
 void tsloop_destroy(void *ctx) {
     LCtx *c = (LCtx *)ctx; if (!c) return;
     hipSetDevice(c->device);
-    if (c->d_buf) hipFree(c->d_buf);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->h_out) hipHostFree(c->h_out);
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    if (c->stream) { hipStreamSynchronize(c->stream); hipStreamDestroy(c->stream); }
+    delete c;                               // the blocks go with the context
 }
 const char *tsloop_last_error(void *ctx) { LCtx *c = (LCtx *)ctx; return c ? c->err.c_str() : "null context"; }
 
@@ -318,8 +315,8 @@ int tsloop_optimize_sim3(void *ctx, tsloop_sim3_problem *p, const tsloop_options
     Layout L(256);
     const auto a_P1 = L.take<double>(3*n), a_P2 = L.take<double>(3*n); const auto a_u1 = L.take<float>(2*n), a_u2 = L.take<float>(2*n);
     const auto a_sim = L.take<double>(8); const auto a_rep = L.take<tsloop_report>(1); const auto a_inl = L.take<uint8_t>(n);
-    CKL(grow_pinned(c->h_stage, c->h_cap, L.mark())); CKL(grow_device(c->d_buf, c->d_cap, L.mark()));
-    void *h = c->h_stage, *d = c->d_buf;
+    CKL(c->h_stage.grow(L.mark())); CKL(c->d_buf.grow(L.mark()));
+    void *h = c->h_stage.as(), *d = c->d_buf.as();
     a_P1.put(h, p->P1); a_P2.put(h, p->P2); a_u1.put(h, p->uv1); a_u2.put(h, p->uv2);
     a_sim.put(h, p->sim); memset(a_rep.at(h), 0, a_rep.bytes()); a_inl.put(h, p->inlier);
     CKL(hipMemcpyAsync(d, h, L.mark(), hipMemcpyHostToDevice, c->stream));            // one staged copy in, one out
@@ -391,8 +388,8 @@ int tsloop_sim3_batch(void *ctx, tsloop_sim3_batch_problem *p, const tsloop_opti
     const auto a_u1 = L.take<float>(2*n), a_u2 = L.take<float>(2*n);
     const auto a_ok = Lo.take<int32_t>(NC), a_sel = Lo.take<int32_t>(NC), a_ni = Lo.take<int32_t>(NC), a_hc = Lo.take<int32_t>(nh);
     const auto a_sr = Lo.take<double>(8*NC), a_sim = Lo.take<double>(8*NC), a_hs = Lo.take<double>(8*nh); const auto a_rep = Lo.take<tsloop_report>(NC); const auto a_inl = Lo.take<uint8_t>(n);
-    CKL(grow_pinned(c->h_stage, c->h_cap, L.mark())); CKL(grow_pinned(c->h_out, c->h_out_cap, Lo.mark())); CKL(grow_device(c->d_buf, c->d_cap, L.mark() + Lo.mark()));
-    void *h = c->h_stage, *d = c->d_buf, *dout = (uint8_t *)d + L.mark(); const void *ho = c->h_out;
+    CKL(c->h_stage.grow(L.mark())); CKL(c->h_out.grow(Lo.mark())); CKL(c->d_buf.grow(L.mark() + Lo.mark()));
+    void *h = c->h_stage.as(), *d = c->d_buf.as(), *dout = (uint8_t *)d + L.mark(); const void *ho = c->h_out.as();
     a_cand.put(h, act.data()); a_off.put(h, p->off); a_hoff.put(h, p->hyp_off); a_tri.put(h, p->triple); a_K2.put(h, p->K2);
     a_P1.put(h, p->P1); a_P2.put(h, p->P2); a_q1.put(h, p->pred1); a_q2.put(h, p->pred2); a_u1.put(h, p->uv1); a_u2.put(h, p->uv2);
     CKL(hipMemcpyAsync(d, h, L.mark(), hipMemcpyHostToDevice, c->stream));                          // one copy in, one launch, one copy out
@@ -403,7 +400,7 @@ int tsloop_sim3_batch(void *ctx, tsloop_sim3_batch_problem *p, const tsloop_opti
     B.ok = a_ok.at(dout); B.sel = a_sel.at(dout); B.ninl = a_ni.at(dout); B.hyp_count = a_hc.at(dout);
     B.sim_ransac = a_sr.at(dout); B.sim = a_sim.at(dout); B.hyp_sim = a_hs.at(dout); B.rep = a_rep.at(dout); B.inlier = a_inl.at(dout);
     hipLaunchKernelGGL(k_sim3_batch, dim3((unsigned)na), dim3(SIM_T), 0, c->stream, B, *o);
-    CKL(hipMemcpyAsync(c->h_out, dout, Lo.mark(), hipMemcpyDeviceToHost, c->stream));
+    CKL(hipMemcpyAsync(c->h_out.as(), dout, Lo.mark(), hipMemcpyDeviceToHost, c->stream));
     CKL(hipStreamSynchronize(c->stream)); CKL(hipGetLastError());
     const double t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     fill_idle();
@@ -474,8 +471,8 @@ int tsloop_detect_loop(void *ctx, tsloop_detect_problem *p) {
     const auto a_rec = Lo.take<TdRec>(nq*mm);
     // the packed lists come last: the one copy out takes as many records as the default capacity holds, a second one only what lies beyond them
     const size_t n_first = nq*std::min(mm, (size_t)64), out_sz = a_rec.off + sizeof(TdRec)*n_first;
-    CKL(grow_pinned(c->h_stage, c->h_cap, in_end)); CKL(grow_pinned(c->h_out, c->h_out_cap, out_sz)); CKL(grow_device(c->d_buf, c->d_cap, L.mark() + Lo.mark()));
-    void *h = c->h_stage, *d = c->d_buf, *dout = (uint8_t *)d + L.mark(); const void *ho = c->h_out;
+    CKL(c->h_stage.grow(in_end)); CKL(c->h_out.grow(out_sz)); CKL(c->d_buf.grow(L.mark() + Lo.mark()));
+    void *h = c->h_stage.as(), *d = c->d_buf.as(), *dout = (uint8_t *)d + L.mark(); const void *ho = c->h_out.as();
     a_qoff.put(h, p->q_off); a_qstr.put(h, p->q_str); a_qself.put(h, p->q_self); a_moff.put(h, p->m_off); a_mstr.put(h, p->m_str); a_mskip.put(h, p->m_skip);
     a_ooff.put(h, p->obs_off); a_okf.put(h, p->obs_kf);
     CKL(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, c->stream));                            // one copy in, three launches, one copy out (two after a max_match above the default)
@@ -490,7 +487,7 @@ int tsloop_detect_loop(void *ctx, tsloop_detect_problem *p) {
     hipLaunchKernelGGL(k_td_scan, dim3((unsigned)(n_tile*nq)), dim3(TD_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_td_pick, dim3((unsigned)nq), dim3(TD_T), 0, c->stream, D);
     hipLaunchKernelGGL(k_td_vote, dim3(1), dim3(TD_T), 0, c->stream, D);
-    CKL(hipMemcpyAsync(c->h_out, dout, out_sz, hipMemcpyDeviceToHost, c->stream));
+    CKL(hipMemcpyAsync(c->h_out.as(), dout, out_sz, hipMemcpyDeviceToHost, c->stream));
     CKL(hipStreamSynchronize(c->stream)); CKL(hipGetLastError());
     const int32_t *cnt = a_cnt.at(ho), *roff = a_roff.at(ho);
     const TdRec *first = a_rec.at(ho);
@@ -563,8 +560,8 @@ int tsloop_optimize_loop(void *ctx, tsloop_graph_problem *p, const tsloop_option
     const auto a_r = L.take<double>(7*NE), a_J1 = L.take<double>(49*NE), a_J2 = L.take<double>(49*NE), a_ce = L.take<double>(NE), a_cce = L.take<double>(NE), a_qe = L.take<double>(NE),
                a_sc = L.take<double>(N6), a_part = L.take<double>(4*NF), a_g = L.take<double>(N6), a_dp = L.take<double>(N6), a_Sy = L.take<double>(N6),
                a_LD = L.take<double>((size_t)std::max(n6, 32*nb6)); const auto a_dbg = L.take<long long>(64); const auto a_S = L.take<double>((N6 + 1)*N6);
-    CKL(grow_pinned(c->h_stage, c->h_cap, in_end)); CKL(grow_device(c->d_buf, c->d_cap, L.mark()));
-    void *h = c->h_stage, *d = c->d_buf;
+    CKL(c->h_stage.grow(in_end)); CKL(c->d_buf.grow(L.mark()));
+    void *h = c->h_stage.as(), *d = c->d_buf.as();
     a_x0.put(h, p->pose); a_x1.put(h, p->pose); a_fidx.put(h, fidx.data()); a_free.put(h, free_kf.data());
     a_ei.put(h, p->edge_i); a_ej.put(h, p->edge_j); a_meas.put(h, p->meas); a_kfoff.put(h, kf_off.data()); a_poff.put(h, pair_off.data());
     std::copy(kf_inc.begin(), kf_inc.end(), a_kfinc.at(h)); std::copy(pair_a.begin(), pair_a.end(), a_pa.at(h)); std::copy(pair_b.begin(), pair_b.end(), a_pb.at(h));

@@ -1343,12 +1343,12 @@ struct OCtx {
     int pyr_shape = -1, pyr_split = P1_SPLIT; PyrOne Q[3 + MAXL/2 + 1]; int q_inst[3 + MAXL/2 + 1], n_pairs = 0;           // (tsorb_debug_pyramid) k_pyramid_one's launches: [0] levels 0 .. split from the image, [1] the rest from level split, [2] every level from the image; instance 0 = small buffers, 1 = large, -1 = does not fit
     OrbDev D;
     // the SLAM front-end calls once per frame with the same geometry: buffers and pinned staging are kept between calls
-    MatchGrid M; int m_n = 0; bool m_set = false; void *m_buf = nullptr; size_t m_cap = 0; void *m_feat = nullptr; size_t m_feat_cap = 0;   // search grid of the current frame
-    void *mq_host = nullptr; size_t mq_cap = 0;                                 // tsorb_match_search: pinned block, read and written by the kernel through its device alias
+    MatchGrid M; int m_n = 0; bool m_set = false; DeviceBlock m_buf, m_feat;   // search grid of the current frame
+    PinnedBlock mq_host;                                 // tsorb_match_search: pinned block, read and written by the kernel through its device alias
     bool ran = false;                                                           // the resident batch has been through tsorb_run (its level 0 is in place)
-    CvoDev CV; int cv_w = 0, cv_h = 0, cv_nd = 0; void *cv_geo = nullptr, *cv_det = nullptr, *cv_sel = nullptr, *cv_pin = nullptr; size_t cv_det_cap = 0, cv_sel_cap = 0, cv_pin_cap = 0;   // tsorb_text_extract's scratch, kept between calls
-    void *br_dev = nullptr, *br_pin = nullptr; size_t br_dev_cap = 0, br_pin_cap = 0;                       // tsorb_match_brute_*: device block and pinned staging, kept between calls
-    void *fz_dev = nullptr, *fz_pin = nullptr, *fz_set[2] = {nullptr, nullptr}; size_t fz_dev_cap = 0, fz_pin_cap = 0, fz_set_cap[2] = {0, 0}; int fz_cur = 1;   // tsorb_fuse_frame: device scratch, pinned staging, the fused set (two blocks taken in turn: a call that fails leaves the set the grid reads alone)
+    CvoDev CV; int cv_w = 0, cv_h = 0, cv_nd = 0; void *cv_geo = nullptr; DeviceBlock cv_det, cv_sel; PinnedBlock cv_pin;   // tsorb_text_extract's scratch, kept between calls
+    DeviceBlock br_dev; PinnedBlock br_pin;                       // tsorb_match_brute_*: device block and pinned staging, kept between calls
+    DeviceBlock fz_dev, fz_set[2]; PinnedBlock fz_pin; int fz_cur = 1;   // tsorb_fuse_frame: device scratch, pinned staging, the fused set (two blocks taken in turn: a call that fails leaves the set the grid reads alone)
     int key[5] = {0, 0, 0, 0, 0}; uint8_t *h_img = nullptr; void *h_out = nullptr; size_t h_img_sz = 0, h_out_sz = 0;
 };
 static int cv_round_f(float v) { return (int)lrintf(v); }
@@ -1389,13 +1389,10 @@ int tsorb_create(void **ctx, int nfeatures, float scale, int nlevels, int ini_th
     if (hipMemcpyToSymbol(HIP_SYMBOL(d_pattern), ORB_BIT_PATTERN_31, 1024) != hipSuccess) { delete c; return TSORB_ERR_DEVICE; }
     *ctx = c; return TSORB_OK;
 }
-int tsorb_destroy(void *ctx) { OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG; hipSetDevice(c->device); ofree(c);
+int tsorb_destroy(void *ctx) { OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG; hipSetDevice(c->device); ofree(c);      // (ofree waits for the stream)
     if (c->h_fb) hipHostFree(c->h_fb);
-    if (c->cv_geo) hipFree(c->cv_geo); if (c->cv_det) hipFree(c->cv_det); if (c->cv_sel) hipFree(c->cv_sel); if (c->cv_pin) hipHostFree(c->cv_pin);
-    if (c->m_buf) hipFree(c->m_buf); if (c->m_feat) hipFree(c->m_feat); if (c->mq_host) hipHostFree(c->mq_host);
-    if (c->br_dev) hipFree(c->br_dev); if (c->br_pin) hipHostFree(c->br_pin);
-    if (c->fz_dev) hipFree(c->fz_dev); if (c->fz_pin) hipHostFree(c->fz_pin); if (c->fz_set[0]) hipFree(c->fz_set[0]); if (c->fz_set[1]) hipFree(c->fz_set[1]);
-    hipStreamDestroy(c->stream); delete c; return TSORB_OK; }
+    if (c->cv_geo) hipFree(c->cv_geo);
+    hipStreamDestroy(c->stream); delete c; return TSORB_OK; }      // the blocks that only grow go with the context
 const char *tsorb_last_error(void *ctx) { return ctx ? ((OCtx *)ctx)->err.c_str() : "null ctx"; }
 int tsorb_get_levels(void *ctx) { return ctx ? ((OCtx *)ctx)->nlevels : TSORB_ERR_ARG; }
 int tsorb_get_scale_factors(void *ctx, float *sf, float *isf) { OCtx *c = (OCtx *)ctx; if (!c) return TSORB_ERR_ARG;
@@ -1622,11 +1619,11 @@ int tsorb_debug_level(void *ctx, int frame, int level, int blurred, uint8_t *out
 // ---- window / projection search
 static int match_build(OCtx *c, const float *kp_dev, const uint8_t *desc_dev, int n, double min_x, double max_x, double min_y, double max_y) {
     if (!(max_x > min_x) || !(max_y > min_y) || n < 0) return TSORB_ERR_ARG;
-    OCK(grow_device(c->m_buf, c->m_cap, sizeof(int)*((size_t)std::max(n, 1) + MG_CELLS + 1)));
+    OCK(c->m_buf.grow(sizeof(int)*((size_t)std::max(n, 1) + MG_CELLS + 1)));
     MatchGrid &M = c->M;
     double g[4]; grid_scale(min_x, max_x, min_y, max_y, g);
     M.kp = kp_dev; M.desc = desc_dev; M.min_x = g[0]; M.min_y = g[1]; M.iw = g[2]; M.ih = g[3];
-    M.off = (int *)c->m_buf; M.list = M.off + MG_CELLS + 1;
+    M.off = c->m_buf.as<int>(); M.list = M.off + MG_CELLS + 1;
     hipLaunchKernelGGL(k_grid, dim3(1), dim3(WS_T), 0, c->stream, M, n);
     c->m_n = n; c->m_set = true; return TSORB_OK;
 }
@@ -1643,10 +1640,10 @@ int tsorb_match_set_features(void *ctx, const float *kp6, const uint8_t *desc, i
     OCtx *c = (OCtx *)ctx; if (!c || n < 0 || (n > 0 && (!kp6 || !desc))) return TSORB_ERR_ARG;
     hipSetDevice(c->device);
     const size_t bk = sizeof(float)*6*(size_t)std::max(n, 1), need = bk + 32*(size_t)std::max(n, 1);
-    OCK(grow_device(c->m_feat, c->m_feat_cap, need));
-    if (n > 0) { OCK(hipMemcpyAsync(c->m_feat, kp6, sizeof(float)*6*(size_t)n, hipMemcpyHostToDevice, c->stream));
-                 OCK(hipMemcpyAsync((char *)c->m_feat + bk, desc, 32*(size_t)n, hipMemcpyHostToDevice, c->stream)); OCK(hipStreamSynchronize(c->stream)); }
-    return match_build(c, (const float *)c->m_feat, (const uint8_t *)c->m_feat + bk, n, min_x, max_x, min_y, max_y);
+    OCK(c->m_feat.grow(need));
+    if (n > 0) { OCK(hipMemcpyAsync(c->m_feat.as(), kp6, sizeof(float)*6*(size_t)n, hipMemcpyHostToDevice, c->stream));
+                 OCK(hipMemcpyAsync(c->m_feat.as<char>() + bk, desc, 32*(size_t)n, hipMemcpyHostToDevice, c->stream)); OCK(hipStreamSynchronize(c->stream)); }
+    return match_build(c, c->m_feat.as<const float>(), c->m_feat.as<const uint8_t>() + bk, n, min_x, max_x, min_y, max_y);
 }
 int tsorb_match_search(void *ctx, int nq, const float *qxy, const float *qr, const int32_t *qlev, const uint8_t *qdesc, int max_cand,
                        int32_t *cand_idx, int32_t *cand_dist, int32_t *cand_cnt, int32_t *best_idx, int32_t *best_dist, int32_t *best_dist2) {
@@ -1660,13 +1657,13 @@ int tsorb_match_search(void *ctx, int nq, const float *qxy, const float *qr, con
     const auto a_xy = L.take<float>(2*NQ), a_r = L.take<float>(NQ); const auto a_lev = L.take<int32_t>(2*NQ); const auto a_d = L.take<uint8_t>(32*NQ);
     const auto a_ci = L.take<int32_t>(NQ*(size_t)max_cand), a_cd = L.take<int32_t>(NQ*(size_t)max_cand), a_cc = L.take<int32_t>(NQ), a_bi = L.take<int32_t>(NQ),
                a_bd = L.take<int32_t>(NQ), a_bd2 = L.take<int32_t>(NQ);
-    OCK(grow_pinned(c->mq_host, c->mq_cap, L.mark()));
-    void *h = c->mq_host, *d = nullptr;
+    OCK(c->mq_host.grow(L.mark()));
+    void *h = c->mq_host.as(), *d = nullptr;
     a_xy.put(h, qxy); a_r.put(h, qr); a_d.put(h, qdesc);
     if (qlev) a_lev.put(h, qlev); else std::fill_n(a_lev.at(h), a_lev.n, -1);
     // (round 6: the kernel reads the queries from, and stores the results into, the pinned block itself -- a wave reads its query's 52 bytes once, the results are a few KB (or
     // the candidate lists' 8 bytes per entry): two copies on the stream cost the call more than the bus does; d = the block's device address)
-    OCK(hipHostGetDevicePointer(&d, c->mq_host, 0));
+    OCK(hipHostGetDevicePointer(&d, h, 0));
     hipLaunchKernelGGL(k_match, dim3((nq + 3)/4), dim3(256), 0, c->stream, c->M, nq, a_xy.at(d), a_r.at(d), a_lev.at(d), a_d.at(d), max_cand,
                        a_ci.at(d), a_cd.at(d), a_cc.at(d), a_bi.at(d), a_bd.at(d), a_bd2.at(d));
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
@@ -1717,12 +1714,12 @@ static int cvo_launch(OCtx *c, int frame, int nd, const double *quad, int nfeatu
         const auto a_mask = Ld.take<unsigned>(MS_MASK_WORDS*n); const auto a_dfoot = Ld.take<int>(4*CVO_NL*n); const auto a_M = Ld.take<uint8_t>(C.m_stride*n);
         const auto a_tkp = Ld.take<uint32_t>(NT*CVO_TCAP*n), a_tkey = Ld.take<uint32_t>(NT*CVO_TCAP*n);
         const auto a_tcnt = Ld.take<int>(NT*n), a_rowoff = Ld.take<int>((size_t)CVO_NL*CVO_MAX_H*n), a_lvlcnt = Ld.take<int>(CVO_NL*n); const auto a_thr = Ld.take<uint32_t>(2*CVO_NL*n);
-        OCK(grow_device(c->cv_det, c->cv_det_cap, Ld.mark())); c->cv_nd = (int)n;
-        void *p = c->cv_det;
+        OCK(c->cv_det.grow(Ld.mark())); c->cv_nd = (int)n;
+        void *p = c->cv_det.as();
         C.mask = a_mask.at(p); C.dfoot = a_dfoot.at(p); C.M = a_M.at(p); C.tkp = a_tkp.at(p); C.tkey = a_tkey.at(p); C.tcnt = a_tcnt.at(p);
         C.rowoff = a_rowoff.at(p); C.lvlcnt = a_lvlcnt.at(p); C.thr = a_thr.at(p); }
-    OCK(grow_device(c->cv_sel, c->cv_sel_cap, sizeof(float4)*(size_t)nd*cap));
-    C.sel = (float4 *)c->cv_sel;
+    OCK(c->cv_sel.grow(sizeof(float4)*(size_t)nd*cap));
+    C.sel = c->cv_sel.as<float4>();
     int *h_quad = in.quad.at(h), *h_foot = in.foot.at(h);
     for (int d = 0; d < nd; d++) {
         int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
@@ -1772,9 +1769,9 @@ int tsorb_text_extract(void *ctx, int frame, int n_dete, const double *quad, int
     Layout L(16);
     const CvoIn in = cvo_take_inputs(L, nd);
     const auto a_cnt = L.take<int>((size_t)nd); const auto a_kp = L.take<float>(6*(size_t)nd*cap); const auto a_desc = L.take<uint8_t>(32*(size_t)nd*cap);
-    OCK(grow_pinned(c->cv_pin, c->cv_pin_cap, L.mark()));
-    void *h = c->cv_pin, *dp = nullptr;
-    OCK(hipHostGetDevicePointer(&dp, c->cv_pin, 0));
+    OCK(c->cv_pin.grow(L.mark()));
+    void *h = c->cv_pin.as(), *dp = nullptr;
+    OCK(hipHostGetDevicePointer(&dp, h, 0));
     { const int rc0 = cvo_launch(c, frame, nd, quad, nfeatures, cap, h, dp, in, a_cnt.at(dp), a_kp.at(dp), a_desc.at(dp)); if (rc0) return rc0; }
     OCK(hipStreamSynchronize(c->stream)); OCK(hipGetLastError());
     const int *o_cnt = a_cnt.at(h); const float *o_kp = a_kp.at(h); const uint8_t *o_desc = a_desc.at(h);
@@ -1811,17 +1808,17 @@ int tsorb_fuse_frame(void *ctx, int frame, int n_dete, const double *quad, const
     Layout L(16);
     const CvoIn in = cvo_take_inputs(L, n_dete); const auto a_poly = L.take<int>(16*nd);
     const auto a_head = L.take<int>(nd + 5), a_raw = L.take<int>(nd), a_obj = L.take<int>(CP), a_src = L.take<int>(CP); const auto a_kp = L.take<float>(6*CP); const auto a_desc = L.take<uint8_t>(32*CP);
-    OCK(grow_pinned(c->fz_pin, c->fz_pin_cap, L.mark()));
+    OCK(c->fz_pin.grow(L.mark()));
     // ---- device scratch: [raw count | raw kp | raw desc | kept indices | kept counts | text_off, n_out, verdicts]; the fused set in the block the grid does not read now
     Layout Ls(16);
     const auto s_cnt = Ls.take<int>(nd); const auto s_kp = Ls.take<float>(6*nd*CT); const auto s_desc = Ls.take<uint8_t>(32*nd*CT); const auto s_idx = Ls.take<int>(nd*CT), s_keep = Ls.take<int>(nd), s_head = Ls.take<int>(nd + 5);
-    OCK(grow_device(c->fz_dev, c->fz_dev_cap, Ls.mark()));
+    OCK(c->fz_dev.grow(Ls.mark()));
     const int nxt = 1 - c->fz_cur;
     Layout Lf(16);
     const auto f_kp = Lf.take<float>(6*CP); const auto f_desc = Lf.take<uint8_t>(32*CP);
-    OCK(grow_device(c->fz_set[nxt], c->fz_set_cap[nxt], Lf.mark()));
-    void *h = c->fz_pin, *dp = nullptr, *sp = c->fz_dev, *fp = c->fz_set[nxt];
-    OCK(hipHostGetDevicePointer(&dp, c->fz_pin, 0));
+    OCK(c->fz_set[nxt].grow(Lf.mark()));
+    void *h = c->fz_pin.as(), *dp = nullptr, *sp = c->fz_dev.as(), *fp = c->fz_set[nxt].as();
+    OCK(hipHostGetDevicePointer(&dp, h, 0));
     if (n_dete > 0) {
         int *h_poly = a_poly.at(h);
         for (int d = 0; d < n_dete; d++) { fuse_shrunk_quad(quad + 8*(size_t)d, win, h_poly + 16*(size_t)d); fuse_bbox_quad(bbox + 4*(size_t)d, h_poly + 16*(size_t)d + 8); }
@@ -1888,8 +1885,8 @@ int tsorb_match_brute_text(void *ctx, int n_pair, const int32_t *off1, const uin
     const auto a_d1 = L.take<uint8_t>(32*nq), a_d2 = L.take<uint8_t>(32*nt);
     const size_t in_sz = L.mark();
     const auto a_train = L.take<int32_t>(nq), a_dist = L.take<int32_t>(nq); const auto a_good = L.take<uint8_t>(nq);
-    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
-    void *h = c->br_pin, *d = c->br_dev;
+    OCK(c->br_dev.grow(L.mark())); OCK(c->br_pin.grow(L.mark()));
+    void *h = c->br_pin.as(), *d = c->br_dev.as();
     a_off1.put(h, off1); a_off2.put(h, off2);
     { int32_t *t = a_tile.at(h); size_t k = 0;
       for (int p = 0; p < n_pair; p++) for (int q0 = off1[p]; q0 < off1[p + 1]; q0 += BR_T) { t[2*k] = p; t[2*k + 1] = q0; k++; }
@@ -1938,8 +1935,8 @@ int tsorb_match_brute_scene(void *ctx, int w, int h, int n1, const float *xy1, c
     const auto a_md = L.take<int32_t>(N2), a_own = L.take<int32_t>(N2);
     Layout Lo(16);                                                              // the outputs, a layout of their own: behind the scratch on the device, behind the inputs in the pinned block
     const auto a_m12 = Lo.take<int32_t>(N1*(size_t)n_cand), a_nm = Lo.take<int32_t>((size_t)n_cand);
-    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark() + Lo.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, in_sz + Lo.mark()));
-    void *hp = c->br_pin, *d = c->br_dev, *ho = (char *)hp + in_sz, *dout = (char *)d + L.mark();
+    OCK(c->br_dev.grow(L.mark() + Lo.mark())); OCK(c->br_pin.grow(in_sz + Lo.mark()));
+    void *hp = c->br_pin.as(), *d = c->br_dev.as(), *ho = (char *)hp + in_sz, *dout = (char *)d + L.mark();
     a_off2.put(hp, off2); a_qoff.put(hp, qoff);
     { int32_t *cur = a_qcur.at(hp), *can = a_qcan.at(hp);
       for (size_t i = 0; i < a_qcur.n; i++) { cur[i] = (int)quad_cur[i]; can[i] = (int)quad_can[i]; } }          // cv::Point(double, double): truncation
@@ -1995,8 +1992,8 @@ int tsorb_match_search_sets(void *ctx, int n_set, const int32_t *foff, const flo
     const auto a_qxy = L.take<float>(2*NQ), a_qr = L.take<float>(NQ); const auto a_lev = L.take<int32_t>(2*NQ), a_set = L.take<int32_t>(NQ), a_di = L.take<int32_t>(NQ);
     const auto a_ci = L.take<int32_t>(NQ*(size_t)max_cand), a_cd = L.take<int32_t>(NQ*(size_t)max_cand), a_cc = L.take<int32_t>(NQ), a_bi = L.take<int32_t>(NQ),
                a_bd = L.take<int32_t>(NQ), a_bd2 = L.take<int32_t>(NQ);
-    OCK(grow_device(c->br_dev, c->br_dev_cap, Ld.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
-    void *h = c->br_pin, *d = c->br_dev;
+    OCK(c->br_dev.grow(Ld.mark())); OCK(c->br_pin.grow(L.mark()));
+    void *h = c->br_pin.as(), *d = c->br_dev.as();
     a_foff.put(h, foff);
     for (int s = 0; s < n_set; s++) { const double *b = bounds + 4*(size_t)s; grid_scale(b[0], b[1], b[2], b[3], a_grid.at(h) + 4*(size_t)s); }
     a_kp.put(h, kp6); a_desc.put(h, desc); a_qd.put(h, qdesc);
@@ -2004,7 +2001,7 @@ int tsorb_match_search_sets(void *ctx, int n_set, const int32_t *foff, const flo
     if (qlev) a_lev.put(h, qlev); else std::fill_n(a_lev.at(h), a_lev.n, -1);
     if (qdi) a_di.put(h, qdi); else for (size_t k = 0; k < NQ; k++) a_di.at(h)[k] = (int32_t)k;
     OCK(hipMemcpyAsync(d, h, up_sz, hipMemcpyHostToDevice, c->stream));
-    void *p = nullptr; OCK(hipHostGetDevicePointer(&p, c->br_pin, 0));          // the search kernel reads the queries from, and stores the results into, the pinned block
+    void *p = nullptr; OCK(hipHostGetDevicePointer(&p, h, 0));          // the search kernel reads the queries from, and stores the results into, the pinned block
     WindowSets W;
     W.n_set = n_set; W.nq = nq; W.max_cand = max_cand;
     W.foff = a_foff.at(d); W.grid = a_grid.at(d); W.kp = a_kp.at(d); W.desc = a_desc.at(d); W.qdesc = a_qd.at(d); W.off = a_off.at(d); W.list = a_list.at(d);
@@ -2041,8 +2038,8 @@ int tsorb_match_pnp_ransac(void *ctx, int n, const float *Pw, const float *uv, c
     const size_t in_sz = L.mark();
     const auto a_res = L.take<int32_t>(4); const auto a_pose = L.take<double>(12); const auto a_cnt = L.take<int32_t>(H); const auto a_hp = L.take<double>(12*H);
     const auto a_inl = L.take<uint8_t>(N);
-    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
-    void *h = c->br_pin, *d = c->br_dev;
+    OCK(c->br_dev.grow(L.mark())); OCK(c->br_pin.grow(L.mark()));
+    void *h = c->br_pin.as(), *d = c->br_dev.as();
     a_pw.put(h, Pw); a_uv.put(h, uv); a_sub.put(h, subset);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
     PnpDev D;
@@ -2085,8 +2082,8 @@ int tsorb_match_two_view_ransac(void *ctx, int n, const float *xy1, const float 
     const size_t in_sz = L.mark();
     const auto a_pick = L.take<Pick>(1); const auto a_mdl = L.take<Models>(1); const auto a_hs = L.take<float>(2*H), a_hm = L.take<float>(18*H);
     const auto a_ih = L.take<uint8_t>(N), a_if = L.take<uint8_t>(N);
-    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
-    void *h = c->br_pin, *d = c->br_dev;
+    OCK(c->br_dev.grow(L.mark())); OCK(c->br_pin.grow(L.mark()));
+    void *h = c->br_pin.as(), *d = c->br_dev.as();
     a_xy1.put(h, xy1); a_xy2.put(h, xy2); a_sub.put(h, subset);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
     TvDev D;
@@ -2138,8 +2135,8 @@ int tsorb_match_two_view_reconstruct(void *ctx, int n, const float *xy1, const f
     const size_t out_end = L.mark();
     const auto a_cosall = L.take<float>(NH*N); const auto a_sv = L.take<int32_t>(4);
     const size_t down = (hyp_p3d ? out_end : hyp_state ? a_hp.off : a_state.off) - in_sz;      // what the caller did not ask for stays on the device
-    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, out_end));
-    void *h = c->br_pin, *d = c->br_dev;
+    OCK(c->br_dev.grow(L.mark())); OCK(c->br_pin.grow(out_end));
+    void *h = c->br_pin.as(), *d = c->br_dev.as();
     a_xy1.put(h, xy1); a_xy2.put(h, xy2); a_inl.put(h, inlier);
     int n_inl = 0; for (size_t i = 0; i < N; i++) n_inl += inlier[i] != 0;
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
@@ -2195,8 +2192,8 @@ int tsorb_match_text_theta_ransac(void *ctx, int n_plane, const int32_t *off, co
     const auto a_sel = L.take<int32_t>(P); const auto a_theta = L.take<double>(3*P), a_score = L.take<double>(P), a_hs = L.take<double>(H), a_ht = L.take<double>(3*H),
                a_rho = L.take<double>(N); const auto a_p3d = L.take<float>(3*N);
     const size_t down = (p3d ? L.mark() : rho_out ? a_p3d.off : hyp_theta ? a_rho.off : hyp_score ? a_ht.off : a_hs.off) - in_sz;    // what the caller did not ask for stays on the device
-    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, L.mark()));
-    void *h = c->br_pin, *d = c->br_dev;
+    OCK(c->br_dev.grow(L.mark())); OCK(c->br_pin.grow(L.mark()));
+    void *h = c->br_pin.as(), *d = c->br_dev.as();
     a_off.put(h, off); a_hoff.put(h, hyp_off); a_hxy.put(h, host_xy); a_txy.put(h, targ_xy); a_rin.put(h, rho); a_tri.put(h, triple);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
     TtDev D;
@@ -2242,8 +2239,8 @@ static int claim_call(const char *name, bool points, void *ctx, int nq, const fl
     const auto a_m12 = L.take<int32_t>(Q), a_dist = L.take<int32_t>(Q), a_cnt = L.take<int32_t>(2); const auto a_p3d = L.take<float>(points ? 3*Q : 0); const auto a_good = L.take<uint8_t>(points ? Q : 0);
     const size_t out_end = L.mark();
     const auto a_ridx = L.take<int32_t>(Q*CL_ROW), a_rdist = L.take<int32_t>(Q*CL_ROW), a_rcnt = L.take<int32_t>(Q), a_own = L.take<int32_t>(std::max<size_t>(N2, 1));
-    OCK(grow_device(c->br_dev, c->br_dev_cap, L.mark())); OCK(grow_pinned(c->br_pin, c->br_pin_cap, out_end));
-    void *h = c->br_pin, *d = c->br_dev;
+    OCK(c->br_dev.grow(L.mark())); OCK(c->br_pin.grow(out_end));
+    void *h = c->br_pin.as(), *d = c->br_dev.as();
     a_qxy.put(h, qxy); a_qr.put(h, qr); a_lev.put(h, qlev); a_qd.put(h, qdesc); a_el.put(h, elig2); a_px.put(h, q_px);
     OCK(hipMemcpyAsync(d, h, in_sz, hipMemcpyHostToDevice, c->stream));
     ClaimDev D;

@@ -1,11 +1,17 @@
-// tsstage.h -- how a one-call entry point (tsorb_match_*, tsorb_text_extract, tsloop_*, libtsframe's feature calls) stages its data.  Host only.
+// tsstage.h -- how a one-call entry point (tsorb_match_*, tsorb_text_extract, tsloop_*, libtsframe's feature calls, libtsba's staged calls) stages its data.  Host only.
 //
-// Such a call keeps one pinned block and one device block on its context, grown on demand (grow_pinned / grow_device), and lays its
+// Such a call keeps one pinned block and one device block on its context, grown on demand (Block::grow), and lays its
 // sub-arrays [in | scratch | out] into them at aligned offsets: a Layout hands out Spans in the order of the call's layout comment.  A
 // span's element count is written once, at its take(); the copy up (put), the pointer a kernel gets (at(device block)) and the copy down
 // (get) all come from the span, so they cannot disagree.  Everything between two mark()s is one contiguous range: the copy up is
 // [0, mark() after the inputs), the copy down starts at the first output's offset.  Where the outputs sit at different offsets in the two
 // blocks (a pinned block of their own, or device scratch between inputs and outputs) they get a Layout of their own and two bases.
+//
+// A context's block that only grows is a Block member (DeviceBlock, PinnedBlock) and is owned by it alone: it has no capacity field beside it and
+// no line in a destroy function, which sets the device, waits for the context's stream(s) and deletes the context; the blocks go with it.
+// Deliberately outside, because they are not grow-only: libtsba's slabs, st_host, st_log and hprog (allocated once, or retired while in use);
+// libtsorb's per-geometry allocs, h_img, h_out, h_fb and cv_geo (replaced when the geometry changes); libtsframe's map_xy / map_frac (swapped in
+// only after the new pair is complete); the plane cache's ic.dev (replaced whole, with its bookkeeping, when the image geometry changes).
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -30,22 +36,34 @@ private:
     size_t align_, cur_ = 0;
 };
 
+// a block that only grows, and its owner.  Mem has two static functions: alloc(void **p, size_t n), which returns an error value that compares equal to a
+// value-initialised one on success (0), and release(void *p).  Not copyable: a copied context would free its blocks twice.
+template <class Mem> struct Block {
+    using Err = decltype(Mem::alloc((void **)nullptr, (size_t)0));
+    Block() = default;
+    Block(const Block &) = delete;
+    Block &operator=(const Block &) = delete;
+    ~Block() { if (p_) Mem::release(p_); }
+    // room for `need` bytes: freed and allocated again, with max(need, room) bytes, only when need > cap(); holds nullptr and cap() == 0 after a failure.
+    // The caller sees to it that nothing in flight uses the block when it may move.
+    Err grow(size_t need, size_t room = 0) {
+        if (need <= cap_) return Err{};
+        if (p_) Mem::release(p_);
+        p_ = nullptr; cap_ = 0;
+        const size_t n = need > room ? need : room;
+        const Err e = Mem::alloc(&p_, n);
+        if (e == Err{}) cap_ = n; else p_ = nullptr;
+        return e;
+    }
+    template <class T = void> T *as() const { return (T *)p_; }
+    size_t cap() const { return cap_; }
+private:
+    void *p_ = nullptr; size_t cap_ = 0;
+};
+
 #ifdef __HIPCC__
-// room for `need` bytes in a block that only grows: freed and allocated again only when need > cap; p == nullptr, cap == 0 after a failure
-static inline hipError_t grow_device(void *&p, size_t &cap, size_t need) {
-    if (need <= cap) return hipSuccess;
-    if (p) hipFree(p);
-    p = nullptr; cap = 0;
-    const hipError_t e = hipMalloc(&p, need);
-    if (e == hipSuccess) cap = need; else p = nullptr;
-    return e;
-}
-static inline hipError_t grow_pinned(void *&p, size_t &cap, size_t need) {
-    if (need <= cap) return hipSuccess;
-    if (p) hipHostFree(p);
-    p = nullptr; cap = 0;
-    const hipError_t e = hipHostMalloc(&p, need, hipHostMallocDefault);
-    if (e == hipSuccess) cap = need; else p = nullptr;
-    return e;
-}
+struct DeviceMem { static hipError_t alloc(void **p, size_t n) { return hipMalloc(p, n); }  static void release(void *p) { hipFree(p); } };
+struct PinnedMem { static hipError_t alloc(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }  static void release(void *p) { hipHostFree(p); } };
+using DeviceBlock = Block<DeviceMem>;
+using PinnedBlock = Block<PinnedMem>;
 #endif
